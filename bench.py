@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- the hot path of multilingual_kws on MI355X, one JSON line per run.
 
-  python bench.py [--config embed|frontend|finetune|stream] --gpus N --steps K --warmup W
+  python bench.py [--config embed|frontend|finetune|stream] --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = wall milliseconds of one timed step) and nothing else.  --full adds everything the headline figure does not
+need: the per-kernel roofline table, the `sustained` continuation, the `secondary` runs of the other configs, the CPU baseline and
+the stream config's batch-1 latency legs.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 
 --config selects the BASELINE.json configuration (default `embed` = configs[2], the one the headline metric
 is quoted on):
@@ -19,8 +24,8 @@ one rank; started plainly with --gpus N it re-launches itself under torch.distri
 relays rank 0's JSON line.  Clips are sharded across ranks ("scaling": "weak"); the only collective is the
 fine-tune step's gradient all-reduce.
 
-Rank 0 prints ONE JSON line: whole-job throughput + `roofline` (dominant kernel, hipEvent-timed live on the
-launch stream) + `cpu_baseline` (the CPU oracle on this box's host cores, bounded sample, N = 1 only).
+Rank 0 prints ONE JSON line: whole-job throughput; with --full also `roofline` (dominant kernel, hipEvent-timed live on the
+launch stream) + `cpu_baseline` (the CPU oracle on the host's cores, bounded sample, N = 1 only).
 """
 import argparse
 import hashlib
@@ -59,7 +64,14 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true", help="embed at N = 1: do not append short runs of the other three BASELINE configs (`secondary`)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="A/B execution switch passed to mkws_embed_set_option (e.g. fuse_block=1); default = shipped plan")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline / kernel table, "
+                    "`sustained`, `single_stream`, `secondary` (embed), the CPU baseline, batch-1 latency (stream); off: the plain run only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -220,6 +232,8 @@ def _cpu_run(kind, budget_s, procs=None, threads=None):
 
 # ---------------------------------------------------------------------------------------------------------------------
 PREWARM_S = 0.3          # untimed clock warm-up before the W warm-up steps (see main)
+PREWARM_FT_STEPS = 600   # the same warm-up for the fine-tune config as a step count (~0.3 s at 512 clips per step): see main
+DUMP_MAX_BYTES = 63_000_000   # --dump-outputs: all arrays together, .npy headers left room under 64 MB
 
 
 def source_hash():
@@ -331,6 +345,31 @@ def roofline_of(per_kernel, batch=1024):
     return roof, kernels
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the last timed step computed, one DIR/<name>.npy per array (float64 stays float64, the rest is written as
+    float32).  Above DUMP_MAX_BYTES in all, every array is cut to a fixed, seeded sample of its flattened elements (same size, same
+    sample from run to run).  Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, a in host.items():
+        if total > DUMP_MAX_BYTES:
+            k = max(1, DUMP_MAX_BYTES // len(host) // a.itemsize)
+            if a.size > k:
+                a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, k))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def event_ms(fn, reps):
     """Average duration of fn() on torch's current stream (the stream every mkws_* call is launched on)."""
     import torch
@@ -390,6 +429,7 @@ def main():
     spec = torch.empty((FB, 49, 40), dtype=torch.float32, device=dev)
     emb = torch.empty((FB, 1024), dtype=torch.float32, device=dev)
     units_per_step, unit, extra_out = B, "clips/s", {}
+    last = [None]            # what the newest step returned (finetune / stream), for --dump-outputs
 
     if cfg == "embed":
         metric = "clips/sec end-to-end (log-mel + embedding fwd), batch 1024, 1s@16kHz"
@@ -419,12 +459,18 @@ def main():
         def step():
             step_on(lanes_[turn[0] % nl])
             turn[0] += 1
+
+        def outputs():
+            return {"embeddings": lanes_[(turn[0] - 1) % nl]["emb"]}
     elif cfg == "frontend":
         metric = "clips/sec micro-frontend only, batch 1024, 1s@16kHz"
         workload = "configs[1]: batch=1024/GPU synthetic 1s@16kHz fp32 clips -> micro-frontend -> [1024,49,40] fp32 (71 840 algorithmic bytes/clip)"
 
         def step():
             fe.forward(audio, out=spec)
+
+        def outputs():
+            return {"spectrograms": spec}
     elif cfg == "finetune":
         from multilingual_kws_amd.embedding import input_data
         metric = "clips/sec 5-shot 3-class head fine-tune step (augment + log-mel + frozen embedding fwd + head fwd/bwd/Adam), batch 512/GPU"
@@ -445,7 +491,12 @@ def main():
         extra_out.update({"steps_per_forward": ft.G, "head_steps_on_second_stream": ft.overlap})
 
         def step():
-            ft.step()          # ONE optimizer step on its own B clips (every ft.G-th call also launches the next group's forward chain)
+            # ONE optimizer step on its own B clips (every ft.G-th call also launches the next group's forward chain)
+            last[0] = ft.step()
+
+        def outputs():
+            ft.finish()                      # the optimizer stream's last step has run before the head is read
+            return {"head_params": head.get_params(), "step_stats": last[0]}
     else:   # stream
         from multilingual_kws_amd.embedding import batch_streaming_analysis as bsa, input_data
         metric = "windows/sec streaming inference, 50 keywords on one shared embedding, 20 ms hop, batch 256"
@@ -463,8 +514,11 @@ def main():
         def step():
             # = batch_streaming_analysis.streaming_inferences without the final device-to-host copy: full batches replay captured hipGraphs
             # (embedding + 50 heads), `lanes` of them side by side on their own streams; the ragged last batch runs launch by launch beside them
-            bsa.serve_spectrograms(em, heads, bsa.stream_spectrograms(ms, stream, 16000, 320), B)
+            last[0] = bsa.serve_spectrograms(em, heads, bsa.stream_spectrograms(ms, stream, 16000, 320), B)
         extra_out["serving_lanes"] = lanes
+
+        def outputs():
+            return {"probabilities": last[0]}
 
         def stream_check():
             # outside the timed region: the probabilities of one more pass are finite and no handle recorded a failed exchange (a graph replay
@@ -485,9 +539,16 @@ def main():
     # Untimed clock warm-up in front of the W warm-up steps: a process's first ~dozen forward passes run at a lower shader clock (rocprofv3 reads
     # the 235 us chain kernel at 251 us in a 13-step run; `--steps 20 --warmup 5` read 1.05-1.06 M clips/s where 200 / 20 reads 1.085 M, same box,
     # same call: profiles/r04_notes.md).  0.3 s of the same step, reported in the line as `prewarm_s`; the timed region is still exactly K steps.
-    if world > 1:
-        for _ in range(200):             # a fixed count: a step may hold a collective, every rank must run the same number of them
+    # A fine-tune step changes the head and advances the data stream, so there the warm-up is a step count (`prewarm_steps`): what the last
+    # timed step computes (--dump-outputs) is then the same from run to run.
+    prewarm = {"prewarm_s": PREWARM_S}
+    if world > 1 or cfg == "finetune":
+        # a fixed count: a step may hold a collective, every rank must run the same number of them
+        n_pre = 200 if world > 1 else PREWARM_FT_STEPS
+        for _ in range(n_pre):
             step()
+        if cfg == "finetune":
+            prewarm = {"prewarm_steps": n_pre}
     else:
         t_pre = time.perf_counter()
         while time.perf_counter() - t_pre < PREWARM_S:
@@ -516,6 +577,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        extra_out["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs())
     if cfg == "stream":
         stream_check()
     value = world * units_per_step * args.steps / elapsed
@@ -544,14 +607,14 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 el = float(t.item())
             return {"value": round(world * units_per_step * n / el, 1), "ms_per_step": round(el / n * 1e3, 4), "steps": n, "seconds": round(el, 3)}
-        if args.sustain_s > 0:
+        if args.full and args.sustain_s > 0:
             # the driver's K steps last ~20 ms: too short for a power / clock sampler to see.  The same step for >= sustain_s seconds.
             extra_out["sustained"] = timed(step, args.sustain_s, 50)
-        if nl > 1:
+        if args.full and nl > 1:
             extra_out["single_stream"] = timed(lambda: step_on(lanes_[0]), 0.0, max(50, args.steps))
 
-    result = None
-    if rank == 0:
+    result, full = None, {}
+    if rank == 0 and args.full:
         fe.forward(audio, out=spec)
         fe_ms = event_ms(lambda: fe.forward(audio, out=spec), args.profile_reps)
         fw = int(os.environ.get("MKWS_FRONTEND_WAVES", "0"))          # waves per clip (mkws_frontend.hip clip_waves: 4 unless the experiment knob is set)
@@ -601,25 +664,27 @@ def main():
             extra_out["latency_ms_batch1"] = latency(lambda: sess.infer(one))
             assert torch.equal(sess.infer(one), Head.forward_many(heads, em1.forward(fe.forward(one))))
             extra_out["windows_per_stream"] = nwin
+        full = {"roofline": roof, "kernels": kernels, "whole_step": whole}
+    if rank == 0:
         result = {
             "metric": metric, "value": round(value, 1), "unit": unit, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic", "prewarm_s": PREWARM_S,
+            "dtype": "f32", "data": "synthetic", **prewarm, "full": args.full,
             "config": {"workload": workload, "name": cfg, "clips_per_gpu": units_per_step, "samples_per_clip": 16000,
                        "weights": "synthetic seed 1234", "parallelism": f"clip-sharded x{world}", "build": source_hash()},
-            "roofline": roof, "kernels": kernels, "whole_step": whole,
+            **full,
         }
         result.update(extra_out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and world == 1 and cfg == "embed" and not args.no_secondary:
+    if rank == 0 and world == 1 and cfg == "embed" and args.full and not args.no_secondary:
         # The other three BASELINE configs as SHORT runs of this same file (`--config X`: same code path as a full run of that config), so that
         # the one line the driver records carries all four.  Each is its own process: its own handles, its own clock warm-up, no CPU baseline.
         result["secondary"] = {}
         for name, extra in (("frontend", ["--steps", "400", "--warmup", "40"]), ("finetune", ["--steps", "240", "--warmup", "48"]),
                             ("stream", ["--steps", "30", "--warmup", "4"])):
-            cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--no-cpu-baseline", "--no-secondary"] + extra
+            cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--full", "--no-cpu-baseline", "--no-secondary"] + extra
             try:
                 out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=dict(os.environ))
                 d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -634,7 +699,7 @@ def main():
             except Exception as exc:
                 result["secondary"][name] = {"value": None, "error": repr(exc)[:300]}
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0 at N = 1 only
             del em, fe
             torch.cuda.empty_cache()
             try:

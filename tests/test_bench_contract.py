@@ -122,7 +122,7 @@ def test_dominant_kernel_choice_is_stable_under_timing_noise():
 
 
 def test_headline_line_carries_the_other_configs_and_a_sustained_run():
-    """Round 6 (verdict item 6): the ONE line `python bench.py` prints -- the line the driver records -- also holds short runs of the other
+    """Round 6 (verdict item 6): the ONE line `python bench.py --full` prints also holds short runs of the other
     three BASELINE configs (`secondary`, same code path as `--config X`) and a >= 2 s continuation of the headline step (`sustained`: long
     enough for a clock / power sampler to see the GPU busy); `value` stays the K-step figure."""
     d = _latest_bench_lines()["embed"]
@@ -147,3 +147,66 @@ def test_bench_cli_has_the_round6_switches():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     for flag in ("--lanes", "--sustain-s", "--no-secondary"):
         assert flag in out.stdout
+
+
+def test_bench_cli_has_full_and_dump_outputs(monkeypatch):
+    """A plain run is lean: everything beyond the headline figure sits behind --full (off by default)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    for flag in ("--full", "--dump-outputs"):
+        assert flag in out.stdout
+    bench = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_float_arrays_under_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    bench = _load_bench()
+    rng = np.random.default_rng(3)
+    arrays = {"emb": rng.standard_normal((64, 32)).astype(np.float32), "wide": rng.standard_normal(10), "count": np.arange(5)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert shapes == {"emb": [64, 32], "wide": [10], "count": [5]}
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert got["emb"].dtype == np.float32 and np.array_equal(got["emb"], arrays["emb"])
+    assert got["wide"].dtype == np.float64 and np.array_equal(got["wide"], arrays["wide"])
+    assert got["count"].dtype == np.float32 and np.array_equal(got["count"], np.arange(5, dtype=np.float32))
+    # above the cap: a fixed, seeded sample of each array, the same from call to call
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1000)
+    s1 = bench.dump_outputs(str(tmp_path / "b"), arrays)
+    s2 = bench.dump_outputs(str(tmp_path / "c"), arrays)
+    assert s1 == s2 and sum(np.load(tmp_path / "b" / f"{k}.npy").nbytes for k in arrays) <= 1000
+    for k in arrays:
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy"))
+    assert set(np.load(tmp_path / "b" / "emb.npy").tolist()) <= set(arrays["emb"].reshape(-1).tolist())
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: exactly K timed steps, the headline fields, none of the --full
+    figures; --dump-outputs holds the embeddings of the last step, which a direct forward pass on the same clips reproduces."""
+    import numpy as np
+    import torch
+    from multilingual_kws_amd import synth, weights
+    from multilingual_kws_amd.embedding_model import EmbeddingModel
+    from multilingual_kws_amd.frontend import Frontend
+    d = str(tmp_path / "out")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", d],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str), ("ms_per_step", float)):
+        assert isinstance(line[k], t), k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False and line["cpu_baseline"] is None
+    assert not {"roofline", "kernels", "whole_step", "sustained", "secondary"} & set(line)
+    assert abs(line["value"] - 1024 / (line["ms_per_step"] * 1e-3)) / line["value"] < 0.01
+    assert line["dumped_outputs"] == {"embeddings": [1024, 1024]}
+    got = np.load(os.path.join(d, "embeddings.npy"))
+    assert got.dtype == np.float32 and np.isfinite(got).all()
+    dev = torch.device("cuda:0")
+    audio = torch.from_numpy(synth.clips_float32(1024, first_clip=0)).to(dev)
+    ref = EmbeddingModel(weights.synthetic_blob(), max_batch=1024, device=dev).forward(Frontend(max_samples=16000).forward(audio)).cpu().numpy()
+    assert np.abs(got - ref).max() <= 1e-5 * np.abs(ref).max()

@@ -4,7 +4,7 @@ O=gpurun_out/ab_$1; mkdir -p $O
 timeout 600 python -m pytest tests/test_embedding_gpu.py -x -q > $O/pytest.log 2>&1; echo "rc=$?" >> $O/pytest.log; tail -4 $O/pytest.log
 shift_opt=$1; shift
 for v in "$@"; do
-  timeout 300 python bench.py --no-cpu-baseline --steps 30 --opt $shift_opt=$v > $O/bench_$v.json 2> $O/bench_$v.err
+  timeout 300 python bench.py --full --no-cpu-baseline --steps 30 --opt $shift_opt=$v > $O/bench_$v.json 2> $O/bench_$v.err
 done
 python - "$O" "$@" <<'PY'
 import json, sys

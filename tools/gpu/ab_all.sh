@@ -4,10 +4,10 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/ab_all; mkdir -p $O
 timeout 900 python -m pytest tests/test_embedding_gpu.py tests/test_streaming.py tests/test_train_gpu.py tests/test_head_gpu.py -x -q -m gpu > $O/pytest.log 2>&1; echo "rc=$?" >> $O/pytest.log; tail -3 $O/pytest.log
 for c in embed finetune stream; do
-  timeout 300 python bench.py --no-cpu-baseline --steps 50 --config $c > $O/${c}_new.json 2> $O/${c}_new.err
-  MKWS_LIB=$PWD/$1 timeout 300 python bench.py --no-cpu-baseline --steps 50 --config $c > $O/${c}_prev.json 2> $O/${c}_prev.err
+  timeout 300 python bench.py --full --no-cpu-baseline --steps 50 --config $c > $O/${c}_new.json 2> $O/${c}_new.err
+  MKWS_LIB=$PWD/$1 timeout 300 python bench.py --full --no-cpu-baseline --steps 50 --config $c > $O/${c}_prev.json 2> $O/${c}_prev.err
 done
-timeout 300 python bench.py --no-cpu-baseline --steps 50 > $O/embed_new2.json 2> $O/embed_new2.err
+timeout 300 python bench.py --full --no-cpu-baseline --steps 50 > $O/embed_new2.json 2> $O/embed_new2.err
 python - <<'PY'
 import json, os
 for c in ("embed", "finetune", "stream"):

@@ -5,7 +5,7 @@ O=gpurun_out/ablibs; mkdir -p $O
 i=0
 for l in "$@"; do
   if [ "$l" = "-" ]; then unset MKWS_LIB; else export MKWS_LIB=$PWD/$l; fi
-  timeout 300 python bench.py --no-cpu-baseline --steps 50 > $O/bench_$i.json 2> $O/bench_$i.err
+  timeout 300 python bench.py --full --no-cpu-baseline --steps 50 > $O/bench_$i.json 2> $O/bench_$i.err
   i=$((i+1))
 done
 python - "$@" <<'PY'

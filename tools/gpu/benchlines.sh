@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/benchlines; rm -rf $O; mkdir -p $O
 for c in embed frontend finetune stream; do
-  timeout 400 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err; echo "bench $c rc=$?"
+  timeout 400 python bench.py --full --config $c > $O/bench_$c.json 2> $O/bench_$c.err; echo "bench $c rc=$?"
 done
 python - <<'PY'
 import json

@@ -6,7 +6,7 @@ O=gpurun_out/evidence
 rm -rf $O; mkdir -p $O
 if [ -z "$SKIP_BENCH" ]; then
 for c in embed frontend finetune stream; do
-  timeout 400 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err; echo "bench $c rc=$?"
+  timeout 400 python bench.py --full --config $c > $O/bench_$c.json 2> $O/bench_$c.err; echo "bench $c rc=$?"
 done
 fi
 export TMPDIR=/tmp

@@ -3,9 +3,9 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/pair; mkdir -p $O
 timeout 900 python -m pytest tests/test_embedding_gpu.py tests/test_streaming.py -x -q -m gpu > $O/pytest.log 2>&1; echo "rc=$?" >> $O/pytest.log; tail -3 $O/pytest.log
-timeout 300 python bench.py --no-cpu-baseline --steps 50 > $O/bench_new.json 2> $O/bench_new.err
-if [ -n "$1" ]; then MKWS_LIB=$PWD/$1 timeout 300 python bench.py --no-cpu-baseline --steps 50 > $O/bench_prev.json 2> $O/bench_prev.err; fi
-timeout 300 python bench.py --no-cpu-baseline --steps 50 > $O/bench_new2.json 2> $O/bench_new2.err
+timeout 300 python bench.py --full --no-cpu-baseline --steps 50 > $O/bench_new.json 2> $O/bench_new.err
+if [ -n "$1" ]; then MKWS_LIB=$PWD/$1 timeout 300 python bench.py --full --no-cpu-baseline --steps 50 > $O/bench_prev.json 2> $O/bench_prev.err; fi
+timeout 300 python bench.py --full --no-cpu-baseline --steps 50 > $O/bench_new2.json 2> $O/bench_new2.err
 python - <<'PY'
 import json, os
 for v in ("bench_new", "bench_prev", "bench_new2"):
