@@ -306,6 +306,43 @@ int mkws_head_adam_step_dev(mkws_head* hd, float lr, float beta1, float beta2, f
                             float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming detector.  Replaces SingleTargetRecognizeCommands.process_latest_result
+ * (multilingual_kws/embedding/single_target_recognize_commands.py:94-207) and the per-window, per-keyword, per-threshold Python loop
+ * that drives it (batch_streaming_analysis.py:124-177): every window of a stream, n_heads keyword heads x n_thr detection thresholds,
+ * in ONE launch.  multilingual_kws_amd/embedding/single_target_recognize_commands.py is the host restatement and the specification.
+ * For window w at time t[w] (milliseconds): head = the smallest j <= w with t[j] >= t[w] - average_window_duration_ms;
+ * how_many = w - head + 1.  A window with how_many < minimum_count or t[w] - t[head] < average_window_duration_ms / 4 is not evaluated
+ * (score 0.0, the label of the previous event, no event).  Otherwise score = sum over j = head..w, in that order, of
+ * (double)p[j][target_id] / (double)how_many, in float64 with one IEEE division and one IEEE addition per term (bit-equal to the host
+ * class); a score above the threshold fires when the last event's label is silence, a score below it releases, either only when more
+ * than suppression_ms have passed since the last event that left the label at the keyword.  A NaN score is no event.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mkws_detect_event {
+  int32_t window;   /* index of the window the event happened in */
+  int32_t fired;    /* 1: the keyword fired; 0: release (is_new_command with the silence label) */
+  double score;
+} mkws_detect_event;
+
+/* d_probs [n_heads, n_windows, classes] float32 (what mkws_heads_forward writes) or float64 (probs_f64 != 0);
+ * d_times_ms int64 [n_windows], non-decreasing and within +-2^61 (the caller checks; unsorted times give wrong answers, never a
+ * wild access);
+ * d_thresholds double [n_thr].
+ * d_events [n_heads, n_thr, event_cap], d_counts int32 [n_heads, n_thr] = events that OCCURRED (a count above event_cap tells the
+ * caller that the list is cut; nothing is stored past the cap).  fired_only = 0: every is_new_command step is an event.  The host
+ * class also reports a release on EVERY evaluated sub-threshold window while the label already is silence, so a quiet stream has
+ * about one event per window and lane.  fired_only != 0: only fired events are stored and counted -- what the callers of detect()
+ * keep -- and successive fires of a lane are more than suppression_ms apart, which bounds the list.
+ * Optional dense trace for parity checks (either may be NULL): d_scores double [n_heads, n_windows] (0.0 where not evaluated),
+ * d_flags uint8 [n_heads, n_thr, n_windows]: bit 0 found_command is the keyword, bit 1 is_new_command.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers, negative sizes, target_id outside [0, classes), average_window_duration_ms < 0
+ * (the host class would pop its own newest entry) and n_thr < 1; n_windows == 0 or n_heads == 0 returns MKWS_OK with nothing
+ * launched and nothing written.  Asynchronous on `stream`, allocates nothing, never synchronises: capturable like every other call. */
+int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_windows, int classes, int target_id,
+                       const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
+                       double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
+                       int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-batch assembly.  Replaces the per-clip tf.data map of AudioDataset.augment /
  * random_timeshift / random_background_sample / add_background
  * (multilingual_kws/embedding/input_data.py:141-157,227-304) and spec_augment (:306-369).

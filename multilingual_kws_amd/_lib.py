@@ -32,6 +32,11 @@ class FrontendCfg(ctypes.Structure):
     ]
 
 
+class DetectEvent(ctypes.Structure):
+    """mkws_detect_event (include/mkws.h)."""
+    _fields_ = [("window", ctypes.c_int32), ("fired", ctypes.c_int32), ("score", ctypes.c_double)]
+
+
 # every symbol include/mkws.h declares: (name, restype, argtypes)
 _P, _I, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _CFG = ctypes.POINTER(FrontendCfg)
@@ -56,6 +61,7 @@ SYMBOLS = [
     ("mkws_embed_get_option", _I, [_P, ctypes.c_char_p]),
     ("mkws_embed_profile", _I, [_P, _P, _I, _I, _P, ctypes.c_char_p, _SZ, _P]),
     ("mkws_embed_forward_tap", _I, [_P, _P, _I, ctypes.c_char_p, _P, _SZ, _P]),
+    ("mkws_detect_stream", _I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
     ("mkws_augment_batch", _I, [_P, _P, _P, ctypes.c_int64, _P, _I, _I, _P, _P]),
     ("mkws_specaug_apply", _I, [_P, _P, _I, _I, _I, _P]),
     ("mkws_specaug_apply_n", _I, [_P, _P, _I, _I, _I, _I, _I, _P]),

@@ -1,0 +1,178 @@
+// Streaming detector (mkws_detect_stream, include/mkws.h): SingleTargetRecognizeCommands.process_latest_result over every window of a
+// stream, for n_heads keyword heads x n_thr detection thresholds in ONE launch.  The host class
+// (multilingual_kws_amd/embedding/single_target_recognize_commands.py) is the specification; scores are bit-equal to CPython's.
+//
+// Two facts shape the kernel.  (1) The score of a window -- the float64 in-order mean of the target confidence over the windows the
+// host deque would hold -- depends on neither the threshold nor the detector state: it is computed once per (head, window), all
+// threads of the workgroup in parallel, into an LDS tile.  (2) The state walk is sequential in windows but only COMPARES, and is
+// independent per (head, threshold): lane i walks the tile for threshold i, every lane of a wave reads the same LDS word in the
+// same step (a broadcast, no bank conflict) and carries {previous label is the keyword, time after which it may change, events so
+// far} in registers across tiles.
+//
+// One workgroup of 1024 threads per (head, group of 1024 thresholds).  A window of a tile may average over windows that precede the tile: those are
+// read from global memory again (the whole stream of one head is a few tens of KB and stays in cache); there is no halo.
+// Events are appended by their own lane with ordinary vector stores: a lane owns its (head, threshold) list, so there are no atomics.
+#include "mkws_common.h"
+
+#include <cmath>
+#include <cstdint>
+
+using mkws::fail;
+
+namespace {
+
+constexpr int kDetectThreads = 1024;  // = thresholds per workgroup; phase 1 spreads a tile's windows over all of them
+constexpr int kDetectTile = 2048;     // windows per LDS tile: 16 KB scores + 16 KB times + 2 KB flags
+constexpr int kDetectChunk = 8;       // windows a walking lane reads from LDS ahead of the state chain (divides the tile)
+
+struct DetectArgs {
+  const void* probs;
+  const int64_t* times;
+  const double* thr;
+  mkws_detect_event* events;
+  int32_t* counts;
+  double* scores;
+  uint8_t* flags;
+  double avg_ms;
+  int64_t suppression;   // floor(suppression_ms): for integer times, t - t0 > suppression_ms exactly when t - t0 > floor(suppression_ms)
+  int n_windows, classes, target, n_thr, min_count, event_cap, fired_only, never;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
+  __shared__ double s_score[kDetectTile];
+  __shared__ int64_t s_time[kDetectTile];
+  __shared__ uint8_t s_eval[kDetectTile];
+  const int head = blockIdx.x;
+  const int W = a.n_windows;
+  const T* __restrict__ p = static_cast<const T*>(a.probs) + (size_t)head * W * a.classes + a.target;
+  const int64_t* __restrict__ t = a.times;
+  const int ti = blockIdx.y * kDetectThreads + threadIdx.x;          // this lane's threshold
+  const bool walker = ti < a.n_thr;
+  const double thr = walker ? a.thr[ti] : 0.0;
+  const size_t lane_row = (size_t)head * a.n_thr + (walker ? ti : 0);
+  mkws_detect_event* __restrict__ ev = a.events + lane_row * (size_t)a.event_cap;
+  uint8_t* __restrict__ fl = a.flags ? a.flags + lane_row * (size_t)W : nullptr;
+  const double quarter = a.avg_ms / 4;
+  const bool can_change = !a.never;
+  bool prev_kw = false;           // the previous top label is the keyword ("_silence_" before anything has fired)
+  int64_t deadline = 0;           // time of the event that made it so + suppression: the label may change after it; read only while prev_kw
+  int n_events = 0;
+
+  for (int w0 = 0; w0 < W; w0 += kDetectTile) {
+    const int nw = min(kDetectTile, W - w0);
+    // phase 1: scores of the tile, one window per thread and step
+    for (int i = threadIdx.x; i < nw; i += kDetectThreads) {
+      const int w = w0 + i;
+      const int64_t tw = t[w];
+      // head of the host deque after its pops: the smallest j <= w with t[j] >= t[w] - avg (times are non-decreasing, so the
+      // predicate is monotone; it holds at j = w because avg >= 0, which keeps every index below inside [0, w])
+      const double limit = (double)tw - a.avg_ms;
+      int lo = 0, hi = w;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((double)t[mid] >= limit) hi = mid; else lo = mid + 1;
+      }
+      const int how_many = w - lo + 1;
+      const double duration = (double)(tw - t[lo]);
+      const bool evaluated = !(how_many < a.min_count || duration < quarter);
+      double score = 0.0;
+      if (evaluated) {
+        const double n = (double)how_many;
+        for (int j = lo; j <= w; ++j) score += (double)p[(size_t)j * a.classes] / n;     // one IEEE division, one IEEE addition per term, in order
+      }
+      s_score[i] = score;
+      s_time[i] = tw;
+      s_eval[i] = evaluated;
+      if (a.scores && blockIdx.y == 0) a.scores[(size_t)head * W + w] = score;
+    }
+    __syncthreads();
+    // phase 2: lane = threshold; compares only.  A chunk of windows is read from LDS first (the reads do not depend on the state),
+    // then the state chain runs over registers: two compares, a few logic operations and two selects per window.
+    if (walker) {
+      for (int i0 = 0; i0 < nw; i0 += kDetectChunk) {
+        double c_score[kDetectChunk];
+        int64_t c_time[kDetectChunk];
+        bool c_eval[kDetectChunk];
+#pragma unroll
+        for (int u = 0; u < kDetectChunk; ++u) {                     // (past nw: stale words of the tile, read but not used)
+          c_score[u] = s_score[i0 + u];
+          c_time[u] = s_time[i0 + u];
+          c_eval[u] = s_eval[i0 + u] != 0;
+        }
+#pragma unroll
+        for (int u = 0; u < kDetectChunk; ++u) {
+          if (i0 + u < nw) {
+            const double score = c_score[u];
+            const int64_t tw = c_time[u];
+            const bool above = c_eval[u] & (score > thr);
+            const bool below = c_eval[u] & (score < thr);            // a NaN score is neither above nor below
+            const bool may = can_change & (!prev_kw | (tw > deadline));   // `since` is infinite while the label is silence
+            const bool fire = above & !prev_kw & may;
+            const bool release = below & may;
+            const bool is_new = fire | release;
+            const bool is_kw = c_eval[u] ? above : prev_kw;          // not evaluated: the label of the last event
+            if (fire | (release & !a.fired_only)) {
+              if (n_events < a.event_cap) {
+                mkws_detect_event e;
+                e.window = w0 + i0 + u;
+                e.fired = fire ? 1 : 0;
+                e.score = score;
+                ev[n_events] = e;
+              }
+              ++n_events;
+            }
+            prev_kw = is_new ? above : prev_kw;
+            deadline = is_new ? tw + a.suppression : deadline;
+            if (fl) fl[w0 + i0 + u] = (uint8_t)((is_kw ? 1 : 0) | (is_new ? 2 : 0));
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (walker) a.counts[lane_row] = n_events;
+}
+
+}  // namespace
+
+extern "C" int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_windows, int classes, int target_id,
+                                  const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
+                                  double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
+                                  int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream) {
+  if (n_heads < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
+  if (classes < 1 || target_id < 0 || target_id >= classes) return fail(MKWS_ERR_INVALID_ARG, "target_id %d outside [0, %d)", target_id, classes);
+  if (!(average_window_duration_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "average_window_duration_ms must be >= 0 (the host detector would pop its newest entry)");
+  if (std::isnan(suppression_ms)) return fail(MKWS_ERR_INVALID_ARG, "suppression_ms is NaN");
+  if (!d_probs || !d_times_ms || !d_thresholds || !d_counts || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_heads == 0 || n_windows == 0) return MKWS_OK;
+  const int groups = (n_thr + kDetectThreads - 1) / kDetectThreads;
+  if (groups > 65535) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per call", n_thr, 65535 * kDetectThreads);
+  DetectArgs a;
+  a.probs = d_probs;
+  a.times = d_times_ms;
+  a.thr = d_thresholds;
+  a.events = d_events;
+  a.counts = d_counts;
+  a.scores = d_scores;
+  a.flags = d_flags;
+  a.avg_ms = average_window_duration_ms;
+  // since > suppression_ms with integer times: since > floor(suppression_ms).  Negative: every difference (>= 0) exceeds it.  Not below
+  // 2^62 (+inf included): no difference of two times does (the host class then never reports an event, `inf > inf` being false)
+  a.never = suppression_ms >= 4611686018427387904.0;
+  a.suppression = suppression_ms < 0 ? -1 : a.never ? 0 : (int64_t)std::floor(suppression_ms);
+  a.n_windows = n_windows;
+  a.classes = classes;
+  a.target = target_id;
+  a.n_thr = n_thr;
+  a.min_count = minimum_count;
+  a.event_cap = event_cap;
+  a.fired_only = fired_only != 0;
+  if (probs_f64)
+    hipLaunchKernelGGL(detect_kernel<double>, dim3(n_heads, groups), dim3(kDetectThreads), 0, static_cast<hipStream_t>(stream), a);
+  else
+    hipLaunchKernelGGL(detect_kernel<float>, dim3(n_heads, groups), dim3(kDetectThreads), 0, static_cast<hipStream_t>(stream), a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}

@@ -1,0 +1,115 @@
+"""Device streaming detector: host wrapper over mkws_detect_stream (include/mkws.h).
+
+SingleTargetRecognizeCommands (embedding/single_target_recognize_commands.py) stepped over every window of a stream, for N keyword
+heads x T detection thresholds in one launch.  The host class is the specification: labels, is_new_command and the float64 scores
+are equal bit for bit (tests/test_detector_device.py)."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+# mkws_detect_event as a numpy record (the layout of _lib.DetectEvent)
+EVENT_DTYPE = np.dtype([("window", "<i4"), ("fired", "<i4"), ("score", "<f8")])
+assert EVENT_DTYPE.itemsize == ctypes.sizeof(_lib.DetectEvent) == 16
+
+
+class DetectResult:
+    """counts int32 [N, T]; events[n][k]: EVENT_DTYPE records of head n at thresholds[k], in window order (views of `event_buffer`
+    [N, T, cap]); with trace=True scores float64 [N, W] (0.0 where the window was not evaluated) and flags uint8 [N, T, W] (bit 0
+    found_command is the keyword, bit 1 is_new_command), else None."""
+
+    def __init__(self, counts, event_buffer, scores=None, flags=None):
+        self.counts, self.event_buffer, self.scores, self.flags = counts, event_buffer, scores, flags
+
+    @property
+    def events(self):
+        return [[self.event_buffer[n, k, :c] for k, c in enumerate(row)] for n, row in enumerate(self.counts.tolist())]
+
+
+def check_times(times_ms):
+    """int64 [W], non-decreasing -- with the ValueError of SingleTargetRecognizeCommands.process_latest_result (which compares a new
+    timestamp with the oldest one it still holds; here the whole list is known up front, so any step backwards is refused)."""
+    t = np.asarray(times_ms)
+    if t.ndim != 1 or (t.size and not np.issubdtype(t.dtype, np.integer) and not np.array_equal(t, np.floor(t))):
+        raise ValueError("times_ms must be a one-dimensional list of integer milliseconds")
+    t = np.ascontiguousarray(t, dtype=np.int64)
+    if t.size and max(abs(int(t[0])), abs(int(t[-1]))) > 2 ** 61:
+        raise ValueError("times_ms must lie within +-2**61 milliseconds")
+    bad = np.nonzero(t[1:] < t[:-1])[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError("Results must be fed in increasing time order, but receive a timestamp of {}, which was "
+                         "earlier than the previous one of {}".format(int(t[i + 1]), int(t[i])))
+    return t
+
+
+def event_capacity(times_ms, suppression_ms, fired_only=False):
+    """Upper bound on the events of one (head, threshold) lane that leave or enter the keyword state.  A release out of the keyword
+    state needs more than suppression_ms since the fire, but a fire may follow a release in the very next window (the class takes
+    `since` as infinite while the label is silence): at most two such events per suppression_ms of stream.  Fires alone are more than
+    suppression_ms apart.  (With fired_only=False the class's repeated releases of an already silent label count as events too and can
+    exceed this: detect_on_device then repeats the call with capacity W.)"""
+    W = len(times_ms)
+    if W == 0:
+        return 0
+    if not suppression_ms > 0 or not np.isfinite(suppression_ms):
+        return W
+    per = int((int(times_ms[-1]) - int(times_ms[0])) // suppression_ms)
+    return min(W, per + 2 if fired_only else 2 * per + 2)
+
+
+def detect_on_device(probs, times_ms, thresholds, average_window_duration_ms, suppression_ms, minimum_count, target_id=2, trace=False,
+                     fired_only=False):
+    """probs: CUDA tensor [N, W, C], float32 or float64 (made contiguous if it is a view), or a numpy array, which is uploaded.
+    times_ms: W non-decreasing integers.  thresholds: T floats.  -> DetectResult; never a cut event list.  One launch and one
+    device-to-host copy (= one synchronisation) per call; a second round only if a lane had more events than event_capacity() allows
+    for (fired_only=False on a stream with quiet stretches)."""
+    import torch
+    times = check_times(times_ms)                                      # before anything touches the device
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if thr.size < 1:
+        raise ValueError("at least one threshold")
+    if not average_window_duration_ms >= 0:
+        raise ValueError("average_window_duration_ms must be >= 0")
+    if not torch.is_tensor(probs):
+        a = np.asarray(probs)
+        probs = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)).cuda()
+    if probs.dim() != 3 or not probs.is_cuda or probs.dtype not in (torch.float32, torch.float64):
+        raise ValueError("probs must be a CUDA tensor or numpy array [heads, windows, classes] of float32 or float64")
+    N, W, C = probs.shape
+    if W != times.shape[0]:
+        raise ValueError(f"{W} windows but {times.shape[0]} timestamps")
+    if not 0 <= int(target_id) < C:
+        raise ValueError(f"target_id {target_id} outside [0, {C})")
+    probs = probs.contiguous()
+    T = int(thr.size)
+    if N == 0 or W == 0:                                               # nothing to launch (the C call would write nothing either)
+        return DetectResult(np.zeros((N, T), np.int32), np.zeros((N, T, 0), EVENT_DTYPE),
+                            np.zeros((N, W), np.float64) if trace else None, np.zeros((N, T, W), np.uint8) if trace else None)
+    L = _lib.lib()
+    dev = probs.device
+    with torch.cuda.device(dev):
+        # times and thresholds travel in one upload: int64 times, then the float64 thresholds' bit patterns
+        host_in = np.concatenate([times, thr.view(np.int64)])
+        d_in = torch.from_numpy(host_in).to(dev, non_blocking=True)
+        d_scores = torch.empty((N, W), dtype=torch.float64, device=dev) if trace else None
+        d_flags = torch.empty((N, T, W), dtype=torch.uint8, device=dev) if trace else None
+        cap = event_capacity(times, suppression_ms, fired_only)
+        while True:
+            # counts (int32 pairs padded to whole 8-byte words) and events in ONE buffer, so that they cross in one copy
+            cwords = (N * T + 1) // 2
+            d_out = torch.empty(cwords + 2 * N * T * cap, dtype=torch.int64, device=dev)
+            base = d_out.data_ptr()
+            _lib.check(L.mkws_detect_stream(
+                probs.data_ptr(), int(probs.dtype == torch.float64), N, W, C, int(target_id), d_in.data_ptr(), d_in.data_ptr() + 8 * W, T,
+                float(average_window_duration_ms), float(suppression_ms), int(minimum_count), int(bool(fired_only)),
+                base + 8 * cwords, cap, base, d_scores.data_ptr() if trace else None, d_flags.data_ptr() if trace else None,
+                _lib.current_stream_ptr()))
+            out = d_out.cpu().numpy()                                  # the call's one synchronisation
+            counts = out[:cwords].view(np.int32)[:N * T].reshape(N, T)
+            if counts.size == 0 or int(counts.max()) <= cap:
+                break
+            cap = W                                                    # a lane cannot have more events than windows
+        events = out[cwords:].view(EVENT_DTYPE).reshape(N, T, cap)
+        return DetectResult(counts, events, d_scores.cpu().numpy() if trace else None, d_flags.cpu().numpy() if trace else None)

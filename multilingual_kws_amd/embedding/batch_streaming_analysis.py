@@ -4,8 +4,10 @@ The reference (:99-117) slices a long recording into 1 s windows every 20 ms, ca
 on each window in a Python loop and runs one full model per keyword.  Here one call produces every
 window's features on the GPU with per-frame FFT / filterbank work shared across the 49x-overlapping
 windows (mkws_frontend_stream_f32; bit-identical to per-window calls), the embedding is computed once and
-any number of few-shot heads are applied to it.  The detector (SingleTargetRecognizeCommands) stays on the
-host.  StreamTarget / eval_stream_test (:188-241) are the per-keyword entry points run.py drives; multi_keyword_detections is
+any number of few-shot heads are applied to it.  The detector runs on the device as well: detect_many steps
+every keyword head and every detection threshold over the stream in one launch (mkws_detect_stream, ..detector);
+SingleTargetRecognizeCommands and detect() are its host restatement -- the yardstick the device path is held to bit
+for bit, and the path for hosts without a GPU.  StreamTarget / eval_stream_test (:188-241) are the per-keyword entry points run.py drives; multi_keyword_detections is
 their multi-keyword form on ONE shared embedding pass (run.py:89-152 runs one full model per keyword)."""
 import os
 import pickle
@@ -256,16 +258,18 @@ def serve_spectrograms(emb_model, heads, specs, batch_windows=4096, use_graph=Tr
 
 
 def streaming_inferences(models, model_settings, audio, sample_rate=16000, clip_duration_ms=1000, clip_stride_ms=20,
-                         batch_windows=4096, max_chunk_length_sec=None, use_graph=True, _retry=True):
+                         batch_windows=4096, max_chunk_length_sec=None, use_graph=True, _retry=True, as_device=False):
     """Softmax outputs for every window.  `models`: one TransferLearnedModel or a list sharing one embedding
     (multi-keyword serving: the EfficientNet forward runs once, each keyword adds only its 18.5 k-parameter
-    head).  Returns [num_windows, 3] (or a list of them)."""
+    head).  Returns [num_windows, 3] (or a list of them) as numpy arrays; with as_device=True the CUDA tensor
+    [num_windows, 3] (or [n_models, num_windows, 3] for a list) instead, for detect_many -- after the same
+    exchange-failure check and repeat."""
     import torch
     single = not isinstance(models, (list, tuple))
     mlist = [models] if single else list(models)
     clip = int(clip_duration_ms * sample_rate / 1000)
     stride = int(clip_stride_ms * sample_rate / 1000)
-    outs = [[] for _ in mlist]
+    chunks = []                                # per chunk: CUDA [n_models, windows of the chunk, 3]
     emb_model = mlist[0].embedding
     graphs_used = {}                           # graph -> its heal count when this stream first used it
 
@@ -278,9 +282,7 @@ def streaming_inferences(models, model_settings, audio, sample_rate=16000, clip_
     for chunk in chunk_audio(audio_arr, max_chunk):
         specs = stream_spectrograms(model_settings, chunk, clip, stride)
         heads = [m.head for m in mlist]
-        probs = serve_spectrograms(emb_model, heads, specs, batch_windows, use_graph, graphs_used)
-        for k in range(len(mlist)):
-            outs[k].append(probs[k])
+        chunks.append(serve_spectrograms(emb_model, heads, specs, batch_windows, use_graph, graphs_used))
     if graphs_used:
         # a failed exchange inside a replay leaves NaN rows and no return code: look at the handles once everything has run, and redo
         # the stream on the healed handles (the first run() of the repeat re-captures; a healed handle cannot fail again).  A heal in
@@ -305,8 +307,14 @@ def streaming_inferences(models, model_settings, audio, sample_rate=16000, clip_
                 e.set_option("fuse_cluster", 0)
             _BatchGraph.forget(emb_model)                                       # graphs captured on the old plan
             return streaming_inferences(models, model_settings, audio, sample_rate, clip_duration_ms, clip_stride_ms, batch_windows, max_chunk_length_sec,
-                                        use_graph, _retry=False)
-    res = [torch.cat(o).cpu().numpy() if o else np.zeros((0, 3), np.float32) for o in outs]
+                                        use_graph, _retry=False, as_device=as_device)
+    if as_device:
+        if not chunks:
+            full = torch.zeros((len(mlist), 0, 3), dtype=torch.float32, device=emb_model.device)
+        else:
+            full = chunks[0] if len(chunks) == 1 else torch.cat(chunks, dim=1)
+        return full[0] if single else full
+    res = [torch.cat([c[k] for c in chunks]).cpu().numpy() if chunks else np.zeros((0, 3), np.float32) for k in range(len(mlist))]
     return res[0] if single else res
 
 
@@ -402,6 +410,60 @@ def detect(inferences, flags: StreamFlags, threshold, sample_rate=16000, data_sa
     return found, found_conf
 
 
+def detect_many(inferences, flags: StreamFlags, thresholds, sample_rate=16000, data_samples=None, keywords=None):
+    """detect() for every keyword and every threshold of a stream at once.  inferences: [W, 3] for one keyword, or [N, W, 3] / a list
+    of N [W, 3] for several (numpy arrays or CUDA tensors); keywords: the N target words (default: flags.target_keyword for each).
+    -> {threshold: (found_words, found_words_w_confidences)} for [W, 3] input, a list of N such dicts otherwise, holding exactly the
+    lists detect() builds.  CUDA tensors, and numpy input on a host with a GPU, take ONE device launch for all keywords and thresholds
+    (..detector.detect_on_device); numpy input on a host without a GPU loops over detect().  More inference rows than window offsets
+    are cut to the offsets (chunk_audio as shipped can return more); fewer raise IndexError, as detect() does."""
+    import dataclasses
+    import torch
+    thresholds = list(thresholds)
+    as_list = isinstance(inferences, (list, tuple))
+    on_device = torch.is_tensor(inferences[0] if as_list and len(inferences) else inferences)
+    if as_list:
+        inferences = (torch.stack(list(inferences)) if on_device else np.stack([np.asarray(x) for x in inferences])) if len(inferences) \
+            else np.zeros((0, 0, 3), np.float32)
+    elif not on_device:
+        inferences = np.asarray(inferences)
+    single = not as_list and inferences.ndim == 2
+    if single:
+        inferences = inferences[None]
+    if inferences.ndim != 3:
+        raise ValueError("inferences must be [windows, classes] or [keywords, windows, classes]")
+    N = inferences.shape[0]
+    keywords = [flags.target_keyword] * N if keywords is None else list(keywords)
+    if len(keywords) != N:
+        raise ValueError(f"{len(keywords)} keywords for {N} rows of inferences")
+    clip = int(flags.clip_duration_ms * sample_rate / 1000)
+    stride = int(flags.clip_stride_ms * sample_rate / 1000)
+    offsets = window_offsets(data_samples, clip, stride) if data_samples is not None else [i * stride for i in range(inferences.shape[1])]
+    if inferences.shape[1] < len(offsets):
+        raise IndexError(f"index {inferences.shape[1]} is out of bounds: {inferences.shape[1]} rows of inferences for {len(offsets)} windows")
+    if not on_device and not torch.cuda.is_available():
+        out = [{thr: detect(inferences[n], dataclasses.replace(flags, target_keyword=keywords[n]), thr, sample_rate, data_samples)
+                for thr in thresholds} for n in range(N)]
+        return out[0] if single else out
+    if len(flags.labels()) != inferences.shape[2]:
+        raise ValueError("The results for recognition should contain {} elements, but there are {} produced".format(
+            len(flags.labels()), inferences.shape[2]))
+    from ..detector import detect_on_device
+    t_ms = [int(off * 1000 / sample_rate) for off in offsets]
+    out = [{} for _ in range(N)]
+    if thresholds:
+        res = detect_on_device(inferences[:, :len(offsets)], t_ms, thresholds, flags.average_window_duration_ms, flags.suppression_ms,
+                               flags.minimum_count, target_id=2, fired_only=True)
+        counts = res.counts.tolist()
+        for n in range(N):
+            kw = keywords[n]
+            for k, thr in enumerate(thresholds):
+                ev = res.event_buffer[n, k, :counts[n][k]]
+                times = [t_ms[w] for w in ev["window"].tolist()]
+                out[n][thr] = ([[kw, t] for t in times], [[kw, t, s] for t, s in zip(times, ev["score"].tolist())])
+    return out[0] if single else out
+
+
 def calculate_streaming_accuracy(model, model_settings, flag_list, existing_inferences=None):
     """Reference signature (:50-179): one wav, several StreamFlags; returns (results, inferences) with
     results = [(FLAGS, {threshold: (found_words, found_words_w_confidences)})]."""
@@ -414,13 +476,16 @@ def calculate_streaming_accuracy(model, model_settings, flag_list, existing_infe
         inferences = existing_inferences
     else:
         inferences = streaming_inferences(model, model_settings, audio, sample_rate, flag_list[0].clip_duration_ms,
-                                          flag_list[0].clip_stride_ms, max_chunk_length_sec=flag_list[0].max_chunk_length_sec)
+                                          flag_list[0].clip_stride_ms, max_chunk_length_sec=flag_list[0].max_chunk_length_sec, as_device=True)
+    import torch
+    dev_inferences = inferences                                      # what the detector reads: the device copy where there is a device
+    if torch.is_tensor(inferences):
+        inferences = inferences.cpu().numpy()
+    elif torch.cuda.is_available():
+        dev_inferences = torch.from_numpy(np.ascontiguousarray(inferences)).cuda()
     results = []
-    for FLAGS in flag_list:
-        res_thresh = {}
-        for threshold in FLAGS.detection_thresholds:
-            res_thresh[threshold] = detect(inferences, FLAGS, threshold, sample_rate, data_samples=audio.shape[0])
-        results.append((FLAGS, res_thresh))
+    for FLAGS in flag_list:                                          # all thresholds of a StreamFlags in one launch
+        results.append((FLAGS, detect_many(dev_inferences, FLAGS, FLAGS.detection_thresholds, sample_rate, data_samples=audio.shape[0])))
     return results, inferences
 
 
@@ -477,8 +542,8 @@ def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inf
 
     The reference loads one full Keras model per keyword and repeats the window loop, the micro-frontend and the EfficientNet forward
     for each (one child process per keyword); here `models` (TransferLearnedModels sharing one embedding, transfer_learning.
-    load_models_shared) are N 18.5 k-parameter heads on one embedding pass (streaming_inferences), and each keyword's detector runs over
-    its own head's outputs.  Per keyword the detections are exactly what eval_stream_test yields for StreamFlags(detection_thresholds=
+    load_models_shared) are N 18.5 k-parameter heads on one embedding pass (streaming_inferences), and every keyword's detector runs over
+    its own head's outputs in one launch (detect_many).  Per keyword the detections are exactly what eval_stream_test yields for StreamFlags(detection_thresholds=
     [detection_threshold], average_window_duration_ms=100, suppression_ms=500, max_chunk_length_sec=inference_chunk_len_seconds);
     they are merged and sorted by time (stable, like the reference's sorted()).  -> dict(keywords=..., detections=[dict(keyword, time_ms,
     confidence, groundtruth)], min_threshold=...): groundtruth "ng" without a ground-truth file, otherwise tpr_fpr.get_groundtruth's
@@ -492,21 +557,22 @@ def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inf
     with open(wav, "rb") as f:
         audio, sample_rate = input_data.decode_wav(f.read())
     model_settings = input_data.standard_microspeech_model_settings(label_count=3)
-    per_keyword = [None] * len(models)
+    per_keyword = [None] * len(models)                              # keyword -> its found_words_w_confidences
+    flags = StreamFlags(wav=wav, ground_truth=groundtruth, target_keyword=keywords[0] if keywords else "", detection_thresholds=[detection_threshold],
+                        average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms, time_tolerance_ms=750,
+                        max_chunk_length_sec=inference_chunk_len_seconds)
     by_embedding = {}
     for i, m in enumerate(models):                                  # one pass per distinct embedding (normally one)
         by_embedding.setdefault(id(m.embedding), []).append(i)
     for idxs in by_embedding.values():
         got = streaming_inferences([models[i] for i in idxs], model_settings, audio, sample_rate, 1000, 20,
-                                   max_chunk_length_sec=inference_chunk_len_seconds)
-        for i, inf in zip(idxs, got):
-            per_keyword[i] = inf
+                                   max_chunk_length_sec=inference_chunk_len_seconds, as_device=True)
+        found = detect_many(got, flags, [detection_threshold], sample_rate, data_samples=audio.shape[0], keywords=[keywords[i] for i in idxs])
+        for i, by_threshold in zip(idxs, found):
+            per_keyword[i] = by_threshold[detection_threshold][1]
     unsorted_detections = []
-    for keyword, inferences in zip(keywords, per_keyword):
-        flags = StreamFlags(wav=wav, ground_truth=groundtruth, target_keyword=keyword, detection_thresholds=[detection_threshold],
-                            average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms, time_tolerance_ms=750,
-                            max_chunk_length_sec=inference_chunk_len_seconds)
-        unsorted_detections.extend(detect(inferences, flags, detection_threshold, sample_rate, data_samples=audio.shape[0])[1])
+    for found_conf in per_keyword:
+        unsorted_detections.extend(found_conf)
     detections_with_confidence = sorted(unsorted_detections, key=lambda d: d[1])
     if groundtruth is None:
         detections_with_confidence = [dict(keyword=d[0], time_ms=d[1], confidence=d[2], groundtruth="ng") for d in detections_with_confidence]

@@ -1,6 +1,8 @@
 """Drop-in for multilingual_kws/embedding/single_target_recognize_commands.py: the single-target
-sliding-average detector applied to streaming softmax outputs (reference :54-207).  Host-side, sequential,
-O(windows) scalar work -- it stays on the CPU; the GPU work is the window loop that feeds it."""
+sliding-average detector applied to streaming softmax outputs (reference :54-207).  This class is the host
+restatement of the detector and its specification: the device detector (mkws_detect_stream, ..detector, which
+batch_streaming_analysis.detect_many runs over every keyword and threshold of a stream in one launch) is held to it
+bit for bit, and it is what runs on a host without a GPU and one window at a time."""
 import collections
 
 import numpy as np
