@@ -9,16 +9,32 @@
 // up with 4 consecutive output channels of one row (float4 stores).  The reduction index is permuted (lane group g of chunk j
 // owns k = 16j+4g..+3) and the weights are pre-packed on the host in exactly that order: operands go memory -> registers as
 // float4 without an LDS transpose.  Kernels (DESIGN.md section 4 has the measured numbers):
-//   stem_block1a_kernel   stem conv + whole block 1a, one clip per workgroup            (B >= 1)
-//   mbconv_front_kernel   expand (MFMA) + BN + swish -> LDS -> depthwise + BN + swish, SE sums        (blocks 2a, 2b, 3b; all
-//                         blocks of small-batch handles)
-//   mbconv_back_kernel    SE FCs + gated projection + BN (+ residual) behind the front kernel         (2a, 2b, 3b)
-//   mbconv_mid_kernel     whole block, big images, depthwise output resident in LDS                  (3a, 4a)
-//   mbconv_block_kernel   whole block, 4x3 / 2x2 images, 4 (or 2) clips per workgroup                 (4b .. 6a)
-//   mbconv_pair_kernel    whole block, 2x2 images, two workgroups of one XCD share the clips and split the channels (6b .. 7a)
-//   pw_gemm_kernel        top conv (+ global average pool), dense layers; every 1x1 conv of the unfused / small-batch paths;
-//                         epilogue = BN or bias, activation, SE gate on the input side, residual
-//   se_reduce / se_expand, dw_kernel, stem_kernel, mean_hw_kernel, splitk_reduce_kernel: the unfused chain (parity taps, small batches)
+//   stem_block1a_kernel          stem conv + whole block 1a, a workgroup walks clips
+//   mbconv_front_kernel          expand (MFMA) + BN + swish -> LDS -> depthwise + BN + swish, SE sums
+//   mbconv_back_kernel           SE FCs + gated projection + BN (+ residual) behind the front kernel
+//   mbconv_mid_kernel            whole block, big images (2a .. 4a), depthwise output resident in LDS
+//   mbconv_rows_kernel           whole block 2b / 3b, depthwise output in registers (mkws_embed_rows.hip; option fuse_rows, off)
+//   mbconv_block_kernel          whole block, 4x3 / 2x2 images (4b .. 7a), 4, 2 or 1 clips per workgroup
+//   mbconv_chain_kernel          consecutive 4x3-image blocks in one launch, activations in LDS
+//   mbconv_pair_kernel           whole block, stride-1 2x2 images (6b .. 7a): two workgroups of one XCD share the clips, split the channels
+//   mbconv_pair_chain_kernel     consecutive paired blocks in one launch, optionally + top conv + global average pool
+//   mbconv_cluster_kernel        whole block, 4x3 / 2x2 images: up to 14 workgroups share one 16-row tile and split the channels
+//   mbconv_cluster_chain_kernel  every cluster block of a one-clip forward in one launch
+//   pw_gemm_kernel               top conv (+ pool), dense layers, every 1x1 conv of the unfused path (+ splitk_reduce_kernel when K is split)
+//   gemv_kernel                  the same layers at up to 4 rows (one clip)
+//   stem_kernel, dw_kernel, se_reduce / se_expand_kernel, mean_hw_kernel: the unfused path (parity taps, A/B options)
+// Which of them a forward pass launches is decided per block by route_block() from the handle's options, and those default by handle
+// size at create.  With the defaults, no tap, and the pair probe passed (pair_layout_ok), per block group:
+//   1a            every handle: inside stem_block1a_kernel                                                              1 launch
+//   2a .. 4a      one clip: front + back per block (10); larger: mid for 2b, 3a, 4a, front + back for 2a, 3b             10 / 7
+//   4b .. 6a      one clip: ONE cluster chain launch for 4b .. 7a; up to kClusterMaxBatch (32) clips: a cluster
+//                 launch per block (6); larger: ONE chain launch                                                          1 / 6 / 1
+//   6b .. 7a, top one clip: in the cluster chain above, top conv + pool on gemv (1); up to 32: a cluster launch per block
+//                 + pw_gemm with the pool (5); larger: ONE pair chain launch that ends in the top conv + pool             1 / 5 / 1
+//   dense x 3     up to 4 clips: gemv (3); larger: pw_gemm, + a split-K fold for every layer pick_tile() splits           3 .. 6
+// Launches per forward: one clip 16; 2 .. 4 clips 22; 5 .. 32 clips 25; 33 .. 256 clips 14 at 256 (dense_2 splits K); larger 13 at 1024.
+// Handles of 129 .. 256 clips differ from larger ones in workgroup shape only: one clip per workgroup of 4a's mid kernel and of the chain.
+// Without the probe the pair / cluster kernels fall to mbconv_block_kernel.  tests/golden/embed_launch_sequences.json records the sequences.
 // Streaming loops address their operands as buffer descriptor + per-lane 32-bit offset + SGPR chunk offset (WBuf): VALU and MFMA
 // work serialize on a SIMD of this part, so the MFMA loops contain no VALU instructions.
 #include "mkws_common.h"
@@ -4473,6 +4489,9 @@ struct ProfScope {
   ~ProfScope() { if (g_prof) g_prof->end(); }
 };
 
+// Development-build reporting (`make timing`): timing_arm / timing_report_* / wg_trace_*, empty stubs in the product build
+#include "mkws_embed_timing.h"
+
 // Kernels launched with more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once per
 // (kernel, device): a process-wide flag would leave the second GPU of a multi-device process at the default.
 int ensure_dynamic_lds(const void* fn, int bytes) {
@@ -4485,6 +4504,15 @@ int ensure_dynamic_lds(const void* fn, int bytes) {
   const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e != hipSuccess) return fail(MKWS_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed: %s", bytes, hipGetErrorString(e));
   done.insert({fn, dev});
+  return MKWS_OK;
+}
+
+// One launch of a kernel that takes its arguments as one struct and may need more than 64 KB of dynamic LDS (limit raised to `lds_cap`).
+// A launcher's ladder picks the instantiation; this is the only place that raises the limit and launches it.
+template <class Args>
+int launch_big_lds(void (*kernel)(Args), int lds_cap, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args& a) {
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_cap)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, a);
   return MKWS_OK;
 }
 
@@ -4533,6 +4561,36 @@ GemmOff pack_gemm(Packer& pk, const float* W, int K, int N, const std::vector<fl
   for (int i = 0; i < N; ++i) { sc[i] = scale[i]; sh[i] = shift[i]; }
   o.scale = pk.add(sc.data(), Np);
   o.shift = pk.add(sh.data(), Np);
+  return o;
+}
+
+// 4x4x1-instruction packing of both squeeze-excite FCs of a 4x3-image block (Se4 in the kernel section: lane l of instruction 4 q + e reads
+// float e of dwordx4 (q, l)).  wr: Keras [C][se], we: [se][C].  Reduce: wave w, half kh = l / 32, unit l % 32; channel w cpw + t (half 0,
+// t < cpw - T0) or w cpw + cpw - T0 + t (half 1).  Expand: group of 64 channels, channel 64 group + l, unit 4 q + e.  Zero where a channel /
+// unit does not exist, and zero padded to the kernels' fixed step counts.  T0 == 0 in the result: the block does not fit the packing.
+struct Se4Off { size_t r = 0, e = 0; int T0 = 0, NQ = 0; };
+Se4Off pack_se4(Packer& pk, const float* wr, const float* we, int ce, int se, int waves) {
+  Se4Off o;
+  const int cpw = ce / waves, T0 = 4 * ((cpw + 7) / 8), NQ = (se + 3) / 4, NG = (ce + 63) / 64;
+  if (ce % (4 * waves) != 0 || se > 32 || T0 / 4 > kSe4MaxTQ || NQ > kSe4MaxNQ || NG > kSe4MaxGroups * waves ||
+      waves * 4 * 32 > 4 * ce) return o;      // (the wave partials [8][G][32] live where the gate used to: G * Cexp floats)
+  std::vector<float> qr((size_t)waves * kSe4MaxTQ * 256, 0.0f), qe((size_t)NG * kSe4MaxNQ * 256, 0.0f);
+  for (int w = 0; w < waves; ++w)
+    for (int t = 0; t < T0; ++t)
+      for (int l = 0; l < 64; ++l) {
+        const int kh = l / 32, n = l % 32;
+        const int ch = w * cpw + (kh ? cpw - T0 + t : t);
+        const bool ok = n < se && (kh || t < cpw - T0);
+        qr[(((size_t)w * kSe4MaxTQ + t / 4) * 64 + l) * 4 + t % 4] = ok ? wr[(size_t)ch * se + n] : 0.0f;
+      }
+  for (int gq = 0; gq < NG; ++gq)
+    for (int n = 0; n < 4 * NQ; ++n)
+      for (int l = 0; l < 64; ++l) {
+        const int ch = 64 * gq + l;
+        qe[(((size_t)gq * kSe4MaxNQ + n / 4) * 64 + l) * 4 + n % 4] = (n < se && ch < ce) ? we[(size_t)n * ce + ch] : 0.0f;
+      }
+  o.r = pk.add(qr.data(), qr.size()); o.e = pk.add(qe.data(), qe.size());
+  o.T0 = T0; o.NQ = NQ;
   return o;
 }
 
@@ -4602,7 +4660,7 @@ TileChoice pick_tile(int M, int NTtot, int KC) {
 
 void launch_gemm(hipStream_t s, const SplitWs& sw, const char* stage, const GemmLayer& L, const float* X, int ldx, int M, int Mplan, int act, const float* gate, int HW,
                  const float* R, int ldr, float* Y, int ldy, int pool4 = 0) {
-  GemmArgs a;
+  GemmArgs a = {};
   a.pool4 = pool4;
   a.poison = sw.poison;
   a.X = X; a.ldx = ldx; a.Wp = L.Wp; a.scale = L.scale; a.shift = L.shift; a.gate = gate; a.HW = HW > 0 ? HW : 1;
@@ -4611,9 +4669,6 @@ void launch_gemm(hipStream_t s, const SplitWs& sw, const char* stage, const Gemm
   // size of a handle takes the same path)
   if (sw.gemv && Mplan <= 4 && !gate && !R && L.KC <= 128 && L.NTtot >= 32 && L.K % 4 == 0 && (!pool4 || (Mplan == 4 && M == 4))) {
     a.splitk = 1; a.part = nullptr; a.ldp = 0;
-#ifdef MKWS_FRONT_TIMING
-    a.dbg_clk = nullptr;
-#endif
     const int rows = Mplan <= 1 ? 1 : 4, nj = (L.KC + 15) / 16;
     ProfScope ps(stage, std::string("gemv_kernel<") + std::to_string(rows) + "," + std::to_string(nj <= 2 ? 2 : nj <= 5 ? 5 : 8) + ">");
     const dim3 grid(L.NTtot), block(1024);     // (two / four workgroups per tile, by columns, so that every CU streams: measured, no faster -- a launch of this size is ~6 us whatever it does)
@@ -4642,27 +4697,13 @@ void launch_gemm(hipStream_t s, const SplitWs& sw, const char* stage, const Gemm
     else a.part = sw.p;
   }
   dim3 grid((M + 64 * MT - 1) / (64 * MT), (L.NTtot + NT - 1) / NT, a.splitk);
-#ifdef MKWS_FRONT_TIMING
-  static unsigned long long* d_gc = nullptr;
-  if (!d_gc) (void)hipMalloc(&d_gc, sizeof(unsigned long long) * 2 * 65536);
-  a.dbg_clk = (grid.x * grid.y <= 65536 && a.splitk == 1) ? d_gc : nullptr;
-#endif
+  timing_arm(a, grid);
   {
     ProfScope ps(stage, std::string("pw_gemm_kernel<") + std::to_string(MT) + "," + std::to_string(NT) + (gate ? ",true>" : ",false>"));
     if (MT == 2) { if (gate) launch_gemm_nt<2, true>(NT, grid, s, a); else launch_gemm_nt<2, false>(NT, grid, s, a); }
     else { if (gate) launch_gemm_nt<1, true>(NT, grid, s, a); else launch_gemm_nt<1, false>(NT, grid, s, a); }
   }
-#ifdef MKWS_FRONT_TIMING
-  if (a.dbg_clk) {
-    (void)hipStreamSynchronize(s);
-    const size_t nb = (size_t)grid.x * grid.y;
-    std::vector<unsigned long long> h(2 * nb);
-    (void)hipMemcpy(h.data(), d_gc, sizeof(unsigned long long) * 2 * nb, hipMemcpyDeviceToHost);
-    double mhz = 0, us = 0;
-    for (size_t i = 0; i < nb; ++i) { mhz += (double)h[2 * i] / ((double)h[2 * i + 1] / 100.0); us += (double)h[2 * i + 1] / 100.0; }
-    fprintf(stderr, "[gemm-timing] %s <%d,%d>: %zu workgroups, K loop of wave 0: %.2f us mean, shader clock %.0f MHz\n", stage, MT, NT, nb, us / nb, mhz / nb);
-  }
-#endif
+  timing_report_gemm(s, stage, MT, NT, grid, a);
   if (a.splitk > 1) {
     ProfScope ps(std::string(stage) + "#reduce", "splitk_reduce_kernel");
     const long total = (long)M * (L.N / 4);
@@ -4702,77 +4743,8 @@ bool front_supported(const BlockPlan& b) {
   return false;
 }
 
-#ifdef MKWS_FRONT_TIMING
-// timing build: per-CU timeline of the last launch from the (start, end, CU) triples the workgroups left (wg_trace_begin / _end)
-static unsigned long long* wg_trace_buffer() {
-  static unsigned long long* d = nullptr;
-  if (!d) {
-    (void)hipMalloc(&d, sizeof(unsigned long long) * (3 + 8) * 131072);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wgtrace), &d, sizeof(d));
-    const char* ab = getenv("MKWS_ABLATE");
-    const int abv = ab ? atoi(ab) : 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &abv, sizeof(abv));
-  }
-  return d;
-}
-static void wg_trace_report(hipStream_t s, const char* stage, const char* kernel, size_t nblk) {
-  (void)hipStreamSynchronize(s);
-  std::vector<unsigned long long> h(nblk * 3);
-  (void)hipMemcpy(h.data(), wg_trace_buffer(), h.size() * 8, hipMemcpyDeviceToHost);
-  std::map<unsigned, std::vector<std::pair<unsigned long long, unsigned long long>>> cu;
-  unsigned long long t0 = ~0ull, t1 = 0; double dur = 0;
-  for (size_t i = 0; i < nblk; ++i) {
-    cu[(unsigned)h[3 * i + 2]].push_back({h[3 * i], h[3 * i + 1]});
-    if (h[3 * i] < t0) t0 = h[3 * i];
-    if (h[3 * i + 1] > t1) t1 = h[3 * i + 1];
-    dur += (double)(h[3 * i + 1] - h[3 * i]);
-  }
-  // per CU: peak number of resident workgroups, time with >= 1 resident, slot time = peak x (last end - first start)
-  size_t wmin = ~(size_t)0, wmax = 0; int peak_all = 0; double busy1 = 0, first = 0, last = 0, gap = 0; size_t ngap = 0;
-  for (auto& kv : cu) {
-    auto& v = kv.second;
-    if (v.size() < wmin) wmin = v.size();
-    if (v.size() > wmax) wmax = v.size();
-    std::vector<std::pair<unsigned long long, int>> ev;
-    for (auto& w : v) { ev.push_back({w.first, +1}); ev.push_back({w.second, -1}); }
-    std::sort(ev.begin(), ev.end());
-    int cur = 0, peak = 0; unsigned long long prev = ev[0].first; double b1 = 0;
-    for (auto& e : ev) { if (cur > 0) b1 += (double)(e.first - prev); prev = e.first; cur += e.second; if (cur > peak) peak = cur; }
-    if (peak > peak_all) peak_all = peak;
-    busy1 += b1;
-    first += (double)(ev.front().first - t0); last += (double)(t1 - ev.back().first);
-    // gap between a workgroup's end and the next start on the same CU (slots paired greedily in time order)
-    std::sort(v.begin(), v.end());
-    std::vector<unsigned long long> ends;
-    for (auto& w : v) {
-      size_t best = ends.size();
-      for (size_t k = 0; k < ends.size(); ++k) if (ends[k] <= w.first && (best == ends.size() || ends[k] > ends[best])) best = k;
-      if (best == ends.size()) ends.push_back(w.second);
-      else { gap += (double)(w.first - ends[best]); ++ngap; ends[best] = w.second; }
-    }
-  }
-  const double span = (double)(t1 - t0), ncu = (double)cu.size();
-  fprintf(stderr, "[wg-trace] %s %s: %zu workgroups on %zu CUs (%zu-%zu per CU, peak %d resident); mean workgroup %.2f us; span %.2f us; "
-                  "mean residency %.2f; CU busy (>=1 resident) %.2f of span; first start +%.2f us, last end -%.2f us; slot gap %.2f us (n %zu)\n",
-          stage, kernel, nblk, cu.size(), wmin, wmax, peak_all, dur / nblk / 100.0, span / 100.0, dur / (ncu * span), busy1 / (ncu * span),
-          first / ncu / 100.0, last / ncu / 100.0, ngap ? gap / ngap / 100.0 : 0.0, ngap);
-}
-static void wg_phase_report(const char* stage, size_t nblk, int nph) {
-  std::vector<unsigned long long> h(nblk * 8);
-  (void)hipMemcpy(h.data(), wg_trace_buffer() + 3 * 131072, h.size() * 8, hipMemcpyDeviceToHost);
-  fprintf(stderr, "[wg-phase] %s: shader-clock cycles per workgroup (mean):", stage);
-  for (int k = 0; k < nph; ++k) { double t = 0; for (size_t i = 0; i < nblk; ++i) t += (double)h[8 * i + k]; fprintf(stderr, " %d: %.0f", k, t / nblk); }
-  fprintf(stderr, "\n");
-}
-#define MKWS_WG_TRACE_ARM() (void)wg_trace_buffer()
-#define MKWS_WG_TRACE_REPORT(s, stage, kernel, nblk) wg_trace_report(s, stage, kernel, nblk)
-#else
-#define MKWS_WG_TRACE_ARM()
-#define MKWS_WG_TRACE_REPORT(s, stage, kernel, nblk)
-#endif
-
 void launch_front(hipStream_t s, const char* stage, const BlockPlan& b, const float* X, float* Y, float* sums, int B, int walk) {
-  FrontArgs a;
+  FrontArgs a = {};
   a.X = X; a.Cin = b.spec.in_ch; a.WpE = b.expand.Wp; a.scE = b.expand.scale; a.shE = b.expand.shift; a.KC = b.expand.KC;
   a.NTtotE = b.expand.NTtot;
   a.Wd = b.dw.Wd; a.scD = b.dw.scale; a.shD = b.dw.shift; a.Y = Y; a.sums = sums;
@@ -4796,13 +4768,9 @@ void launch_front(hipStream_t s, const char* stage, const BlockPlan& b, const fl
   const dim3 grid((B + G - 1) / G, nblk_c / a.ncb);
   ProfScope ps(stage, std::string("mbconv_front_kernel<") + std::to_string(ks) + "," + std::to_string(st) + "," + std::to_string(CC) + "," +
                           (tiny ? "0," : std::to_string(kc) + ",") + std::to_string(b.H) + "," + std::to_string(b.W) + ">");
-#ifdef MKWS_FRONT_TIMING
-  static unsigned long long* d_t = nullptr;
   const size_t nblk = (size_t)grid.x * grid.y;
-  if (!d_t) (void)hipMalloc(&d_t, sizeof(unsigned long long) * 4 * 65536);
-  a.dbg_t = d_t;
-#endif
-  MKWS_WG_TRACE_ARM();
+  timing_arm(a);
+  wg_trace_arm();
 #define MKWS_FRONT(KS, S, C_, KC_, H_, W_) \
   hipLaunchKernelGGL((mbconv_front_kernel<KS, S, C_, KC_, H_, W_>), grid, dim3((KC_) > 0 ? 256 : 512), lds, s, a)
   if (!tiny) {
@@ -4820,49 +4788,9 @@ void launch_front(hipStream_t s, const char* stage, const BlockPlan& b, const fl
     else if (ks == 3 && st == 1) MKWS_FRONT(3, 1, 128, 0, 2, 2);             // 7a
   }
 #undef MKWS_FRONT
-#ifdef MKWS_FRONT_TIMING
-  {
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h(nblk * 4);
-    (void)hipMemcpy(h.data(), d_t, h.size() * 8, hipMemcpyDeviceToHost);
-    double p1 = 0, bar = 0, p2 = 0; unsigned long long t0 = ~0ull, t1 = 0;
-    for (size_t i = 0; i < nblk; ++i) {
-      p1 += (double)(h[4 * i + 1] - h[4 * i]); bar += (double)(h[4 * i + 2] - h[4 * i + 1]); p2 += (double)(h[4 * i + 3] - h[4 * i + 2]);
-      if (h[4 * i] < t0) t0 = h[4 * i];
-      if (h[4 * i + 3] > t1) t1 = h[4 * i + 3];
-    }
-    // wall_clock64 ticks at 100 MHz
-    fprintf(stderr, "[front-timing] %s ks%d s%d blocks %zu: phase1 %.2f us  barrier %.2f us  phase2 %.2f us  kernel span %.2f us\n", stage, ks, st, nblk,
-            p1 / nblk / 100.0, bar / nblk / 100.0, p2 / nblk / 100.0, (double)(t1 - t0) / 100.0);
-  }
-  MKWS_WG_TRACE_REPORT(s, stage, "front", nblk);
-#endif
+  timing_report_front(s, stage, ks, st, nblk);
+  wg_trace_report(s, stage, "front", nblk);
 }
-
-#ifdef MKWS_FRONT_TIMING
-// timing build: per-phase means of the wall_clock64 stamps the whole-block kernels leave (8 per workgroup)
-static unsigned long long* block_timing_buffer() {
-  static unsigned long long* d_bt = nullptr;
-  if (!d_bt) (void)hipMalloc(&d_bt, sizeof(unsigned long long) * 8 * 4096);
-  return d_bt;
-}
-static void report_block_timing(hipStream_t s, const char* stage, unsigned nblk, const unsigned long long* d_bt) {
-  (void)hipStreamSynchronize(s);
-  std::vector<unsigned long long> h((size_t)nblk * 8);
-  (void)hipMemcpy(h.data(), d_bt, h.size() * 8, hipMemcpyDeviceToHost);
-  double ph[6] = {0, 0, 0, 0, 0, 0}; unsigned long long t0 = ~0ull, t1 = 0;
-  for (size_t i = 0; i < nblk; ++i) {
-    for (int k = 0; k < 6; ++k) ph[k] += (double)(h[8 * i + k + 1] - h[8 * i + k]);
-    if (h[8 * i] < t0) t0 = h[8 * i];
-    if (h[8 * i + 6] > t1) t1 = h[8 * i + 6];
-  }
-  double clk = 0; for (size_t i = 0; i < nblk; ++i) clk += (double)h[8 * i + 7] / ((double)(h[8 * i + 6] - h[8 * i]) / 100.0);
-  fprintf(stderr, "[block-timing] shader clock %.0f MHz\n", clk / nblk);
-  fprintf(stderr, "[block-timing] %s blocks %u: stage %.2f  A %.2f  B %.2f  C1 %.2f  C2 %.2f  D %.2f us; span %.2f us\n", stage, nblk,
-          ph[0] / nblk / 100.0, ph[1] / nblk / 100.0, ph[2] / nblk / 100.0, ph[3] / nblk / 100.0, ph[4] / nblk / 100.0,
-          ph[5] / nblk / 100.0, (double)(t1 - t0) / 100.0);
-}
-#endif
 
 // Whole-block kernel for 4x3 / 2x2 images (blocks 4b..7a): 4 clips per workgroup either way.
 static constexpr int kBlockWaves = 8;
@@ -4881,68 +4809,61 @@ bool block_supported(const BlockPlan& b, int mode) {
   return (ks == 5 && st == 1) || (ks == 3 && st == 1);
 }
 
-int launch_block(hipStream_t s, const char* stage, const BlockPlan& b, int mt43, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B, bool se4 = true) {
+// The constants of one block as the whole-block kernels (block, pair, cluster, and the chain kernels through the device table) read them.
+// Everything else is zero: a launcher sets X, Y, B and the debug pointers, and clears WrQ where the 4x4x1 squeeze-excite is switched off.
+static BlockArgs block_args(const BlockPlan& b) {
   BlockArgs a;
-  a.X = X; a.Cin = b.spec.in_ch;
+  memset(static_cast<void*>(&a), 0, sizeof(a));
+  a.Cin = b.spec.in_ch;
   a.WpE = b.expand.Wp; a.scE = b.expand.scale; a.shE = b.expand.shift; a.KCe = b.expand.KC; a.NTe = b.expand.NTtot;
   a.Wd = b.dw.Wd; a.scD = b.dw.scale; a.shD = b.dw.shift;
   a.WrP = b.se.WrP; a.br = b.se.br; a.NTR = b.se.NTR; a.We2P = b.se.WeP; a.be = b.se.be;
   a.WpP = b.project.Wp; a.scP = b.project.scale; a.shP = b.project.shift; a.NTp = b.project.NTtot;
-  a.Y = Y; a.Cout = b.spec.out_ch; a.residual = b.residual ? 1 : 0;
-  a.dbg_dw = dbg_dw; a.dbg_gate = dbg_gate;
-  a.B = B; a.Cexp = b.ce; a.se = b.se.se;
-  a.WrQ = se4 ? b.se.WrQ : nullptr; a.We2Q = b.se.WeQ; a.seT0 = b.se.T0; a.seNQ = b.se.NQ;
+  a.Cout = b.spec.out_ch; a.residual = b.residual ? 1 : 0;
+  a.Cexp = b.ce; a.se = b.se.se;
+  a.WrQ = b.se.WrQ; a.We2Q = b.se.WeQ; a.seT0 = b.se.T0; a.seNQ = b.se.NQ;
+  return a;
+}
+// ... with the pointers of one launch
+static BlockArgs block_args(const BlockPlan& b, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
+  BlockArgs a = block_args(b);
+  a.X = X; a.Y = Y; a.dbg_dw = dbg_dw; a.dbg_gate = dbg_gate; a.B = B;
+  return a;
+}
+
+int launch_block(hipStream_t s, const char* stage, const BlockPlan& b, int mt43, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B, bool se4 = true) {
+  BlockArgs a = block_args(b, X, Y, dbg_dw, dbg_gate, B);
+  if (!se4) a.WrQ = nullptr;
   const int HW = b.H * b.W, MT = block_row_tiles(b, mt43), G = MT * 16 / HW;
   const size_t lds = block_lds_bytes(b, mt43);
   const dim3 grid((B + G - 1) / G);
   const int ks = b.spec.kernel, st = b.spec.stride;
-#ifdef MKWS_FRONT_TIMING
-  unsigned long long* d_bt = block_timing_buffer();
-  a.dbg_t = d_bt;
-#endif
   ProfScope ps(stage, std::string("mbconv_block_kernel<") + std::to_string(ks) + "," + std::to_string(st) + "," + std::to_string(b.H) + "," +
                           std::to_string(b.W) + "," + std::to_string(MT) + "," + std::to_string(kBlockWaves) + ">");
-#define MKWS_BLOCK(KS, S, H_, W_, MT_) do { \
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_block_kernel<KS, S, H_, W_, MT_, kBlockWaves>), 160 * 1024)) return rc_; \
-    hipLaunchKernelGGL((mbconv_block_kernel<KS, S, H_, W_, MT_, kBlockWaves>), grid, dim3(kBlockWaves * 64), lds, s, a); } while (0)
+  void (*k)(BlockArgs);
   if (b.H == 4 && b.W == 3 && MT == 3) {
-    if (ks == 3 && st == 1) MKWS_BLOCK(3, 1, 4, 3, 3);
-    else if (ks == 5 && st == 1) MKWS_BLOCK(5, 1, 4, 3, 3);
-    else MKWS_BLOCK(5, 2, 4, 3, 3);
+    if (ks == 3 && st == 1) k = &mbconv_block_kernel<3, 1, 4, 3, 3, kBlockWaves>;
+    else if (ks == 5 && st == 1) k = &mbconv_block_kernel<5, 1, 4, 3, 3, kBlockWaves>;
+    else k = &mbconv_block_kernel<5, 2, 4, 3, 3, kBlockWaves>;
   } else if (b.H == 4 && b.W == 3 && MT == 2) {
-    if (ks == 3 && st == 1) MKWS_BLOCK(3, 1, 4, 3, 2);
-    else if (ks == 5 && st == 1) MKWS_BLOCK(5, 1, 4, 3, 2);
-    else MKWS_BLOCK(5, 2, 4, 3, 2);
+    if (ks == 3 && st == 1) k = &mbconv_block_kernel<3, 1, 4, 3, 2, kBlockWaves>;
+    else if (ks == 5 && st == 1) k = &mbconv_block_kernel<5, 1, 4, 3, 2, kBlockWaves>;
+    else k = &mbconv_block_kernel<5, 2, 4, 3, 2, kBlockWaves>;
   } else if (b.H == 4 && b.W == 3) {                     // one clip per workgroup (handles of <= 256 clips: a workgroup for every CU)
-    if (ks == 3 && st == 1) MKWS_BLOCK(3, 1, 4, 3, 1);
-    else if (ks == 5 && st == 1) MKWS_BLOCK(5, 1, 4, 3, 1);
-    else MKWS_BLOCK(5, 2, 4, 3, 1);
+    if (ks == 3 && st == 1) k = &mbconv_block_kernel<3, 1, 4, 3, 1, kBlockWaves>;
+    else if (ks == 5 && st == 1) k = &mbconv_block_kernel<5, 1, 4, 3, 1, kBlockWaves>;
+    else k = &mbconv_block_kernel<5, 2, 4, 3, 1, kBlockWaves>;
   } else {
-    if (ks == 5) MKWS_BLOCK(5, 1, 2, 2, 1);
-    else MKWS_BLOCK(3, 1, 2, 2, 1);
+    if (ks == 5) k = &mbconv_block_kernel<5, 1, 2, 2, 1, kBlockWaves>;
+    else k = &mbconv_block_kernel<3, 1, 2, 2, 1, kBlockWaves>;
   }
-#undef MKWS_BLOCK
-#ifdef MKWS_FRONT_TIMING
-  report_block_timing(s, stage, grid.x, d_bt);
-#endif
+  timing_arm(a);
+  if (int rc = launch_big_lds(k, 160 * 1024, grid, dim3(kBlockWaves * 64), lds, s, a)) return rc;
+  timing_report_block(s, stage, grid.x);
   return MKWS_OK;
 }
 
 // Depth-fused chain (mbconv_chain_kernel): consecutive 4x3-image blocks [i0, i1] of the plan in one launch.
-static void fill_block_args(BlockArgs& a, const BlockPlan& b, int B) {
-  a.X = nullptr; a.Cin = b.spec.in_ch;
-  a.WpE = b.expand.Wp; a.scE = b.expand.scale; a.shE = b.expand.shift; a.KCe = b.expand.KC; a.NTe = b.expand.NTtot;
-  a.Wd = b.dw.Wd; a.scD = b.dw.scale; a.shD = b.dw.shift;
-  a.WrP = b.se.WrP; a.br = b.se.br; a.NTR = b.se.NTR; a.We2P = b.se.WeP; a.be = b.se.be;
-  a.WpP = b.project.Wp; a.scP = b.project.scale; a.shP = b.project.shift; a.NTp = b.project.NTtot;
-  a.Y = nullptr; a.Cout = b.spec.out_ch; a.residual = b.residual ? 1 : 0;
-  a.dbg_dw = nullptr; a.dbg_gate = nullptr;
-  a.B = B; a.Cexp = b.ce; a.se = b.se.se;
-  a.WrQ = b.se.WrQ; a.We2Q = b.se.WeQ; a.seT0 = b.se.T0; a.seNQ = b.se.NQ;
-#ifdef MKWS_FRONT_TIMING
-  a.dbg_t = nullptr;
-#endif
-}
 // May block i+1 follow block i inside one chain launch?  (The chain keeps activations in LDS and the residual in registers.)
 static bool chain_link_ok(const BlockPlan& b, const BlockPlan& next) {
   if (b.spec.stride != 1) return false;                                  // a stride-2 block ends the chain (the image shrinks)
@@ -4952,14 +4873,15 @@ static bool chain_link_ok(const BlockPlan& b, const BlockPlan& next) {
 }
 bool cluster_supported(const BlockPlan& b);
 bool pair_supported(const BlockPlan& b);
+// Does this handle run block b on the cluster kernel?  (Its blocks are members of no other chain.)
+static bool cluster_enabled(const mkws_embed* em, const BlockPlan& b) { return em->fuse_cluster && cluster_supported(b) && em->cl_flags; }
 static bool chain_member(const mkws_embed* em, const BlockPlan& b) {
   if (!(em->fuse_chain == 1 || em->fuse_chain == 2) || !em->fuse_block || !block_supported(b, em->fuse_block)) return false;
   if (!(b.H == 4 && b.W == 3)) return false;
-  if (em->fuse_cluster && cluster_supported(b) && em->cl_flags) return false;
-  return true;
+  return !cluster_enabled(em, b);
 }
 int launch_chain(hipStream_t s, const mkws_embed* em, int i0, int i1, const float* X, float* Y, int B) {
-  ChainArgs ca;
+  ChainArgs ca = {};
   const int n = i1 - i0 + 1, mt43 = em->block_mt43;
   if (!em->d_chain_tab) return fail(MKWS_ERR_UNSUPPORTED, "chain: no block table");
   ca.tab = em->d_chain_tab; ca.i0 = i0; ca.n = n; ca.kinds = 0; ca.ldsU = ca.ldsE = 0;
@@ -4981,57 +4903,19 @@ int launch_chain(hipStream_t s, const mkws_embed* em, int i0, int i1, const floa
   const int G = mt43 * 16 / 12;
   const dim3 grid((B + G - 1) / G);
   ProfScope ps("chain:" + names, std::string("mbconv_chain_kernel<") + std::to_string(mt43) + "," + std::to_string(kBlockWaves) + ">");
-#ifdef MKWS_FRONT_TIMING
-  static unsigned long long* d_ct = nullptr;
-  const size_t nstamp = (size_t)grid.x * kChainMax * 8 + grid.x;
-  if (!d_ct) (void)hipMalloc(&d_ct, sizeof(unsigned long long) * (4096 * kChainMax * 8 + 4096));
-  ca.dbg_t = (grid.x <= 4096) ? d_ct : nullptr;
-#endif
-  if (mt43 == 3) {
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_chain_kernel<3, kBlockWaves>), 160 * 1024)) return rc_;
-    hipLaunchKernelGGL((mbconv_chain_kernel<3, kBlockWaves>), grid, dim3(kBlockWaves * 64), lds, s, ca);
-  } else if (mt43 == 2) {
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_chain_kernel<2, kBlockWaves>), 160 * 1024)) return rc_;
-    hipLaunchKernelGGL((mbconv_chain_kernel<2, kBlockWaves>), grid, dim3(kBlockWaves * 64), lds, s, ca);
-  } else {
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_chain_kernel<1, kBlockWaves>), 160 * 1024)) return rc_;
-    hipLaunchKernelGGL((mbconv_chain_kernel<1, kBlockWaves>), grid, dim3(kBlockWaves * 64), lds, s, ca);
-  }
-#ifdef MKWS_FRONT_TIMING
-  if (ca.dbg_t) {
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h(nstamp);
-    (void)hipMemcpy(h.data(), d_ct, nstamp * 8, hipMemcpyDeviceToHost);
-    unsigned long long t0 = ~0ull, t1 = 0;
-    for (unsigned w = 0; w < grid.x; ++w) {
-      t0 = std::min(t0, h[(size_t)grid.x * kChainMax * 8 + w]);
-      t1 = std::max(t1, h[((size_t)w * kChainMax + (n - 1)) * 8 + 6]);
-    }
-    double pro = 0;
-    for (unsigned w = 0; w < grid.x; ++w) pro += (double)(h[((size_t)w * kChainMax) * 8 + 7] - h[(size_t)grid.x * kChainMax * 8 + w]);
-    fprintf(stderr, "[chain-timing] %s: %u workgroups, span %.2f us, prologue %.2f us\n", names.c_str(), grid.x, (double)(t1 - t0) / 100.0, pro / grid.x / 100.0);
-    for (int k = 0; k < n; ++k) {
-      double ph[7] = {0, 0, 0, 0, 0, 0, 0};
-      unsigned long long e_min = ~0ull, e_max = 0;
-      for (unsigned w = 0; w < grid.x; ++w) {
-        const unsigned long long* q = &h[((size_t)w * kChainMax + k) * 8];
-        ph[0] += (double)(q[0] - q[7]);
-        for (int j = 0; j < 6; ++j) ph[j + 1] += (double)(q[j + 1] - q[j]);
-        e_min = std::min(e_min, q[6]); e_max = std::max(e_max, q[6]);
-      }
-      fprintf(stderr, "[chain-timing]   %s: args %.2f  A %.2f  B %.2f  C1 %.2f  C2 %.2f  gate %.2f  D %.2f us; end skew %.2f us\n", em->blocks[i0 + k].spec.name,
-              ph[0] / grid.x / 100.0, ph[1] / grid.x / 100.0, ph[2] / grid.x / 100.0, ph[3] / grid.x / 100.0, ph[4] / grid.x / 100.0, ph[5] / grid.x / 100.0,
-              ph[6] / grid.x / 100.0, (double)(e_max - e_min) / 100.0);
-    }
-  }
-#endif
+  void (*k)(ChainArgs);
+  if (mt43 == 3) k = &mbconv_chain_kernel<3, kBlockWaves>;
+  else if (mt43 == 2) k = &mbconv_chain_kernel<2, kBlockWaves>;
+  else k = &mbconv_chain_kernel<1, kBlockWaves>;
+  timing_arm(ca, grid.x);
+  if (int rc = launch_big_lds(k, 160 * 1024, grid, dim3(kBlockWaves * 64), lds, s, ca)) return rc;
+  timing_report_chain(s, em->blocks + i0, n, names, grid.x, ca);
   return MKWS_OK;
 }
 
 // Paired whole-block kernel (mbconv_pair_kernel): the stride-1 2x2-image blocks (6b, 6c, 6d, 7a).
 struct PairWs { float* xc1 = nullptr; float* xd = nullptr; int* flags = nullptr; int* err_dev = nullptr; int* err_host = nullptr; int fault = 0; int mt = 2; };
 static int pair_count(int B, int mt) { const int G = 4 * mt; return ((B + G - 1) / G + 7) / 8 * 8; }   // padded to whole groups of 8 pairs (16 workgroups)
-static size_t pair_ws_floats(int max_batch, int mt) { return (size_t)pair_count(max_batch, mt) * (2 * kPairXc1 + 2 * kPairXdAll * 2 * 256 + 4 + 4 * kPairChainMax); }   // exchange buffers (sized for the chain's all-tiles exchange) + flags of both kernels
 // Row tiles per pair for a handle: 8 clips per pair fill the chip from ~1024 clips up; smaller handles use 4-clip pairs so
 // that twice as many workgroups exist (512 clips: 256 instead of 128).  Per handle, like every other plan decision.
 // Row tiles per workgroup of the 4x3-image whole-block / chain kernels: 3 (4 clips), 2 (2 clips) or 1 (1 clip) -- the largest that still gives
@@ -5078,42 +4962,27 @@ bool pair_supported(const BlockPlan& b) {
 }
 
 int launch_pair(hipStream_t s, const char* stage, const BlockPlan& b, const PairWs& ws, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
-  PairArgs pa;
-  BlockArgs& a = pa.b;
-  a.X = X; a.Cin = b.spec.in_ch;
-  a.WpE = b.expand.Wp; a.scE = b.expand.scale; a.shE = b.expand.shift; a.KCe = b.expand.KC; a.NTe = b.expand.NTtot;
-  a.Wd = b.dw.Wd; a.scD = b.dw.scale; a.shD = b.dw.shift;
-  a.WrP = b.se.WrP; a.br = b.se.br; a.NTR = b.se.NTR; a.We2P = b.se.WeP; a.be = b.se.be;
-  a.WpP = b.project.Wp; a.scP = b.project.scale; a.shP = b.project.shift; a.NTp = b.project.NTtot;
-  a.Y = Y; a.Cout = b.spec.out_ch; a.residual = b.residual ? 1 : 0;
-  a.dbg_dw = dbg_dw; a.dbg_gate = dbg_gate;
-  a.B = B; a.Cexp = b.ce; a.se = b.se.se;
+  PairArgs pa = {};
+  pa.b = block_args(b, X, Y, dbg_dw, dbg_gate, B);
   pa.xc1 = ws.xc1; pa.xd = ws.xd; pa.flags = ws.flags; pa.err_dev = ws.err_dev; pa.err_host = ws.err_host; pa.fault = ws.fault;
   const PairLds L = pair_lds(b.expand.KC, b.ce / 2, ws.mt);
   const size_t lds = ((size_t)L.U + L.E + L.Z) * sizeof(float);
   const dim3 grid(2 * pair_count(B, ws.mt));
   const int ks = b.spec.kernel;
-#ifdef MKWS_FRONT_TIMING
-  unsigned long long* d_bt = block_timing_buffer();
-  a.dbg_t = d_bt;
-#endif
   ProfScope ps(stage, std::string("mbconv_pair_kernel<") + std::to_string(ks) + "," + std::to_string(ws.mt) + "," + std::to_string(kBlockWaves) + ">");
-#define MKWS_PAIR(KS, MT_) do { \
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_pair_kernel<KS, MT_, kBlockWaves>), 160 * 1024)) return rc_; \
-    hipLaunchKernelGGL((mbconv_pair_kernel<KS, MT_, kBlockWaves>), grid, dim3(kBlockWaves * 64), lds, s, pa); } while (0)
-  if (ks == 5) { if (ws.mt == 2) MKWS_PAIR(5, 2); else MKWS_PAIR(5, 1); }
-  else         { if (ws.mt == 2) MKWS_PAIR(3, 2); else MKWS_PAIR(3, 1); }
-#undef MKWS_PAIR
-#ifdef MKWS_FRONT_TIMING
-  report_block_timing(s, stage, grid.x, d_bt);
-#endif
+  void (*k)(PairArgs);
+  if (ks == 5) k = (ws.mt == 2) ? &mbconv_pair_kernel<5, 2, kBlockWaves> : &mbconv_pair_kernel<5, 1, kBlockWaves>;
+  else         k = (ws.mt == 2) ? &mbconv_pair_kernel<3, 2, kBlockWaves> : &mbconv_pair_kernel<3, 1, kBlockWaves>;
+  timing_arm(pa.b);
+  if (int rc = launch_big_lds(k, 160 * 1024, grid, dim3(kBlockWaves * 64), lds, s, pa)) return rc;
+  timing_report_block(s, stage, grid.x);
   return MKWS_OK;
 }
 
 // Paired chain (mbconv_pair_chain_kernel): consecutive stride-1 2x2-image blocks [i0, i1] in one paired launch.
 static bool pair_chain_member(const mkws_embed* em, const BlockPlan& b) {
   if (!(em->fuse_chain == 1 || em->fuse_chain == 3) || !em->fuse_block || !em->fuse_pair || !block_supported(b, em->fuse_block) || !pair_supported(b)) return false;
-  if (em->fuse_cluster && cluster_supported(b) && em->cl_flags) return false;
+  if (cluster_enabled(em, b)) return false;
   return b.ce / 2 <= 2 * kBlockWaves * 64 && b.project.NTtot <= kPairXdAll && b.project.NTtot <= 3 * kBlockWaves;
 }
 static bool pair_chain_link_ok(const BlockPlan& b, const BlockPlan& next) {
@@ -5121,7 +4990,7 @@ static bool pair_chain_link_ok(const BlockPlan& b, const BlockPlan& next) {
   return b.spec.stride == 1 && next.spec.in_ch == b.spec.out_ch && next.expand.KC == b.project.NTtot;
 }
 int launch_pair_chain(hipStream_t s, const mkws_embed* em, int i0, int i1, const float* X, float* Y, int B, bool with_top) {
-  PairChainArgs pa;
+  PairChainArgs pa = {};
   const int n = i1 - i0 + 1, mt = em->pair_mt;
   if (!em->d_chain_tab || n > kPairChainMax) return fail(MKWS_ERR_UNSUPPORTED, "pair chain: no block table / too many blocks");
   pa.tab = em->d_chain_tab; pa.i0 = i0; pa.n = n; pa.kinds = 0; pa.ldsU = pa.ldsE = pa.ldsZ = 0;
@@ -5147,14 +5016,8 @@ int launch_pair_chain(hipStream_t s, const mkws_embed* em, int i0, int i1, const
   if (lds > 160 * 1024) return fail(MKWS_ERR_UNSUPPORTED, "pair chain: LDS carve %zu bytes", lds);
   const dim3 grid(2 * pair_count(B, mt));
   ProfScope ps("chain:" + names, std::string("mbconv_pair_chain_kernel<") + std::to_string(mt) + "," + std::to_string(kBlockWaves) + ">");
-  if (mt == 2) {
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_pair_chain_kernel<2, kBlockWaves>), 160 * 1024)) return rc_;
-    hipLaunchKernelGGL((mbconv_pair_chain_kernel<2, kBlockWaves>), grid, dim3(kBlockWaves * 64), lds, s, pa);
-  } else {
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_pair_chain_kernel<1, kBlockWaves>), 160 * 1024)) return rc_;
-    hipLaunchKernelGGL((mbconv_pair_chain_kernel<1, kBlockWaves>), grid, dim3(kBlockWaves * 64), lds, s, pa);
-  }
-  return MKWS_OK;
+  void (*k)(PairChainArgs) = (mt == 2) ? &mbconv_pair_chain_kernel<2, kBlockWaves> : &mbconv_pair_chain_kernel<1, kBlockWaves>;
+  return launch_big_lds(k, 160 * 1024, grid, dim3(kBlockWaves * 64), lds, s, pa);
 }
 
 // Cluster kernel (mbconv_cluster_kernel): tiny-image blocks of small-batch handles.
@@ -5177,21 +5040,8 @@ bool cluster_supported(const BlockPlan& b) {
 }
 
 int launch_cluster(hipStream_t s, const char* stage, const BlockPlan& b, int block_index, const mkws_embed* em, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
-  ClusterArgs ca;
-  BlockArgs& a = ca.b;
-  a.X = X; a.Cin = b.spec.in_ch;
-  a.WpE = b.expand.Wp; a.scE = b.expand.scale; a.shE = b.expand.shift; a.KCe = b.expand.KC; a.NTe = b.expand.NTtot;
-  a.Wd = b.dw.Wd; a.scD = b.dw.scale; a.shD = b.dw.shift;
-  a.WrP = b.se.WrP; a.br = b.se.br; a.NTR = b.se.NTR; a.We2P = b.se.WeP; a.be = b.se.be;
-  a.WpP = b.project.Wp; a.scP = b.project.scale; a.shP = b.project.shift; a.NTp = b.project.NTtot;
-  a.Y = Y; a.Cout = b.spec.out_ch; a.residual = b.residual ? 1 : 0;
-  a.dbg_dw = dbg_dw; a.dbg_gate = dbg_gate;
-  a.B = B; a.Cexp = b.ce; a.se = b.se.se;
-#ifdef MKWS_FRONT_TIMING
-  unsigned long long* d_bt = block_timing_buffer();
-  (void)hipMemsetAsync(d_bt, 0, sizeof(unsigned long long) * 8 * 4096, s);
-  a.dbg_t = d_bt;
-#endif
+  ClusterArgs ca = {};
+  ca.b = block_args(b, X, Y, dbg_dw, dbg_gate, B);
   ca.Wr = b.se.Wr; ca.We = b.se.We;
   // generation flags are PER BLOCK: a member's generation counts the launches it took part in, and blocks differ in their member count
   ca.xc1 = em->cl_xc1; ca.xd = em->cl_xd; ca.flags = em->cl_flags + (size_t)block_index * (em->cl_flag_count / kNumBlocks);
@@ -5199,46 +5049,22 @@ int launch_cluster(hipStream_t s, const char* stage, const BlockPlan& b, int blo
   ca.P = cluster_members(b.ce);
   const int G = 16 / (b.H * b.W);
   const dim3 grid(cluster_count(B, G) * ca.P);
-  const size_t lds = (size_t)kClusterLdsFloats * sizeof(float);
+  const size_t lds = (size_t)kClusterLdsFloats * sizeof(float);      // (+ 16 B static)
   const int ks = b.spec.kernel, st = b.spec.stride;
   ProfScope ps(stage, std::string("mbconv_cluster_kernel<") + std::to_string(ks) + "," + std::to_string(st) + "," + std::to_string(b.H) + "," + std::to_string(b.W) + ">");
-#define MKWS_CLUSTER(KS, S, H_, W_) do { \
-    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_cluster_kernel<KS, S, H_, W_>), (int)lds)) return rc_;   /* (+ 16 B static) */ \
-    hipLaunchKernelGGL((mbconv_cluster_kernel<KS, S, H_, W_>), grid, dim3(256), lds, s, ca); } while (0)
+  void (*k)(ClusterArgs);
   if (b.H == 4) {
-    if (ks == 3) MKWS_CLUSTER(3, 1, 4, 3);
-    else if (st == 1) MKWS_CLUSTER(5, 1, 4, 3);
-    else MKWS_CLUSTER(5, 2, 4, 3);
+    if (ks == 3) k = &mbconv_cluster_kernel<3, 1, 4, 3>;
+    else if (st == 1) k = &mbconv_cluster_kernel<5, 1, 4, 3>;
+    else k = &mbconv_cluster_kernel<5, 2, 4, 3>;
   } else {
-    if (ks == 5) MKWS_CLUSTER(5, 1, 2, 2);
-    else MKWS_CLUSTER(3, 1, 2, 2);
+    if (ks == 5) k = &mbconv_cluster_kernel<5, 1, 2, 2>;
+    else k = &mbconv_cluster_kernel<3, 1, 2, 2>;
   }
-#undef MKWS_CLUSTER
-#ifdef MKWS_FRONT_TIMING
-  static const bool twice = getenv("MKWS_CLUSTER_TWICE") != nullptr;      // dev aid: time a second launch whose weights are hot in the XCD's L2
-  for (int rep = 0; rep < (twice ? 2 : 1); ++rep) {
-    if (rep == 1) {
-      (void)hipMemsetAsync(d_bt, 0, sizeof(unsigned long long) * 8 * 4096, s);
-      if (b.H == 4) { if (ks == 3) hipLaunchKernelGGL((mbconv_cluster_kernel<3, 1, 4, 3>), grid, dim3(256), lds, s, ca); else if (st == 1) hipLaunchKernelGGL((mbconv_cluster_kernel<5, 1, 4, 3>), grid, dim3(256), lds, s, ca); else hipLaunchKernelGGL((mbconv_cluster_kernel<5, 2, 4, 3>), grid, dim3(256), lds, s, ca); }
-      else { if (ks == 5) hipLaunchKernelGGL((mbconv_cluster_kernel<5, 1, 2, 2>), grid, dim3(256), lds, s, ca); else hipLaunchKernelGGL((mbconv_cluster_kernel<3, 1, 2, 2>), grid, dim3(256), lds, s, ca); }
-    }
-    // members of live clusters only (padding workgroups leave before the first stamp)
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h((size_t)grid.x * 8);
-    (void)hipMemcpy(h.data(), d_bt, h.size() * 8, hipMemcpyDeviceToHost);
-    double ph[6] = {0, 0, 0, 0, 0, 0}; int n = 0; unsigned long long t0 = ~0ull, t1 = 0; double clk = 0;
-    for (size_t i = 0; i < grid.x; ++i) {
-      if (h[8 * i + 6] == 0) continue;
-      clk += (double)h[8 * i + 7] / ((double)(h[8 * i + 6] - h[8 * i]) / 100.0);      // shader-clock ticks per us of wall clock = MHz
-      for (int k = 0; k < 6; ++k) ph[k] += (double)(h[8 * i + k + 1] - h[8 * i + k]);
-      if (h[8 * i] < t0) t0 = h[8 * i];
-      if (h[8 * i + 6] > t1) t1 = h[8 * i + 6];
-      ++n;
-    }
-    if (n) fprintf(stderr, "[cluster-timing] %s%s members %d: stage %.2f  A %.2f  B %.2f  C1+x1 %.2f  C2 %.2f  D+x2 %.2f us; span %.2f us; shader clock %.0f MHz\n", stage, rep ? " (again: L2-hot)" : "", n,
-                   ph[0] / n / 100.0, ph[1] / n / 100.0, ph[2] / n / 100.0, ph[3] / n / 100.0, ph[4] / n / 100.0, ph[5] / n / 100.0, (double)(t1 - t0) / 100.0, clk / n);
-  }
-#endif
+  auto launch = [&] { return launch_big_lds(k, (int)lds, grid, dim3(256), lds, s, ca); };
+  timing_arm(ca.b, s);
+  if (int rc = launch()) return rc;
+  timing_report_cluster(s, stage, grid.x, launch);
   return MKWS_OK;
 }
 
@@ -5285,33 +5111,9 @@ int launch_cluster_chain(hipStream_t s, const mkws_embed* em, int i0, int i1, fl
   cc.err_dev = em->pair_err_dev; cc.err_host = em->pair_err_host; cc.fault = em->pair_fault;
   const size_t lds = (size_t)kClusterLdsFloats * sizeof(float);
   ProfScope ps("chain:" + names, "mbconv_cluster_chain_kernel");
-  if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&mbconv_cluster_chain_kernel), (int)lds)) return rc_;
-#ifdef MKWS_FRONT_TIMING
-  unsigned long long* d_bt = block_timing_buffer();
-  (void)hipMemsetAsync(d_bt, 0, sizeof(unsigned long long) * 8 * 4096, s);
-  cc.dbg_t = d_bt;
-#endif
-  hipLaunchKernelGGL(mbconv_cluster_chain_kernel, dim3(base), dim3(256), lds, s, cc);
-#ifdef MKWS_FRONT_TIMING
-  {
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h((size_t)base * 8);
-    (void)hipMemcpy(h.data(), d_bt, h.size() * 8, hipMemcpyDeviceToHost);
-    unsigned long long t0 = ~0ull;
-    for (int i = 0; i < base; ++i) if (h[8 * (size_t)i + 6] != 0 && h[8 * (size_t)i] < t0) t0 = h[8 * (size_t)i];
-    for (int k = 0; k < cc.n; ++k) {
-      // per block, over its members: latest start, latest end of the wait, then the phases from there
-      double st[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nm = 0;
-      for (int i = cc.base[k]; i < cc.base[k + 1]; ++i) {
-        if (h[8 * (size_t)i + 6] == 0) continue;
-        for (int q = 0; q < 8; ++q) st[q] = std::max(st[q], (double)(h[8 * (size_t)i + q] - t0) / 100.0);
-        ++nm;
-      }
-      fprintf(stderr, "[cluster-chain] %-3s members %2d: started %6.2f  wait over %6.2f | input staged %6.2f  A %6.2f  B %6.2f  C1+x1 %6.2f  C2 %6.2f  D+x2+publish %6.2f us (latest member, since the launch's first stamp)\n",
-              em->blocks[i0 + k].spec.name, nm, st[0], st[7], st[1], st[2], st[3], st[4], st[5], st[6]);
-    }
-  }
-#endif
+  timing_arm(cc, s);
+  if (int rc = launch_big_lds(&mbconv_cluster_chain_kernel, (int)lds, dim3(base), dim3(256), lds, s, cc)) return rc;
+  timing_report_cluster_chain(s, em->blocks + i0, cc);
   return MKWS_OK;
 }
 
@@ -5325,36 +5127,18 @@ bool mid_supported(const BlockPlan& b) {
 }
 
 template <int KS, int S, int KCT, int HT, int WT, int CEXP, int CC, int NTP, int G, int SEG, int NTHR, int WPE, bool PAIR = false>
-int launch_mid_inst(hipStream_t s, const char* stage, const MidArgs& a) {
+int launch_mid_inst(hipStream_t s, const char* stage, MidArgs a) {
   using GM = MidGeom<KS, S, KCT, HT, WT, CEXP, CC, G, SEG>;
   constexpr size_t lds = (size_t)GM::lds_floats * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS carve exceeds one CU");
-  auto* fn = &mbconv_mid_kernel<KS, S, KCT, HT, WT, CEXP, CC, NTP, G, SEG, NTHR, WPE, PAIR>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(fn), 160 * 1024)) return rc;
   ProfScope ps(stage, std::string("mbconv_mid_kernel<") + std::to_string(KS) + "," + std::to_string(S) + "," + std::to_string(HT) + "," + std::to_string(WT) +
                           "," + std::to_string(CEXP) + "," + std::to_string(CC) + "," + std::to_string(G) + "," + std::to_string(NTHR) + ">");
   const dim3 grid((a.B + G - 1) / G);
-#ifdef MKWS_FRONT_TIMING
-  static unsigned long long* d_t = nullptr;
-  if (!d_t) (void)hipMalloc(&d_t, sizeof(unsigned long long) * 8 * 65536);
-  MidArgs at = a; at.dbg_t = d_t;
-  MKWS_WG_TRACE_ARM();
-  hipLaunchKernelGGL(fn, grid, dim3(NTHR), lds, s, at);
-  (void)hipStreamSynchronize(s);
-  std::vector<unsigned long long> h((size_t)grid.x * 8);
-  (void)hipMemcpy(h.data(), d_t, h.size() * 8, hipMemcpyDeviceToHost);
-  double p1 = 0, p2 = 0, se = 0, pj = 0, tot = 0; unsigned long long t0 = ~0ull, t1 = 0;
-  for (size_t i = 0; i < grid.x; ++i) {
-    p1 += (double)h[8 * i + 1]; p2 += (double)h[8 * i + 2]; se += (double)h[8 * i + 3]; pj += (double)h[8 * i + 4]; tot += (double)(h[8 * i + 5] - h[8 * i]);
-    if (h[8 * i] < t0) t0 = h[8 * i];
-    if (h[8 * i + 5] > t1) t1 = h[8 * i + 5];
-  }
-  fprintf(stderr, "[mid-timing] %s CC %d G %d: %u workgroups x %d thr, lds %zu: expand %.2f  depthwise %.2f  SE %.2f  project %.2f  total %.2f us per workgroup; span %.2f us\n",
-          stage, CC, G, grid.x, NTHR, lds, p1 / grid.x / 100.0, p2 / grid.x / 100.0, se / grid.x / 100.0, pj / grid.x / 100.0, tot / grid.x / 100.0, (double)(t1 - t0) / 100.0);
-  MKWS_WG_TRACE_REPORT(s, stage, "mid", (size_t)grid.x);
-#else
-  hipLaunchKernelGGL(fn, grid, dim3(NTHR), lds, s, a);
-#endif
+  timing_arm(a);
+  wg_trace_arm();
+  if (int rc = launch_big_lds(&mbconv_mid_kernel<KS, S, KCT, HT, WT, CEXP, CC, NTP, G, SEG, NTHR, WPE, PAIR>, 160 * 1024, grid, dim3(NTHR), lds, s, a)) return rc;
+  timing_report_mid(s, stage, CC, G, grid.x, NTHR, lds);
+  wg_trace_report(s, stage, "mid", (size_t)grid.x);
   return MKWS_OK;
 }
 
@@ -5367,8 +5151,10 @@ bool mid_enabled(const BlockPlan& b, int fuse_mid) {
   return (b.H == 13 && b.spec.kernel == 5) || (b.H == 7 && b.spec.stride == 2);
 }
 
-int launch_mid(hipStream_t s, const char* stage, const BlockPlan& b, int one_clip, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
+// One launch's arguments for the big-image whole-block kernels (mbconv_mid_kernel, mbconv_rows_kernel); what is not set here is zero
+static MidArgs mid_args(const BlockPlan& b, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
   MidArgs a;
+  memset(static_cast<void*>(&a), 0, sizeof(a));
   a.X = X; a.Cin = b.spec.in_ch;
   a.WpE = b.expand.Wp; a.scE = b.expand.scale; a.shE = b.expand.shift; a.NTtotE = b.expand.NTtot;
   a.Wd = b.dw.Wd; a.scD = b.dw.scale; a.shD = b.dw.shift;
@@ -5376,6 +5162,11 @@ int launch_mid(hipStream_t s, const char* stage, const BlockPlan& b, int one_cli
   a.WpP = b.project.Wp; a.scP = b.project.scale; a.shP = b.project.shift;
   a.Y = Y; a.Cout = b.spec.out_ch; a.residual = b.residual ? 1 : 0;
   a.dbg_dw = dbg_dw; a.dbg_gate = dbg_gate; a.B = B;
+  return a;
+}
+
+int launch_mid(hipStream_t s, const char* stage, const BlockPlan& b, int one_clip, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
+  const MidArgs a = mid_args(b, X, Y, dbg_dw, dbg_gate, B);
   const int ks = b.spec.kernel, st = b.spec.stride;
   //                              KS S KCT  H   W  CEXP CC NTP G SEG NTHR WPE
   if (b.H == 25) return launch_mid_inst<3, 2, 1, 25, 20, 96, 16, 2, 1, 1, 1024, 4>(s, stage, a);                  // 2a
@@ -5396,17 +5187,7 @@ int rows_variant(const BlockPlan& b) {
 }
 
 int launch_rows(hipStream_t s, const char* stage, const BlockPlan& b, int alt, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
-  MidArgs a;
-  a.X = X; a.Cin = b.spec.in_ch;
-  a.WpE = b.expand.Wp; a.scE = b.expand.scale; a.shE = b.expand.shift; a.NTtotE = b.expand.NTtot;
-  a.Wd = b.dw.Wd; a.scD = b.dw.scale; a.shD = b.dw.shift;
-  a.Wr = b.se.Wr; a.br = b.se.br; a.We = b.se.We; a.be = b.se.be; a.se = b.se.se;
-  a.WpP = b.project.Wp; a.scP = b.project.scale; a.shP = b.project.shift;
-  a.Y = Y; a.Cout = b.spec.out_ch; a.residual = b.residual ? 1 : 0;
-  a.dbg_dw = dbg_dw; a.dbg_gate = dbg_gate; a.B = B;
-#ifdef MKWS_FRONT_TIMING
-  a.dbg_t = nullptr;
-#endif
+  const MidArgs a = mid_args(b, X, Y, dbg_dw, dbg_gate, B);
   const int v = rows_variant(b) + (alt ? 16 : 0);          // fuse_rows = 2: the A/B shapes of mkws_embed_rows.hip (clips per wave / workgroups per CU the other way round)
   ProfScope ps(stage, rows_kernel_name(v));
   return launch_rows_variant(s, v, a);
@@ -5426,17 +5207,15 @@ template <int HOWO, int CEXP, int NTP, int RS, int NTHR, int WPE>
 int launch_back_inst(hipStream_t s, const char* stage, const BackArgs& a) {
   constexpr int SCR = (RS * CEXP > NTHR) ? RS * CEXP : NTHR;
   constexpr size_t lds = ((size_t)HOWO * (CEXP + 4) + 2 * CEXP + 16 + SCR) * sizeof(float);
-  auto* fn = &mbconv_back_kernel<HOWO, CEXP, NTP, RS, NTHR, WPE>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(fn), 160 * 1024)) return rc;
   ProfScope ps(stage, std::string("mbconv_back_kernel<") + std::to_string(HOWO) + "," + std::to_string(CEXP) + "," + std::to_string(NTP) + "," + std::to_string(NTHR) + ">");
-  MKWS_WG_TRACE_ARM();
-  hipLaunchKernelGGL(fn, dim3(a.B), dim3(NTHR), lds, s, a);
-  MKWS_WG_TRACE_REPORT(s, stage, "back", (size_t)a.B);
+  wg_trace_arm();
+  if (int rc = launch_big_lds(&mbconv_back_kernel<HOWO, CEXP, NTP, RS, NTHR, WPE>, 160 * 1024, dim3(a.B), dim3(NTHR), lds, s, a)) return rc;
+  wg_trace_report(s, stage, "back", (size_t)a.B);
   return MKWS_OK;
 }
 
 int launch_back(hipStream_t s, const char* stage, const BlockPlan& b, const float* D, const float* X, float* Y, float* dbg_gate, int B) {
-  BackArgs a;
+  BackArgs a = {};
   a.D = D; a.X = X; a.Cin = b.spec.in_ch;
   a.Wr = b.se.Wr; a.br = b.se.br; a.We = b.se.We; a.be = b.se.be; a.se = b.se.se;
   a.WpP = b.project.Wp; a.scP = b.project.scale; a.shP = b.project.shift;
@@ -5499,6 +5278,66 @@ int check_pair_health(mkws_embed* em, hipStream_t s) {
               code == kPairErrXcc ? "the two halves of a pair ran on different XCDs" : "a half timed out waiting for its partner");
 }
 
+// ---- routing: which launch path a block takes ----------------------------------------------------------------------------------
+// In order of precedence.  The three chain paths run blocks i .. last in one launch; every other path runs block i alone.
+enum class Path {
+  Fused1a,        // block 1a inside stem_block1a_kernel (already launched with the stem)
+  Rows,           // mbconv_rows_kernel (option fuse_rows; stride-1 big-image blocks)
+  Mid,            // mbconv_mid_kernel (big-image blocks)
+  Chain,          // mbconv_chain_kernel (4x3-image blocks)
+  PairChain,      // mbconv_pair_chain_kernel (stride-1 2x2-image blocks, + top conv and pool when with_top)
+  ClusterChain,   // mbconv_cluster_chain_kernel (one-clip handles: every tiny-image block)
+  Cluster,        // mbconv_cluster_kernel
+  Pair,           // mbconv_pair_kernel
+  Block,          // mbconv_block_kernel
+  Split           // front (or expand GEMM + depthwise) then back (or SE FCs + gated projection GEMM)
+};
+struct Route { Path path; int last; bool with_top; };
+
+static bool tap_is(const char* stop, const BlockPlan& b, const char* suffix) { return stop && std::string("block") + b.spec.name + suffix == stop; }
+// "_expand" / "_dw" / "_gate" of a block: a chain stops in front of such a block and leaves it to the single-block paths
+static bool inner_tap(const char* stop, const BlockPlan& b) { return tap_is(stop, b, "_expand") || tap_is(stop, b, "_dw") || tap_is(stop, b, "_gate"); }
+// whole block 1a with the stem (its inner taps come from the separate kernels); SE is at most 8 units wide there
+static bool fused_1a(const mkws_embed* em, const char* stop) {
+  const BlockPlan& b = em->blocks[0];
+  return em->fuse_stem && !(stop && strcmp(stop, "stem") == 0) && b.se.se <= 8 && !b.has_expand && b.spec.out_ch == 16 && !tap_is(stop, b, "_dw") && !tap_is(stop, b, "_gate");
+}
+
+Route route_block(const mkws_embed* em, int i, int B, const char* stop) {
+  const BlockPlan& b = em->blocks[i];
+  if (i == 0 && fused_1a(em, stop)) return {Path::Fused1a, i, false};
+  const bool want_expand_tap = tap_is(stop, b, "_expand");      // only the unfused path materialises the expand output
+  if (em->fuse_rows && rows_variant(b) >= 0 && !want_expand_tap) return {Path::Rows, i, false};
+  if (mid_enabled(b, em->fuse_mid) && !want_expand_tap) return {Path::Mid, i, false};
+  // depth-fused chains: a block whose output is tapped ends the chain, a block whose inner taps are wanted is not entered
+  auto extend = [&](int max_len, bool (*member)(const mkws_embed*, const BlockPlan&), bool (*link_ok)(const BlockPlan&, const BlockPlan&)) {
+    int e = i;
+    while (e + 1 < kNumBlocks && e + 1 - i < max_len && !tap_is(stop, em->blocks[e], "") && member(em, em->blocks[e + 1]) &&
+           link_ok(em->blocks[e], em->blocks[e + 1]) && !inner_tap(stop, em->blocks[e + 1])) ++e;
+    return e;
+  };
+  if (chain_member(em, b) && !inner_tap(stop, b)) return {Path::Chain, extend(kChainMax, chain_member, chain_link_ok), false};
+  if (pair_chain_member(em, b) && !inner_tap(stop, b)) {
+    const int e = extend(kPairChainMax, pair_chain_member, pair_chain_link_ok);
+    // the top conv (+ BN + swish + global average pool) rides as the chain's last phase when nothing between here and the pooled
+    // features is tapped
+    const bool with_top = em->fuse_top && em->fuse_gap && (!stop || strcmp(stop, "gap") == 0 || strncmp(stop, "dense", 5) == 0) && e == kNumBlocks - 1 && em->topH * em->topW == 4;
+    return {Path::PairChain, e, with_top};
+  }
+  if (B == 1 && em->fuse_block && em->fuse_cluster_chain && cluster_supported(b) && !stop) {
+    // a live window's tiny-image blocks from here to the top conv as ONE launch (no taps inside: those run launch by launch)
+    int e = i;
+    while (e + 1 < kNumBlocks && e + 1 - i < kClusterChainMax && cluster_supported(em->blocks[e + 1])) ++e;
+    if (cluster_chain_ok(em, i, e)) return {Path::ClusterChain, e, false};
+  }
+  if (em->fuse_block && block_supported(b, em->fuse_block) && !want_expand_tap) {
+    if (cluster_enabled(em, b)) return {Path::Cluster, i, false};
+    if (em->fuse_pair && pair_supported(b)) return {Path::Pair, i, false};
+    return {Path::Block, i, false};
+  }
+  return {Path::Split, i, false};
+}
+
 // Runs the network; stops after `stop` (nullptr = run everything).  On stop, *tap_src/*tap_count describe
 // the buffer holding that stage's output.
 int run_forward(mkws_embed* em, const float* d_spec, int B, float* d_emb, hipStream_t s, const char* stop,
@@ -5508,23 +5347,18 @@ int run_forward(mkws_embed* em, const float* d_spec, int B, float* d_emb, hipStr
     if (stop && name == stop) { *tap_src = p; *tap_count = n; return true; }
     return false;
   };
-  const bool want_stem_tap = stop && strcmp(stop, "stem") == 0;
   const BlockPlan& blk1a = em->blocks[0];
-  // whole block 1a with the stem (its inner taps come from the separate kernels); SE is at most 8 units wide there
-  const bool fused_1a = em->fuse_stem && !want_stem_tap && blk1a.se.se <= 8 && !blk1a.has_expand && blk1a.spec.out_ch == 16 &&
-                        !(stop && (strcmp(stop, "block1a_dw") == 0 || strcmp(stop, "block1a_gate") == 0));
-  if (fused_1a) {
+  if (fused_1a(em, stop)) {
     ProfScope ps("block1a", "stem_block1a_kernel");
     const size_t lds = ((size_t)((51 * 41 + 3) & ~3) + 27 * 22 * 32 + 500 * 36 + 64 * 4 + 32 + 16 + 32) * sizeof(float);
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&stem_block1a_kernel), 160 * 1024)) return rc;
-    MKWS_WG_TRACE_ARM();
-    hipLaunchKernelGGL(stem_block1a_kernel, dim3(B < device_cu_count() ? B : device_cu_count()), dim3(512), lds, s, d_spec, em->stem_w, em->stem_scale, em->stem_shift, em->norm_mean,
+    const int nwg = B < device_cu_count() ? B : device_cu_count();
+    wg_trace_arm();
+    hipLaunchKernelGGL(stem_block1a_kernel, dim3(nwg), dim3(512), lds, s, d_spec, em->stem_w, em->stem_scale, em->stem_shift, em->norm_mean,
                        em->norm_std, blk1a.dw.Wd, blk1a.dw.scale, blk1a.dw.shift, blk1a.se.Wr, blk1a.se.br, blk1a.se.We, blk1a.se.be,
                        blk1a.se.se, blk1a.project.Wp, blk1a.project.scale, blk1a.project.shift, em->bufB, B);
-    MKWS_WG_TRACE_REPORT(s, "block1a", "stem_block1a", (size_t)(B < device_cu_count() ? B : device_cu_count()));
-#ifdef MKWS_FRONT_TIMING
-    wg_phase_report("block1a: prologue / stem / depthwise + next stage / SE / projection", (size_t)(B < device_cu_count() ? B : device_cu_count()), 5);
-#endif
+    wg_trace_report(s, "block1a", "stem_block1a", (size_t)nwg);
+    wg_phase_report("block1a: prologue / stem / depthwise + next stage / SE / projection", (size_t)nwg, 5);
   } else {
     const long pix = (long)B * 500;
     int grid = (int)((pix + 31) / 32);
@@ -5541,125 +5375,67 @@ int run_forward(mkws_embed* em, const float* d_spec, int B, float* d_emb, hipStr
     const BlockPlan& b = em->blocks[i];
     const std::string p = std::string("block") + b.spec.name;
     const int Min = B * b.H * b.W, Mout = B * b.Ho * b.Wo;
-    if (i == 0 && fused_1a) {          // already computed into nxt (= bufB) by stem_block1a_kernel
-      if (hit(p, nxt, (size_t)Mout * b.spec.out_ch)) return MKWS_OK;
-      float* t = cur; cur = nxt; nxt = t;
-      continue;
-    }
-    const bool want_expand_tap = stop && (p + "_expand") == stop;
-    if (em->fuse_rows && rows_variant(b) >= 0 && !want_expand_tap) {
-      // stride-1 big-image blocks: one launch, the depthwise output stays in registers; "_dw" / "_gate" taps come from the kernel's debug stores
-      const bool tap_dw = stop && (p + "_dw") == stop, tap_gate = stop && (p + "_gate") == stop;
-      if (int rc = launch_rows(s, p.c_str(), b, em->fuse_rows == 2, cur, nxt, tap_dw ? em->bufD : nullptr, tap_gate ? em->gate : nullptr, B)) return rc;
-      if (hit(p + "_dw", em->bufD, (size_t)Mout * b.ce)) return MKWS_OK;
-      if (hit(p + "_gate", em->gate, (size_t)B * b.ce)) return MKWS_OK;
-      if (hit(p, nxt, (size_t)Mout * b.spec.out_ch)) return MKWS_OK;
-      float* t = cur; cur = nxt; nxt = t;
-      continue;
-    }
-    if (mid_enabled(b, em->fuse_mid) && !want_expand_tap) {
-      // big-image blocks: one launch for the whole block; "_dw" / "_gate" taps come from the kernel's debug stores
-      const bool tap_dw = stop && (p + "_dw") == stop, tap_gate = stop && (p + "_gate") == stop;
-      if (int rc = launch_mid(s, p.c_str(), b, em->block_mt43 == 1, cur, nxt, tap_dw ? em->bufD : nullptr, tap_gate ? em->gate : nullptr, B)) return rc;
-      if (hit(p + "_dw", em->bufD, (size_t)Mout * b.ce)) return MKWS_OK;
-      if (hit(p + "_gate", em->gate, (size_t)B * b.ce)) return MKWS_OK;
-      if (hit(p, nxt, (size_t)Mout * b.spec.out_ch)) return MKWS_OK;
-      float* t = cur; cur = nxt; nxt = t;
-      continue;
-    }
-    {
-      // depth-fused chain: blocks i .. e in one launch.  A block whose output is tapped ends the chain; a block whose inner taps
-      // ("_expand" / "_dw" / "_gate") are wanted is left to the single-block paths below (the chain stops in front of it)
-      auto inner_tap = [&](int j) {
-        if (!stop) return false;
-        const std::string q = std::string("block") + em->blocks[j].spec.name;
-        return (q + "_expand") == stop || (q + "_dw") == stop || (q + "_gate") == stop;
-      };
-      if (chain_member(em, b) && !inner_tap(i)) {
-        int e = i;
-        while (e + 1 < kNumBlocks && e + 1 - i < kChainMax && !(stop && (std::string("block") + em->blocks[e].spec.name) == stop) &&
-               chain_member(em, em->blocks[e + 1]) && chain_link_ok(em->blocks[e], em->blocks[e + 1]) && !inner_tap(e + 1)) ++e;
-        const BlockPlan& bl = em->blocks[e];
-        if (int rc = launch_chain(s, em, i, e, cur, nxt, B)) return rc;
-        if (hit(std::string("block") + bl.spec.name, nxt, (size_t)B * bl.Ho * bl.Wo * bl.spec.out_ch)) return MKWS_OK;
-        float* t = cur; cur = nxt; nxt = t;
-        i = e;
-        continue;
-      }
-      if (pair_chain_member(em, b) && !inner_tap(i)) {
-        int e = i;
-        while (e + 1 < kNumBlocks && e + 1 - i < kPairChainMax && !(stop && (std::string("block") + em->blocks[e].spec.name) == stop) &&
-               pair_chain_member(em, em->blocks[e + 1]) && pair_chain_link_ok(em->blocks[e], em->blocks[e + 1]) && !inner_tap(e + 1)) ++e;
-        const BlockPlan& bl = em->blocks[e];
-        // the top conv (+ BN + swish + global average pool) rides as the chain's last phase when nothing between here and the pooled
-        // features is tapped
-        const bool with_top = em->fuse_top && em->fuse_gap && (!stop || strcmp(stop, "gap") == 0 || strncmp(stop, "dense", 5) == 0) && e == kNumBlocks - 1 && em->topH * em->topW == 4;
-        if (int rc = launch_pair_chain(s, em, i, e, cur, nxt, B, with_top)) return rc;
-        top_done = with_top;
-        if (hit(std::string("block") + bl.spec.name, nxt, (size_t)B * bl.Ho * bl.Wo * bl.spec.out_ch)) return MKWS_OK;
-        float* t = cur; cur = nxt; nxt = t;
-        i = e;
-        continue;
-      }
-    }
-    if (B == 1 && em->fuse_block && em->fuse_cluster_chain && cluster_supported(b) && !stop) {
-      // a live window's tiny-image blocks from here to the top conv as ONE launch (no taps inside: those run launch by launch below)
-      int e = i;
-      while (e + 1 < kNumBlocks && e + 1 - i < kClusterChainMax && cluster_supported(em->blocks[e + 1])) ++e;
-      if (cluster_chain_ok(em, i, e)) {
-        if (int rc = launch_cluster_chain(s, em, i, e, cur, nxt)) return rc;
-        if (((e - i + 1) & 1) != 0) { float* t = cur; cur = nxt; nxt = t; }       // (an even number of blocks ends in the buffer it started from)
-        i = e;
-        continue;
-      }
-    }
-    if (em->fuse_block && block_supported(b, em->fuse_block) && !want_expand_tap) {
-      // one launch for the whole block; "_dw" / "_gate" taps come from the kernel's debug stores
-      const bool tap_dw = stop && (p + "_dw") == stop, tap_gate = stop && (p + "_gate") == stop;
-      if (em->fuse_cluster && cluster_supported(b) && em->cl_flags) {
-        if (int rc = launch_cluster(s, p.c_str(), b, i, em, cur, nxt, tap_dw ? em->bufD : nullptr, tap_gate ? em->gate : nullptr, B)) return rc;
-      } else if (em->fuse_pair && pair_supported(b)) {
+    const Route r = route_block(em, i, B, stop);
+    // the single-block kernels serve the "_dw" / "_gate" taps from their debug stores
+    float* const dbg_dw = tap_is(stop, b, "_dw") ? em->bufD : nullptr;
+    float* const dbg_gate = tap_is(stop, b, "_gate") ? em->gate : nullptr;
+    bool swap = true;       // the path leaves its output in nxt
+    int rc = MKWS_OK;
+    switch (r.path) {
+      case Path::Fused1a: break;          // already computed into nxt (= bufB) by stem_block1a_kernel
+      case Path::Rows: rc = launch_rows(s, p.c_str(), b, em->fuse_rows == 2, cur, nxt, dbg_dw, dbg_gate, B); break;
+      case Path::Mid: rc = launch_mid(s, p.c_str(), b, em->block_mt43 == 1, cur, nxt, dbg_dw, dbg_gate, B); break;
+      case Path::Chain: rc = launch_chain(s, em, i, r.last, cur, nxt, B); break;
+      case Path::PairChain:
+        rc = launch_pair_chain(s, em, i, r.last, cur, nxt, B, r.with_top);
+        top_done = r.with_top;
+        break;
+      case Path::ClusterChain:
+        rc = launch_cluster_chain(s, em, i, r.last, cur, nxt);
+        swap = ((r.last - i + 1) & 1) != 0;       // (an even number of blocks ends in the buffer it started from)
+        break;
+      case Path::Cluster: rc = launch_cluster(s, p.c_str(), b, i, em, cur, nxt, dbg_dw, dbg_gate, B); break;
+      case Path::Pair: {
         PairWs pw; pw.xc1 = em->pair_xc1; pw.xd = em->pair_xd; pw.flags = em->pair_flags; pw.mt = em->pair_mt;
         pw.err_dev = em->pair_err_dev; pw.err_host = em->pair_err_host; pw.fault = em->pair_fault;
-        if (int rc = launch_pair(s, p.c_str(), b, pw, cur, nxt, tap_dw ? em->bufD : nullptr, tap_gate ? em->gate : nullptr, B)) return rc;
-      } else {
-        if (int rc = launch_block(s, p.c_str(), b, em->block_mt43, cur, nxt, tap_dw ? em->bufD : nullptr, tap_gate ? em->gate : nullptr, B, em->fuse_se4 != 0)) return rc;
+        rc = launch_pair(s, p.c_str(), b, pw, cur, nxt, dbg_dw, dbg_gate, B);
+        break;
       }
-      if (hit(p + "_dw", em->bufD, (size_t)Mout * b.ce)) return MKWS_OK;
-      if (hit(p + "_gate", em->gate, (size_t)B * b.ce)) return MKWS_OK;
-      if (hit(p, nxt, (size_t)Mout * b.spec.out_ch)) return MKWS_OK;
-      float* t = cur; cur = nxt; nxt = t;
-      continue;
+      case Path::Block: rc = launch_block(s, p.c_str(), b, em->block_mt43, cur, nxt, dbg_dw, dbg_gate, B, em->fuse_se4 != 0); break;
+      case Path::Split:
+        if (b.has_expand && (tap_is(stop, b, "_expand") || !em->fuse_front)) {
+          // unfused path: kept for the "<block>_expand" parity tap and as an A/B switch (mkws_embed_set_option)
+          launch_gemm(s, sw, (p + "_expand").c_str(), b.expand, cur, b.spec.in_ch, Min, em->max_batch * b.H * b.W, ACT_SWISH, nullptr, 0, nullptr, 0, em->bufE, b.ce);
+          if (hit(p + "_expand", em->bufE, (size_t)Min * b.ce)) return MKWS_OK;
+          launch_dw(s, (p + "_dw").c_str(), b, em->bufE, em->bufD, em->sums, B);
+        } else if (b.has_expand && front_supported(b)) {
+          launch_front(s, (p + "_dw").c_str(), b, cur, em->bufD, em->sums, B, em->fuse_walk && em->max_batch >= 128);   // (small handles keep one workgroup per channel block: three CUs per clip instead of one)
+        } else if (b.has_expand) {
+          launch_gemm(s, sw, (p + "_expand").c_str(), b.expand, cur, b.spec.in_ch, Min, em->max_batch * b.H * b.W, ACT_SWISH, nullptr, 0, nullptr, 0, em->bufE, b.ce);
+          launch_dw(s, (p + "_dw").c_str(), b, em->bufE, em->bufD, em->sums, B);
+        } else {
+          launch_dw(s, (p + "_dw").c_str(), b, cur, em->bufD, em->sums, B);
+        }
+        if (hit(p + "_dw", em->bufD, (size_t)Mout * b.ce)) return MKWS_OK;       // (here and below: a tap returns before the launches behind it)
+        if (em->fuse_back && back_supported(b)) {
+          // SE + gated projection of this block in one launch, the clip's depthwise output staged in LDS once
+          rc = launch_back(s, p.c_str(), b, em->bufD, cur, nxt, dbg_gate, B);
+          break;
+        }
+        launch_se(s, (p + "_gate").c_str(), b, em->sums, em->se_part, em->gate, B);
+        if (hit(p + "_gate", em->gate, (size_t)B * b.ce)) return MKWS_OK;
+        launch_gemm(s, sw, p.c_str(), b.project, em->bufD, b.ce, Mout, em->max_batch * b.Ho * b.Wo, ACT_NONE, em->gate, b.Ho * b.Wo, b.residual ? cur : nullptr,
+                    b.spec.out_ch, nxt, b.spec.out_ch);
+        break;
     }
-    if (b.has_expand && (want_expand_tap || !em->fuse_front)) {
-      // unfused path: kept for the "<block>_expand" parity tap and as an A/B switch (mkws_embed_set_option)
-      launch_gemm(s, sw, (p + "_expand").c_str(), b.expand, cur, b.spec.in_ch, Min, em->max_batch * b.H * b.W, ACT_SWISH, nullptr, 0, nullptr, 0, em->bufE, b.ce);
-      if (hit(p + "_expand", em->bufE, (size_t)Min * b.ce)) return MKWS_OK;
-      launch_dw(s, (p + "_dw").c_str(), b, em->bufE, em->bufD, em->sums, B);
-    } else if (b.has_expand && front_supported(b)) {
-      launch_front(s, (p + "_dw").c_str(), b, cur, em->bufD, em->sums, B, em->fuse_walk && em->max_batch >= 128);   // (small handles keep one workgroup per channel block: three CUs per clip instead of one)
-    } else if (b.has_expand) {
-      launch_gemm(s, sw, (p + "_expand").c_str(), b.expand, cur, b.spec.in_ch, Min, em->max_batch * b.H * b.W, ACT_SWISH, nullptr, 0, nullptr, 0, em->bufE, b.ce);
-      launch_dw(s, (p + "_dw").c_str(), b, em->bufE, em->bufD, em->sums, B);
-    } else {
-      launch_dw(s, (p + "_dw").c_str(), b, cur, em->bufD, em->sums, B);
-    }
+    if (rc) return rc;
+    // taps of the block(s) just run (a chain never holds block i's inner taps, and its output tap is its last block's), then on to the next
+    const BlockPlan& bl = em->blocks[r.last];
     if (hit(p + "_dw", em->bufD, (size_t)Mout * b.ce)) return MKWS_OK;
-    if (em->fuse_back && back_supported(b)) {
-      // SE + gated projection of this block in one launch, the clip's depthwise output staged in LDS once
-      const bool tap_gate = stop && (p + "_gate") == stop;
-      if (int rc = launch_back(s, p.c_str(), b, em->bufD, cur, nxt, tap_gate ? em->gate : nullptr, B)) return rc;
-      if (hit(p + "_gate", em->gate, (size_t)B * b.ce)) return MKWS_OK;
-      if (hit(p, nxt, (size_t)Mout * b.spec.out_ch)) return MKWS_OK;
-      float* t = cur; cur = nxt; nxt = t;
-      continue;
-    }
-    launch_se(s, (p + "_gate").c_str(), b, em->sums, em->se_part, em->gate, B);
     if (hit(p + "_gate", em->gate, (size_t)B * b.ce)) return MKWS_OK;
-    launch_gemm(s, sw, p.c_str(), b.project, em->bufD, b.ce, Mout, em->max_batch * b.Ho * b.Wo, ACT_NONE, em->gate, b.Ho * b.Wo, b.residual ? cur : nullptr,
-                b.spec.out_ch, nxt, b.spec.out_ch);
-    if (hit(p, nxt, (size_t)Mout * b.spec.out_ch)) return MKWS_OK;
-    float* t = cur; cur = nxt; nxt = t;
+    if (hit(std::string("block") + bl.spec.name, nxt, (size_t)B * bl.Ho * bl.Wo * bl.spec.out_ch)) return MKWS_OK;
+    if (swap) { float* t = cur; cur = nxt; nxt = t; }
+    i = r.last;
   }
   const int HWt = em->topH * em->topW;
   const bool fuse_gap = em->fuse_gap && HWt == 4 && !(stop && strcmp(stop, "top") == 0);
@@ -5772,7 +5548,7 @@ int mkws_embed_create(const float* h, size_t n_floats, int max_batch, mkws_embed
   fold_bn(T("stem_bn/gamma"), T("stem_bn/beta"), T("stem_bn/moving_mean"), T("stem_bn/moving_variance"), kStemCh, &sc, &sh);
   const size_t o_stem_sc = pk.add(sc.data(), kStemCh), o_stem_sh = pk.add(sh.data(), kStemCh);
 
-  struct BlockOff { GemmOff expand, project, se_r, se_e; size_t dw_w, dw_sc, dw_sh, se_wr, se_we, se_q_r = 0, se_q_e = 0; int T0 = 0, NQ = 0; } bo[kNumBlocks];
+  struct BlockOff { GemmOff expand, project, se_r, se_e; size_t dw_w, dw_sc, dw_sh, se_wr, se_we; Se4Off se4; } bo[kNumBlocks];
   int H = 25, W = 20;
   for (int i = 0; i < kNumBlocks; ++i) {
     BlockPlan& b = em->blocks[i];
@@ -5809,33 +5585,8 @@ int mkws_embed_create(const float* h, size_t n_floats, int max_batch, mkws_embed
       bo[i].se_we = pk.add(T(p + "_se_expand/kernel"), (size_t)se * b.ce);     // plain [se][C] (stem_block1a_kernel)
       std::vector<float> one_e(b.ce, 1.0f), bias_e(T(p + "_se_expand/bias"), T(p + "_se_expand/bias") + b.ce);
       bo[i].se_e = pack_gemm(pk, T(p + "_se_expand/kernel"), se, b.ce, one_e, bias_e);
-      if (bo[i].se_r.NTtot > 3) { delete em; return fail(MKWS_ERR_UNSUPPORTED, "SE width %d > 48", se); }
-      // 4x4x1-instruction packing of both FCs for the 4x3-image blocks (Se4 in the kernel section: lane l of instruction 4 q + e reads float e of
-      // dwordx4 (q, l)).  Reduce: wave w, half kh = l / 32, unit l % 32; channel w cpw + t (half 0, t < cpw - T0) or w cpw + cpw - T0 + t (half 1).
-      // Expand: group of 64 channels, channel 64 group + l, unit 4 q + e.  Zero where a channel / unit does not exist.
-      const int cpw = b.ce / kBlockWaves, T0 = 4 * ((cpw + 7) / 8), NQ = (se + 3) / 4, NG = (b.ce + 63) / 64;
-      if (H == 4 && W == 3 && b.has_expand && b.ce % (4 * kBlockWaves) == 0 && se <= 32 && T0 / 4 <= kSe4MaxTQ && NQ <= kSe4MaxNQ && NG <= kSe4MaxGroups * kBlockWaves &&
-          kBlockWaves * 4 * 32 <= 4 * b.ce) {      // (the wave partials [8][G][32] live where the gate used to: G * Cexp floats)
-        const float* wr = T(p + "_se_reduce/kernel");      // [C][se]
-        const float* we = T(p + "_se_expand/kernel");      // [se][C]
-        std::vector<float> qr((size_t)kBlockWaves * kSe4MaxTQ * 256, 0.0f), qe((size_t)NG * kSe4MaxNQ * 256, 0.0f);      // (zero padded to the kernels' fixed step counts)
-        for (int w = 0; w < kBlockWaves; ++w)
-          for (int t = 0; t < T0; ++t)
-            for (int l = 0; l < 64; ++l) {
-              const int kh = l / 32, n = l % 32;
-              const int ch = w * cpw + (kh ? cpw - T0 + t : t);
-              const bool ok = n < se && (kh || t < cpw - T0);
-              qr[(((size_t)w * kSe4MaxTQ + t / 4) * 64 + l) * 4 + t % 4] = ok ? wr[(size_t)ch * se + n] : 0.0f;
-            }
-        for (int gq = 0; gq < NG; ++gq)
-          for (int n = 0; n < 4 * NQ; ++n)
-            for (int l = 0; l < 64; ++l) {
-              const int ch = 64 * gq + l;
-              qe[(((size_t)gq * kSe4MaxNQ + n / 4) * 64 + l) * 4 + n % 4] = (n < se && ch < b.ce) ? we[(size_t)n * b.ce + ch] : 0.0f;
-            }
-        bo[i].se_q_r = pk.add(qr.data(), qr.size()); bo[i].se_q_e = pk.add(qe.data(), qe.size());
-        bo[i].T0 = T0; bo[i].NQ = NQ;
-      }
+      if (bo[i].se_r.NTtot > 3) { mkws_embed_destroy(em); return fail(MKWS_ERR_UNSUPPORTED, "SE width %d > 48", se); }
+      if (H == 4 && W == 3 && b.has_expand) bo[i].se4 = pack_se4(pk, T(p + "_se_reduce/kernel"), T(p + "_se_expand/kernel"), b.ce, se, kBlockWaves);
     }
     fold_bn(T(p + "_project_bn/gamma"), T(p + "_project_bn/beta"), T(p + "_project_bn/moving_mean"), T(p + "_project_bn/moving_variance"), b.spec.out_ch, &sc, &sh);
     bo[i].project = pack_gemm(pk, T(p + "_project_conv/kernel"), b.ce, b.spec.out_ch, sc, sh);
@@ -5854,10 +5605,10 @@ int mkws_embed_create(const float* h, size_t n_floats, int max_batch, mkws_embed
 
   // upload
   const size_t wbytes = pk.buf.size() * sizeof(float);
-  if (hipMalloc(reinterpret_cast<void**>(&em->d_weights), wbytes) != hipSuccess) { delete em; return fail(MKWS_ERR_ALLOC, "hipMalloc(%zu) for weights failed", wbytes); }
-  if (hipMemcpy(em->d_weights, pk.buf.data(), wbytes, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(em->d_weights); delete em; return fail(MKWS_ERR_HIP, "weight upload failed");
-  }
+  // every failure exit from here on leaves through mkws_embed_destroy, which frees what has been allocated so far
+  auto give_up = [&](int code, const char* what) { mkws_embed_destroy(em); return fail(code, "%s", what); };
+  if (hipMalloc(reinterpret_cast<void**>(&em->d_weights), wbytes) != hipSuccess) { mkws_embed_destroy(em); return fail(MKWS_ERR_ALLOC, "hipMalloc(%zu) for weights failed", wbytes); }
+  if (hipMemcpy(em->d_weights, pk.buf.data(), wbytes, hipMemcpyHostToDevice) != hipSuccess) return give_up(MKWS_ERR_HIP, "weight upload failed");
   const float* d = em->d_weights;
   auto G = [&](const GemmOff& o) { GemmLayer L; L.Wp = d + o.Wp; L.scale = d + o.scale; L.shift = d + o.shift; L.K = o.K; L.N = o.N; L.KC = o.KC; L.NTtot = o.NTtot; return L; };
   em->stem_w = d + o_stem_w; em->stem_scale = d + o_stem_sc; em->stem_shift = d + o_stem_sh;
@@ -5868,7 +5619,7 @@ int mkws_embed_create(const float* h, size_t n_floats, int max_batch, mkws_embed
     b.dw.Wd = d + bo[i].dw_w; b.dw.scale = d + bo[i].dw_sc; b.dw.shift = d + bo[i].dw_sh;
     b.se.Wr = d + bo[i].se_wr; b.se.We = d + bo[i].se_we; b.se.WrP = d + bo[i].se_r.Wp; b.se.br = d + bo[i].se_r.shift; b.se.WeP = d + bo[i].se_e.Wp; b.se.be = d + bo[i].se_e.shift;
     b.se.KCr = bo[i].se_r.KC; b.se.NTR = bo[i].se_r.NTtot; b.se.NTe = bo[i].se_e.NTtot;
-    if (bo[i].T0) { b.se.WrQ = d + bo[i].se_q_r; b.se.WeQ = d + bo[i].se_q_e; b.se.T0 = bo[i].T0; b.se.NQ = bo[i].NQ; }
+    if (bo[i].se4.T0) { b.se.WrQ = d + bo[i].se4.r; b.se.WeQ = d + bo[i].se4.e; b.se.T0 = bo[i].se4.T0; b.se.NQ = bo[i].se4.NQ; }
     // the expand FC's K (= se) is padded to NTR*16 by pack_gemm: KC of se_e == NTR by construction
   }
   em->top = G(o_top); em->dense0 = G(o_d0); em->dense1 = G(o_d1); em->dense2 = G(o_d2);
@@ -5877,75 +5628,61 @@ int mkws_embed_create(const float* h, size_t n_floats, int max_batch, mkws_embed
     std::vector<BlockArgs> tab(kNumBlocks);
     memset(static_cast<void*>(tab.data()), 0, sizeof(BlockArgs) * kNumBlocks);
     for (int i = 0; i < kNumBlocks; ++i)
-      if (em->blocks[i].has_expand) fill_block_args(tab[i], em->blocks[i], 0);
+      if (em->blocks[i].has_expand) tab[i] = block_args(em->blocks[i]);
     if (hipMalloc(reinterpret_cast<void**>(&em->d_chain_tab), sizeof(BlockArgs) * kNumBlocks) != hipSuccess ||
-        hipMemcpy(em->d_chain_tab, tab.data(), sizeof(BlockArgs) * kNumBlocks, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(em->d_weights); if (em->d_chain_tab) (void)hipFree(em->d_chain_tab); delete em; return fail(MKWS_ERR_ALLOC, "block table upload failed");
-    }
+        hipMemcpy(em->d_chain_tab, tab.data(), sizeof(BlockArgs) * kNumBlocks, hipMemcpyHostToDevice) != hipSuccess) return give_up(MKWS_ERR_ALLOC, "block table upload failed");
   }
 
-  // workspace
-  const size_t per_clip = 16000 * 2 + 48000 + 18720 + 1152 * 2 + 1280 + 2048 * 2 + 20480 + 9 * 48;
-  const size_t pair_floats = pair_ws_floats(max_batch, em->pair_mt);
+  // workspace: ONE list of (buffer, floats), in carve order -- the allocation is its sum, the carve walks it, and in guard-band mode a band
+  // follows every entry (and precedes the first)
+  const size_t mb = (size_t)max_batch, np = (size_t)pair_count(max_batch, em->pair_mt);
   // cluster exchange buffers exist for handles that may ever use the kernel (the option can be set after create up to 64 clips)
   // (a one-clip handle's chain launch gives every block an exchange slot of its own: blocks on different XCDs must never hold dirty copies of one line)
   const size_t ncl = (max_batch == 1) ? 16 : (max_batch <= 64) ? (size_t)cluster_count(max_batch, 1) : 0;
-  const size_t cluster_floats = ncl * ((size_t)kClusterPMax * kClXc1 + (size_t)kClusterPMax * kClMaxTiles * 256 + (size_t)kNumBlocks * 2 * kClFlagRow);
+  em->splitk_floats = 20480 * mb;
+  // mbconv_pair_kernel: [pairs][2 exchanges][2 halves] | mbconv_pair_chain_kernel: [pairs][blocks][2][2] | the error word (cleared with the flags)
+  em->pair_flag_count = np * 4 + np * 4 * kPairChainMax;
+  em->cl_flag_count = ncl * 2 * kClFlagRow * kNumBlocks;
+  float *pair_flags = nullptr, *cl_flags = nullptr;        // (carved like the rest, used as ints)
+  std::vector<std::pair<float**, size_t>> carves = {
+      {&em->bufA, 16000 * mb}, {&em->bufB, 16000 * mb}, {&em->bufE, 48000 * mb}, {&em->bufD, 18720 * mb},
+      {&em->sums, 1152 * mb}, {&em->gate, 1152 * mb}, {&em->gap, 1280 * mb}, {&em->d0, 2048 * mb}, {&em->d1, 2048 * mb},
+      {&em->splitk_ws, em->splitk_floats},
+      {&em->se_part, 9 * 48 * mb + 8 * 768},      // 8 slices x ceil(mb/16) groups x 768 floats <= 384*mb + 6144
+      {&em->pair_xc1, np * 2 * kPairXc1}, {&em->pair_xd, np * 2 * kPairXdAll * 2 * 256}, {&pair_flags, em->pair_flag_count + 4}};
+  if (ncl > 0) {
+    carves.push_back({&em->cl_xc1, ncl * kClusterPMax * kClXc1});
+    carves.push_back({&em->cl_xd, ncl * kClusterPMax * kClMaxTiles * 256});
+    carves.push_back({&cl_flags, em->cl_flag_count});
+  }
   {
     const char* g = getenv("MKWS_EMBED_GUARD");
     const long gv = g ? atol(g) : 0;
     em->guard = gv > 0 ? (size_t)((gv + 63) / 64 * 64) : 0;      // whole 256-byte lines: the carve keeps its alignment
   }
-  const size_t kCarves = 17;      // sub-buffers carved below (14, + 3 for handles that may run the cluster kernel)
-  const size_t ws = per_clip * (size_t)max_batch + 64 + 8 * 768 + pair_floats + 4 + cluster_floats + em->guard * (kCarves + 1);
-  if (hipMalloc(reinterpret_cast<void**>(&em->d_ws), ws * sizeof(float)) != hipSuccess) {
-    (void)hipFree(em->d_weights); (void)hipFree(em->d_chain_tab); delete em; return fail(MKWS_ERR_ALLOC, "hipMalloc(%zu) for workspace failed", ws * sizeof(float));
-  }
-  if (em->guard && hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(em->d_ws), (int)kGuardCanary, ws) != hipSuccess) {
-    (void)hipFree(em->d_weights); (void)hipFree(em->d_chain_tab); (void)hipFree(em->d_ws); delete em; return fail(MKWS_ERR_HIP, "filling the guarded workspace failed");
-  }
+  // one 256-byte line behind the last carve: the kernels read the workspace with 16-byte vector loads, and the end of the last buffer is
+  // then never the end of the allocation
+  constexpr size_t kWsTailPad = 64;
+  size_t ws = em->guard + kWsTailPad;
+  for (const auto& c : carves) ws += c.second + em->guard;
+  if (hipMalloc(reinterpret_cast<void**>(&em->d_ws), ws * sizeof(float)) != hipSuccess) { mkws_embed_destroy(em); return fail(MKWS_ERR_ALLOC, "hipMalloc(%zu) for workspace failed", ws * sizeof(float)); }
+  if (em->guard && hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(em->d_ws), (int)kGuardCanary, ws) != hipSuccess) return give_up(MKWS_ERR_HIP, "filling the guarded workspace failed");
   float* w = em->d_ws;
   if (em->guard) { em->guard_spans.emplace_back(0, em->guard); w += em->guard; }
-  // carve(n): the next n floats of the workspace (+ a guard band behind them in guard-band mode)
-  auto carve = [&](size_t n) {
-    float* p = w;
-    w += n;
+  for (const auto& c : carves) {
+    *c.first = w;
+    w += c.second;
     if (em->guard) { em->guard_spans.emplace_back((size_t)(w - em->d_ws), em->guard); w += em->guard; }
-    return p;
-  };
-  const size_t mb = (size_t)max_batch;
-  em->bufA = carve(16000 * mb); em->bufB = carve(16000 * mb); em->bufE = carve(48000 * mb); em->bufD = carve(18720 * mb);
-  em->sums = carve(1152 * mb); em->gate = carve(1152 * mb); em->gap = carve(1280 * mb); em->d0 = carve(2048 * mb); em->d1 = carve(2048 * mb);
-  em->splitk_floats = 20480 * mb; em->splitk_ws = carve(20480 * mb);
-  em->se_part = carve(9 * 48 * mb + 8 * 768);      // 8 slices x ceil(mb/16) groups x 768 floats <= 384*mb + 6144
-  {
-    const size_t np = (size_t)pair_count(max_batch, em->pair_mt);
-    em->pair_xc1 = carve(np * 2 * kPairXc1);
-    em->pair_xd = carve(np * 2 * kPairXdAll * 2 * 256);
-    // mbconv_pair_kernel: [pairs][2 exchanges][2 halves] | mbconv_pair_chain_kernel: [pairs][blocks][2][2] | the error word (cleared with the flags)
-    em->pair_flags = reinterpret_cast<int*>(carve(np * 4 + np * 4 * kPairChainMax + 4));
-    em->pair_chain_flags = em->pair_flags + np * 4;
-    em->pair_flag_count = np * 4 + np * 4 * kPairChainMax;
-    em->pair_err_dev = em->pair_flags + em->pair_flag_count;
-    if (hipMemset(em->pair_flags, 0, (em->pair_flag_count + 4) * sizeof(int)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&em->pair_err_host), 64, hipHostMallocMapped) != hipSuccess) {
-      (void)hipFree(em->d_weights); (void)hipFree(em->d_chain_tab); (void)hipFree(em->d_ws); delete em; return fail(MKWS_ERR_HIP, "setting up the pair flags failed");
-    }
-    *em->pair_err_host = 0;
-    if (ncl > 0) {
-      em->cl_xc1 = carve(ncl * kClusterPMax * kClXc1);
-      em->cl_xd = carve(ncl * kClusterPMax * kClMaxTiles * 256);
-      em->cl_flags = reinterpret_cast<int*>(carve(ncl * 2 * kClFlagRow * kNumBlocks));
-      em->cl_flag_count = ncl * 2 * kClFlagRow * kNumBlocks;
-      if (hipMemset(em->cl_flags, 0, em->cl_flag_count * sizeof(int)) != hipSuccess) {
-        (void)hipFree(em->d_weights); (void)hipFree(em->d_chain_tab); (void)hipFree(em->d_ws); (void)hipHostFree(em->pair_err_host); delete em; return fail(MKWS_ERR_HIP, "clearing the cluster flags failed");
-      }
-    }
   }
-  if ((size_t)(w - em->d_ws) > ws || em->guard_spans.size() > kCarves + 1) {
-    const size_t used = (size_t)(w - em->d_ws), bands = em->guard_spans.size();
-    mkws_embed_destroy(em);
-    return fail(MKWS_ERR_ALLOC, "workspace carve overran its allocation (%zu of %zu floats, %zu guard bands)", used, ws, bands);
+  em->pair_flags = reinterpret_cast<int*>(pair_flags);
+  em->pair_chain_flags = em->pair_flags + np * 4;
+  em->pair_err_dev = em->pair_flags + em->pair_flag_count;
+  if (hipMemset(em->pair_flags, 0, (em->pair_flag_count + 4) * sizeof(int)) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&em->pair_err_host), 64, hipHostMallocMapped) != hipSuccess) return give_up(MKWS_ERR_HIP, "setting up the pair flags failed");
+  *em->pair_err_host = 0;
+  if (ncl > 0) {
+    em->cl_flags = reinterpret_cast<int*>(cl_flags);
+    if (hipMemset(em->cl_flags, 0, em->cl_flag_count * sizeof(int)) != hipSuccess) return give_up(MKWS_ERR_HIP, "clearing the cluster flags failed");
   }
   *out = em;
   return MKWS_OK;
@@ -5987,92 +5724,114 @@ int mkws_embed_forward(mkws_embed* em, const float* d_spec, int B, float* d_emb,
   return MKWS_OK;
 }
 
-int mkws_embed_set_option(mkws_embed* em, const char* name, int value) {
-  if (!em || !name) return fail(MKWS_ERR_INVALID_ARG, "NULL argument");
-  if (strcmp(name, "fuse_front") == 0) { em->fuse_front = value != 0; return MKWS_OK; }
-  if (strcmp(name, "fuse_block") == 0) { em->fuse_block = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_mid") == 0) { em->fuse_mid = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_rows") == 0) { em->fuse_rows = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_walk") == 0) { em->fuse_walk = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_se4") == 0) { em->fuse_se4 = value ? 1 : 0; return MKWS_OK; }
-  if (strcmp(name, "fuse_gemv") == 0) { em->fuse_gemv = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_back") == 0) { em->fuse_back = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_pair") == 0) { em->fuse_pair = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_chain") == 0) { em->fuse_chain = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_top") == 0) { em->fuse_top = value; return MKWS_OK; }
-  if (strcmp(name, "fuse_cluster") == 0) {
-    if (value && !em->cl_flags) return fail(MKWS_ERR_UNSUPPORTED, "fuse_cluster needs a handle of at most 64 clips (max_batch = %d)", em->max_batch);
-    em->fuse_cluster = value; return MKWS_OK;
-  }
-  if (strcmp(name, "fuse_cluster_chain") == 0) {
-    if (value && (em->max_batch != 1 || !em->cl_flags)) return fail(MKWS_ERR_UNSUPPORTED, "fuse_cluster_chain is the plan of one-clip handles (max_batch = %d)", em->max_batch);
-    em->fuse_cluster_chain = value; return MKWS_OK;
-  }
-  if (strcmp(name, "fuse_stem") == 0) { em->fuse_stem = value; return MKWS_OK; }
-  if (strcmp(name, "big_tiles") == 0) {      // A/B: 8-clip pairs and 4-clip 4x3 workgroups whatever max_batch is (fewer, larger workgroups: the workspaces still fit)
-    if (value) { em->pair_mt = 2; em->block_mt43 = 3; } else { em->pair_mt = pair_row_tiles(em->plan_batch); em->block_mt43 = block43_row_tiles(em->plan_batch); }
-    return MKWS_OK;
-  }
-  if (strcmp(name, "plan_batch") == 0) {
+// ---- options: ONE table for mkws_embed_set_option and mkws_embed_get_option --------------------------------------------------------
+// (what an option means is said once, at its member of struct mkws_embed).  `member`: a plain integer, written and read as it is.
+// Otherwise `set` / `get`, either of which may be missing: the option is then read-only / write-only ("unknown option" the other way).
+namespace {
+struct EmbedOption {
+  const char* name;
+  int mkws_embed::* member;
+  int (*set)(mkws_embed*, int);
+  int (*get)(const mkws_embed*);
+};
+void plan_tiles(mkws_embed* em) { em->pair_mt = pair_row_tiles(em->plan_batch); em->block_mt43 = block43_row_tiles(em->plan_batch); }
+const EmbedOption kEmbedOptions[] = {
+    {"fuse_front", nullptr, [](mkws_embed* em, int v) { em->fuse_front = v != 0; return (int)MKWS_OK; }, [](const mkws_embed* em) { return em->fuse_front ? 1 : 0; }},
+    {"fuse_block", &mkws_embed::fuse_block, nullptr, nullptr},
+    {"fuse_mid", &mkws_embed::fuse_mid, nullptr, nullptr},
+    {"fuse_rows", &mkws_embed::fuse_rows, nullptr, nullptr},
+    {"fuse_walk", &mkws_embed::fuse_walk, nullptr, nullptr},
+    {"fuse_se4", nullptr, [](mkws_embed* em, int v) { em->fuse_se4 = v ? 1 : 0; return (int)MKWS_OK; }, [](const mkws_embed* em) { return em->fuse_se4; }},
+    {"fuse_gemv", &mkws_embed::fuse_gemv, nullptr, nullptr},
+    {"fuse_back", &mkws_embed::fuse_back, nullptr, nullptr},
+    {"fuse_pair", &mkws_embed::fuse_pair, nullptr, nullptr},
+    {"fuse_chain", &mkws_embed::fuse_chain, nullptr, nullptr},
+    {"fuse_top", &mkws_embed::fuse_top, nullptr, nullptr},
+    {"fuse_cluster", nullptr,
+     [](mkws_embed* em, int v) {
+       if (v && !em->cl_flags) return fail(MKWS_ERR_UNSUPPORTED, "fuse_cluster needs a handle of at most 64 clips (max_batch = %d)", em->max_batch);
+       em->fuse_cluster = v; return (int)MKWS_OK;
+     },
+     [](const mkws_embed* em) { return em->fuse_cluster; }},
+    {"fuse_cluster_chain", nullptr,
+     [](mkws_embed* em, int v) {
+       if (v && (em->max_batch != 1 || !em->cl_flags)) return fail(MKWS_ERR_UNSUPPORTED, "fuse_cluster_chain is the plan of one-clip handles (max_batch = %d)", em->max_batch);
+       em->fuse_cluster_chain = v; return (int)MKWS_OK;
+     },
+     [](const mkws_embed* em) { return em->fuse_cluster_chain; }},
+    {"fuse_stem", &mkws_embed::fuse_stem, nullptr, nullptr},
+    {"fuse_gap", &mkws_embed::fuse_gap, nullptr, nullptr},
+    // A/B: 8-clip pairs and 4-clip 4x3 workgroups whatever max_batch is (fewer, larger workgroups: the workspaces still fit)
+    {"big_tiles", nullptr,
+     [](mkws_embed* em, int v) {
+       if (v) { em->pair_mt = 2; em->block_mt43 = 3; } else plan_tiles(em);
+       return (int)MKWS_OK;
+     },
+     nullptr},
     // Plan for `value` clips (0 = back to max_batch): the caller runs several handles CONCURRENTLY on separate streams (serving lanes) and passes
     // the clips they hold together, so that the tiny-image launches (blocks 4a..7a: 60 % of a forward pass) of a 256-clip lane take a quarter of the
     // chip each -- the 1024-clip plan's workgroup shapes: 4-clip workgroups, 8-clip pairs -- instead of spreading one clip per CU and queueing behind the
     // other lanes.  The GEMM tiles stay those of max_batch (measured: the 1024-clip tiles on 256 rows are a few long workgroups, 1.58 vs 0.99 ms per
     // 4 x 256 clips, profiles/r06_notes.md section 8).  Per-clip arithmetic does not depend on the shapes beyond the documented round-off between them;
     // workspaces are sized by max_batch and larger shapes need less of them.
-    if (value != 0 && value < em->max_batch) return fail(MKWS_ERR_INVALID_ARG, "plan_batch %d is below the handle's max_batch %d", value, em->max_batch);
-    em->plan_batch = value ? value : em->max_batch;
-    em->pair_mt = pair_row_tiles(em->plan_batch); em->block_mt43 = block43_row_tiles(em->plan_batch);
-    return MKWS_OK;
-  }
-  if (strcmp(name, "fuse_gap") == 0) { em->fuse_gap = value; return MKWS_OK; }
-  if (strcmp(name, "block_tiles") == 0) {    // A/B: row tiles (3 / 2 / 1 = 4 / 2 / 1 clips) per workgroup of the 4x3-image kernels; 0 = the rule of the handle's max_batch
-    if (value < 0 || value > 3) return fail(MKWS_ERR_INVALID_ARG, "block_tiles is 0 (rule), 1, 2 or 3");
-    em->block_mt43 = value ? value : block43_row_tiles(em->plan_batch);
-    return MKWS_OK;
-  }
-  if (strcmp(name, "pair_fault") == 0) { em->pair_fault = value; return MKWS_OK; }     // test hook: forces the paired kernel's failure paths
-  if (strcmp(name, "inject_exchange_error") == 0) {
+    {"plan_batch", nullptr,
+     [](mkws_embed* em, int v) {
+       if (v != 0 && v < em->max_batch) return fail(MKWS_ERR_INVALID_ARG, "plan_batch %d is below the handle's max_batch %d", v, em->max_batch);
+       em->plan_batch = v ? v : em->max_batch;
+       plan_tiles(em);
+       return (int)MKWS_OK;
+     },
+     [](const mkws_embed* em) { return em->plan_batch; }},
+    // A/B: row tiles (3 / 2 / 1 = 4 / 2 / 1 clips) per workgroup of the 4x3-image kernels; 0 = the rule of the handle's plan_batch.  Reads back the tiles in use
+    {"block_tiles", nullptr,
+     [](mkws_embed* em, int v) {
+       if (v < 0 || v > 3) return fail(MKWS_ERR_INVALID_ARG, "block_tiles is 0 (rule), 1, 2 or 3");
+       em->block_mt43 = v ? v : block43_row_tiles(em->plan_batch);
+       return (int)MKWS_OK;
+     },
+     [](const mkws_embed* em) { return em->block_mt43; }},
+    {"pair_fault", nullptr, [](mkws_embed* em, int v) { em->pair_fault = v; return (int)MKWS_OK; }, nullptr},     // test hook: forces the paired kernel's failure paths
     // test hook: the state a failed exchange of an EARLIER launch leaves behind (sticky device word + host-mapped word), without running
     // one -- what a captured graph meets when a replay before it failed.  Synchronous.
-    if (!em->pair_err_host || !em->pair_err_dev) return fail(MKWS_ERR_UNSUPPORTED, "handle has no exchange kernels");
-    const int code = value ? kPairErrTimeout : 0;
-    MKWS_HIP(hipDeviceSynchronize());
-    MKWS_HIP(hipMemcpy(em->pair_err_dev, &code, sizeof(int), hipMemcpyHostToDevice));
-    *reinterpret_cast<volatile int*>(em->pair_err_host) = code;
-    return MKWS_OK;
-  }
+    {"inject_exchange_error", nullptr,
+     [](mkws_embed* em, int v) {
+       if (!em->pair_err_host || !em->pair_err_dev) return fail(MKWS_ERR_UNSUPPORTED, "handle has no exchange kernels");
+       const int code = v ? kPairErrTimeout : 0;
+       MKWS_HIP(hipDeviceSynchronize());
+       MKWS_HIP(hipMemcpy(em->pair_err_dev, &code, sizeof(int), hipMemcpyHostToDevice));
+       *reinterpret_cast<volatile int*>(em->pair_err_host) = code;
+       return (int)MKWS_OK;
+     },
+     nullptr},
+    {"pair_degraded", nullptr, nullptr, [](const mkws_embed* em) { return em->pair_degraded; }},
+    {"guard_floats", nullptr, nullptr, [](const mkws_embed* em) { return (int)em->guard; }},
+    {"guard_bands", nullptr, nullptr, [](const mkws_embed* em) { return (int)em->guard_spans.size(); }},
+    {"guard_violations", nullptr, nullptr, guard_violations},
+    // nonzero: a launch that has ALREADY EXECUTED recorded a failed exchange and the handle has not been healed yet (the next forward /
+    // tap / profile call heals it and returns MKWS_ERR_EXCHANGE).  A host-mapped word: no synchronisation.  This is what hipGraph users
+    // poll -- a replay does not pass through mkws_embed_forward, so "pair_degraded" cannot move under it.
+    {"exchange_error", nullptr, nullptr, [](const mkws_embed* em) { return em->pair_err_host ? *reinterpret_cast<volatile int*>(em->pair_err_host) : 0; }},
+    {"max_batch", nullptr, nullptr, [](const mkws_embed* em) { return em->max_batch; }},
+};
+const EmbedOption* find_option(const char* name) {
+  for (const EmbedOption& o : kEmbedOptions) if (strcmp(name, o.name) == 0) return &o;
+  return nullptr;
+}
+}  // namespace
+
+int mkws_embed_set_option(mkws_embed* em, const char* name, int value) {
+  if (!em || !name) return fail(MKWS_ERR_INVALID_ARG, "NULL argument");
+  const EmbedOption* o = find_option(name);
+  if (o && o->member) { em->*(o->member) = value; return MKWS_OK; }
+  if (o && o->set) return o->set(em, value);
   return fail(MKWS_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
 int mkws_embed_get_option(const mkws_embed* em, const char* name) {
   if (!em || !name) return fail(MKWS_ERR_INVALID_ARG, "NULL argument");
-  if (strcmp(name, "fuse_front") == 0) return em->fuse_front ? 1 : 0;
-  if (strcmp(name, "fuse_block") == 0) return em->fuse_block;
-  if (strcmp(name, "fuse_mid") == 0) return em->fuse_mid;
-  if (strcmp(name, "fuse_rows") == 0) return em->fuse_rows;
-  if (strcmp(name, "fuse_walk") == 0) return em->fuse_walk;
-  if (strcmp(name, "fuse_se4") == 0) return em->fuse_se4;
-  if (strcmp(name, "fuse_gemv") == 0) return em->fuse_gemv;
-  if (strcmp(name, "fuse_back") == 0) return em->fuse_back;
-  if (strcmp(name, "fuse_pair") == 0) return em->fuse_pair;
-  if (strcmp(name, "fuse_chain") == 0) return em->fuse_chain;
-  if (strcmp(name, "fuse_top") == 0) return em->fuse_top;
-  if (strcmp(name, "fuse_cluster") == 0) return em->fuse_cluster;
-  if (strcmp(name, "fuse_cluster_chain") == 0) return em->fuse_cluster_chain;
-  if (strcmp(name, "fuse_stem") == 0) return em->fuse_stem;
-  if (strcmp(name, "fuse_gap") == 0) return em->fuse_gap;
-  if (strcmp(name, "block_tiles") == 0) return em->block_mt43;
-  if (strcmp(name, "pair_degraded") == 0) return em->pair_degraded;
-  if (strcmp(name, "guard_floats") == 0) return (int)em->guard;
-  if (strcmp(name, "guard_bands") == 0) return (int)em->guard_spans.size();
-  if (strcmp(name, "guard_violations") == 0) return guard_violations(em);
-  // nonzero: a launch that has ALREADY EXECUTED recorded a failed exchange and the handle has not been healed yet (the next forward /
-  // tap / profile call heals it and returns MKWS_ERR_EXCHANGE).  A host-mapped word: no synchronisation.  This is what hipGraph users
-  // poll -- a replay does not pass through mkws_embed_forward, so "pair_degraded" cannot move under it.
-  if (strcmp(name, "exchange_error") == 0) return em->pair_err_host ? *reinterpret_cast<volatile int*>(em->pair_err_host) : 0;
-  if (strcmp(name, "max_batch") == 0) return em->max_batch;
-  if (strcmp(name, "plan_batch") == 0) return em->plan_batch;
+  const EmbedOption* o = find_option(name);
+  if (o && o->member) return em->*(o->member);
+  if (o && o->get) return o->get(em);
   return fail(MKWS_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 

@@ -189,6 +189,38 @@ def test_depth_fused_chain_is_bit_identical_to_the_single_block_kernels(ctx):
         em2.close()
 
 
+def _default_launch_sequences(blob, big, dev):
+    """{"max_batch<N>_B<n>": [[stage, kernel], ...]}: the launches of one forward pass, as mkws_embed_profile names them, for default-option
+    handles of 1, 2, 32 and 256 clips at their full batch and for `big` (the module's 1024-clip handle) at its full batch and at 5 clips."""
+    from multilingual_kws_amd.embedding_model import EmbeddingModel
+    x = torch.from_numpy(_spec(np.random.default_rng(8), big.max_batch)).to(dev)
+    seqs = {}
+    for max_batch in (1, 2, 32, 256):
+        em = EmbeddingModel(blob, max_batch=max_batch)
+        seqs[f"max_batch{max_batch}_B{max_batch}"] = [[s, k] for s, k, _ in em.profile(x[:max_batch], reps=1)]
+        em.close()
+    for b in (big.max_batch, 5):
+        seqs[f"max_batch{big.max_batch}_B{b}"] = [[s, k] for s, k, _ in big.profile(x[:b], reps=1)]
+    return seqs
+
+
+def test_default_launch_sequences(ctx, golden_dir):
+    """The plan a default-option handle runs is part of the product: the (stage, kernel) sequence of one forward pass, per handle class, is
+    the recorded one (tests/golden/embed_launch_sequences.json, written from this function's helper on an MI355X).  A change of routing,
+    of a launcher's template choice or of a default shows here as the first differing launch."""
+    if torch.cuda.get_device_properties(ctx["dev"]).multi_processor_count != 256:
+        pytest.skip("the recorded sequences are those of a 256-CU device (block_mt43 and pair_mt follow the CU count)")
+    if ctx["em"].get_option("fuse_pair") != 1:
+        pytest.skip("this device's dispatch order failed the probe at create: the paired / cluster kernels are not in the plan")
+    want = json.load(open(os.path.join(golden_dir, "embed_launch_sequences.json")))
+    got = _default_launch_sequences(ctx["blob"], ctx["em"], ctx["dev"])
+    assert sorted(got) == sorted(want)
+    for key in want:
+        for i, (g, w) in enumerate(zip(got[key], want[key])):
+            assert g == w, (key, i, g, w)
+        assert len(got[key]) == len(want[key]), (key, len(got[key]), len(want[key]))
+
+
 def test_golden_embedding_on_device(ctx, golden_dir):
     from multilingual_kws_amd import synth
     from multilingual_kws_amd.frontend import Frontend
