@@ -305,6 +305,27 @@ int mkws_head_adam_step(mkws_head* hd, float lr, float beta1, float beta2, float
 int mkws_head_adam_step_dev(mkws_head* hd, float lr, float beta1, float beta2, float eps, const int* d_step,
                             float grad_scale, void* stream);
 
+/* Side-by-side training of several keyword heads: a head group is a thin object over existing mkws_head handles of equal
+ * dimensions (at least one, none NULL, none twice).  One call steps EVERY member -- one launch per stage (rows, dW1 partials,
+ * finish, Adam) per 64 heads, the head being a grid dimension -- where the single-head entry points pay four small dependent
+ * launches per head.  Each head's arithmetic is that of mkws_head_loss_grad / mkws_head_adam_step, bit for bit; the members stay
+ * ordinary heads (serving, get_params, state).  The group keeps device pointers into its members: destroy the group before any
+ * of them.  mkws_head_group_create allocates and uploads the group's pointer table (synchronous); the two step calls only launch
+ * kernels on `stream` (asynchronous, capturable). */
+typedef struct mkws_head_group mkws_head_group;
+int mkws_head_group_create(mkws_head* const* heads, int n_heads, mkws_head_group** out);
+void mkws_head_group_destroy(mkws_head_group* g);      /* does not destroy the heads; NULL is a no-op */
+int mkws_head_group_size(const mkws_head_group* g);
+/* mkws_head_loss_grad of head h on the B rows at d_emb + h * emb_stride (stride in floats) with the labels at
+ * d_labels + h * label_stride (in int32s), for every h; B at most the smallest max_batch of the group.
+ * d_stats (optional, may be NULL): float32 [n_heads][2] = {sum of per-row loss, number of correct rows} of each head; the same
+ * two values are written behind each head's gradient as in the single-head call. */
+int mkws_head_group_loss_grad(mkws_head_group* g, const float* d_emb, int64_t emb_stride, const int32_t* d_labels,
+                              int64_t label_stride, int B, float* d_stats, void* stream);
+/* mkws_head_adam_step of every member with the same step index (lr_t is evaluated once, on the host, in double). */
+int mkws_head_group_adam_step(mkws_head_group* g, float lr, float beta1, float beta2, float eps, int step_t,
+                              float grad_scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Streaming detector.  Replaces SingleTargetRecognizeCommands.process_latest_result
  * (multilingual_kws/embedding/single_target_recognize_commands.py:94-207) and the per-window, per-keyword, per-threshold Python loop

@@ -80,6 +80,12 @@ SYMBOLS = [
     ("mkws_head_adam_step", _I, [_P, _F, _F, _F, _F, _I, _F, _P]),
     ("mkws_head_input_grad", _I, [_P, _P, _I, _P]),
     ("mkws_head_adam_step_dev", _I, [_P, _F, _F, _F, _F, _P, _F, _P]),
+    # side-by-side training of several heads
+    ("mkws_head_group_create", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P)]),
+    ("mkws_head_group_destroy", None, [_P]),
+    ("mkws_head_group_size", _I, [_P]),
+    ("mkws_head_group_loss_grad", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _I, _P, _P]),
+    ("mkws_head_group_adam_step", _I, [_P, _F, _F, _F, _F, _I, _F, _P]),
     # training operators (backprop_into_embedding)
     ("mkws_train_ctx_create", _I, [_P, _SZ, ctypes.POINTER(_P)]),
     ("mkws_train_ctx_destroy", None, [_P]),

@@ -26,6 +26,13 @@ struct HeadDims { int in, hid, cls; };
 constexpr int kHeadsPerLaunch = 64;
 struct HeadTable { const float* p[kHeadsPerLaunch]; };
 
+// Side-by-side training (mkws_head_group): the nine buffers of every member head, one row per head in DEVICE memory (nine pointers
+// x 64 heads do not fit the by-value HeadTable pattern), uploaded once when the group is created.  The GROUP instantiations of the
+// four training kernels carry the head as their last grid dimension and read their row of the table by it: wave-uniform, scalar
+// loads.  Everything after that is the single-head kernel's own code, so a head's arithmetic does not depend on how it is launched.
+struct HeadSlot { float *params, *grads, *m, *v, *hbuf, *dz, *dpre, *rowstat, *partial; };
+constexpr int kGroupHeadsPerLaunch = 64;
+
 // Inference forward on the fp32 matrix cores (mkws_head_forward and the multi-keyword mkws_heads_forward).
 // The per-row kernel below spends its time on latency: 50 heads x 256 windows took 94 us for 0.47 GFLOP, one wave per SIMD with
 // ~300 live registers.  Here a wave owns 16 rows x (up to) 32 hidden units of ONE head: z1^T[hid, rows] = W1^T[hid, in] . x^T[in, rows]
@@ -178,15 +185,22 @@ __global__ __launch_bounds__(256) void head_fwd_mfma_kernel(HeadDims d, const fl
 
 // R rows per wave: every W1 value a lane loads is used for R rows (the 50-head serving launch re-read each head's 73 KB of W1 once
 // per row and wave: 121 us per 256 windows).  The arithmetic of one row does not depend on R, so the results are bit-identical.
-template <bool TRAIN, bool MULTI = false, int R = 1>
+template <bool TRAIN, bool MULTI = false, int R = 1, bool GROUP = false>
 __global__ __launch_bounds__(256) void head_rows_kernel(HeadDims d, const float* __restrict__ params, const float* __restrict__ x,
                                                         const int32_t* __restrict__ labels, int B, float* __restrict__ probs,
                                                         float* __restrict__ hbuf /*[B,hid]*/, float* __restrict__ dz /*[B,cls]*/,
                                                         float* __restrict__ dpre /*[B,hid]*/, float* __restrict__ rowstat /*[B,2]*/,
-                                                        HeadTable table = HeadTable()) {
+                                                        HeadTable table = HeadTable(), const HeadSlot* __restrict__ slots = nullptr,
+                                                        long long x_stride = 0, long long label_stride = 0) {
   const int lane = threadIdx.x & 63;
   const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
   if (row0 >= B) return;
+  if (GROUP) {                      // head blockIdx.y of a training group: its own rows, labels and buffers
+    const HeadSlot& sl = slots[blockIdx.y];
+    params = sl.params; hbuf = sl.hbuf; dz = sl.dz; dpre = sl.dpre; rowstat = sl.rowstat;
+    x += (long long)blockIdx.y * x_stride;
+    labels += (long long)blockIdx.y * label_stride;
+  }
   if (MULTI) {                      // head blockIdx.y: its own parameters, its own [B, cls] slab of the output
     params = table.p[blockIdx.y];
     probs += (size_t)blockIdx.y * B * d.cls;
@@ -314,8 +328,8 @@ __global__ __launch_bounds__(256) void head_rows_kernel(HeadDims d, const float*
 }
 
 // partial dW1: block (kx, split) handles 256 input features x rows [split*rows_per, +rows_per)
-__global__ __launch_bounds__(256) void head_dw1_partial_kernel(HeadDims d, const float* __restrict__ x, const float* __restrict__ dpre,
-                                                               int B, int rows_per, float* __restrict__ partial /*[splits][in*hid]*/) {
+__device__ __forceinline__ void head_dw1_partial_body(HeadDims d, const float* __restrict__ x, const float* __restrict__ dpre, int B, int rows_per,
+                                                      float* __restrict__ partial /*[splits][in*hid]*/) {
   __shared__ float s_dp[64 * kMaxHidden];
   const int k = blockIdx.x * 256 + threadIdx.x;
   const int r0 = blockIdx.y * rows_per;
@@ -346,13 +360,34 @@ __global__ __launch_bounds__(256) void head_dw1_partial_kernel(HeadDims d, const
   }
 }
 
+// GROUP: blockIdx.z = head.  (The body is a function of its own so that the group's pointers, read from the table, are __restrict__
+// arguments like the single-head kernel's: without that the compiler keeps fewer row loads in flight.)
+template <bool GROUP = false>
+__global__ __launch_bounds__(256) void head_dw1_partial_kernel(HeadDims d, const float* __restrict__ x, const float* __restrict__ dpre,
+                                                               int B, int rows_per, float* __restrict__ partial,
+                                                               const HeadSlot* __restrict__ slots = nullptr, long long x_stride = 0) {
+  if (GROUP) {
+    const HeadSlot& sl = slots[blockIdx.z];
+    head_dw1_partial_body(d, x + (long long)blockIdx.z * x_stride, sl.dpre, B, rows_per, sl.partial);
+  } else {
+    head_dw1_partial_body(d, x, dpre, B, rows_per, partial);
+  }
+}
+
 // final reduce: grads = [sum of partials | db1 | dW2 | db2 | sum loss, sum correct]; the two statistics ride
 // behind the gradient so that a data-parallel step is ONE all-reduce of nparams + 2 floats; `stats` (optional)
-// receives a copy of them
+// receives a copy of them; GROUP: blockIdx.y = head, stats is [heads][2]
+template <bool GROUP = false>
 __global__ __launch_bounds__(256) void head_grad_finish_kernel(HeadDims d, const float* __restrict__ partial, int splits,
                                                                const float* __restrict__ hbuf, const float* __restrict__ dz,
                                                                const float* __restrict__ dpre, const float* __restrict__ rowstat, int B,
-                                                               float* __restrict__ grads, float* __restrict__ stats) {
+                                                               float* __restrict__ grads, float* __restrict__ stats,
+                                                               const HeadSlot* __restrict__ slots = nullptr) {
+  if (GROUP) {
+    const HeadSlot& sl = slots[blockIdx.y];
+    partial = sl.partial; hbuf = sl.hbuf; dz = sl.dz; dpre = sl.dpre; rowstat = sl.rowstat; grads = sl.grads;
+    if (stats) stats += 2 * blockIdx.y;
+  }
   const int nW1 = d.in * d.hid;
   const int nsmall = d.hid + d.hid * d.cls + d.cls;
   const int nbW1 = (nW1 + 255) / 256;
@@ -405,12 +440,17 @@ __global__ __launch_bounds__(256) void head_input_grad_kernel(HeadDims d, const 
   }
 }
 
-// Keras Adam (optimizer_v2/adam.py): lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; theta -= lr_t*m/(sqrt(v)+eps)
+// Keras Adam (optimizer_v2/adam.py): lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; theta -= lr_t*m/(sqrt(v)+eps); GROUP: blockIdx.y = head
+template <bool GROUP = false>
 __global__ __launch_bounds__(256) void head_adam_kernel(float* __restrict__ params, const float* __restrict__ grads, float* __restrict__ m,
                                                         float* __restrict__ v, int n, float lr_t, float beta1, float beta2, float eps,
-                                                        float grad_scale) {
+                                                        float grad_scale, const HeadSlot* __restrict__ slots = nullptr) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  if (GROUP) {
+    const HeadSlot& sl = slots[blockIdx.y];
+    params = sl.params; grads = sl.grads; m = sl.m; v = sl.v;
+  }
   const float g = grads[i] * grad_scale;
   const float mi = m[i] + (g - m[i]) * (1.0f - beta1);
   const float vi = v[i] + (g * g - v[i]) * (1.0f - beta2);
@@ -451,6 +491,12 @@ struct mkws_head {
   float* d_work = nullptr;    // hbuf | dz | dpre | rowstat | partial
   float *params, *grads, *m, *v;
   float *hbuf, *dz, *dpre, *rowstat, *partial;
+};
+
+struct mkws_head_group {
+  int n = 0, nparams = 0, max_batch = 0;   // max_batch: the smallest of the members'
+  HeadDims d;
+  HeadSlot* d_slots = nullptr;             // [n], device
 };
 
 extern "C" {
@@ -577,10 +623,10 @@ int mkws_head_loss_grad(mkws_head* hd, const float* d_emb, const int32_t* d_labe
                      hd->hbuf, hd->dz, hd->dpre, hd->rowstat);
   const int rows_per = (B + kGradSplits - 1) / kGradSplits;
   const int splits = (B + rows_per - 1) / rows_per;
-  hipLaunchKernelGGL(head_dw1_partial_kernel, dim3((hd->d.in + 255) / 256, splits), dim3(256), 0, s, hd->d, d_emb, hd->dpre, B, rows_per, hd->partial);
+  hipLaunchKernelGGL((head_dw1_partial_kernel<false>), dim3((hd->d.in + 255) / 256, splits), dim3(256), 0, s, hd->d, d_emb, hd->dpre, B, rows_per, hd->partial);
   const int total = hd->nparams + 2;
   const int fin_blocks = (hd->d.in * hd->d.hid + 255) / 256 + (total - hd->d.in * hd->d.hid + 3) / 4;
-  hipLaunchKernelGGL(head_grad_finish_kernel, dim3(fin_blocks), dim3(256), 0, s, hd->d, hd->partial, splits, hd->hbuf, hd->dz, hd->dpre,
+  hipLaunchKernelGGL((head_grad_finish_kernel<false>), dim3(fin_blocks), dim3(256), 0, s, hd->d, hd->partial, splits, hd->hbuf, hd->dz, hd->dpre,
                      hd->rowstat, B, hd->grads, d_stats);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
@@ -600,8 +646,93 @@ int mkws_head_adam_step(mkws_head* hd, float lr, float beta1, float beta2, float
   if (!hd) return fail(MKWS_ERR_INVALID_ARG, "head handle is NULL");
   if (step_t < 1) return fail(MKWS_ERR_INVALID_ARG, "Adam step index starts at 1");
   const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, step_t)) / (1.0 - std::pow((double)beta1, step_t));
-  hipLaunchKernelGGL(head_adam_kernel, dim3((hd->nparams + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), hd->params, hd->grads,
+  hipLaunchKernelGGL((head_adam_kernel<false>), dim3((hd->nparams + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), hd->params, hd->grads,
                      hd->m, hd->v, hd->nparams, (float)lr_t, beta1, beta2, eps, grad_scale);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+int mkws_head_group_create(mkws_head* const* heads, int n_heads, mkws_head_group** out) {
+  if (!out) return fail(MKWS_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  if (!heads || n_heads < 1) return fail(MKWS_ERR_INVALID_ARG, "a head group needs at least one head");
+  for (int i = 0; i < n_heads; ++i) {
+    if (!heads[i]) return fail(MKWS_ERR_INVALID_ARG, "head %d is NULL", i);
+    if (heads[i]->d.in != heads[0]->d.in || heads[i]->d.hid != heads[0]->d.hid || heads[i]->d.cls != heads[0]->d.cls)
+      return fail(MKWS_ERR_INVALID_ARG, "head %d has different dimensions than head 0", i);
+    for (int j = 0; j < i; ++j)     // two grid slices would write one gradient buffer
+      if (heads[j] == heads[i]) return fail(MKWS_ERR_INVALID_ARG, "head %d is head %d again", i, j);
+  }
+  int rc = require_device();
+  if (rc != MKWS_OK) return rc;
+  mkws_head_group* g = new (std::nothrow) mkws_head_group();
+  HeadSlot* table = new (std::nothrow) HeadSlot[n_heads];
+  if (!g || !table) { delete g; delete[] table; return fail(MKWS_ERR_ALLOC, "out of host memory"); }
+  g->n = n_heads; g->d = heads[0]->d; g->nparams = heads[0]->nparams; g->max_batch = heads[0]->max_batch;
+  for (int i = 0; i < n_heads; ++i) {
+    const mkws_head* h = heads[i];
+    table[i] = {h->params, h->grads, h->m, h->v, h->hbuf, h->dz, h->dpre, h->rowstat, h->partial};
+    if (h->max_batch < g->max_batch) g->max_batch = h->max_batch;
+  }
+  // the one allocation and the one (synchronous) copy of the group's life: loss_grad / adam_step only launch
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->d_slots), (size_t)n_heads * sizeof(HeadSlot));
+  if (e == hipSuccess) e = hipMemcpy(g->d_slots, table, (size_t)n_heads * sizeof(HeadSlot), hipMemcpyHostToDevice);
+  delete[] table;
+  if (e != hipSuccess) {
+    if (g->d_slots) (void)hipFree(g->d_slots);
+    delete g;
+    return fail(MKWS_ERR_ALLOC, "head group table: %s", hipGetErrorString(e));
+  }
+  *out = g;
+  return MKWS_OK;
+}
+
+void mkws_head_group_destroy(mkws_head_group* g) {
+  if (!g) return;
+  if (g->d_slots) (void)hipFree(g->d_slots);
+  delete g;
+}
+
+int mkws_head_group_size(const mkws_head_group* g) { return g ? g->n : fail(MKWS_ERR_INVALID_ARG, "head group handle is NULL"); }
+
+int mkws_head_group_loss_grad(mkws_head_group* g, const float* d_emb, int64_t emb_stride, const int32_t* d_labels, int64_t label_stride, int B,
+                              float* d_stats, void* stream) {
+  if (!g) return fail(MKWS_ERR_INVALID_ARG, "head group handle is NULL");
+  if (B <= 0 || B > g->max_batch) return fail(MKWS_ERR_INVALID_ARG, "batch %d outside [1, smallest max_batch of the group=%d]", B, g->max_batch);
+  if (!d_emb || !d_labels) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (g->n > 1 && (emb_stride < 0 || label_stride < 0)) return fail(MKWS_ERR_INVALID_ARG, "negative stride between heads");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const HeadDims d = g->d;
+  // the single-head rules (mkws_head_loss_grad), so that every head's sums run in the single-head order
+  const int rows_per = (B + kGradSplits - 1) / kGradSplits;
+  const int splits = (B + rows_per - 1) / rows_per;
+  const int total = g->nparams + 2;
+  const int fin_blocks = (d.in * d.hid + 255) / 256 + (total - d.in * d.hid + 3) / 4;
+  for (int h0 = 0; h0 < g->n; h0 += kGroupHeadsPerLaunch) {
+    const int n = (g->n - h0 < kGroupHeadsPerLaunch) ? g->n - h0 : kGroupHeadsPerLaunch;
+    const HeadSlot* slots = g->d_slots + h0;
+    const float* x = d_emb + (long long)h0 * emb_stride;
+    const int32_t* y = d_labels + (long long)h0 * label_stride;
+    hipLaunchKernelGGL((head_rows_kernel<true, false, 1, true>), dim3((B + 3) / 4, n), dim3(256), 0, s, d, nullptr, x, y, B, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, HeadTable(), slots, (long long)emb_stride, (long long)label_stride);
+    hipLaunchKernelGGL((head_dw1_partial_kernel<true>), dim3((d.in + 255) / 256, splits, n), dim3(256), 0, s, d, x, nullptr, B, rows_per, nullptr, slots,
+                       (long long)emb_stride);
+    hipLaunchKernelGGL((head_grad_finish_kernel<true>), dim3(fin_blocks, n), dim3(256), 0, s, d, nullptr, splits, nullptr, nullptr, nullptr, nullptr, B,
+                       nullptr, d_stats ? d_stats + 2 * (size_t)h0 : nullptr, slots);
+  }
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+int mkws_head_group_adam_step(mkws_head_group* g, float lr, float beta1, float beta2, float eps, int step_t, float grad_scale, void* stream) {
+  if (!g) return fail(MKWS_ERR_INVALID_ARG, "head group handle is NULL");
+  if (step_t < 1) return fail(MKWS_ERR_INVALID_ARG, "Adam step index starts at 1");
+  const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, step_t)) / (1.0 - std::pow((double)beta1, step_t));
+  for (int h0 = 0; h0 < g->n; h0 += kGroupHeadsPerLaunch) {
+    const int n = (g->n - h0 < kGroupHeadsPerLaunch) ? g->n - h0 : kGroupHeadsPerLaunch;
+    hipLaunchKernelGGL((head_adam_kernel<true>), dim3((g->nparams + 255) / 256, n), dim3(256), 0, static_cast<hipStream_t>(stream), nullptr, nullptr,
+                       nullptr, nullptr, g->nparams, (float)lr_t, beta1, beta2, eps, grad_scale, g->d_slots + h0);
+  }
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }

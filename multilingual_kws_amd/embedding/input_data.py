@@ -423,6 +423,15 @@ class AudioDataset:
             self._unknown_bank = self._upload_bank(self.unknown_files)
         return self._unknown_bank
 
+    def share_banks(self, other):
+        """Use `other`'s device copies of the unknown-word bank and the background tracks where they hold the same data (K datasets of
+        K keywords over one unknown list and one background directory: decoded and uploaded once).  No draw depends on it."""
+        if self.unknown_files == other.unknown_files and self.model_settings["desired_samples"] == other.model_settings["desired_samples"]:
+            self._unknown_bank = other._unknown()
+        if (self.background_host is not None and other.background_host is not None and self.background_host.shape == other.background_host.shape
+                and np.array_equal(self.background_sizes, other.background_sizes) and np.array_equal(self.background_host, other.background_host)):
+            self._background_dev = other.background_data
+
     # -- random draws (host, vectorised over the batch) ----------------------------------------------
     def _draw_shift(self, size=None):
         m = self.max_time_shift_samples

@@ -17,7 +17,7 @@ import numpy as np
 
 from .. import parallel, weights
 from ..embedding_model import EmbeddingModel
-from ..head import Head, glorot_uniform_params
+from ..head import Head, HeadGroup, glorot_uniform_params
 from . import input_data
 
 CATEGORIES = 3   # silence + unknown + target keyword
@@ -237,6 +237,256 @@ class FrozenHeadTrainer:
             torch.cuda.current_stream(self.device).wait_stream(self.side)
 
 
+class FrozenHeadGroupTrainer:
+    """FrozenHeadTrainer for K keyword heads side by side on ONE frozen embedding (single process).
+
+    Heads of different keywords are independent, so step j of all K of them is one set of launches with the head as a grid dimension
+    (head.HeadGroup) instead of K times four small dependent ones.  Per group of g steps: every target draws its own g batches from
+    its own BatchGroups (its own AudioDataset and generator: the draws of transfer_learn), one forward pass per target writes slab k
+    of a [K, G * bs, features] buffer, then g rounds of HeadGroup.loss_grad(offset=j * bs, rows=bs) + adam_step.  group_limit, the
+    second stream with two alternating buffers and the consumed / ready events are FrozenHeadTrainer's.  Every head ends with the bits
+    FrozenHeadTrainer gives it alone.
+
+    step() performs one optimizer step of EVERY head and returns a [K, 2] device tensor of their {sum of row losses, #correct}, rewritten
+    by the next step()."""
+
+    def __init__(self, embedding, heads, train_dss, batch_size, lr, group=None, overlap=None):
+        import torch
+        self.embedding, self.lr = embedding, lr
+        self.group = heads if isinstance(heads, HeadGroup) else HeadGroup(heads)
+        self.K = len(self.group)
+        self.bs = int(batch_size)
+        self.G = max(1, min(int(group) if group is not None else steps_per_forward(self.bs), embedding.max_batch // self.bs))
+        self.groups = [d if isinstance(d, input_data.BatchGroups) else input_data.BatchGroups(d) for d in train_dss]
+        if len(self.groups) != self.K:
+            raise ValueError(f"{self.K} heads but {len(self.groups)} training streams")
+        for g in self.groups:
+            if g.bs != self.bs:
+                raise ValueError(f"dataset is batched by {g.bs}, trainer by {self.bs}")
+        self.device = embedding.device
+        self.overlap = (self.G >= OVERLAP_FROM_GROUP) if overlap is None else bool(overlap)
+        self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
+        nbuf = 2 if self.overlap else 1
+        rows = self.G * self.bs
+        self.emb = [torch.empty((self.K, rows, embedding.output_dim), dtype=torch.float32, device=self.device) for _ in range(nbuf)]
+        self.labels = [torch.zeros((self.K, rows), dtype=torch.int32, device=self.device) for _ in range(nbuf)]
+        self.consumed = [None] * nbuf            # event: every optimizer step that reads emb[k] / labels[k] has run
+        self.k, self.j, self.g = -1, 0, 0
+        self.forwards = 0
+
+    def _refill(self, g):
+        """Next group of g batches of every target: draws + launch chains on the caller's stream, hand-over to the optimizer stream."""
+        import torch
+        self.k = (self.k + 1) % len(self.emb)
+        main = torch.cuda.current_stream(self.device)
+        n = g * self.bs
+        for h, groups in enumerate(self.groups):
+            spec, labels = groups.take(g)
+            if h == 0 and self.consumed[self.k] is not None:
+                main.wait_event(self.consumed[self.k])       # the steps of two groups ago have finished with these buffers
+            self.embedding.forward(spec, out=self.emb[self.k][h, :n])
+            self.labels[self.k][h, :n].copy_(labels)         # int64 -> int32
+            self.forwards += 1
+        if self.overlap:
+            ready = torch.cuda.Event()
+            ready.record(main)
+            self.side.wait_event(ready)
+        self.g, self.j = g, 0
+
+    def step(self, group_limit=None):
+        """One optimizer step of every head.  group_limit: steps left before the caller needs the heads (end of an epoch)."""
+        import torch
+        if self.j >= self.g:
+            self._refill(self.G if group_limit is None else max(1, min(self.G, int(group_limit))))
+        off = self.j * self.bs
+        self.j += 1
+        if not self.overlap:
+            stats = self.group.loss_grad(self.emb[self.k], self.labels[self.k], rows=self.bs, offset=off)
+            self.group.adam_step(lr=self.lr)
+            return stats
+        with torch.cuda.stream(self.side):
+            stats = self.group.loss_grad(self.emb[self.k], self.labels[self.k], rows=self.bs, offset=off)
+            self.group.adam_step(lr=self.lr)
+            if self.j >= self.g:
+                ev = self.consumed[self.k] = self.consumed[self.k] or torch.cuda.Event()
+                ev.record(self.side)
+        return stats
+
+    accumulate = FrozenHeadTrainer.accumulate
+    finish = FrozenHeadTrainer.finish
+
+    def close(self):
+        """Joins the side stream and drops the group object; the heads stay."""
+        import torch
+        if self.overlap:
+            self.side.synchronize()
+        torch.cuda.current_stream(self.device).synchronize()
+        self.group.close()
+
+
+SIDE_BY_SIDE = 8         # heads trained side by side by transfer_learn_many when side_by_side is None (profiles/finetune_many.txt)
+
+
+def _per_target(what, value, targets):
+    """A sequence aligned with `targets`, or a dict keyed by target -> list aligned with targets."""
+    if isinstance(value, dict):
+        missing = [t for t in targets if t not in value]
+        if missing:
+            raise ValueError(f"{what} has no entry for target(s) {missing}")
+        return [value[t] for t in targets]
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__"):
+        raise ValueError(f"{what} must hold one entry per target (a sequence aligned with targets, or a dict keyed by target)")
+    if len(value) != len(targets):
+        raise ValueError(f"{what} has {len(value)} entries for {len(targets)} targets")
+    return list(value)
+
+
+def transfer_learn_many(
+    targets,
+    train_files,
+    val_files,
+    unknown_files,
+    num_epochs,
+    num_batches,
+    batch_size,
+    primary_lr,
+    model_settings: Dict,
+    base_model_path: os.PathLike,
+    base_model_output: str = "dense_2",
+    UNKNOWN_PERCENTAGE: float = 50.0,
+    bg_datadir: os.PathLike = "/home/mark/tinyspeech_harvard/speech_commands/_background_noise_/",
+    csvlog_dest=None,
+    verbose=1,
+    seed=None,
+    side_by_side=None,
+):
+    """transfer_learn for several target keywords on ONE frozen embedding, their heads trained side by side.
+
+    train_files / val_files: one list per target (a sequence aligned with `targets`, or a dict keyed by target); unknown_files and
+    bg_datadir are shared.  seed: None, an int (target i gets seed + i) or one seed per target; csvlog_dest: None or one path per target.
+    Returns [(name, model, details)] in target order, each entry with transfer_learn's contract, and for the same seed the same bits
+    as transfer_learn(target, ..., backprop_into_embedding=False, seed=seed_i) returns; all models share one EmbeddingModel (as
+    load_models_shared's do), so Head.forward_many / streaming_inferences take them as they are.
+
+    side_by_side heads (default SIDE_BY_SIDE, at most len(targets)) advance together: per group of steps one forward pass per target,
+    then every optimizer step as ONE set of launches for all of them (FrozenHeadGroupTrainer).  More targets run in waves.
+
+    There is no backprop_into_embedding here: that phase trains one embedding per keyword and has nothing to share -- call
+    transfer_learn.  Under torch.distributed with more than one rank the targets run one after the other through transfer_learn (same
+    results; one collective per optimizer step, as there), and each model has its own embedding handle."""
+    from ..embedding_model import OUTPUT_LAYERS
+    targets = list(targets)
+    if len(targets) == 0:
+        raise ValueError("transfer_learn_many needs at least one target")
+    if len(set(targets)) != len(targets):
+        raise ValueError(f"duplicate targets: {sorted(t for t in set(targets) if targets.count(t) > 1)}")
+    train_files = _per_target("train_files", train_files, targets)
+    val_files = _per_target("val_files", val_files, targets)
+    if seed is None:
+        seeds = [None] * len(targets)
+    elif isinstance(seed, (int, np.integer)):
+        seeds = [int(seed) + i for i in range(len(targets))]
+    else:
+        seeds = [None if s is None else int(s) for s in _per_target("seed", seed, targets)]
+    csvs = [None] * len(targets) if csvlog_dest is None else _per_target("csvlog_dest", csvlog_dest, targets)
+    if base_model_output not in OUTPUT_LAYERS:
+        raise ValueError(f"base_model_output {base_model_output!r}: this build cuts the embedding at one of {sorted(OUTPUT_LAYERS)}")
+    if side_by_side is not None and int(side_by_side) < 1:
+        raise ValueError("side_by_side must be at least 1")
+    common = dict(unknown_files=unknown_files, num_epochs=num_epochs, num_batches=num_batches, batch_size=batch_size, primary_lr=primary_lr,
+                  model_settings=model_settings, base_model_path=base_model_path, base_model_output=base_model_output,
+                  UNKNOWN_PERCENTAGE=UNKNOWN_PERCENTAGE, bg_datadir=bg_datadir, verbose=verbose)
+    if parallel.world_size() > 1:
+        return [transfer_learn(t, train_files[i], val_files[i], backprop_into_embedding=False, embedding_lr=0, csvlog_dest=csvs[i],
+                               seed=seeds[i], **common) for i, t in enumerate(targets)]
+    import torch
+    wave = min(len(targets), int(side_by_side) if side_by_side is not None else SIDE_BY_SIDE)
+    group = steps_per_forward(batch_size)
+    embedding, blob = load_base_model(base_model_path, max_batch=max(batch_size * group, 64), base_model_output=base_model_output)
+    feat = embedding.output_dim
+    steps_per_epoch = batch_size * num_batches          # (sic) -- reference :89
+    results, donor = [], None
+    for w0 in range(0, len(targets), wave):
+        idx = list(range(w0, min(w0 + wave, len(targets))))
+        xfers, train_dss, val_dss = [], [], []
+        for i in idx:
+            head = Head(feat, 18, CATEGORIES, max_batch=max(batch_size, 64), params=glorot_uniform_params(feat, 18, CATEGORIES, seeds[i]),
+                        device=embedding.device)
+            xfers.append(TransferLearnedModel(embedding, head, blob, str(base_model_path)))
+            ds = input_data.AudioDataset(model_settings=model_settings, commands=[targets[i]], background_data_dir=bg_datadir,
+                                         unknown_files=unknown_files, unknown_percentage=UNKNOWN_PERCENTAGE,
+                                         spec_aug_params=input_data.SpecAugParams(percentage=80), seed=seeds[i])
+            if donor is None:
+                donor = ds
+            else:
+                ds.share_banks(donor)       # the unknown bank and the background tracks are decoded and uploaded once, not per target
+            tds, vds = _few_shot_datasets(ds, train_files[i], val_files[i], batch_size)
+            train_dss.append(tds)
+            val_dss.append(vds)
+        K = len(idx)
+        frozen = FrozenHeadGroupTrainer(embedding, [x.head for x in xfers], train_dss, batch_size, primary_lr, group=group)
+        histories = [{"loss": [], "accuracy": [], "val_loss": [], "val_accuracy": []} for _ in idx]
+        for epoch in range(num_epochs):
+            acc_stats = torch.zeros((K, 2), dtype=torch.float64, device=embedding.device)
+            for step_i in range(steps_per_epoch):
+                # never across the end of an epoch: validation reads the heads there
+                frozen.accumulate(acc_stats, frozen.step(group_limit=steps_per_epoch - step_i))
+            frozen.finish()
+            train_stats = (acc_stats / max(steps_per_epoch * batch_size, 1)).tolist()
+            for k, i in enumerate(idx):
+                _end_epoch(histories[k], xfers[k], val_dss[k], train_stats[k][0], train_stats[k][1], epoch, num_epochs, steps_per_epoch, verbose,
+                           tag=f"[{targets[i]}] ")
+        frozen.close()
+        for k, i in enumerate(idx):
+            results.append(_finish(xfers[k], histories[k], targets[i], num_epochs, batch_size, num_batches, csvs[i]))
+    return results
+
+
+def _validate(xfer, val_ds):
+    """(mean loss, accuracy) of `xfer` over the validation set (every rank evaluates the full, small set)."""
+    import torch
+    vstats, vseen = np.zeros(2), 0
+    for spec, labels in val_ds:
+        probs = xfer.predict_device(spec[..., 0])
+        lab = labels.long()
+        vstats[0] += float(-torch.log(torch.clamp(probs[torch.arange(len(lab)), lab], min=1e-7)).sum())
+        vstats[1] += float((probs.argmax(1) == lab).sum())
+        vseen += len(lab)
+    return (vstats / max(vseen, 1)).tolist()
+
+
+def _end_epoch(history, xfer, val_ds, tl, ta, epoch, num_epochs, steps_per_epoch, verbose, tag=""):
+    """Validation on the current weights, one more entry in every list of `history`, the Keras-style progress line."""
+    vl, va = _validate(xfer, val_ds)
+    for k, v in zip(("loss", "accuracy", "val_loss", "val_accuracy"), (tl, ta, vl, va)):
+        history[k].append(v)
+    if verbose:
+        print(f"{tag}Epoch {epoch + 1}/{num_epochs} - {steps_per_epoch} steps - loss: {tl:.4f} - accuracy: {ta:.4f} "
+              f"- val_loss: {vl:.4f} - val_accuracy: {va:.4f}")
+
+
+def _finish(xfer, history, target, num_epochs, batch_size, num_batches, csvlog_dest):
+    """The tail of a fine-tune: CSV log, model.history, and the reference's (name, model, details)."""
+    if csvlog_dest is not None:
+        with open(csvlog_dest, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["epoch", "accuracy", "loss", "val_accuracy", "val_loss"])
+            for e in range(num_epochs):
+                w.writerow([e, history["accuracy"][e], history["loss"][e], history["val_accuracy"][e], history["val_loss"][e]])
+    xfer.history = history
+    va = history["val_accuracy"][-1] if history["val_accuracy"] else 0.0
+    name = f"xfer_epochs_{num_epochs}_bs_{batch_size}_nbs_{num_batches}_val_acc_{va:0.2f}_target_{target}"
+    details = dict(num_epochs=num_epochs, batch_size=batch_size, num_batches=num_batches, val_accuracy=va, target=target)
+    return name, xfer, details
+
+
+def _few_shot_datasets(audio_dataset, train_files, val_files, batch_size):
+    AUTOTUNE = input_data.AUTOTUNE
+    init_train_ds = audio_dataset.init_single_target(AUTOTUNE, train_files, is_training=True)
+    init_val_ds = audio_dataset.init_single_target(AUTOTUNE, val_files, is_training=False)
+    return init_train_ds.shuffle(buffer_size=1000).repeat().batch(batch_size), init_val_ds.batch(batch_size)
+
+
 def transfer_learn(
     target,
     train_files,
@@ -288,11 +538,7 @@ def transfer_learn(
         spec_aug_params=input_data.SpecAugParams(percentage=80),
         seed=None if seed is None else int(seed) + 1000003 * rank,   # decorrelated per-rank streams
     )
-    AUTOTUNE = input_data.AUTOTUNE
-    init_train_ds = audio_dataset.init_single_target(AUTOTUNE, train_files, is_training=True)
-    init_val_ds = audio_dataset.init_single_target(AUTOTUNE, val_files, is_training=False)
-    train_ds = init_train_ds.shuffle(buffer_size=1000).repeat().batch(batch_size)
-    val_ds = init_val_ds.batch(batch_size)
+    train_ds, val_ds = _few_shot_datasets(audio_dataset, train_files, val_files, batch_size)
 
     steps_per_epoch = batch_size * num_batches          # (sic) -- reference :89
     train_groups = input_data.BatchGroups(train_ds)      # ONE stream of batches for both phases (the draws continue across them)
@@ -351,32 +597,8 @@ def transfer_learn(
                 embedding = EmbeddingModel(blob, max_batch=max(batch_size, 64), device=embedding.device, output=base_model_output)
                 xfer.embedding, xfer._blob = embedding, blob
                 xfer.base_model_path = "fine-tuned:" + str(base_model_path)
-            # validation: every rank evaluates the full (small) validation set
-            vstats, vseen = np.zeros(2), 0
-            for spec, labels in val_ds:
-                probs = xfer.predict_device(spec[..., 0])
-                lab = labels.long()
-                vstats[0] += float(-torch.log(torch.clamp(probs[torch.arange(len(lab)), lab], min=1e-7)).sum())
-                vstats[1] += float((probs.argmax(1) == lab).sum())
-                vseen += len(lab)
-            vl, va = (vstats / max(vseen, 1)).tolist()
-            for k, v in zip(("loss", "accuracy", "val_loss", "val_accuracy"), (tl, ta, vl, va)):
-                history[k].append(v)
-            if verbose and rank == 0:
-                print(f"Epoch {epoch + 1}/{num_epochs} - {steps_per_epoch} steps - loss: {tl:.4f} - accuracy: {ta:.4f} "
-                      f"- val_loss: {vl:.4f} - val_accuracy: {va:.4f}")
-    if csvlog_dest is not None and rank == 0:
-        with open(csvlog_dest, "w", newline="") as f:
-            w = csv.writer(f)
-            w.writerow(["epoch", "accuracy", "loss", "val_accuracy", "val_loss"])
-            for e in range(num_epochs):
-                w.writerow([e, history["accuracy"][e], history["loss"][e], history["val_accuracy"][e], history["val_loss"][e]])
-    xfer.history = history
-
-    va = history["val_accuracy"][-1] if history["val_accuracy"] else 0.0
-    name = f"xfer_epochs_{num_epochs}_bs_{batch_size}_nbs_{num_batches}_val_acc_{va:0.2f}_target_{target}"
-    details = dict(num_epochs=num_epochs, batch_size=batch_size, num_batches=num_batches, val_accuracy=va, target=target)
-    return name, xfer, details
+            _end_epoch(history, xfer, val_ds, tl, ta, epoch, num_epochs, steps_per_epoch, verbose and rank == 0)
+    return _finish(xfer, history, target, num_epochs, batch_size, num_batches, csvlog_dest if rank == 0 else None)
 
 
 def _specs_for_files(files, model_settings):

@@ -150,3 +150,78 @@ class Head:
         self.step_t += 1
         with torch.cuda.device(self.device):
             _lib.check(self.L.mkws_head_adam_step(self.h, lr, beta1, beta2, eps, self.step_t, grad_scale, _lib.current_stream_ptr()))
+
+
+class HeadGroup:
+    """Several Heads of equal dimensions stepped side by side (mkws_head_group_*, include/mkws.h): one launch per stage for all of
+    them instead of four small dependent launches per head.  Every head computes what Head.loss_grad + Head.adam_step compute on it
+    alone, bit for bit, and stays an ordinary Head; closing the group leaves the heads alive (close the group first)."""
+
+    def __init__(self, heads):
+        import torch
+        self.heads = list(heads)           # also keeps them alive: the group holds device pointers into them
+        self.L = _lib.lib()
+        self.h = None
+        if any(getattr(hd, "h", None) is None for hd in self.heads):
+            raise ValueError("HeadGroup: a head is closed")
+        if len({hd.device for hd in self.heads}) > 1:
+            raise ValueError("HeadGroup: the heads live on different devices")
+        self.device = self.heads[0].device if self.heads else torch.device(f"cuda:{torch.cuda.current_device()}")
+        table = (ctypes.c_void_p * max(len(self.heads), 1))(*[hd.h.value for hd in self.heads])
+        g = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mkws_head_group_create(table, len(self.heads), ctypes.byref(g)))
+        self.h = g
+        self.generation = _lib.next_generation()
+        self.in_dim = self.heads[0].in_dim
+        self._stats = torch.zeros((len(self.heads), 2), dtype=torch.float32, device=self.device)
+
+    def __len__(self):
+        return len(self.heads)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mkws_head_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def loss_grad(self, emb, labels, rows=None, offset=0):
+        """Head k takes rows [offset, offset + rows) of emb[k] (CUDA float32 [K, R, in], contiguous) with labels[k] (CUDA int32
+        [K, R], contiguous); nothing is copied, the stride between heads is the tensors'.  Returns a CUDA [K, 2] tensor of
+        {sum of row losses, number correct} per head that the next call rewrites (asynchronous; .tolist() syncs)."""
+        import torch
+        K = len(self.heads)
+        if emb.dim() != 3 or labels.dim() != 2 or emb.shape[0] != K or labels.shape[0] != K or emb.shape[2] != self.in_dim:
+            raise ValueError(f"HeadGroup.loss_grad: emb {tuple(emb.shape)} / labels {tuple(labels.shape)} for {K} heads of {self.in_dim} inputs")
+        if emb.dtype != torch.float32 or labels.dtype != torch.int32 or not emb.is_contiguous() or not labels.is_contiguous():
+            raise ValueError("HeadGroup.loss_grad takes a contiguous float32 emb and a contiguous int32 labels tensor (no copies are made here)")
+        if emb.device != self.device or labels.device != self.device:
+            raise ValueError(f"HeadGroup.loss_grad: tensors must live on {self.device}")
+        R = emb.shape[1]
+        rows = R - int(offset) if rows is None else int(rows)
+        offset = int(offset)
+        if offset < 0 or rows <= 0 or offset + rows > R or offset + rows > labels.shape[1]:
+            raise ValueError(f"HeadGroup.loss_grad: rows [{offset}, {offset + rows}) outside the {R} rows of emb / {labels.shape[1]} of labels")
+        x = emb.data_ptr() + 4 * offset * self.in_dim
+        y = labels.data_ptr() + 4 * offset
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mkws_head_group_loss_grad(self.h, ctypes.c_void_p(x), emb.stride(0), ctypes.c_void_p(y), labels.stride(0), rows,
+                                                        ctypes.c_void_p(self._stats.data_ptr()), _lib.current_stream_ptr()))
+        return self._stats
+
+    def adam_step(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
+        """Head.adam_step of every member; they must stand at the same step index."""
+        import torch
+        ts = {hd.step_t for hd in self.heads}
+        if len(ts) != 1:
+            raise ValueError(f"HeadGroup.adam_step: the heads stand at different Adam steps {sorted(ts)}")
+        t = ts.pop() + 1
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mkws_head_group_adam_step(self.h, lr, beta1, beta2, eps, t, grad_scale, _lib.current_stream_ptr()))
+        for hd in self.heads:
+            hd.step_t = t
