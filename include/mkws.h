@@ -363,6 +363,29 @@ int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_wi
                        double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
                        int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream);
 
+/* Scoring against ground truth: tpr_fpr's counts (multilingual_kws/embedding/tpr_fpr.py:72-107) for every (head, threshold) lane in
+ * one launch, on what mkws_detect_stream(..., fired_only = 1, ...) left on the same stream: d_events [n_heads, n_thr, event_cap] and
+ * d_counts, with the d_times_ms [n_windows] of that call (an event's time is d_times_ms[window]).  Head n's ground-truth times are
+ * d_gt_ms[d_gt_offsets[n] .. d_gt_offsets[n + 1]) (d_gt_offsets int32 [n_heads + 1], non-decreasing), in the caller's order; the
+ * range may be empty.  d_gt_ms must be a valid pointer even when every range is empty; its values finite.
+ * d_tally int32 [n_heads, n_thr, 4], 16-byte aligned, per lane {found, true_positives_raw, false_negatives, cut}:
+ *   found               = the lane's count;
+ *   true_positives_raw  = detections t for which the scan over the head's ground truth IN LIST ORDER meets an entry >= t - tol before
+ *                         it meets one > t + tol (the scan stops there: on an unsorted list an in-window entry behind an out-of-window
+ *                         one is not seen).  NOT capped to the number of ground-truth entries: that, and every rate derived from it,
+ *                         is host arithmetic on these integers;
+ *   false_negatives     = ground-truth entries g with no detection of the lane in [g - tol, g + tol];
+ *   cut                 = 1 when count > event_cap: the list is incomplete, true_positives_raw and false_negatives are unspecified.
+ * t +- tol and g +- tol are formed in float64 with one IEEE operation each and compared with the other side converted to double
+ * (exact while |t| < 2^53, which the caller checks); an entry on the edge of the window matches.  n_windows == 0 (the detector then
+ * launched nothing and wrote no counts): every lane is {0, 0, entries of its head, 0} and d_counts is not read.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers (d_events may be NULL when event_cap is 0), negative sizes, n_thr < 1 and a
+ * time_tolerance_ms that is NaN or negative; n_heads == 0 returns MKWS_OK with nothing launched.  Asynchronous on `stream`,
+ * allocates nothing, never synchronises: capturable like every other call. */
+int mkws_detect_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_heads, int n_thr, int event_cap,
+                      const int64_t* d_times_ms, int n_windows, const double* d_gt_ms, const int32_t* d_gt_offsets,
+                      double time_tolerance_ms, int32_t* d_tally, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training-batch assembly.  Replaces the per-clip tf.data map of AudioDataset.augment /
  * random_timeshift / random_background_sample / add_background

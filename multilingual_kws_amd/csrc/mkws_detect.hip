@@ -134,6 +134,98 @@ __global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
   if (walker) a.counts[lane_row] = n_events;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Scoring against ground truth (mkws_detect_score, include/mkws.h): tpr_fpr's two scans (multilingual_kws_amd/embedding/tpr_fpr.py,
+// _in_window_sorted_scan) for every (head, threshold) lane, on the fired-only event lists detect_kernel left behind.
+//
+// Both scans are restated so that a lane needs one pass, with the same answers on any list order of the ground truth:
+//  * true positives.  The scan for a detection t stops at the first ground-truth entry above t + tol and has matched when an entry
+//    before that stop is >= t - tol.  Every entry before the stop is <= t + tol, so "one of them is >= t - tol" is "their maximum
+//    is".  Detection times are non-decreasing, t + tol (one rounding, monotone) is too, and so the stop index never moves back from
+//    one detection to the next: the lane walks the ground truth ONCE, keeps the running maximum of what it has passed, and settles
+//    its pending detections whenever an entry exceeds their upper edge.  The pending index is the scan's "stopped" state; it lives in
+//    a register across the pieces of a list longer than the LDS stage.
+//  * false negatives.  The scan for an entry g runs over the lane's detections, stops at the first one above g + tol and has matched
+//    when one before it is >= g - tol; with non-decreasing detections that is the LAST one before the stop: a binary search.
+// All lanes of a workgroup take the ground truth of their head in the same order: one LDS word per step for the whole wave (a
+// broadcast).  A lane's own events come from global memory (lists of neighbouring lanes are event_cap * 16 bytes apart).
+constexpr int kScoreTile = 2048;      // ground-truth entries per LDS stage (16 KB); detector.SCORE_GT_TILE
+
+struct ScoreArgs {
+  const mkws_detect_event* events;
+  const int32_t* counts;
+  const int64_t* times;
+  const double* gt;
+  const int32_t* gt_off;
+  int32_t* tally;
+  double tol;
+  int n_thr, event_cap, n_windows;
+};
+
+__global__ __launch_bounds__(kDetectThreads) void score_kernel(ScoreArgs a) {
+  __shared__ double s_gt[kScoreTile];
+  const int head = blockIdx.x;
+  const int ti = blockIdx.y * kDetectThreads + threadIdx.x;          // this lane's threshold
+  const bool walker = ti < a.n_thr;
+  const size_t lane_row = (size_t)head * a.n_thr + (walker ? ti : 0);
+  const mkws_detect_event* __restrict__ ev = a.events + lane_row * (size_t)a.event_cap;
+  const int64_t* __restrict__ t = a.times;
+  // a stream without windows launched no detector: there are no counts to read
+  const int found = (walker && a.n_windows > 0) ? a.counts[lane_row] : 0;
+  const bool cut = found > a.event_cap;
+  const int c = cut ? 0 : max(found, 0);                              // a cut list is not scored
+  const int last_w = a.n_windows - 1;
+  // the time of event k (a window index outside the stream -- a buffer no detector wrote -- is clamped: wrong answers, no wild access)
+  auto when = [&](int k) { return (double)t[min(max(ev[k].window, 0), last_w)]; };
+  const int g0 = a.gt_off[head];
+  const int G = max(a.gt_off[head + 1] - g0, 0);
+  const double* __restrict__ gt = a.gt + g0;
+  const double tol = a.tol;
+
+  int k = 0;                          // first detection whose scan has not stopped yet
+  double tk = c > 0 ? when(0) : 0.0;  // its time
+  double passed = 0.0;                // maximum of the ground truth passed so far; valid once j > 0
+  int tp = 0, fn = 0;
+  for (int j0 = 0; j0 < G; j0 += kScoreTile) {
+    const int ng = min(kScoreTile, G - j0);
+    for (int i = threadIdx.x; i < ng; i += blockDim.x) s_gt[i] = gt[j0 + i];
+    __syncthreads();
+    if (walker && !cut) {
+      for (int i = 0; i < ng; ++i) {
+        const double g = s_gt[i];
+        // detections whose upper edge this entry exceeds stop here: they matched if something passed before reaches their lower edge
+        while (k < c && g > tk + tol) {
+          tp += (j0 + i > 0) & (passed >= tk - tol);
+          ++k;
+          if (k < c) tk = when(k);
+        }
+        passed = (j0 + i > 0) ? fmax(passed, g) : g;
+        // this entry against the lane's detections: lo = the first one above g + tol
+        const double hi_edge = g + tol, lo_edge = g - tol;
+        int lo = 0, hi = c;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (when(mid) > hi_edge) hi = mid; else lo = mid + 1;
+        }
+        fn += !(lo > 0 && when(lo - 1) >= lo_edge);
+      }
+    }
+    __syncthreads();
+  }
+  if (walker) {
+    for (; k < c; ++k) {              // scans that ran to the end of the list
+      tk = when(k);
+      tp += (G > 0) & (passed >= tk - tol);
+    }
+    int4 out;
+    out.x = found;
+    out.y = tp;
+    out.z = fn;
+    out.w = cut ? 1 : 0;
+    reinterpret_cast<int4*>(a.tally)[lane_row] = out;
+  }
+}
+
 }  // namespace
 
 extern "C" int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_windows, int classes, int target_id,
@@ -173,6 +265,34 @@ extern "C" int mkws_detect_stream(const void* d_probs, int probs_f64, int n_head
     hipLaunchKernelGGL(detect_kernel<double>, dim3(n_heads, groups), dim3(kDetectThreads), 0, static_cast<hipStream_t>(stream), a);
   else
     hipLaunchKernelGGL(detect_kernel<float>, dim3(n_heads, groups), dim3(kDetectThreads), 0, static_cast<hipStream_t>(stream), a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+extern "C" int mkws_detect_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_heads, int n_thr, int event_cap,
+                                 const int64_t* d_times_ms, int n_windows, const double* d_gt_ms, const int32_t* d_gt_offsets,
+                                 double time_tolerance_ms, int32_t* d_tally, void* stream) {
+  if (n_heads < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
+  if (!(time_tolerance_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "time_tolerance_ms must be >= 0");
+  if (!d_counts || !d_times_ms || !d_gt_ms || !d_gt_offsets || !d_tally || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_heads == 0) return MKWS_OK;
+  const int groups = (n_thr + kDetectThreads - 1) / kDetectThreads;
+  if (groups > 65535) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per call", n_thr, 65535 * kDetectThreads);
+  ScoreArgs a;
+  a.events = d_events;
+  a.counts = d_counts;
+  a.times = d_times_ms;
+  a.gt = d_gt_ms;
+  a.gt_off = d_gt_offsets;
+  a.tally = d_tally;
+  a.tol = time_tolerance_ms;
+  a.n_thr = n_thr;
+  a.event_cap = event_cap;
+  a.n_windows = n_windows;
+  // whole waves, no more of them than there are thresholds to walk (a curve of 20 thresholds is one wave per head)
+  const int threads = groups > 1 ? kDetectThreads : (n_thr + 63) / 64 * 64;
+  hipLaunchKernelGGL(score_kernel, dim3(n_heads, groups), dim3(threads), 0, static_cast<hipStream_t>(stream), a);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }

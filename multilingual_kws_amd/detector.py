@@ -2,7 +2,8 @@
 
 SingleTargetRecognizeCommands (embedding/single_target_recognize_commands.py) stepped over every window of a stream, for N keyword
 heads x T detection thresholds in one launch.  The host class is the specification: labels, is_new_command and the float64 scores
-are equal bit for bit (tests/test_detector_device.py)."""
+are equal bit for bit (tests/test_detector_device.py).  score_on_device goes on to mkws_detect_score: the fires of every lane matched
+against ground-truth times on the device, embedding/tpr_fpr.py being the specification (tests/test_operating_curve_gpu.py)."""
 import ctypes
 
 import numpy as np
@@ -113,3 +114,84 @@ def detect_on_device(probs, times_ms, thresholds, average_window_duration_ms, su
             cap = W                                                    # a lane cannot have more events than windows
         events = out[cwords:].view(EVENT_DTYPE).reshape(N, T, cap)
         return DetectResult(counts, events, d_scores.cpu().numpy() if trace else None, d_flags.cpu().numpy() if trace else None)
+
+
+SCORE_GT_TILE = 2048      # ground-truth entries of a head the score kernel stages in LDS at a time (kScoreTile, csrc/mkws_detect.hip)
+
+
+def pack_groundtruth(gt_times_per_head, n_heads):
+    """Per-head lists of ground-truth times (any order, may be empty) -> (float64 values back to back, int32 offsets [n_heads + 1])."""
+    lists = [np.asarray(g, dtype=np.float64).reshape(-1) for g in gt_times_per_head]
+    if len(lists) != n_heads:
+        raise ValueError(f"{len(lists)} ground-truth lists for {n_heads} heads")
+    values = np.concatenate(lists) if lists else np.zeros(0, np.float64)
+    if not np.all(np.isfinite(values)):
+        raise ValueError("ground-truth times must be finite")
+    if values.size >= 2 ** 31:
+        raise ValueError("too many ground-truth entries")
+    offsets = np.zeros(n_heads + 1, np.int32)
+    np.cumsum([g.size for g in lists], out=offsets[1:])
+    return np.ascontiguousarray(values), offsets
+
+
+def score_on_device(probs, times_ms, thresholds, gt_times_per_head, time_tolerance_ms, average_window_duration_ms, suppression_ms, minimum_count,
+                    target_id=2):
+    """The fires of N heads x T thresholds (detect_on_device(..., fired_only=True)) matched against each head's ground-truth times on the
+    device (mkws_detect_score): -> int32 [N, T, 3] = (found, true_positives_raw, false_negatives) per lane, the three integers
+    embedding/tpr_fpr.tpr_fpr derives everything from (true_positives_raw is not yet capped to the number of occurrences).  probs,
+    times_ms, thresholds as detect_on_device; gt_times_per_head: N lists of times in ms, in the order tpr_fpr would be given them.
+    One upload (times, thresholds, ground truth, offsets), two launches, one copy of 16 * N * T bytes: no event list reaches the host."""
+    import torch
+    times = check_times(times_ms)
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if thr.size < 1:
+        raise ValueError("at least one threshold")
+    if not average_window_duration_ms >= 0:
+        raise ValueError("average_window_duration_ms must be >= 0")
+    tol = float(time_tolerance_ms)
+    if not tol >= 0:
+        raise ValueError("time_tolerance_ms must be >= 0")
+    # the device forms t +- tol in float64; CPython does so too for a float tolerance and exactly for an int one: the same while both fit 2^53
+    span = max(abs(int(times[0])), abs(int(times[-1]))) if times.size else 0
+    if span > 2 ** 53 or (np.isfinite(tol) and span + tol > 2 ** 53):
+        raise ValueError("times_ms (and times_ms +- time_tolerance_ms) must lie within +-2**53 milliseconds: they are compared as float64")
+    gt, offsets = pack_groundtruth(gt_times_per_head, len(probs))       # refused before anything is uploaded
+    if not torch.is_tensor(probs):
+        a = np.asarray(probs)
+        probs = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)).cuda()
+    if probs.dim() != 3 or not probs.is_cuda or probs.dtype not in (torch.float32, torch.float64):
+        raise ValueError("probs must be a CUDA tensor or numpy array [heads, windows, classes] of float32 or float64")
+    N, W, C = probs.shape
+    if W != times.shape[0]:
+        raise ValueError(f"{W} windows but {times.shape[0]} timestamps")
+    if not 0 <= int(target_id) < C:
+        raise ValueError(f"target_id {target_id} outside [0, {C})")
+    T = int(thr.size)
+    if N == 0:
+        return np.zeros((0, T, 3), np.int32)
+    probs = probs.contiguous()
+    L = _lib.lib()
+    dev = probs.device
+    with torch.cuda.device(dev):
+        # one upload of 8-byte words: int64 times, the bit patterns of the float64 thresholds and ground truth, the int32 offsets in pairs
+        off_words = np.zeros((N + 2) // 2 * 2, np.int32)
+        off_words[:N + 1] = offsets
+        host_in = np.concatenate([times, thr.view(np.int64), gt.view(np.int64), off_words.view(np.int64)])
+        d_in = torch.from_numpy(host_in).to(dev, non_blocking=True)
+        p_times = d_in.data_ptr()
+        p_thr, p_gt, p_off = p_times + 8 * W, p_times + 8 * (W + T), p_times + 8 * (W + T + gt.size)
+        cap = event_capacity(times, suppression_ms, fired_only=True)
+        d_events = torch.empty(2 * N * T * cap, dtype=torch.int64, device=dev)
+        d_counts = torch.empty(N * T, dtype=torch.int32, device=dev)
+        d_tally = torch.empty((N, T, 4), dtype=torch.int32, device=dev)
+        stream = _lib.current_stream_ptr()
+        _lib.check(L.mkws_detect_stream(
+            probs.data_ptr(), int(probs.dtype == torch.float64), N, W, C, int(target_id), p_times, p_thr, T,
+            float(average_window_duration_ms), float(suppression_ms), int(minimum_count), 1, d_events.data_ptr(), cap, d_counts.data_ptr(),
+            None, None, stream))
+        _lib.check(L.mkws_detect_score(d_events.data_ptr(), d_counts.data_ptr(), N, T, cap, p_times, W, p_gt, p_off, tol, d_tally.data_ptr(), stream))
+        tally = d_tally.cpu().numpy()                                  # the call's one synchronisation: 16 bytes per lane
+    if tally[:, :, 3].any():
+        n, k = (int(x[0]) for x in np.nonzero(tally[:, :, 3]))
+        raise RuntimeError(f"head {n}, threshold {k}: {int(tally[n, k, 0])} fires for an event list of {cap}; the list was cut and cannot be scored")
+    return np.ascontiguousarray(tally[:, :, :3])

@@ -8,7 +8,9 @@ any number of few-shot heads are applied to it.  The detector runs on the device
 every keyword head and every detection threshold over the stream in one launch (mkws_detect_stream, ..detector);
 SingleTargetRecognizeCommands and detect() are its host restatement -- the yardstick the device path is held to bit
 for bit, and the path for hosts without a GPU.  StreamTarget / eval_stream_test (:188-241) are the per-keyword entry points run.py drives; multi_keyword_detections is
-their multi-keyword form on ONE shared embedding pass (run.py:89-152 runs one full model per keyword)."""
+their multi-keyword form on ONE shared embedding pass (run.py:89-152 runs one full model per keyword).  operating_curves /
+multi_keyword_operating_curves go on from the detector to tpr_fpr's summary per keyword and threshold without leaving the device
+(mkws_detect_score); tpr_fpr.tpr_fpr is their yardstick and their path on a host without a GPU."""
 import os
 import pickle
 from dataclasses import dataclass
@@ -462,6 +464,157 @@ def detect_many(inferences, flags: StreamFlags, thresholds, sample_rate=16000, d
                 times = [t_ms[w] for w in ev["window"].tolist()]
                 out[n][thr] = ([[kw, t] for t in times], [[kw, t, s] for t, s in zip(times, ev["score"].tolist())])
     return out[0] if single else out
+
+
+def _groundtruth_times(groundtruth, keywords):
+    """Per keyword its ground-truth times in the caller's order: from rows (keyword, time_ms) as run.py reads its CSV, or a dict."""
+    if isinstance(groundtruth, dict):
+        return [list(groundtruth.get(kw, [])) for kw in keywords]
+    rows = list(groundtruth)
+    return [[t for k, t in rows if k == kw] for kw in keywords]
+
+
+def summary_from_tally(keyword, thresh, found, true_positives_raw, false_negatives, n_gt, duration_s, num_nontarget_words=None):
+    """tpr_fpr.tpr_fpr's summary dict from the three integers of a (keyword, threshold) lane (..detector.score_on_device), in tpr_fpr's own
+    expressions.  -> (dict, whether the true-positive count was capped to n_gt, where tpr_fpr prints its warning)."""
+    true_positives = true_positives_raw
+    capped = true_positives > n_gt
+    if capped:
+        true_positives = n_gt
+    false_positives = found - true_positives
+    result = dict(
+        keyword=keyword,
+        tpr=true_positives / n_gt,
+        thresh=thresh,
+        true_positives=true_positives,
+        false_positives=false_positives,
+        false_negatives=false_negatives,
+        false_rejections_per_instance=false_negatives / n_gt,
+        false_accepts_per_hour=false_positives / duration_s * 3600,
+        groundtruth_positives=n_gt,
+    )
+    if num_nontarget_words is not None:
+        result["fpr"] = false_positives / num_nontarget_words
+    return result, capped
+
+
+def operating_curves(inferences, flags: StreamFlags, thresholds, groundtruth, keywords=None, sample_rate=16000, data_samples=None,
+                     duration_s=None, num_nontarget_words=None):
+    """The operating curve of every keyword of a stream: tpr_fpr.tpr_fpr's summary dict (true-positive rate, false accepts per hour, ...)
+    at every threshold, for detect_many's detections matched against `groundtruth` within flags.time_tolerance_ms.
+
+    inferences, thresholds, keywords, sample_rate, data_samples as detect_many.  groundtruth: rows (keyword, time_ms) as run.py reads
+    them from its CSV, or a dict keyword -> times; each keyword's times are used in the order given (tpr_fpr expects them ascending and
+    stops its scan early on a list that is not).  duration_s: default data_samples / sample_rate, and without data_samples the samples
+    the windows cover, ((windows - 1) * stride + clip) / sample_rate.
+    -> for [W, 3] input a list over thresholds of the dicts tpr_fpr(keyword, threshold, detect(...)[0], times, duration_s,
+    flags.time_tolerance_ms, num_nontarget_words) returns, equal to them key for key, int for int and float for float; a list of N such
+    lists otherwise.  A keyword without ground truth raises ZeroDivisionError, as tpr_fpr does.  tpr_fpr's "WARNING: weird timing issue"
+    (more matched detections than occurrences; the count is capped) is printed once per call with the number of lanes it applied to.
+    CUDA tensors, and numpy input on a host with a GPU, stay on the device: the detector and the matching are two launches
+    (..detector.score_on_device) and three integers per (keyword, threshold) come back instead of the event lists.  numpy input on a
+    host without a GPU loops over detect() and tpr_fpr."""
+    import torch
+    from .tpr_fpr import tpr_fpr
+    thresholds = list(thresholds)
+    as_list = isinstance(inferences, (list, tuple))
+    on_device = torch.is_tensor(inferences[0] if as_list and len(inferences) else inferences)
+    if as_list:
+        inferences = (torch.stack(list(inferences)) if on_device else np.stack([np.asarray(x) for x in inferences])) if len(inferences) \
+            else np.zeros((0, 0, 3), np.float32)
+    elif not on_device:
+        inferences = np.asarray(inferences)
+    single = not as_list and inferences.ndim == 2
+    if single:
+        inferences = inferences[None]
+    if inferences.ndim != 3:
+        raise ValueError("inferences must be [windows, classes] or [keywords, windows, classes]")
+    N = inferences.shape[0]
+    keywords = [flags.target_keyword] * N if keywords is None else list(keywords)
+    if len(keywords) != N:
+        raise ValueError(f"{len(keywords)} keywords for {N} rows of inferences")
+    tol = flags.time_tolerance_ms
+    if not tol >= 0:
+        raise ValueError("time_tolerance_ms must be >= 0")
+    gt = _groundtruth_times(groundtruth, keywords)
+    if not all(np.isfinite(np.asarray(g, dtype=np.float64)).all() for g in gt):
+        raise ValueError("ground-truth times must be finite")
+    clip = int(flags.clip_duration_ms * sample_rate / 1000)
+    stride = int(flags.clip_stride_ms * sample_rate / 1000)
+    offsets = window_offsets(data_samples, clip, stride) if data_samples is not None else [i * stride for i in range(inferences.shape[1])]
+    if inferences.shape[1] < len(offsets):
+        raise IndexError(f"index {inferences.shape[1]} is out of bounds: {inferences.shape[1]} rows of inferences for {len(offsets)} windows")
+    if duration_s is None:
+        duration_s = (data_samples if data_samples is not None else (inferences.shape[1] - 1) * stride + clip) / sample_rate
+    capped = 0
+    if not on_device and not torch.cuda.is_available():
+        import contextlib
+        import dataclasses
+        import io
+        curves = []
+        said = io.StringIO()
+        for n in range(N):
+            kw_flags = dataclasses.replace(flags, target_keyword=keywords[n])
+            curve = []
+            for thr in thresholds:
+                found = detect(inferences[n], kw_flags, thr, sample_rate, data_samples)[0]
+                with contextlib.redirect_stdout(said):
+                    curve.append(tpr_fpr(keywords[n], thr, found, gt[n], duration_s, tol, num_nontarget_words))
+            curves.append(curve)
+        capped = said.getvalue().count("WARNING: weird timing issue")
+    else:
+        if len(flags.labels()) != inferences.shape[2]:
+            raise ValueError("The results for recognition should contain {} elements, but there are {} produced".format(
+                len(flags.labels()), inferences.shape[2]))
+        from ..detector import score_on_device
+        t_ms = [int(off * 1000 / sample_rate) for off in offsets]
+        curves = [[] for _ in range(N)]
+        if thresholds:
+            tally = score_on_device(inferences[:, :len(offsets)], t_ms, thresholds, gt, tol, flags.average_window_duration_ms,
+                                    flags.suppression_ms, flags.minimum_count, target_id=2).tolist()
+            for n in range(N):
+                n_gt = len(gt[n])
+                for k, thr in enumerate(thresholds):
+                    result, was_capped = summary_from_tally(keywords[n], thr, *tally[n][k], n_gt, duration_s, num_nontarget_words)
+                    capped += was_capped
+                    curves[n].append(result)
+    if capped:
+        print(f"WARNING: weird timing issue ({capped} of {N * len(thresholds)} keyword x threshold lanes: true positives capped to the ground-truth count)")
+    return curves[0] if single else curves
+
+
+def multi_keyword_operating_curves(keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds=1200,
+                                   average_window_duration_ms=100, suppression_ms=500, time_tolerance_ms=750, num_nontarget_words=None):
+    """From a recording to {keyword: [tpr_fpr's dict per threshold]} for N keywords: one pass over the wav on the shared embedding
+    (streaming_inferences(as_device=True), as multi_keyword_detections), then operating_curves on the device tensor -- the probabilities,
+    the detections and the matching never visit the host.  groundtruth_csv: rows `keyword,time_ms` (run.py's ground-truth file).  The
+    other arguments are multi_keyword_detections' flags; the recording's duration is its sample count over its sample rate."""
+    import csv
+    keywords, models, thresholds = list(keywords), list(models), list(thresholds)
+    if len(models) != len(keywords) or len(set(keywords)) != len(keywords):
+        raise ValueError(f"discrepancy: {len(models)} models provided for {len(set(keywords))} keywords")
+    if inference_chunk_len_seconds <= 0:
+        raise ValueError("inference_chunk_len_seconds must be positive")
+    with open(wav, "rb") as f:
+        audio, sample_rate = input_data.decode_wav(f.read())
+    with open(groundtruth_csv, "r") as fh:
+        groundtruth_data = [(row[0], float(row[1])) for row in csv.reader(fh) if row]
+    model_settings = input_data.standard_microspeech_model_settings(label_count=3)
+    flags = StreamFlags(wav=wav, ground_truth=groundtruth_csv, target_keyword=keywords[0] if keywords else "", detection_thresholds=thresholds,
+                        average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms,
+                        time_tolerance_ms=time_tolerance_ms, max_chunk_length_sec=inference_chunk_len_seconds)
+    by_embedding = {}
+    for i, m in enumerate(models):                                  # one pass per distinct embedding (normally one)
+        by_embedding.setdefault(id(m.embedding), []).append(i)
+    curves = {}
+    for idxs in by_embedding.values():
+        got = streaming_inferences([models[i] for i in idxs], model_settings, audio, sample_rate, 1000, 20,
+                                   max_chunk_length_sec=inference_chunk_len_seconds, as_device=True)
+        per = operating_curves(got, flags, thresholds, groundtruth_data, keywords=[keywords[i] for i in idxs], sample_rate=sample_rate,
+                               data_samples=audio.shape[0], num_nontarget_words=num_nontarget_words)
+        for i, curve in zip(idxs, per):
+            curves[keywords[i]] = curve
+    return {kw: curves[kw] for kw in keywords}
 
 
 def calculate_streaming_accuracy(model, model_settings, flag_list, existing_inferences=None):
