@@ -387,6 +387,34 @@ int mkws_detect_score(const mkws_detect_event* d_events, const int32_t* d_counts
                       double time_tolerance_ms, int32_t* d_tally, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Classification ROC counts: roc_single_target / roc_sc / calc_roc
+ * (multilingual_kws/embedding/transfer_learning_analysis.py:181-222, :345-404) for n_heads keyword heads and n_thr thresholds in one
+ * launch.  d_probs [n_heads, n_rows, classes] float32 (what mkws_heads_forward writes).  Head h's positive clips are the rows
+ * d_pos_rows[d_pos_offsets[h] .. d_pos_offsets[h + 1]) of ITS OWN probability plane, its negatives d_neg_rows[d_neg_offsets[h] ..
+ * d_neg_offsets[h + 1]) (offsets int32 [n_heads + 1], non-decreasing and inside their list: the caller checks).  A row may appear
+ * several times and then counts several times (the reference counts list entries); either range may be empty.  An entry outside
+ * [0, n_rows) is never dereferenced: it is skipped and counted in d_invalid[h] (int32 [n_heads], entries of both lists).
+ * d_thresholds double [n_thr], ascending (non-decreasing, equal neighbours allowed) and NaN-free: the caller checks; an unsorted list
+ * gives wrong counts, never a wild access.
+ * d_counts int32 [n_heads, n_thr, 2]: {positive entries with score > thr[j], negative entries with score > thr[j]}, exact, the same
+ * on every run.  The comparison is (double)score > thr[j] -- the float32 probability widened, strictly greater, which is what NumPy
+ * computes for a float32 array against an np.float64 threshold; it is NOT the float32 comparison.  A NaN score is above no threshold.
+ *   mode 0 (roc_single_target): score = p[row][pos_class] on both sides; neg_class is ignored.
+ *   mode 1 (roc_sc / calc_roc on evaluate_files_multiclass dicts): a = first index of the row's maximum (np.argmax); a positive entry
+ *     takes part only when a == pos_class, a negative one only when a != neg_class; score = p[row][a].  A row holding a NaN is never
+ *     counted.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers (d_probs may be NULL when n_rows is 0), negative sizes, n_thr < 1, classes < 1, a mode
+ * other than 0 / 1, pos_class (mode 1: and neg_class) outside [0, classes); MKWS_ERR_UNSUPPORTED for n_thr above
+ * MKWS_ROC_MAX_THRESHOLDS (the thresholds and one bin each live in LDS): run a longer list in pieces.  n_heads == 0 returns MKWS_OK
+ * with nothing launched (the buffers may then be NULL); n_rows == 0 with empty lists writes zero counts.  Asynchronous on `stream`, allocates nothing, never
+ * synchronises: capturable like every other call.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_ROC_MAX_THRESHOLDS 4096
+int mkws_roc_count(const float* d_probs, int n_heads, int n_rows, int classes, const int32_t* d_pos_rows, const int32_t* d_pos_offsets,
+                   const int32_t* d_neg_rows, const int32_t* d_neg_offsets, const double* d_thresholds, int n_thr, int mode,
+                   int pos_class, int neg_class, int32_t* d_counts, int32_t* d_invalid, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-batch assembly.  Replaces the per-clip tf.data map of AudioDataset.augment /
  * random_timeshift / random_background_sample / add_background
  * (multilingual_kws/embedding/input_data.py:141-157,227-304) and spec_augment (:306-369).

@@ -3,7 +3,8 @@ the reference's own import path."""
 import importlib
 import sys
 
-_MODULES = ("input_data", "transfer_learning", "batch_streaming_analysis", "single_target_recognize_commands", "distance_filtering", "tpr_fpr")
+_MODULES = ("input_data", "transfer_learning", "batch_streaming_analysis", "single_target_recognize_commands", "distance_filtering", "tpr_fpr",
+            "transfer_learning_analysis")
 
 for _m in _MODULES:
     _mod = importlib.import_module("multilingual_kws_amd.embedding." + _m)

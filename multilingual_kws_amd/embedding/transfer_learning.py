@@ -654,3 +654,70 @@ def evaluate_files_single_target(files_to_evaluate: List[os.PathLike], target_id
     specs = _specs_for_files(files_to_evaluate, model_settings)
     preds = model.predict(np.expand_dims(specs, -1))
     return preds[:, target_id], preds
+
+
+def _shared_embedding(models):
+    """The one embedding handle and the heads of `models`; ValueError unless they share it (load_models_shared / transfer_learn_many)."""
+    models = list(models)
+    if not models:
+        raise ValueError("at least one model")
+    embedding = models[0].embedding
+    if any(m.embedding is not embedding for m in models):
+        raise ValueError("the models do not share one embedding handle: load them with load_models_shared, or train them with "
+                         "transfer_learn_many")
+    heads = [m.head for m in models]
+    if len({(h.in_dim, h.hidden, h.classes) for h in heads}) != 1:
+        raise ValueError("the models' heads differ in their dimensions")
+    return embedding, heads
+
+
+def evaluate_files_many(files_to_evaluate: List[os.PathLike], models, model_settings: Dict, as_device=False):
+    """evaluate_files_single_target for K models on one embedding handle: every clip is decoded, featurised and embedded ONCE (in
+    batches of the handle's max_batch) and all K heads run in one launch per batch.  -> preds [K, N, classes], numpy or (as_device=True)
+    a CUDA tensor; preds[k] has the bits of evaluate_files_single_target(files_to_evaluate, 2, models[k], model_settings)[1]."""
+    import torch
+    embedding, heads = _shared_embedding(models)
+    files = [os.fspath(f) for f in files_to_evaluate]
+    n_samples, mb = model_settings["desired_samples"], embedding.max_batch
+    specs = []                                           # featurised once, whatever happens to the embedding passes below
+    with torch.cuda.device(embedding.device):
+        for s in range(0, len(files), mb):
+            audio = np.stack([input_data._read_wav(f, n_samples) for f in files[s:s + mb]])
+            specs.append(input_data.to_micro_spectrogram(model_settings, torch.from_numpy(audio).to(embedding.device)))
+
+    def run():
+        preds = torch.empty((len(heads), len(files), heads[0].classes), dtype=torch.float32, device=embedding.device)
+        for i, spec in enumerate(specs):
+            preds[:, i * mb:i * mb + spec.shape[0]] = Head.forward_many(heads, embedding.forward(spec))
+        if as_device:
+            torch.cuda.current_stream(embedding.device).synchronize()     # checked() looks at the handle after the passes have run
+            return preds
+        return preds.cpu().numpy()
+
+    # the exchange-failure check of TransferLearnedModel.predict: a poisoned batch is never handed back
+    return embedding.checked(run)
+
+
+def classification_curves(models, target_files, unknown_files, model_settings: Optional[Dict] = None, thresholds=None, multiclass=False):
+    """The classification ROC of K keyword models on one embedding handle (the reference's batch_transfer_learning_analysis.py:114-171
+    followed by roc_single_target, one keyword at a time there).  target_files / unknown_files: K lists of WAV paths, model k's target
+    clips and its non-target clips; the lists may overlap (one non-target pool for all keywords is the usual case) and a path listed
+    twice counts twice.  Every distinct path is embedded once, all heads run in one launch per batch (evaluate_files_many) and the counts
+    are taken on the device (transfer_learning_analysis.roc_many): no probability leaves the device.
+    -> one dict per keyword: tprs, fprs, threshs (what roc_single_target -- multiclass=True: roc_sc -- returns for that keyword's
+    confidences, at `thresholds`, default the reference's 101), n_target, n_unknown."""
+    from .transfer_learning_analysis import roc_many
+    models = list(models)
+    _shared_embedding(models)
+    target_files, unknown_files = [list(x) for x in target_files], [list(x) for x in unknown_files]
+    if len(target_files) != len(models) or len(unknown_files) != len(models):
+        raise ValueError(f"{len(target_files)} lists of target files and {len(unknown_files)} of unknown files for {len(models)} models")
+    if model_settings is None:
+        model_settings = input_data.standard_microspeech_model_settings(label_count=3)
+    row = {}                                             # distinct paths in first-seen order
+    positives = [[row.setdefault(os.fspath(f), len(row)) for f in fs] for fs in target_files]
+    negatives = [[row.setdefault(os.fspath(f), len(row)) for f in fs] for fs in unknown_files]
+    preds = evaluate_files_many(list(row), models, model_settings, as_device=True)
+    curves = roc_many(preds, positives, negatives, thresholds=thresholds, multiclass=multiclass, target_id=2, negative_class=1)
+    return [dict(tprs=tprs, fprs=fprs, threshs=threshs, n_target=len(positives[k]), n_unknown=len(negatives[k]))
+            for k, (tprs, fprs, threshs) in enumerate(curves)]
