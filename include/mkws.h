@@ -415,6 +415,53 @@ int mkws_roc_count(const float* d_probs, int n_heads, int n_rows, int classes, c
                    int pos_class, int neg_class, int32_t* d_counts, int32_t* d_invalid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * k-means of the MSWC outlier filter: what distance_filtering.cluster_and_sort
+ * (multilingual_kws/embedding/distance_filtering.py:30-83) does per keyword with sklearn.cluster.KMeans(n_clusters, random_state).fit
+ * and np.linalg.norm, for n_groups keywords in one launch.  multilingual_kws_amd/kmeans.py (kmeans_host) is the specification:
+ * mean-centring, greedy k-means++ with n_trials local trials, Lloyd with sklearn's two stopping rules (labels unchanged; squared centre
+ * shift <= tol * mean column variance), the final assignment; float64 arithmetic on the widened float32 points throughout.  The random
+ * draws are data-independent uniforms and are made by the host (kmeans.kmeans_draws).  An empty cluster in a Lloyd step is NOT restated
+ * (sklearn relocates a centre there): it is reported, and the caller runs sklearn for that group.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_KMEANS_MAX_POINTS 1024        /* points of one group */
+#define MKWS_KMEANS_MAX_CLUSTERS 16
+#define MKWS_KMEANS_MAX_CENTER_VALUES 16384 /* n_clusters * dim: the float64 centres of a group live in LDS (128 KB) ... */
+#define MKWS_KMEANS_MAX_LDS_VALUES 17408    /* ... beside the float64 column means: (n_clusters + 1) * dim */
+#define MKWS_KMEANS_MAX_TRIALS 64          /* n_trials (sklearn's is 2 + int(log(n_clusters)) <= 4 at the cluster cap) */
+
+/* d_x float32 [rows, dim]; group g = rows d_offsets[g] .. d_offsets[g+1]  (int32 [n_groups+1], non-decreasing and inside d_x: the
+ * caller checks).
+ * d_draws double [n_groups, 1 + (n_clusters-1) * n_trials]: u0, then U[1], U[2], ... (n_trials each; made by the host).
+ * d_centers float32 [n_groups, n_clusters, dim] (the float64 result rounded once); d_centers_f64 (optional, may be NULL) the unrounded
+ * values; d_labels int32 [rows]; d_init int32 [n_groups, n_clusters] (optional, may be NULL) = the rows (within the group) k-means++
+ * picked; d_info int32 [n_groups, 4] = {status, n_iter, stop reason, smallest cluster size}; stop reason 0 = the labels did not change,
+ * 1 = the centre shift fell to the tolerance, 2 = max_iter reached.
+ *   status 0 ok;
+ *   status 1 = a Lloyd step met an empty cluster: d_info = {1, the iteration, 0, 0}; the other outputs of the group are unspecified
+ *              (finite or not; never a wild access);
+ *   status 2 = the group has fewer points than n_clusters or more than MKWS_KMEANS_MAX_POINTS: d_info = {2, 0, 0, 0}, nothing else is
+ *              written for it.  Neighbouring groups of the same call are not affected by either.
+ * One workgroup per group; no floating-point atomics, no workspace: two calls on the same input write the same bytes.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers, negative sizes, dim < 1, n_clusters < 1, n_trials < 1, max_iter < 1 and a NaN or
+ * negative tol; MKWS_ERR_UNSUPPORTED above MKWS_KMEANS_MAX_CLUSTERS, MKWS_KMEANS_MAX_CENTER_VALUES, MKWS_KMEANS_MAX_LDS_VALUES or
+ * MKWS_KMEANS_MAX_TRIALS.  n_groups == 0 returns MKWS_OK with nothing launched.  Asynchronous on `stream`, allocates nothing, never
+ * synchronises: capturable like every other call. */
+int mkws_kmeans_fit(const float* d_x, int dim, const int32_t* d_offsets, int n_groups, int n_clusters, const double* d_draws,
+                    int n_trials, int max_iter, double tol, float* d_centers, double* d_centers_f64, int32_t* d_labels,
+                    int32_t* d_init, int32_t* d_info, void* stream);
+
+/* Distance of every row to the nearest centre of ITS group: d_x float32 [n_rows, dim], d_group int32 [n_rows] (rows in any order; a
+ * batch may straddle groups), d_centers float32 [n_groups, n_clusters, dim] (what mkws_kmeans_fit wrote).
+ * d_dist float32 [n_rows] = (float) sqrt( sum_d ((double)c[d] - (double)x[d])^2 ), the minimum over the group's centres taken on the
+ * float64 values; d_which int32 [n_rows] = the first index of that minimum.  A row whose group is outside [0, n_groups) is never
+ * dereferenced against a centre: it gets NaN / -1 and is counted in *d_invalid (int32 [1], set by every call that launches).
+ * MKWS_ERR_INVALID_ARG for NULL required pointers (d_centers may be NULL when n_groups is 0), negative sizes, dim < 1 and
+ * n_clusters < 1; MKWS_ERR_UNSUPPORTED above MKWS_KMEANS_MAX_CLUSTERS.  n_rows == 0 returns MKWS_OK with nothing launched and nothing
+ * written.  Asynchronous on `stream`, allocates nothing, never synchronises: capturable like every other call. */
+int mkws_kmeans_nearest(const float* d_x, int dim, int n_rows, const int32_t* d_group, const float* d_centers, int n_groups,
+                        int n_clusters, float* d_dist, int32_t* d_which, int32_t* d_invalid, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-batch assembly.  Replaces the per-clip tf.data map of AudioDataset.augment /
  * random_timeshift / random_background_sample / add_background
  * (multilingual_kws/embedding/input_data.py:141-157,227-304) and spec_augment (:306-369).

@@ -64,6 +64,8 @@ SYMBOLS = [
     ("mkws_detect_stream", _I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
     ("mkws_detect_score", _I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, ctypes.c_double, _P, _P]),
     ("mkws_roc_count", _I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    ("mkws_kmeans_fit", _I, [_P, _I, _P, _I, _I, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    ("mkws_kmeans_nearest", _I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     ("mkws_augment_batch", _I, [_P, _P, _P, ctypes.c_int64, _P, _I, _I, _P, _P]),
     ("mkws_specaug_apply", _I, [_P, _P, _I, _I, _I, _P]),
     ("mkws_specaug_apply_n", _I, [_P, _P, _I, _I, _I, _I, _I, _P]),
