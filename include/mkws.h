@@ -316,6 +316,24 @@ typedef struct mkws_head_group mkws_head_group;
 int mkws_head_group_create(mkws_head* const* heads, int n_heads, mkws_head_group** out);
 void mkws_head_group_destroy(mkws_head_group* g);      /* does not destroy the heads; NULL is a no-op */
 int mkws_head_group_size(const mkws_head_group* g);
+/* Serving with the group as a head table: every row of a batch under the head of the SEGMENT it lies in (K keyword recordings
+ * concatenated, each with its own fine-tuned head), in one launch.  Reads the members' parameters only; the training buffers are not
+ * touched.  d_emb float32 [B, in] is one batch of the concatenation, its first row being global row row_base (>= 0).  Segment s holds
+ * global rows d_seg_offsets[s] .. d_seg_offsets[s + 1] (int32 [n_seg + 1], non-decreasing: the caller checks; a range may be empty; an
+ * unsorted list gives wrong answers, never an access outside the buffers named here: the search over it is bounded by [0, n_seg]) and is
+ * served by member d_seg_head[s] (int32 [n_seg]; one head may serve several segments).  d_probs float32 [B, classes] in row order.
+ * A row's output is, bit for bit, what mkws_head_forward of its head writes for that row: the kernel is that call's -- the K walk in
+ * ascending chunks of 16, the four-wave K split joined in wave order, the epilogue -- and only the mapping of a 16-row tile to heads is
+ * new: a tile that straddles segments (runs of one-row and empty segments included) is finished once per segment it intersects, with the
+ * stores masked to that segment's rows.
+ * A row that lies in no segment, or in a segment whose head index is outside [0, mkws_head_group_size), gets NaN in every class (the
+ * detector treats a NaN score as no event) and is counted in *d_invalid (int32 [1], set by every call that launches); such a head index
+ * is never dereferenced.  Rows outside [0, B) are not written.
+ * MKWS_ERR_UNSUPPORTED unless in % 16 == 0 and hidden <= 32 (the matrix-core path only); MKWS_ERR_INVALID_ARG for NULL pointers and
+ * negative B, n_seg or row_base; B == 0 or n_seg == 0 returns MKWS_OK with nothing launched and nothing written.  Asynchronous on
+ * `stream`, allocates nothing, never synchronises: capturable like every other call. */
+int mkws_head_group_forward_segments(mkws_head_group* g, const float* d_emb, int B, int64_t row_base, const int32_t* d_seg_offsets,
+                                     const int32_t* d_seg_head, int n_seg, float* d_probs, int32_t* d_invalid, void* stream);
 /* mkws_head_loss_grad of head h on the B rows at d_emb + h * emb_stride (stride in floats) with the labels at
  * d_labels + h * label_stride (in int32s), for every h; B at most the smallest max_batch of the group.
  * d_stats (optional, may be NULL): float32 [n_heads][2] = {sum of per-row loss, number of correct rows} of each head; the same
@@ -385,6 +403,34 @@ int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_wi
 int mkws_detect_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_heads, int n_thr, int event_cap,
                       const int64_t* d_times_ms, int n_windows, const double* d_gt_ms, const int32_t* d_gt_offsets,
                       double time_tolerance_ms, int32_t* d_tally, void* stream);
+
+/* mkws_detect_stream with "head" replaced by "segment": n_seg recordings concatenated, each with its own windows, times and
+ * probabilities (K keyword recordings, one fine-tuned head each), in ONE launch.  d_probs [n_rows, classes] float32 or float64
+ * (probs_f64 != 0): what mkws_head_group_forward_segments writes; d_times_ms int64 [n_rows], non-decreasing WITHIN each segment.
+ * Segment s holds rows d_seg_offsets[s] .. d_seg_offsets[s + 1] (int32 [n_seg + 1], non-decreasing with values in [0, n_rows]: the caller
+ * checks; the kernel clamps what it reads into [0, n_rows], so a bad list gives wrong answers, never a wild access).
+ * d_events [n_seg, n_thr, event_cap], d_counts int32 [n_seg, n_thr]; event.window is the index INSIDE the segment, so that segment s of
+ * this call equals mkws_detect_stream(n_heads = 1) on that slice alone, byte for byte: the lookback of a window's average is searched
+ * over [segment start, w] and never leaves the segment.  Counts are written for EVERY segment: an empty one gets 0 (the unsegmented
+ * call launches nothing for zero windows).
+ * Optional trace (either may be NULL): d_scores double [n_rows]; d_flags uint8 [n_thr * n_rows]: the per-segment [n_thr, len_s] blocks
+ * back to back, i.e. segment s, threshold k, window w at n_thr * d_seg_offsets[s] + k * len_s + w.
+ * The argument checks are those of mkws_detect_stream (d_probs and d_times_ms may be NULL when n_rows is 0); n_seg == 0 returns MKWS_OK with nothing launched and nothing written.
+ * Asynchronous on `stream`, allocates nothing, never synchronises: capturable like every other call. */
+int mkws_detect_segments(const void* d_probs, int probs_f64, const int32_t* d_seg_offsets, int n_seg, int n_rows, int classes, int target_id,
+                         const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
+                         double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
+                         int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream);
+
+/* mkws_detect_score on what mkws_detect_segments(..., fired_only = 1, ...) left on the same stream, with that call's d_seg_offsets,
+ * n_rows and d_times_ms: the time of an event of segment s is d_times_ms[d_seg_offsets[s] + window], window clamped into the segment.
+ * Segment s is matched against d_gt_ms[d_gt_offsets[s] .. d_gt_offsets[s + 1]) (int32 [n_seg + 1]).  d_tally int32 [n_seg, n_thr, 4],
+ * 16-byte aligned, the four fields of mkws_detect_score; an empty segment gives {0, 0, entries of its ground truth, 0}.
+ * MKWS_ERR_INVALID_ARG as mkws_detect_score; n_seg == 0 returns MKWS_OK with nothing launched.  Asynchronous on `stream`, allocates
+ * nothing, never synchronises: capturable like every other call. */
+int mkws_detect_score_segments(const mkws_detect_event* d_events, const int32_t* d_counts, const int32_t* d_seg_offsets, int n_seg, int n_rows,
+                               int n_thr, int event_cap, const int64_t* d_times_ms, const double* d_gt_ms, const int32_t* d_gt_offsets,
+                               double time_tolerance_ms, int32_t* d_tally, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Classification ROC counts: roc_single_target / roc_sc / calc_roc

@@ -63,6 +63,8 @@ SYMBOLS = [
     ("mkws_embed_forward_tap", _I, [_P, _P, _I, ctypes.c_char_p, _P, _SZ, _P]),
     ("mkws_detect_stream", _I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
     ("mkws_detect_score", _I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, ctypes.c_double, _P, _P]),
+    ("mkws_detect_segments", _I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
+    ("mkws_detect_score_segments", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_double, _P, _P]),
     ("mkws_roc_count", _I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     ("mkws_kmeans_fit", _I, [_P, _I, _P, _I, _I, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
     ("mkws_kmeans_nearest", _I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
@@ -88,6 +90,7 @@ SYMBOLS = [
     ("mkws_head_group_create", _I, [ctypes.POINTER(_P), _I, ctypes.POINTER(_P)]),
     ("mkws_head_group_destroy", None, [_P]),
     ("mkws_head_group_size", _I, [_P]),
+    ("mkws_head_group_forward_segments", _I, [_P, _P, _I, ctypes.c_int64, _P, _P, _I, _P, _P, _P]),
     ("mkws_head_group_loss_grad", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _I, _P, _P]),
     ("mkws_head_group_adam_step", _I, [_P, _F, _F, _F, _F, _I, _F, _P]),
     # training operators (backprop_into_embedding)

@@ -36,23 +36,37 @@ struct DetectArgs {
   double avg_ms;
   int64_t suppression;   // floor(suppression_ms): for integer times, t - t0 > suppression_ms exactly when t - t0 > floor(suppression_ms)
   int n_windows, classes, target, n_thr, min_count, event_cap, fired_only, never;
+  const int32_t* seg_off;   // SEG only: [gridDim.x + 1] row offsets into a concatenation of n_windows rows
 };
 
-template <typename T>
+// SEG (mkws_detect_segments): blockIdx.x is a segment of a concatenated stream instead of a head over a shared one.  Its windows are
+// rows [base, base + W) of probs AND of times (both clamped into [0, n_windows], so a bad offset list reads nothing outside them); the
+// lookback search below runs over [0, w] of the segment's own slice and so never leaves it; window indices are those inside the segment.
+// With `base` = the first row of the lane's plane in either form, the addressing of the two forms is one expression.
+template <typename T, bool SEG = false>
 __global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
   __shared__ double s_score[kDetectTile];
   __shared__ int64_t s_time[kDetectTile];
   __shared__ uint8_t s_eval[kDetectTile];
   const int head = blockIdx.x;
-  const int W = a.n_windows;
-  const T* __restrict__ p = static_cast<const T*>(a.probs) + (size_t)head * W * a.classes + a.target;
-  const int64_t* __restrict__ t = a.times;
+  size_t base;
+  int W;
+  if (SEG) {
+    const int b0 = min(max(a.seg_off[head], 0), a.n_windows);
+    base = (size_t)b0;
+    W = min(max(a.seg_off[head + 1], b0), a.n_windows) - b0;
+  } else {
+    W = a.n_windows;
+    base = (size_t)head * W;
+  }
+  const T* __restrict__ p = static_cast<const T*>(a.probs) + base * a.classes + a.target;
+  const int64_t* __restrict__ t = SEG ? a.times + base : a.times;
   const int ti = blockIdx.y * kDetectThreads + threadIdx.x;          // this lane's threshold
   const bool walker = ti < a.n_thr;
   const double thr = walker ? a.thr[ti] : 0.0;
   const size_t lane_row = (size_t)head * a.n_thr + (walker ? ti : 0);
   mkws_detect_event* __restrict__ ev = a.events + lane_row * (size_t)a.event_cap;
-  uint8_t* __restrict__ fl = a.flags ? a.flags + lane_row * (size_t)W : nullptr;
+  uint8_t* __restrict__ fl = a.flags ? a.flags + (SEG ? (size_t)a.n_thr * base + (size_t)(walker ? ti : 0) * W : lane_row * (size_t)W) : nullptr;
   const double quarter = a.avg_ms / 4;
   const bool can_change = !a.never;
   bool prev_kw = false;           // the previous top label is the keyword ("_silence_" before anything has fired)
@@ -84,7 +98,7 @@ __global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
       s_score[i] = score;
       s_time[i] = tw;
       s_eval[i] = evaluated;
-      if (a.scores && blockIdx.y == 0) a.scores[(size_t)head * W + w] = score;
+      if (a.scores && blockIdx.y == 0) a.scores[base + w] = score;
     }
     __syncthreads();
     // phase 2: lane = threshold; compares only.  A chunk of windows is read from LDS first (the reads do not depend on the state),
@@ -160,21 +174,30 @@ struct ScoreArgs {
   int32_t* tally;
   double tol;
   int n_thr, event_cap, n_windows;
+  const int32_t* seg_off;   // SEG only, as in DetectArgs
 };
 
+// SEG (mkws_detect_score_segments): blockIdx.x is a segment; an event's window indexes the segment's own slice of times (clamped into
+// it), and the segment's counts were always written (mkws_detect_segments writes 0 for an empty one).
+template <bool SEG = false>
 __global__ __launch_bounds__(kDetectThreads) void score_kernel(ScoreArgs a) {
   __shared__ double s_gt[kScoreTile];
   const int head = blockIdx.x;
+  int seg_base = 0, seg_W = a.n_windows;
+  if (SEG) {
+    seg_base = min(max(a.seg_off[head], 0), a.n_windows);
+    seg_W = min(max(a.seg_off[head + 1], seg_base), a.n_windows) - seg_base;
+  }
   const int ti = blockIdx.y * kDetectThreads + threadIdx.x;          // this lane's threshold
   const bool walker = ti < a.n_thr;
   const size_t lane_row = (size_t)head * a.n_thr + (walker ? ti : 0);
   const mkws_detect_event* __restrict__ ev = a.events + lane_row * (size_t)a.event_cap;
-  const int64_t* __restrict__ t = a.times;
+  const int64_t* __restrict__ t = a.times + seg_base;
   // a stream without windows launched no detector: there are no counts to read
-  const int found = (walker && a.n_windows > 0) ? a.counts[lane_row] : 0;
+  const int found = (walker && seg_W > 0) ? a.counts[lane_row] : 0;
   const bool cut = found > a.event_cap;
   const int c = cut ? 0 : max(found, 0);                              // a cut list is not scored
-  const int last_w = a.n_windows - 1;
+  const int last_w = seg_W - 1;
   // the time of event k (a window index outside the stream -- a buffer no detector wrote -- is clamped: wrong answers, no wild access)
   auto when = [&](int k) { return (double)t[min(max(ev[k].window, 0), last_w)]; };
   const int g0 = a.gt_off[head];
@@ -228,17 +251,12 @@ __global__ __launch_bounds__(kDetectThreads) void score_kernel(ScoreArgs a) {
 
 }  // namespace
 
-extern "C" int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_windows, int classes, int target_id,
-                                  const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
-                                  double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
-                                  int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream) {
-  if (n_heads < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
-  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
-  if (classes < 1 || target_id < 0 || target_id >= classes) return fail(MKWS_ERR_INVALID_ARG, "target_id %d outside [0, %d)", target_id, classes);
-  if (!(average_window_duration_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "average_window_duration_ms must be >= 0 (the host detector would pop its newest entry)");
-  if (std::isnan(suppression_ms)) return fail(MKWS_ERR_INVALID_ARG, "suppression_ms is NaN");
-  if (!d_probs || !d_times_ms || !d_thresholds || !d_counts || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
-  if (n_heads == 0 || n_windows == 0) return MKWS_OK;
+// the launch behind mkws_detect_stream (seg_off NULL: n_planes heads over n_windows shared windows) and mkws_detect_segments (n_planes
+// segments of a concatenation of n_windows rows); the arguments have been checked
+static int launch_detect(const void* d_probs, int probs_f64, int n_planes, int n_windows, const int32_t* seg_off, int classes, int target_id,
+                         const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+                         int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap, int32_t* d_counts, double* d_scores,
+                         uint8_t* d_flags, void* stream) {
   const int groups = (n_thr + kDetectThreads - 1) / kDetectThreads;
   if (groups > 65535) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per call", n_thr, 65535 * kDetectThreads);
   DetectArgs a;
@@ -261,22 +279,55 @@ extern "C" int mkws_detect_stream(const void* d_probs, int probs_f64, int n_head
   a.min_count = minimum_count;
   a.event_cap = event_cap;
   a.fired_only = fired_only != 0;
-  if (probs_f64)
-    hipLaunchKernelGGL(detect_kernel<double>, dim3(n_heads, groups), dim3(kDetectThreads), 0, static_cast<hipStream_t>(stream), a);
-  else
-    hipLaunchKernelGGL(detect_kernel<float>, dim3(n_heads, groups), dim3(kDetectThreads), 0, static_cast<hipStream_t>(stream), a);
+  a.seg_off = seg_off;
+  const dim3 grid(n_planes, groups), block(kDetectThreads);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (seg_off) {
+    if (probs_f64) hipLaunchKernelGGL((detect_kernel<double, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((detect_kernel<float, true>), grid, block, 0, s, a);
+  } else {
+    if (probs_f64) hipLaunchKernelGGL((detect_kernel<double, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((detect_kernel<float, false>), grid, block, 0, s, a);
+  }
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }
 
-extern "C" int mkws_detect_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_heads, int n_thr, int event_cap,
-                                 const int64_t* d_times_ms, int n_windows, const double* d_gt_ms, const int32_t* d_gt_offsets,
-                                 double time_tolerance_ms, int32_t* d_tally, void* stream) {
+extern "C" int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_windows, int classes, int target_id,
+                                  const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
+                                  double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
+                                  int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream) {
   if (n_heads < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
   if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
-  if (!(time_tolerance_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "time_tolerance_ms must be >= 0");
-  if (!d_counts || !d_times_ms || !d_gt_ms || !d_gt_offsets || !d_tally || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
-  if (n_heads == 0) return MKWS_OK;
+  if (classes < 1 || target_id < 0 || target_id >= classes) return fail(MKWS_ERR_INVALID_ARG, "target_id %d outside [0, %d)", target_id, classes);
+  if (!(average_window_duration_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "average_window_duration_ms must be >= 0 (the host detector would pop its newest entry)");
+  if (std::isnan(suppression_ms)) return fail(MKWS_ERR_INVALID_ARG, "suppression_ms is NaN");
+  if (!d_probs || !d_times_ms || !d_thresholds || !d_counts || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_heads == 0 || n_windows == 0) return MKWS_OK;
+  return launch_detect(d_probs, probs_f64, n_heads, n_windows, nullptr, classes, target_id, d_times_ms, d_thresholds, n_thr, average_window_duration_ms,
+                       suppression_ms, minimum_count, fired_only, d_events, event_cap, d_counts, d_scores, d_flags, stream);
+}
+
+extern "C" int mkws_detect_segments(const void* d_probs, int probs_f64, const int32_t* d_seg_offsets, int n_seg, int n_rows, int classes, int target_id,
+                                    const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
+                                    double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
+                                    int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream) {
+  if (n_seg < 0 || n_rows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
+  if (classes < 1 || target_id < 0 || target_id >= classes) return fail(MKWS_ERR_INVALID_ARG, "target_id %d outside [0, %d)", target_id, classes);
+  if (!(average_window_duration_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "average_window_duration_ms must be >= 0 (the host detector would pop its newest entry)");
+  if (std::isnan(suppression_ms)) return fail(MKWS_ERR_INVALID_ARG, "suppression_ms is NaN");
+  if (((!d_probs || !d_times_ms) && n_rows > 0) || !d_seg_offsets || !d_thresholds || !d_counts || (!d_events && event_cap > 0))
+    return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_seg == 0) return MKWS_OK;
+  return launch_detect(d_probs, probs_f64, n_seg, n_rows, d_seg_offsets, classes, target_id, d_times_ms, d_thresholds, n_thr, average_window_duration_ms,
+                       suppression_ms, minimum_count, fired_only, d_events, event_cap, d_counts, d_scores, d_flags, stream);
+}
+
+// the launch behind mkws_detect_score (seg_off NULL) and mkws_detect_score_segments; the arguments have been checked
+static int launch_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_planes, int n_thr, int event_cap, const int64_t* d_times_ms,
+                        int n_windows, const int32_t* seg_off, const double* d_gt_ms, const int32_t* d_gt_offsets, double time_tolerance_ms,
+                        int32_t* d_tally, void* stream) {
   const int groups = (n_thr + kDetectThreads - 1) / kDetectThreads;
   if (groups > 65535) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per call", n_thr, 65535 * kDetectThreads);
   ScoreArgs a;
@@ -290,9 +341,33 @@ extern "C" int mkws_detect_score(const mkws_detect_event* d_events, const int32_
   a.n_thr = n_thr;
   a.event_cap = event_cap;
   a.n_windows = n_windows;
+  a.seg_off = seg_off;
   // whole waves, no more of them than there are thresholds to walk (a curve of 20 thresholds is one wave per head)
   const int threads = groups > 1 ? kDetectThreads : (n_thr + 63) / 64 * 64;
-  hipLaunchKernelGGL(score_kernel, dim3(n_heads, groups), dim3(threads), 0, static_cast<hipStream_t>(stream), a);
+  if (seg_off) hipLaunchKernelGGL(score_kernel<true>, dim3(n_planes, groups), dim3(threads), 0, static_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL(score_kernel<false>, dim3(n_planes, groups), dim3(threads), 0, static_cast<hipStream_t>(stream), a);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
+}
+
+extern "C" int mkws_detect_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_heads, int n_thr, int event_cap,
+                                 const int64_t* d_times_ms, int n_windows, const double* d_gt_ms, const int32_t* d_gt_offsets,
+                                 double time_tolerance_ms, int32_t* d_tally, void* stream) {
+  if (n_heads < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
+  if (!(time_tolerance_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "time_tolerance_ms must be >= 0");
+  if (!d_counts || !d_times_ms || !d_gt_ms || !d_gt_offsets || !d_tally || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_heads == 0) return MKWS_OK;
+  return launch_score(d_events, d_counts, n_heads, n_thr, event_cap, d_times_ms, n_windows, nullptr, d_gt_ms, d_gt_offsets, time_tolerance_ms, d_tally, stream);
+}
+
+extern "C" int mkws_detect_score_segments(const mkws_detect_event* d_events, const int32_t* d_counts, const int32_t* d_seg_offsets, int n_seg, int n_rows,
+                                          int n_thr, int event_cap, const int64_t* d_times_ms, const double* d_gt_ms, const int32_t* d_gt_offsets,
+                                          double time_tolerance_ms, int32_t* d_tally, void* stream) {
+  if (n_seg < 0 || n_rows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
+  if (!(time_tolerance_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "time_tolerance_ms must be >= 0");
+  if (!d_counts || !d_seg_offsets || (!d_times_ms && n_rows > 0) || !d_gt_ms || !d_gt_offsets || !d_tally || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_seg == 0) return MKWS_OK;
+  return launch_score(d_events, d_counts, n_seg, n_thr, event_cap, d_times_ms, n_rows, d_seg_offsets, d_gt_ms, d_gt_offsets, time_tolerance_ms, d_tally, stream);
 }

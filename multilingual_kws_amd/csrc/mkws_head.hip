@@ -47,18 +47,15 @@ constexpr int kGroupHeadsPerLaunch = 64;
 // groups by two xor-shuffles, softmax on every lane, lane group 0 stores.  Needs in % 16 == 0 and hid <= 32.
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-template <int NT, bool MULTI>
-__global__ __launch_bounds__(256) void head_fwd_mfma_kernel(HeadDims d, const float* __restrict__ params, const float* __restrict__ x, int B,
-                                                            float* __restrict__ probs, HeadTable table) {
-  __shared__ float s_part[3][NT][64][4];
+// The tile's work as a function of its own: the 16 rows from row0 under ONE head's parameters, stores masked to rows [store_lo, store_hi)
+// (the whole-batch kernels pass [0, B); the segmented kernel the rows of the tile that belong to the segment it is finishing).  Waves
+// 1..3 return after the barrier.
+template <int NT>
+__device__ __forceinline__ void head_fwd_tile(const HeadDims& d, const float* __restrict__ params, const float* __restrict__ x, int B,
+                                              float* __restrict__ probs, int row0, int store_lo, int store_hi, float (&s_part)[3][NT][64][4]) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c = lane & 15;
-  const int row0 = blockIdx.x * 16;
-  if (MULTI) {
-    params = table.p[blockIdx.y];
-    probs += (size_t)blockIdx.y * B * d.cls;
-  }
   const float* W1 = params;
   const float* b1 = W1 + (size_t)d.in * d.hid;
   const float* W2 = b1 + d.hid;
@@ -176,10 +173,66 @@ __global__ __launch_bounds__(256) void head_fwd_mfma_kernel(HeadDims d, const fl
     esum += e[k];
   }
   const float inv = 1.0f / esum;
-  if (g == 0 && row < B) {
+  if (g == 0 && row >= store_lo && row < store_hi) {
 #pragma unroll
     for (int k = 0; k < kMaxClasses; ++k)
       if (k < d.cls) probs[(size_t)row * d.cls + k] = e[k] * inv;
+  }
+}
+
+template <int NT, bool MULTI>
+__global__ __launch_bounds__(256) void head_fwd_mfma_kernel(HeadDims d, const float* __restrict__ params, const float* __restrict__ x, int B,
+                                                            float* __restrict__ probs, HeadTable table) {
+  __shared__ float s_part[3][NT][64][4];
+  if (MULTI) {
+    params = table.p[blockIdx.y];
+    probs += (size_t)blockIdx.y * B * d.cls;
+  }
+  head_fwd_tile<NT>(d, params, x, B, probs, blockIdx.x * 16, 0, B, s_part);
+}
+
+// Segmented forward (mkws_head_group_forward_segments): the B rows are global rows row_base .. row_base + B of a concatenation of segments,
+// segment s = rows off[s] .. off[s + 1] under head seg_head[s] of the group's table.  A 16-row tile is finished ONCE PER SEGMENT IT
+// INTERSECTS -- the whole K walk and epilogue of head_fwd_tile under that segment's head, stores masked to that segment's rows -- so a
+// row's bytes are those of mkws_head_forward of its head whatever its neighbours in the tile are (a tile inside one segment, the usual
+// case, is one pass).  The first segment that reaches into the tile is found by a binary search bounded by [0, n_seg]; the walk from it
+// stops at n_seg or at the first segment starting behind the tile, so an unsorted list costs wrong answers, never a wild access.  Rows no
+// valid (segment, head) covered get NaN and are counted; a head index outside the table is never dereferenced.
+template <int NT>
+__global__ __launch_bounds__(256) void head_fwd_segments_kernel(HeadDims d, const HeadSlot* __restrict__ slots, int n_heads, const float* __restrict__ x,
+                                                                int B, long long row_base, const int32_t* __restrict__ off,
+                                                                const int32_t* __restrict__ seg_head, int n_seg, float* __restrict__ probs,
+                                                                int32_t* invalid) {
+  __shared__ float s_part[3][NT][64][4];
+  const int row0 = blockIdx.x * 16;
+  const int nrows = min(16, B - row0);
+  const long long g0 = row_base + row0, g1 = g0 + nrows;       // the tile's global rows
+  int lo = 0, hi = n_seg;                                      // the first segment that ends behind g0
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((long long)off[mid + 1] > g0) hi = mid; else lo = mid + 1;
+  }
+  const int row = row0 + (int)(threadIdx.x & 15);
+  bool covered = false;
+  for (int s = lo; s < n_seg; ++s) {                           // (everything that steers this loop is uniform over the workgroup)
+    const long long a = off[s], b = off[s + 1];
+    if (a >= g1) break;
+    const long long first = a > g0 ? a : g0, last = b < g1 ? b : g1;
+    if (first >= last) continue;                               // empty, or (unsorted list) wholly outside the tile
+    const int h = seg_head[s];
+    if (h < 0 || h >= n_heads) continue;
+    const int store_lo = (int)(first - row_base), store_hi = (int)(last - row_base);
+    covered |= row >= store_lo && row < store_hi;
+    head_fwd_tile<NT>(d, slots[h].params, x, B, probs, row0, store_lo, store_hi, s_part);
+    __syncthreads();                                           // wave 0 has read s_part before the next pass rewrites it
+  }
+  if (threadIdx.x < 16) {
+    const bool bad = row < B && !covered;
+    if (bad) {
+      for (int k = 0; k < d.cls; ++k) probs[(size_t)row * d.cls + k] = __builtin_nanf("");
+    }
+    const int n_bad = __popcll(__ballot(bad));
+    if (threadIdx.x == 0 && n_bad) atomicAdd(invalid, n_bad);  // an integer count
   }
 }
 
@@ -694,6 +747,26 @@ void mkws_head_group_destroy(mkws_head_group* g) {
 }
 
 int mkws_head_group_size(const mkws_head_group* g) { return g ? g->n : fail(MKWS_ERR_INVALID_ARG, "head group handle is NULL"); }
+
+int mkws_head_group_forward_segments(mkws_head_group* g, const float* d_emb, int B, int64_t row_base, const int32_t* d_seg_offsets,
+                                     const int32_t* d_seg_head, int n_seg, float* d_probs, int32_t* d_invalid, void* stream) {
+  if (!g) return fail(MKWS_ERR_INVALID_ARG, "head group handle is NULL");
+  if (B < 0 || n_seg < 0 || row_base < 0) return fail(MKWS_ERR_INVALID_ARG, "negative batch, segment count or row_base");
+  if (g->d.in % 16 != 0 || g->d.hid > 32)
+    return fail(MKWS_ERR_UNSUPPORTED, "the segmented forward runs on the matrix cores only: in %% 16 == 0 and hidden <= 32 (got %d, %d)", g->d.in, g->d.hid);
+  if (B == 0 || n_seg == 0) return MKWS_OK;
+  if (!d_emb || !d_seg_offsets || !d_seg_head || !d_probs || !d_invalid) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  MKWS_HIP(hipMemsetAsync(d_invalid, 0, sizeof(int32_t), s));
+  if (g->d.hid <= 16)
+    hipLaunchKernelGGL((head_fwd_segments_kernel<1>), dim3((B + 15) / 16), dim3(256), 0, s, g->d, g->d_slots, g->n, d_emb, B, (long long)row_base,
+                       d_seg_offsets, d_seg_head, n_seg, d_probs, d_invalid);
+  else
+    hipLaunchKernelGGL((head_fwd_segments_kernel<2>), dim3((B + 15) / 16), dim3(256), 0, s, g->d, g->d_slots, g->n, d_emb, B, (long long)row_base,
+                       d_seg_offsets, d_seg_head, n_seg, d_probs, d_invalid);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
 
 int mkws_head_group_loss_grad(mkws_head_group* g, const float* d_emb, int64_t emb_stride, const int32_t* d_labels, int64_t label_stride, int B,
                               float* d_stats, void* stream) {

@@ -195,3 +195,167 @@ def score_on_device(probs, times_ms, thresholds, gt_times_per_head, time_toleran
         n, k = (int(x[0]) for x in np.nonzero(tally[:, :, 3]))
         raise RuntimeError(f"head {n}, threshold {k}: {int(tally[n, k, 0])} fires for an event list of {cap}; the list was cut and cannot be scored")
     return np.ascontiguousarray(tally[:, :, :3])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Segmented forms (mkws_detect_segments / mkws_detect_score_segments): S recordings concatenated, each with its own windows, times and
+# probabilities -- K (keyword, recording) pairs in one launch where detect_on_device takes N heads over ONE recording.
+
+
+def check_segments(seg_offsets, times_ms):
+    """seg_offsets: S + 1 non-decreasing integers from 0 to len(times_ms); times_ms: the segments' times back to back, non-decreasing
+    inside each segment (check_times per segment, with its ValueError).  -> (int32 offsets [S + 1], int64 times [rows]); ValueError
+    before anything touches a device."""
+    off = np.asarray(seg_offsets)
+    if off.ndim != 1 or off.size < 1 or (not np.issubdtype(off.dtype, np.integer) and not np.array_equal(off, np.floor(off))):
+        raise ValueError("seg_offsets must be a one-dimensional list of S + 1 integers")
+    off = off.astype(np.int64)
+    if np.any(off[1:] < off[:-1]):
+        s = int(np.nonzero(off[1:] < off[:-1])[0][0])
+        raise ValueError(f"seg_offsets must be non-decreasing, but segment {s} runs from {int(off[s])} to {int(off[s + 1])}")
+    t = np.asarray(times_ms)
+    if t.ndim != 1:
+        raise ValueError("times_ms must be a one-dimensional list of integer milliseconds")
+    if int(off[0]) != 0 or int(off[-1]) != t.shape[0]:
+        raise ValueError(f"seg_offsets run from {int(off[0])} to {int(off[-1])} for {t.shape[0]} timestamps: they must cover exactly [0, rows]")
+    if t.shape[0] >= 2 ** 31:
+        raise ValueError("too many rows")
+    parts = [check_times(t[a:b]) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+    times = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+    return off.astype(np.int32), np.ascontiguousarray(times, dtype=np.int64)
+
+
+class SegmentDetectResult(DetectResult):
+    """DetectResult over S segments: counts int32 [S, T]; events[s][k] in window order, `window` being the index inside segment s; with
+    trace=True scores is a list of S float64 [len_s] and flags a list of S uint8 [T, len_s], else None."""
+
+
+def _segment_probs(probs, rows):
+    import torch
+    if not torch.is_tensor(probs):
+        a = np.asarray(probs)
+        probs = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)).cuda()
+    if probs.dim() != 2 or not probs.is_cuda or probs.dtype not in (torch.float32, torch.float64):
+        raise ValueError("probs must be a CUDA tensor or numpy array [rows, classes] of float32 or float64")
+    if probs.shape[0] != rows:
+        raise ValueError(f"{probs.shape[0]} rows of probabilities but {rows} timestamps")
+    return probs.contiguous()
+
+
+def _segment_capacity(times, off, suppression_ms, fired_only):
+    """The largest event_capacity over the segments, and the longest segment."""
+    spans = list(zip(off[:-1].tolist(), off[1:].tolist()))
+    return (max([event_capacity(times[a:b], suppression_ms, fired_only) for a, b in spans], default=0),
+            max([b - a for a, b in spans], default=0))
+
+
+def detect_segments_on_device(probs, seg_offsets, times_ms, thresholds, average_window_duration_ms, suppression_ms, minimum_count, target_id=2,
+                              trace=False, fired_only=False):
+    """detect_on_device for S concatenated recordings: probs CUDA tensor (or numpy array, which is uploaded) [rows, C], float32 or
+    float64; segment s = rows seg_offsets[s] .. seg_offsets[s + 1] with its own non-decreasing times_ms[those rows]; thresholds: T
+    floats.  -> SegmentDetectResult whose segment s equals detect_on_device on that slice alone; never a cut event list.  One upload,
+    one launch and one device-to-host copy per call; a second round at the longest segment's length only if a lane had more events
+    than the largest event_capacity() over the segments allows for."""
+    import torch
+    off, times = check_segments(seg_offsets, times_ms)                 # before anything touches the device
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if thr.size < 1:
+        raise ValueError("at least one threshold")
+    if not average_window_duration_ms >= 0:
+        raise ValueError("average_window_duration_ms must be >= 0")
+    R, S, T = int(times.shape[0]), int(off.shape[0]) - 1, int(thr.size)
+    probs = _segment_probs(probs, R)
+    C = probs.shape[1]
+    if not 0 <= int(target_id) < C:
+        raise ValueError(f"target_id {target_id} outside [0, {C})")
+    spans = list(zip(off[:-1].tolist(), off[1:].tolist()))
+    if S == 0:
+        return SegmentDetectResult(np.zeros((0, T), np.int32), np.zeros((0, T, 0), EVENT_DTYPE), [] if trace else None, [] if trace else None)
+    L = _lib.lib()
+    dev = probs.device
+    with torch.cuda.device(dev):
+        # times, thresholds and offsets travel in one upload of 8-byte words
+        off_words = np.zeros((S + 2) // 2 * 2, np.int32)
+        off_words[:S + 1] = off
+        d_in = torch.from_numpy(np.concatenate([times, thr.view(np.int64), off_words.view(np.int64)])).to(dev, non_blocking=True)
+        p_times = d_in.data_ptr()
+        p_thr, p_off = p_times + 8 * R, p_times + 8 * (R + T)
+        d_scores = torch.empty(R, dtype=torch.float64, device=dev) if trace else None
+        d_flags = torch.empty(T * R, dtype=torch.uint8, device=dev) if trace else None
+        cap, longest = _segment_capacity(times, off, suppression_ms, fired_only)
+        while True:
+            cwords = (S * T + 1) // 2
+            d_out = torch.empty(cwords + 2 * S * T * cap, dtype=torch.int64, device=dev)
+            base = d_out.data_ptr()
+            _lib.check(L.mkws_detect_segments(
+                probs.data_ptr(), int(probs.dtype == torch.float64), p_off, S, R, C, int(target_id), p_times, p_thr, T,
+                float(average_window_duration_ms), float(suppression_ms), int(minimum_count), int(bool(fired_only)),
+                base + 8 * cwords, cap, base, d_scores.data_ptr() if trace else None, d_flags.data_ptr() if trace else None,
+                _lib.current_stream_ptr()))
+            out = d_out.cpu().numpy()                                  # the call's one synchronisation
+            counts = out[:cwords].view(np.int32)[:S * T].reshape(S, T)
+            if int(counts.max()) <= cap:
+                break
+            cap = longest                                              # a lane cannot have more events than its segment has windows
+        events = out[cwords:].view(EVENT_DTYPE).reshape(S, T, cap)
+        scores = flags = None
+        if trace:
+            h_scores, h_flags = d_scores.cpu().numpy(), d_flags.cpu().numpy()
+            scores = [h_scores[a:b] for a, b in spans]
+            flags = [h_flags[T * a:T * b].reshape(T, b - a) for a, b in spans]
+        return SegmentDetectResult(counts, events, scores, flags)
+
+
+def score_segments_on_device(probs, seg_offsets, times_ms, thresholds, gt_times_per_segment, time_tolerance_ms, average_window_duration_ms,
+                             suppression_ms, minimum_count, target_id=2):
+    """score_on_device for S concatenated recordings (mkws_detect_segments + mkws_detect_score_segments): -> int32 [S, T, 3] = (found,
+    true_positives_raw, false_negatives) per (segment, threshold) lane; segment s equals score_on_device on that slice with
+    gt_times_per_segment[s].  One upload, two launches, one copy of 16 * S * T bytes; RuntimeError if a lane's event list was cut."""
+    import torch
+    off, times = check_segments(seg_offsets, times_ms)
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if thr.size < 1:
+        raise ValueError("at least one threshold")
+    if not average_window_duration_ms >= 0:
+        raise ValueError("average_window_duration_ms must be >= 0")
+    tol = float(time_tolerance_ms)
+    if not tol >= 0:
+        raise ValueError("time_tolerance_ms must be >= 0")
+    span = int(np.abs(times).max()) if times.size else 0
+    if span > 2 ** 53 or (np.isfinite(tol) and span + tol > 2 ** 53):
+        raise ValueError("times_ms (and times_ms +- time_tolerance_ms) must lie within +-2**53 milliseconds: they are compared as float64")
+    R, S, T = int(times.shape[0]), int(off.shape[0]) - 1, int(thr.size)
+    gt, gt_off = pack_groundtruth(gt_times_per_segment, S)             # refused before anything is uploaded
+    probs = _segment_probs(probs, R)
+    C = probs.shape[1]
+    if not 0 <= int(target_id) < C:
+        raise ValueError(f"target_id {target_id} outside [0, {C})")
+    if S == 0:
+        return np.zeros((0, T, 3), np.int32)
+    L = _lib.lib()
+    dev = probs.device
+    with torch.cuda.device(dev):
+        words = np.zeros((2, (S + 2) // 2 * 2), np.int32)
+        words[0, :S + 1], words[1, :S + 1] = off, gt_off
+        host_in = np.concatenate([times, thr.view(np.int64), gt.view(np.int64), words[0].view(np.int64), words[1].view(np.int64)])
+        d_in = torch.from_numpy(host_in).to(dev, non_blocking=True)
+        p_times = d_in.data_ptr()
+        p_thr, p_gt = p_times + 8 * R, p_times + 8 * (R + T)
+        p_off = p_gt + 8 * gt.size
+        p_gt_off = p_off + 4 * words.shape[1]
+        cap, _ = _segment_capacity(times, off, suppression_ms, True)
+        d_events = torch.empty(2 * S * T * cap, dtype=torch.int64, device=dev)
+        d_counts = torch.empty(S * T, dtype=torch.int32, device=dev)
+        d_tally = torch.empty((S, T, 4), dtype=torch.int32, device=dev)
+        stream = _lib.current_stream_ptr()
+        _lib.check(L.mkws_detect_segments(
+            probs.data_ptr(), int(probs.dtype == torch.float64), p_off, S, R, C, int(target_id), p_times, p_thr, T,
+            float(average_window_duration_ms), float(suppression_ms), int(minimum_count), 1, d_events.data_ptr(), cap, d_counts.data_ptr(),
+            None, None, stream))
+        _lib.check(L.mkws_detect_score_segments(d_events.data_ptr(), d_counts.data_ptr(), p_off, S, R, T, cap, p_times, p_gt, p_gt_off, tol,
+                                                d_tally.data_ptr(), stream))
+        tally = d_tally.cpu().numpy()                                  # the call's one synchronisation: 16 bytes per lane
+    if tally[:, :, 3].any():
+        s, k = (int(x[0]) for x in np.nonzero(tally[:, :, 3]))
+        raise RuntimeError(f"segment {s}, threshold {k}: {int(tally[s, k, 0])} fires for an event list of {cap}; the list was cut and cannot be scored")
+    return np.ascontiguousarray(tally[:, :, :3])

@@ -740,3 +740,339 @@ def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inf
         with open(write_detections, "w") as fh:
             json.dump(detections, fh)
     return detections
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The batch entry point (reference :244-337): K (keyword, recording) pairs -- every target its own recording, its own fine-tuned head and
+# its own ground truth -- in one device pass instead of one eval_stream_test after the other.
+
+
+class _Prepared:
+    """One StreamTarget of a batch pass: its recording, the rows its inferences take in the pass's [rows, 3] tensor, and what is known
+    about them so far."""
+
+    def __init__(self, index, st):
+        self.index, self.st = index, st
+        self.audio = self.sample_rate = self.loaded = self.inferences = self.model = None
+        self.rows = self.base = 0
+        self.plain = True               # float32 [rows, 3] inferences: the target's rows live in the shared device tensor
+
+
+def _read_target(p, live_model):
+    """What calculate_streaming_accuracy establishes before it runs anything: one wav, one clip length, one stride."""
+    flag_list = p.st.stream_flags
+    assert len(set([f.wav for f in flag_list])) == 1, "can only process one wav"
+    assert len(set([f.clip_duration_ms for f in flag_list])) == 1, "cannot vary"
+    assert len(set([f.clip_stride_ms for f in flag_list])) == 1, "cannot vary"
+    with open(flag_list[0].wav, "rb") as f:
+        p.audio, p.sample_rate = input_data.decode_wav(f.read())
+    p.model = live_model
+    f0 = flag_list[0]
+    p.clip = int(f0.clip_duration_ms * p.sample_rate / 1000)
+    p.stride = int(f0.clip_stride_ms * p.sample_rate / 1000)
+    p.offsets = window_offsets(p.audio.shape[0], p.clip, p.stride)
+    if p.loaded is not None:
+        a = np.asarray(p.loaded)
+        p.inferences = a
+        p.plain = a.ndim == 2 and a.shape[1] == 3 and a.dtype == np.float32
+        p.rows = a.shape[0] if p.plain else 0
+    else:
+        max_chunk = None if f0.max_chunk_length_sec is None else int(f0.max_chunk_length_sec * p.sample_rate)
+        p.chunks = chunk_audio(p.audio, max_chunk)
+        p.rows = sum(max(0, len(window_offsets(c.shape[0], p.clip, p.stride))) for c in p.chunks)
+
+
+def _batch_inferences(prepared):
+    """The softmax outputs of every prepared target in ONE device tensor [rows, 3] (target p at rows p.base .. p.base + p.rows): stored
+    inferences are uploaded into their rows; the other targets are grouped by (embedding handle, head dimensions, clip length, stride,
+    sample rate) and each group is one pass -- the recordings windowed one after the other (chunk_audio as shipped, per recording), the
+    windows packed into full batches of the handle's max_batch regardless of recording boundaries, the embedding run eagerly on the
+    caller's handle and HeadGroup.forward_segments writing each batch's probabilities under the head of the recording each row belongs to.
+    Device memory: one recording's spectrograms, one batch of embeddings, 12 bytes per row.  Sets p.inferences (host) for every target;
+    -> the device tensor, or None on a host without a GPU (then every target must have come with stored inferences)."""
+    import torch
+    from ..head import HeadGroup
+    at = 0
+    for p in prepared:
+        p.base, at = at, at + p.rows
+    todo = [p for p in prepared if p.loaded is None]
+    if not torch.cuda.is_available() and not todo:
+        return None
+    groups = {}
+    for p in todo:
+        hd = p.model.head
+        key = (id(p.model.embedding), hd.in_dim, hd.hidden, hd.classes, p.clip, p.stride, p.sample_rate)
+        groups.setdefault(key, []).append(p)
+    dev = todo[0].model.embedding.device if todo else torch.device(f"cuda:{torch.cuda.current_device()}")
+    d_all = torch.empty((at, 3), dtype=torch.float32, device=dev)
+    for p in prepared:
+        if p.loaded is not None and p.plain and p.rows:
+            d_all[p.base:p.base + p.rows].copy_(torch.from_numpy(np.ascontiguousarray(p.inferences)), non_blocking=True)
+    model_settings = input_data.standard_microspeech_model_settings(label_count=3)
+    for members in groups.values():
+        emb_model = members[0].model.embedding
+        if members[0].model.head.classes != 3:
+            raise ValueError("The results for recognition should contain 3 elements, but there are {} produced".format(members[0].model.head.classes))
+        if emb_model.device != dev:
+            raise ValueError("eval_stream_tests: the targets' embeddings live on different devices")
+        heads, slot = [], {}
+        for p in members:                                           # a head shared by several targets is one member of the group
+            if id(p.model.head) not in slot:
+                slot[id(p.model.head)] = len(heads)
+                heads.append(p.model.head)
+        seg_off = np.zeros(len(members) + 1, np.int64)
+        np.cumsum([p.rows for p in members], out=seg_off[1:])
+        if seg_off[-1] == 0:
+            continue
+        if seg_off[-1] >= 2 ** 31:
+            raise ValueError("too many windows for one pass")
+        mb, dim = emb_model.max_batch, emb_model.output_dim
+        rows = int(seg_off[-1])
+        group = HeadGroup(heads)
+        try:
+            with torch.cuda.device(dev):
+                d_off = torch.from_numpy(seg_off.astype(np.int32)).to(dev)
+                d_head = torch.tensor([slot[id(p.model.head)] for p in members], dtype=torch.int32, device=dev)
+                contiguous = all(a.base + a.rows == b.base for a, b in zip(members, members[1:]))
+                d_probs = d_all[members[0].base:members[0].base + rows] if contiguous else torch.empty((rows, 3), dtype=torch.float32, device=dev)
+
+                def one_pass():
+                    d_emb = torch.empty((min(mb, rows), dim), dtype=torch.float32, device=dev)
+                    d_bad = torch.zeros((rows + mb - 1) // mb, dtype=torch.int32, device=dev)
+                    carry, done = None, 0
+
+                    def run(spec):
+                        nonlocal done
+                        r = spec.shape[0]
+                        emb_model.forward(spec, out=d_emb[:r])
+                        group.forward_segments(d_emb[:r], d_off, d_head, row_base=done, out=d_probs[done:done + r], invalid=d_bad[done // mb:done // mb + 1])
+                        done += r
+                    for p in members:
+                        for chunk in p.chunks:
+                            specs = stream_spectrograms(model_settings, chunk, p.clip, p.stride)
+                            if specs.shape[0] == 0:
+                                continue
+                            if carry is not None:
+                                specs = torch.cat([carry, specs])
+                            full = specs.shape[0] // mb * mb
+                            for s in range(0, full, mb):
+                                run(specs[s:s + mb])
+                            carry = specs[full:].clone() if full < specs.shape[0] else None     # (a copy: the recording's spectrograms are released)
+                    if carry is not None:
+                        run(carry)
+                    assert done == rows, (done, rows)
+                    return d_probs.cpu().numpy(), int(d_bad.sum().cpu())
+                host, n_bad = emb_model.checked(one_pass)
+        finally:
+            group.close()
+        if n_bad:
+            raise RuntimeError(f"{n_bad} windows reached the device outside every recording's rows")
+        for i, p in enumerate(members):
+            p.inferences = host[int(seg_off[i]):int(seg_off[i + 1])]
+            if not contiguous and p.rows:
+                d_all[p.base:p.base + p.rows].copy_(d_probs[int(seg_off[i]):int(seg_off[i + 1])])
+    return d_all
+
+
+def _detector_segments(prepared, d_all, keyed):
+    """The (target, StreamFlags) pairs of a pass grouped by `keyed(flags)`, each group with what one segmented detector call needs:
+    -> {key: (pairs [(p, flags)], probs [rows, 3] on the device, offsets [S + 1], times [rows])}.  A segment is the target's rows cut to
+    its window offsets (chunk_audio as shipped can yield more rows than offsets: detect_many cuts them too); fewer rows raise IndexError."""
+    import torch
+    by_key = {}
+    for p in prepared:
+        if not p.plain:
+            continue
+        for flags in p.st.stream_flags:
+            if flags.detection_thresholds:
+                by_key.setdefault(keyed(flags), []).append((p, flags))
+    out = {}
+    for key, pairs in by_key.items():
+        spans, times = [], []
+        for p, _ in pairs:
+            n = len(p.offsets)
+            if p.rows < n:
+                raise IndexError(f"index {p.rows} is out of bounds: {p.rows} rows of inferences for {n} windows")
+            spans.append((p.base, p.base + n))
+            times.append(np.asarray([int(off * 1000 / p.sample_rate) for off in p.offsets], dtype=np.int64))
+        off = np.zeros(len(pairs) + 1, np.int64)
+        np.cumsum([b - a for a, b in spans], out=off[1:])
+        whole = spans[0][0] == 0 and spans[-1][1] == d_all.shape[0] and all(a[1] == b[0] for a, b in zip(spans, spans[1:]))
+        probs = d_all if whole else (torch.cat([d_all[a:b] for a, b in spans]) if spans else d_all[:0])
+        out[key] = (pairs, probs, off, np.concatenate(times) if times else np.zeros(0, np.int64))
+    return out
+
+
+def _prepare(stream_targets, live_models, skip_done):
+    targets = list(stream_targets)
+    if live_models is not None:
+        live_models = list(live_models)
+        if len(live_models) != len(targets):
+            raise ValueError(f"{len(live_models)} live models for {len(targets)} stream targets")
+    prepared = []
+    for i, st in enumerate(targets):
+        if skip_done and st.destination_result_pkl is not None and os.path.isfile(st.destination_result_pkl):
+            print("results already present", st.destination_result_pkl, flush=True)
+            continue
+        p = _Prepared(i, st)
+        if st.destination_result_inferences is not None and os.path.isfile(st.destination_result_inferences):
+            print("inferences already present", flush=True)
+            p.loaded = np.load(st.destination_result_inferences)
+        prepared.append(p)
+    need = [p for p in prepared if p.loaded is None]
+    if live_models is None and need:
+        from .transfer_learning import load_models_shared
+        for p, m in zip(need, load_models_shared([p.st.model_path for p in need])):
+            p.model = m
+    for p in prepared:
+        _read_target(p, live_models[p.index] if live_models is not None else p.model)
+    return targets, prepared
+
+
+def _save_inferences(p):
+    if p.loaded is None and p.st.destination_result_inferences is not None:
+        print("SAVING inferences TO\n", p.st.destination_result_inferences, flush=True)
+        np.save(p.st.destination_result_inferences, p.inferences)
+
+
+def eval_stream_tests(stream_targets, live_models=None):
+    """eval_stream_test for a list of StreamTargets in one device pass: -> a list aligned with the targets, entry i being exactly what
+    eval_stream_test(stream_targets[i], live_models[i]) returns (None after its "results already present" message), with the same
+    pickle and .npy files written and stored inferences re-used.  Models: `live_models` (aligned with the targets), or
+    transfer_learning.load_models_shared over the model_paths of the targets that need one.
+
+    Where eval_stream_test pays, per target, an embedding pass that ends in a ragged batch, an upload, a detector launch per StreamFlags
+    and a synchronising copy for each, this is one embedding pass per (embedding handle, clip length, stride, sample rate) over full
+    batches that ignore recording boundaries (_batch_inferences: each row under its own recording's head), and ONE
+    detector.detect_segments_on_device call per distinct (average window, suppression, minimum count, thresholds) over all targets and
+    flags.  No hipGraph and no serving lanes: the eager path of one handle is bit-identical across batch sizes, which is what makes the
+    results equal eval_stream_test's.  On a host without a GPU targets whose inferences are all stored run through the host detect()
+    loop, as in eval_stream_test; anything that needs an embedding fails as it does there."""
+    import torch
+    from ..detector import detect_segments_on_device
+    targets, prepared = _prepare(stream_targets, live_models, skip_done=True)
+    out = [None] * len(targets)
+    d_all = _batch_inferences(prepared)
+    by_pair = {}
+    if d_all is not None:
+        keyed = lambda f: (f.average_window_duration_ms, f.suppression_ms, f.minimum_count, tuple(f.detection_thresholds))   # noqa: E731
+        for key, (pairs, probs, off, times) in _detector_segments(prepared, d_all, keyed).items():
+            thresholds = list(key[3])
+            res = detect_segments_on_device(probs, off, times, thresholds, key[0], key[1], key[2], target_id=2, fired_only=True)
+            counts = res.counts.tolist()
+            for s, (p, flags) in enumerate(pairs):
+                kw, t_ms, found = flags.target_keyword, times[off[s]:off[s + 1]].tolist(), {}
+                for k, thr in enumerate(thresholds):
+                    ev = res.event_buffer[s, k, :counts[s][k]]
+                    when = [t_ms[w] for w in ev["window"].tolist()]
+                    found[thr] = ([[kw, t] for t in when], [[kw, t, sc] for t, sc in zip(when, ev["score"].tolist())])
+                by_pair[(p.index, id(flags))] = found
+    for p in prepared:
+        per_flags = []
+        for flags in p.st.stream_flags:
+            found = by_pair.get((p.index, id(flags)))
+            if found is None:             # no device, no thresholds, or stored inferences that are not float32 [rows, 3]: detect_many's own routes
+                found = detect_many(p.inferences, flags, flags.detection_thresholds, p.sample_rate, data_samples=p.audio.shape[0])
+            per_flags.append((flags, found))
+        results = {p.st.target_word: per_flags}
+        if p.st.destination_result_pkl is not None:
+            print("SAVING results TO\n", p.st.destination_result_pkl)
+            with open(p.st.destination_result_pkl, "wb") as fh:
+                pickle.dump(results, fh)
+        _save_inferences(p)
+        out[p.index] = results
+    return out
+
+
+def stream_operating_curves(stream_targets, live_models=None, num_nontarget_words=None):
+    """Per target and per StreamFlags the list of tpr_fpr dicts operating_curves gives for that target's inferences, its flags'
+    thresholds and the ground truth in flags.ground_truth (rows `keyword,time_ms`; the recording's duration is its samples over its
+    sample rate) -- from the pass of eval_stream_tests (stored inferences re-used, new ones saved; result pickles are neither read nor
+    written) and ONE detector.score_segments_on_device call per distinct detector setting, thresholds and tolerance, summary_from_tally
+    on three integers per lane.  A host without a GPU takes operating_curves' host route per target."""
+    import csv
+    from ..detector import score_segments_on_device
+    targets, prepared = _prepare(stream_targets, live_models, skip_done=False)
+    d_all = _batch_inferences(prepared)
+    gt_cache = {}
+
+    def groundtruth(flags):
+        path = os.fspath(flags.ground_truth)
+        if path not in gt_cache:
+            with open(path, "r") as fh:
+                gt_cache[path] = [(row[0], float(row[1])) for row in csv.reader(fh) if row]
+        return gt_cache[path]
+    by_pair, capped, lanes = {}, 0, 0
+    if d_all is not None:
+        keyed = lambda f: (f.average_window_duration_ms, f.suppression_ms, f.minimum_count, tuple(f.detection_thresholds), f.time_tolerance_ms)   # noqa: E731
+        for key, (pairs, probs, off, times) in _detector_segments(prepared, d_all, keyed).items():
+            thresholds = list(key[3])
+            gts = [_groundtruth_times(groundtruth(flags), [flags.target_keyword])[0] for _, flags in pairs]
+            tally = score_segments_on_device(probs, off, times, thresholds, gts, key[4], key[0], key[1], key[2], target_id=2).tolist()
+            for s, (p, flags) in enumerate(pairs):
+                curve = []
+                for k, thr in enumerate(thresholds):
+                    result, was_capped = summary_from_tally(flags.target_keyword, thr, *tally[s][k], len(gts[s]), p.audio.shape[0] / p.sample_rate,
+                                                            num_nontarget_words)
+                    capped += was_capped
+                    curve.append(result)
+                lanes += len(thresholds)
+                by_pair[(p.index, id(flags))] = curve
+    if capped:
+        print(f"WARNING: weird timing issue ({capped} of {lanes} keyword x threshold lanes: true positives capped to the ground-truth count)")
+    out = [None] * len(targets)
+    for p in prepared:
+        curves = []
+        for flags in p.st.stream_flags:
+            curve = by_pair.get((p.index, id(flags)))
+            if curve is None:
+                curve = operating_curves(p.inferences, flags, flags.detection_thresholds, groundtruth(flags), sample_rate=p.sample_rate,
+                                         data_samples=p.audio.shape[0], num_nontarget_words=num_nontarget_words)
+            curves.append(curve)
+        _save_inferences(p)
+        out[p.index] = curves
+    return out
+
+
+def batch_streaming_analysis(sse, dest_dir, detection_thresholds=None, shuffle=True, **flag_overrides):
+    """Reference :244-337 with its two undefined globals as parameters: walks sse/<lang>/<word>/{model/<one entry>, streaming_test.wav,
+    streaming_labels.txt}, builds one StreamTarget per keyword with results under dest_dir/<lang>/<word>/{stream_results.pkl,
+    raw_inferences.npy} (ValueError "extra models or no models", AssertionError "missing stream info" / "result data already present",
+    as there), shuffles them (np.random.shuffle, as there) unless shuffle=False, creates every result directory and evaluates them all
+    with eval_stream_tests (the reference: one child process per target).  detection_thresholds: default np.linspace(0.05, 1, 20);
+    flag_overrides: further StreamFlags fields.  -> (targets, results), aligned."""
+    from pathlib import Path
+    sse, dest_dir = Path(sse), Path(dest_dir)
+    if detection_thresholds is None:
+        detection_thresholds = np.linspace(0.05, 1, 20).tolist()       # step threshold 0.05
+    batch_data_to_process = []
+    for lang_dir in os.listdir(sse):
+        if not os.path.isdir(sse / lang_dir):
+            continue                                                   # skip the data generator shellscript and the logfiles
+        target_lang = lang_dir.split("_")[-1]
+        for word_dir in os.listdir(sse / lang_dir):
+            target_word = word_dir.split("_")[-1]
+            print(target_lang, target_word)
+            model_files = os.listdir(sse / lang_dir / word_dir / "model")
+            if len(model_files) != 1:
+                raise ValueError("extra models or no models")
+            model_path = sse / lang_dir / word_dir / "model" / model_files[0]
+            stream_wav = sse / lang_dir / word_dir / "streaming_test.wav"
+            stream_label = sse / lang_dir / word_dir / "streaming_labels.txt"
+            assert os.path.isfile(stream_wav) and os.path.isfile(stream_label), "missing stream info"
+            destination_result_pkl = dest_dir / lang_dir / word_dir / "stream_results.pkl"
+            destination_result_inferences = dest_dir / lang_dir / word_dir / "raw_inferences.npy"
+            assert not os.path.isfile(destination_result_pkl) and not os.path.isfile(destination_result_inferences), "result data already present"
+            flags = StreamFlags(wav=str(stream_wav), ground_truth=str(stream_label), target_keyword=target_word,
+                                detection_thresholds=list(detection_thresholds), **flag_overrides)
+            batch_data_to_process.append(StreamTarget(target_lang=target_lang, target_word=target_word, model_path=model_path, stream_flags=[flags],
+                                                      destination_result_pkl=destination_result_pkl,
+                                                      destination_result_inferences=destination_result_inferences))
+    if shuffle:
+        np.random.shuffle(batch_data_to_process)
+    print("n wavs", len(batch_data_to_process), flush=True)
+    for d in batch_data_to_process:
+        result_dir = os.path.split(d.destination_result_pkl)[0]
+        print("making dir", result_dir, flush=True)
+        os.makedirs(result_dir, exist_ok=True)
+    return batch_data_to_process, eval_stream_tests(batch_data_to_process)

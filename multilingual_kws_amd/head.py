@@ -190,6 +190,36 @@ class HeadGroup:
         except Exception:
             pass
 
+    def forward_segments(self, emb, seg_offsets, seg_head, row_base=0, out=None, invalid=None):
+        """The group as a head table (mkws_head_group_forward_segments): emb CUDA float32 [B, in] is one batch of a concatenation of
+        segments, its first row being global row `row_base`; segment s = global rows seg_offsets[s] .. seg_offsets[s + 1] (CUDA int32
+        [S + 1], non-decreasing: the caller checks, detector.check_segments) under member seg_head[s] (CUDA int32 [S]).
+        -> (probs CUDA [B, classes] -- `out` if given --, invalid CUDA int32 [1] -- `invalid` if given).  A row's probabilities are
+        Head.forward's of its head, bit for bit; rows in no segment or under a head index outside the group are NaN and counted in
+        `invalid`.  Asynchronous: nothing is copied and nothing synchronises."""
+        import torch
+        classes = self.heads[0].classes
+        if emb.dim() != 2 or emb.shape[1] != self.in_dim or emb.dtype != torch.float32 or not emb.is_contiguous() or emb.device != self.device:
+            raise ValueError(f"HeadGroup.forward_segments takes a contiguous float32 emb [B, {self.in_dim}] on {self.device}, got {tuple(emb.shape)}")
+        for name, t in (("seg_offsets", seg_offsets), ("seg_head", seg_head)):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"HeadGroup.forward_segments: {name} must be a contiguous int32 vector on {self.device}")
+        S = seg_head.shape[0]
+        if seg_offsets.shape[0] != S + 1:
+            raise ValueError(f"HeadGroup.forward_segments: {seg_offsets.shape[0]} offsets for {S} segments (S + 1 expected)")
+        B = emb.shape[0]
+        probs = out if out is not None else torch.empty((B, classes), dtype=torch.float32, device=self.device)
+        if tuple(probs.shape) != (B, classes) or probs.dtype != torch.float32 or not probs.is_contiguous() or probs.device != self.device:
+            raise ValueError(f"HeadGroup.forward_segments: out must be a contiguous float32 [{B}, {classes}] on {self.device}")
+        bad = invalid if invalid is not None else torch.zeros(1, dtype=torch.int32, device=self.device)
+        if bad.numel() != 1 or bad.dtype != torch.int32 or bad.device != self.device:
+            raise ValueError(f"HeadGroup.forward_segments: invalid must be an int32 [1] on {self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mkws_head_group_forward_segments(self.h, ctypes.c_void_p(emb.data_ptr()), B, int(row_base), ctypes.c_void_p(seg_offsets.data_ptr()),
+                                                               ctypes.c_void_p(seg_head.data_ptr()), S, ctypes.c_void_p(probs.data_ptr()),
+                                                               ctypes.c_void_p(bad.data_ptr()), _lib.current_stream_ptr()))
+        return probs, bad
+
     def loss_grad(self, emb, labels, rows=None, offset=0):
         """Head k takes rows [offset, offset + rows) of emb[k] (CUDA float32 [K, R, in], contiguous) with labels[k] (CUDA int32
         [K, R], contiguous); nothing is copied, the stride between heads is the tensors'.  Returns a CUDA [K, 2] tensor of
