@@ -3,6 +3,8 @@ import ctypes
 import itertools
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MKWS_LIB selects another build of the same library (e.g. the phase-timing build of tools/README.md)
 LIB_PATH = os.environ.get("MKWS_LIB") or os.path.join(_HERE, "lib", "libmkws_hip.so")
@@ -191,3 +193,28 @@ def check(code):
 def current_stream_ptr():
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def pack_words(parts):
+    """The host side of "one upload": contiguous numpy arrays of int64, float64 or int32 -> (int64 words, the byte offset of every part).
+    8-byte parts go in as their bit patterns; an int32 part is padded with a zero to whole words, so every offset is a multiple of 8.
+    An empty part gets the offset of whatever follows it."""
+    words, offsets, at = [], [], 0
+    for part in parts:
+        a = part if part.ndim == 1 else part.reshape(-1)
+        if a.dtype.char not in "lqdi":
+            raise TypeError(f"pack_words takes int64, float64 and int32 parts, not {a.dtype}")
+        if a.itemsize == 4 and a.size % 2:
+            a = np.concatenate([a, np.zeros(1, np.int32)])
+        offsets.append(at)
+        words.append(a.view(np.int64))
+        at += a.nbytes
+    return (np.concatenate(words) if words else np.zeros(0, np.int64)), offsets
+
+
+def upload_words(parts, device):
+    """pack_words and its single non-blocking copy to `device` -> (the device tensor, which owns the memory, [device pointer of every part])."""
+    import torch
+    words, offsets = pack_words(parts)
+    d_words = torch.from_numpy(words).to(device, non_blocking=True)
+    return d_words, [d_words.data_ptr() + o for o in offsets]

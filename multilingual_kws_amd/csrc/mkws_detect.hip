@@ -251,14 +251,42 @@ __global__ __launch_bounds__(kDetectThreads) void score_kernel(ScoreArgs a) {
 
 }  // namespace
 
+// workgroups of kDetectThreads thresholds along grid.y, of either kernel
+static int threshold_groups(int n_thr, int* groups) {
+  *groups = (n_thr + kDetectThreads - 1) / kDetectThreads;
+  if (*groups > 65535) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per call", n_thr, 65535 * kDetectThreads);
+  return MKWS_OK;
+}
+
+// what mkws_detect_stream and mkws_detect_segments refuse, in this order; buffers_ok: the form's own rule for NULL pointers
+static int check_detect_args(int n_planes, int n_windows, int event_cap, int n_thr, int classes, int target_id, double average_window_duration_ms,
+                             double suppression_ms, bool buffers_ok) {
+  if (n_planes < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
+  if (classes < 1 || target_id < 0 || target_id >= classes) return fail(MKWS_ERR_INVALID_ARG, "target_id %d outside [0, %d)", target_id, classes);
+  if (!(average_window_duration_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "average_window_duration_ms must be >= 0 (the host detector would pop its newest entry)");
+  if (std::isnan(suppression_ms)) return fail(MKWS_ERR_INVALID_ARG, "suppression_ms is NaN");
+  if (!buffers_ok) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  return MKWS_OK;
+}
+
+// the same for mkws_detect_score and mkws_detect_score_segments
+static int check_score_args(int n_planes, int n_windows, int event_cap, int n_thr, double time_tolerance_ms, bool buffers_ok) {
+  if (n_planes < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
+  if (!(time_tolerance_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "time_tolerance_ms must be >= 0");
+  if (!buffers_ok) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  return MKWS_OK;
+}
+
 // the launch behind mkws_detect_stream (seg_off NULL: n_planes heads over n_windows shared windows) and mkws_detect_segments (n_planes
 // segments of a concatenation of n_windows rows); the arguments have been checked
 static int launch_detect(const void* d_probs, int probs_f64, int n_planes, int n_windows, const int32_t* seg_off, int classes, int target_id,
                          const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
                          int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap, int32_t* d_counts, double* d_scores,
                          uint8_t* d_flags, void* stream) {
-  const int groups = (n_thr + kDetectThreads - 1) / kDetectThreads;
-  if (groups > 65535) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per call", n_thr, 65535 * kDetectThreads);
+  int groups;
+  if (int rc = threshold_groups(n_thr, &groups)) return rc;
   DetectArgs a;
   a.probs = d_probs;
   a.times = d_times_ms;
@@ -297,12 +325,9 @@ extern "C" int mkws_detect_stream(const void* d_probs, int probs_f64, int n_head
                                   const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
                                   double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
                                   int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream) {
-  if (n_heads < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
-  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
-  if (classes < 1 || target_id < 0 || target_id >= classes) return fail(MKWS_ERR_INVALID_ARG, "target_id %d outside [0, %d)", target_id, classes);
-  if (!(average_window_duration_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "average_window_duration_ms must be >= 0 (the host detector would pop its newest entry)");
-  if (std::isnan(suppression_ms)) return fail(MKWS_ERR_INVALID_ARG, "suppression_ms is NaN");
-  if (!d_probs || !d_times_ms || !d_thresholds || !d_counts || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (int rc = check_detect_args(n_heads, n_windows, event_cap, n_thr, classes, target_id, average_window_duration_ms, suppression_ms,
+                                 d_probs && d_times_ms && d_thresholds && d_counts && (d_events || event_cap == 0)))
+    return rc;
   if (n_heads == 0 || n_windows == 0) return MKWS_OK;
   return launch_detect(d_probs, probs_f64, n_heads, n_windows, nullptr, classes, target_id, d_times_ms, d_thresholds, n_thr, average_window_duration_ms,
                        suppression_ms, minimum_count, fired_only, d_events, event_cap, d_counts, d_scores, d_flags, stream);
@@ -312,13 +337,10 @@ extern "C" int mkws_detect_segments(const void* d_probs, int probs_f64, const in
                                     const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
                                     double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
                                     int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream) {
-  if (n_seg < 0 || n_rows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
-  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
-  if (classes < 1 || target_id < 0 || target_id >= classes) return fail(MKWS_ERR_INVALID_ARG, "target_id %d outside [0, %d)", target_id, classes);
-  if (!(average_window_duration_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "average_window_duration_ms must be >= 0 (the host detector would pop its newest entry)");
-  if (std::isnan(suppression_ms)) return fail(MKWS_ERR_INVALID_ARG, "suppression_ms is NaN");
-  if (((!d_probs || !d_times_ms) && n_rows > 0) || !d_seg_offsets || !d_thresholds || !d_counts || (!d_events && event_cap > 0))
-    return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  // (no rows: there is nothing to read probabilities or times from)
+  if (int rc = check_detect_args(n_seg, n_rows, event_cap, n_thr, classes, target_id, average_window_duration_ms, suppression_ms,
+                                 ((d_probs && d_times_ms) || n_rows <= 0) && d_seg_offsets && d_thresholds && d_counts && (d_events || event_cap == 0)))
+    return rc;
   if (n_seg == 0) return MKWS_OK;
   return launch_detect(d_probs, probs_f64, n_seg, n_rows, d_seg_offsets, classes, target_id, d_times_ms, d_thresholds, n_thr, average_window_duration_ms,
                        suppression_ms, minimum_count, fired_only, d_events, event_cap, d_counts, d_scores, d_flags, stream);
@@ -328,8 +350,8 @@ extern "C" int mkws_detect_segments(const void* d_probs, int probs_f64, const in
 static int launch_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_planes, int n_thr, int event_cap, const int64_t* d_times_ms,
                         int n_windows, const int32_t* seg_off, const double* d_gt_ms, const int32_t* d_gt_offsets, double time_tolerance_ms,
                         int32_t* d_tally, void* stream) {
-  const int groups = (n_thr + kDetectThreads - 1) / kDetectThreads;
-  if (groups > 65535) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per call", n_thr, 65535 * kDetectThreads);
+  int groups;
+  if (int rc = threshold_groups(n_thr, &groups)) return rc;
   ScoreArgs a;
   a.events = d_events;
   a.counts = d_counts;
@@ -353,10 +375,9 @@ static int launch_score(const mkws_detect_event* d_events, const int32_t* d_coun
 extern "C" int mkws_detect_score(const mkws_detect_event* d_events, const int32_t* d_counts, int n_heads, int n_thr, int event_cap,
                                  const int64_t* d_times_ms, int n_windows, const double* d_gt_ms, const int32_t* d_gt_offsets,
                                  double time_tolerance_ms, int32_t* d_tally, void* stream) {
-  if (n_heads < 0 || n_windows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
-  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
-  if (!(time_tolerance_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "time_tolerance_ms must be >= 0");
-  if (!d_counts || !d_times_ms || !d_gt_ms || !d_gt_offsets || !d_tally || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (int rc = check_score_args(n_heads, n_windows, event_cap, n_thr, time_tolerance_ms,
+                                d_counts && d_times_ms && d_gt_ms && d_gt_offsets && d_tally && (d_events || event_cap == 0)))
+    return rc;
   if (n_heads == 0) return MKWS_OK;
   return launch_score(d_events, d_counts, n_heads, n_thr, event_cap, d_times_ms, n_windows, nullptr, d_gt_ms, d_gt_offsets, time_tolerance_ms, d_tally, stream);
 }
@@ -364,10 +385,9 @@ extern "C" int mkws_detect_score(const mkws_detect_event* d_events, const int32_
 extern "C" int mkws_detect_score_segments(const mkws_detect_event* d_events, const int32_t* d_counts, const int32_t* d_seg_offsets, int n_seg, int n_rows,
                                           int n_thr, int event_cap, const int64_t* d_times_ms, const double* d_gt_ms, const int32_t* d_gt_offsets,
                                           double time_tolerance_ms, int32_t* d_tally, void* stream) {
-  if (n_seg < 0 || n_rows < 0 || event_cap < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
-  if (n_thr < 1) return fail(MKWS_ERR_INVALID_ARG, "n_thr = %d: at least one threshold", n_thr);
-  if (!(time_tolerance_ms >= 0)) return fail(MKWS_ERR_INVALID_ARG, "time_tolerance_ms must be >= 0");
-  if (!d_counts || !d_seg_offsets || (!d_times_ms && n_rows > 0) || !d_gt_ms || !d_gt_offsets || !d_tally || (!d_events && event_cap > 0)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (int rc = check_score_args(n_seg, n_rows, event_cap, n_thr, time_tolerance_ms,
+                                d_counts && d_seg_offsets && (d_times_ms || n_rows <= 0) && d_gt_ms && d_gt_offsets && d_tally && (d_events || event_cap == 0)))
+    return rc;
   if (n_seg == 0) return MKWS_OK;
   return launch_score(d_events, d_counts, n_seg, n_thr, event_cap, d_times_ms, n_rows, d_seg_offsets, d_gt_ms, d_gt_offsets, time_tolerance_ms, d_tally, stream);
 }

@@ -1,9 +1,15 @@
-"""Device streaming detector: host wrapper over mkws_detect_stream (include/mkws.h).
+"""Device streaming detector: host wrappers over mkws_detect_stream / mkws_detect_segments and their scorers (include/mkws.h).
 
-SingleTargetRecognizeCommands (embedding/single_target_recognize_commands.py) stepped over every window of a stream, for N keyword
-heads x T detection thresholds in one launch.  The host class is the specification: labels, is_new_command and the float64 scores
-are equal bit for bit (tests/test_detector_device.py).  score_on_device goes on to mkws_detect_score: the fires of every lane matched
-against ground-truth times on the device, embedding/tpr_fpr.py being the specification (tests/test_operating_curve_gpu.py)."""
+SingleTargetRecognizeCommands (embedding/single_target_recognize_commands.py) stepped over every window of a stream, for P planes x T
+detection thresholds in one launch.  A plane is one walk of the detector: a keyword head over the windows of ONE recording
+(detect_on_device) or one of S recordings laid back to back, each with its own windows and times (detect_segments_on_device).  The host
+class is the specification: labels, is_new_command and the float64 scores are equal bit for bit (tests/test_detector_device.py).
+score_on_device / score_segments_on_device go on to mkws_detect_score[_segments]: the fires of every lane matched against ground-truth
+times on the device, embedding/tpr_fpr.py being the specification (tests/test_operating_curve_gpu.py).
+
+The four entry points keep what differs between the two forms (how the times are checked, the C call, the event capacity and its
+fallback, the per-plane views of trace output, the empty returns) and share the rest: _check_thresholds, _check_tolerance,
+_device_probs, and the device rounds _detect_round and _score_round, each one upload, one device-to-host copy, one synchronisation."""
 import ctypes
 
 import numpy as np
@@ -60,60 +66,127 @@ def event_capacity(times_ms, suppression_ms, fired_only=False):
     return min(W, per + 2 if fired_only else 2 * per + 2)
 
 
-def detect_on_device(probs, times_ms, thresholds, average_window_duration_ms, suppression_ms, minimum_count, target_id=2, trace=False,
-                     fired_only=False):
-    """probs: CUDA tensor [N, W, C], float32 or float64 (made contiguous if it is a view), or a numpy array, which is uploaded.
-    times_ms: W non-decreasing integers.  thresholds: T floats.  -> DetectResult; never a cut event list.  One launch and one
-    device-to-host copy (= one synchronisation) per call; a second round only if a lane had more events than event_capacity() allows
-    for (fired_only=False on a stream with quiet stretches)."""
-    import torch
-    times = check_times(times_ms)                                      # before anything touches the device
+def _check_thresholds(thresholds, average_window_duration_ms):
+    """-> float64 [T], T >= 1."""
     thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
     if thr.size < 1:
         raise ValueError("at least one threshold")
     if not average_window_duration_ms >= 0:
         raise ValueError("average_window_duration_ms must be >= 0")
+    return thr
+
+
+def _check_tolerance(time_tolerance_ms, span):
+    """-> the tolerance as a float; span: the largest |time| of the call."""
+    tol = float(time_tolerance_ms)
+    if not tol >= 0:
+        raise ValueError("time_tolerance_ms must be >= 0")
+    # the device forms t +- tol in float64; CPython does so too for a float tolerance and exactly for an int one: the same while both fit 2^53
+    if span > 2 ** 53 or (np.isfinite(tol) and span + tol > 2 ** 53):
+        raise ValueError("times_ms (and times_ms +- time_tolerance_ms) must lie within +-2**53 milliseconds: they are compared as float64")
+    return tol
+
+
+def _device_probs(probs, rank, shape_text, n_times, mismatch, target_id):
+    """probs as the C calls read them: a contiguous CUDA tensor of `rank` dimensions [..., rows, classes], float32 or float64, with one
+    row per timestamp (`mismatch`: the message for another count, formatted with the two) and target_id among its classes.  A numpy
+    array is uploaded."""
+    import torch
     if not torch.is_tensor(probs):
         a = np.asarray(probs)
         probs = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)).cuda()
-    if probs.dim() != 3 or not probs.is_cuda or probs.dtype not in (torch.float32, torch.float64):
-        raise ValueError("probs must be a CUDA tensor or numpy array [heads, windows, classes] of float32 or float64")
-    N, W, C = probs.shape
-    if W != times.shape[0]:
-        raise ValueError(f"{W} windows but {times.shape[0]} timestamps")
+    if probs.dim() != rank or not probs.is_cuda or probs.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"probs must be a CUDA tensor or numpy array {shape_text} of float32 or float64")
+    rows, C = probs.shape[-2:]
+    if rows != n_times:
+        raise ValueError(mismatch.format(rows, n_times))
     if not 0 <= int(target_id) < C:
         raise ValueError(f"target_id {target_id} outside [0, {C})")
-    probs = probs.contiguous()
-    T = int(thr.size)
-    if N == 0 or W == 0:                                               # nothing to launch (the C call would write nothing either)
-        return DetectResult(np.zeros((N, T), np.int32), np.zeros((N, T, 0), EVENT_DTYPE),
-                            np.zeros((N, W), np.float64) if trace else None, np.zeros((N, T, W), np.uint8) if trace else None)
+    return probs.contiguous()
+
+
+def _detect_round(probs, parts, launch, P, T, cap, most, fired_only, trace_rows):
+    """The detector over P planes x T thresholds with its events on the host.  parts: what the launch reads beside probs, one upload;
+    launch(L, pointers of the parts, fired_only, events, cap, counts, scores, flags, stream): the form's C call.  -> (counts int32 [P, T],
+    events EVENT_DTYPE [P, T, capacity], scores float64 [trace_rows] and flags uint8 [T * trace_rows] as the kernel lays them out, or None
+    for trace_rows=None).  One launch and one copy (= one synchronisation); a second round at capacity `most` if a lane had more than
+    `cap` events."""
+    import torch
+    L = _lib.lib()
+    dev = probs.device
+    trace = trace_rows is not None
+    with torch.cuda.device(dev):
+        d_in, ptrs = _lib.upload_words(parts, dev)
+        d_scores = torch.empty(trace_rows, dtype=torch.float64, device=dev) if trace else None
+        d_flags = torch.empty(T * trace_rows, dtype=torch.uint8, device=dev) if trace else None
+        while True:
+            # counts (int32 pairs padded to whole 8-byte words) and events in ONE buffer, so that they cross in one copy
+            cwords = (P * T + 1) // 2
+            d_out = torch.empty(cwords + 2 * P * T * cap, dtype=torch.int64, device=dev)
+            base = d_out.data_ptr()
+            _lib.check(launch(L, ptrs, int(bool(fired_only)), base + 8 * cwords, cap, base, d_scores.data_ptr() if trace else None,
+                              d_flags.data_ptr() if trace else None, _lib.current_stream_ptr()))
+            out = d_out.cpu().numpy()                                  # the call's one synchronisation
+            counts = out[:cwords].view(np.int32)[:P * T].reshape(P, T)
+            if int(counts.max()) <= cap:
+                break
+            cap = most
+        events = out[cwords:].view(EVENT_DTYPE).reshape(P, T, cap)
+        return counts, events, d_scores.cpu().numpy() if trace else None, d_flags.cpu().numpy() if trace else None
+
+
+def _score_round(probs, parts, launch, launch_score, P, T, cap, noun):
+    """The fires of P planes x T thresholds matched against ground truth without leaving the device: parts and launch as _detect_round,
+    launch_score(L, pointers of the parts, events, counts, cap, tally, stream): the form's scorer.  -> int32 [P, T, 3].  One upload, two
+    launches, one copy of 16 bytes per lane (= one synchronisation); RuntimeError naming the `noun` ("head", "segment") of a lane whose
+    event list was cut."""
+    import torch
     L = _lib.lib()
     dev = probs.device
     with torch.cuda.device(dev):
-        # times and thresholds travel in one upload: int64 times, then the float64 thresholds' bit patterns
-        host_in = np.concatenate([times, thr.view(np.int64)])
-        d_in = torch.from_numpy(host_in).to(dev, non_blocking=True)
-        d_scores = torch.empty((N, W), dtype=torch.float64, device=dev) if trace else None
-        d_flags = torch.empty((N, T, W), dtype=torch.uint8, device=dev) if trace else None
-        cap = event_capacity(times, suppression_ms, fired_only)
-        while True:
-            # counts (int32 pairs padded to whole 8-byte words) and events in ONE buffer, so that they cross in one copy
-            cwords = (N * T + 1) // 2
-            d_out = torch.empty(cwords + 2 * N * T * cap, dtype=torch.int64, device=dev)
-            base = d_out.data_ptr()
-            _lib.check(L.mkws_detect_stream(
-                probs.data_ptr(), int(probs.dtype == torch.float64), N, W, C, int(target_id), d_in.data_ptr(), d_in.data_ptr() + 8 * W, T,
-                float(average_window_duration_ms), float(suppression_ms), int(minimum_count), int(bool(fired_only)),
-                base + 8 * cwords, cap, base, d_scores.data_ptr() if trace else None, d_flags.data_ptr() if trace else None,
-                _lib.current_stream_ptr()))
-            out = d_out.cpu().numpy()                                  # the call's one synchronisation
-            counts = out[:cwords].view(np.int32)[:N * T].reshape(N, T)
-            if counts.size == 0 or int(counts.max()) <= cap:
-                break
-            cap = W                                                    # a lane cannot have more events than windows
-        events = out[cwords:].view(EVENT_DTYPE).reshape(N, T, cap)
-        return DetectResult(counts, events, d_scores.cpu().numpy() if trace else None, d_flags.cpu().numpy() if trace else None)
+        d_in, ptrs = _lib.upload_words(parts, dev)
+        d_events = torch.empty(2 * P * T * cap, dtype=torch.int64, device=dev)
+        d_counts = torch.empty(P * T, dtype=torch.int32, device=dev)
+        d_tally = torch.empty((P, T, 4), dtype=torch.int32, device=dev)
+        stream = _lib.current_stream_ptr()
+        _lib.check(launch(L, ptrs, 1, d_events.data_ptr(), cap, d_counts.data_ptr(), None, None, stream))
+        _lib.check(launch_score(L, ptrs, d_events.data_ptr(), d_counts.data_ptr(), cap, d_tally.data_ptr(), stream))
+        tally = d_tally.cpu().numpy()                                  # the call's one synchronisation: 16 bytes per lane
+    if tally[:, :, 3].any():
+        n, k = (int(x[0]) for x in np.nonzero(tally[:, :, 3]))
+        raise RuntimeError(f"{noun} {n}, threshold {k}: {int(tally[n, k, 0])} fires for an event list of {cap}; the list was cut and cannot be scored")
+    return np.ascontiguousarray(tally[:, :, :3])
+
+
+def _stream_form(probs, times, T, average_window_duration_ms, suppression_ms, minimum_count, target_id):
+    """The head form: -> (probs [N, W, C] as checked by _device_probs, the `launch` of the two rounds = mkws_detect_stream, for parts that
+    begin with times and thresholds)."""
+    import torch
+    probs = _device_probs(probs, 3, "[heads, windows, classes]", times.shape[0], "{} windows but {} timestamps", target_id)
+    N, W, C = probs.shape
+    return probs, lambda L, ptrs, *out: L.mkws_detect_stream(
+        probs.data_ptr(), int(probs.dtype == torch.float64), N, W, C, int(target_id), ptrs[0], ptrs[1], T,
+        float(average_window_duration_ms), float(suppression_ms), int(minimum_count), *out)
+
+
+def detect_on_device(probs, times_ms, thresholds, average_window_duration_ms, suppression_ms, minimum_count, target_id=2, trace=False,
+                     fired_only=False):
+    """probs: CUDA tensor [N, W, C], float32 or float64 (made contiguous if it is a view), or a numpy array, which is uploaded.
+    times_ms: W non-decreasing integers.  thresholds: T floats.  -> DetectResult; never a cut event list.  One upload (times and
+    thresholds), one launch and one device-to-host copy (= one synchronisation) per call; a second round only if a lane had more events
+    than event_capacity() allows for (fired_only=False on a stream with quiet stretches)."""
+    times = check_times(times_ms)                                      # before anything touches the device
+    thr = _check_thresholds(thresholds, average_window_duration_ms)
+    T = int(thr.size)
+    probs, launch = _stream_form(probs, times, T, average_window_duration_ms, suppression_ms, minimum_count, target_id)
+    N, W, _ = probs.shape
+    if N == 0 or W == 0:                                               # nothing to launch (the C call would write nothing either)
+        return DetectResult(np.zeros((N, T), np.int32), np.zeros((N, T, 0), EVENT_DTYPE),
+                            np.zeros((N, W), np.float64) if trace else None, np.zeros((N, T, W), np.uint8) if trace else None)
+    # a lane cannot have more events than windows
+    counts, events, scores, flags = _detect_round(probs, [times, thr], launch, N, T, event_capacity(times, suppression_ms, fired_only), W,
+                                                  fired_only, N * W if trace else None)
+    return DetectResult(counts, events, scores.reshape(N, W) if trace else None, flags.reshape(N, T, W) if trace else None)
 
 
 SCORE_GT_TILE = 2048      # ground-truth entries of a head the score kernel stages in LDS at a time (kScoreTile, csrc/mkws_detect.hip)
@@ -140,61 +213,21 @@ def score_on_device(probs, times_ms, thresholds, gt_times_per_head, time_toleran
     device (mkws_detect_score): -> int32 [N, T, 3] = (found, true_positives_raw, false_negatives) per lane, the three integers
     embedding/tpr_fpr.tpr_fpr derives everything from (true_positives_raw is not yet capped to the number of occurrences).  probs,
     times_ms, thresholds as detect_on_device; gt_times_per_head: N lists of times in ms, in the order tpr_fpr would be given them.
-    One upload (times, thresholds, ground truth, offsets), two launches, one copy of 16 * N * T bytes: no event list reaches the host."""
-    import torch
+    One upload (times, thresholds, ground truth, offsets), two launches, one copy of 16 * N * T bytes (= one synchronisation): no event
+    list reaches the host; RuntimeError if a lane's event list was cut."""
     times = check_times(times_ms)
-    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    if thr.size < 1:
-        raise ValueError("at least one threshold")
-    if not average_window_duration_ms >= 0:
-        raise ValueError("average_window_duration_ms must be >= 0")
-    tol = float(time_tolerance_ms)
-    if not tol >= 0:
-        raise ValueError("time_tolerance_ms must be >= 0")
-    # the device forms t +- tol in float64; CPython does so too for a float tolerance and exactly for an int one: the same while both fit 2^53
-    span = max(abs(int(times[0])), abs(int(times[-1]))) if times.size else 0
-    if span > 2 ** 53 or (np.isfinite(tol) and span + tol > 2 ** 53):
-        raise ValueError("times_ms (and times_ms +- time_tolerance_ms) must lie within +-2**53 milliseconds: they are compared as float64")
-    gt, offsets = pack_groundtruth(gt_times_per_head, len(probs))       # refused before anything is uploaded
-    if not torch.is_tensor(probs):
-        a = np.asarray(probs)
-        probs = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)).cuda()
-    if probs.dim() != 3 or not probs.is_cuda or probs.dtype not in (torch.float32, torch.float64):
-        raise ValueError("probs must be a CUDA tensor or numpy array [heads, windows, classes] of float32 or float64")
-    N, W, C = probs.shape
-    if W != times.shape[0]:
-        raise ValueError(f"{W} windows but {times.shape[0]} timestamps")
-    if not 0 <= int(target_id) < C:
-        raise ValueError(f"target_id {target_id} outside [0, {C})")
+    thr = _check_thresholds(thresholds, average_window_duration_ms)
+    tol = _check_tolerance(time_tolerance_ms, max(abs(int(times[0])), abs(int(times[-1]))) if times.size else 0)   # (non-decreasing)
+    gt, gt_off = pack_groundtruth(gt_times_per_head, len(probs))        # refused before anything is uploaded
     T = int(thr.size)
+    probs, launch = _stream_form(probs, times, T, average_window_duration_ms, suppression_ms, minimum_count, target_id)
+    N, W, _ = probs.shape
     if N == 0:
         return np.zeros((0, T, 3), np.int32)
-    probs = probs.contiguous()
-    L = _lib.lib()
-    dev = probs.device
-    with torch.cuda.device(dev):
-        # one upload of 8-byte words: int64 times, the bit patterns of the float64 thresholds and ground truth, the int32 offsets in pairs
-        off_words = np.zeros((N + 2) // 2 * 2, np.int32)
-        off_words[:N + 1] = offsets
-        host_in = np.concatenate([times, thr.view(np.int64), gt.view(np.int64), off_words.view(np.int64)])
-        d_in = torch.from_numpy(host_in).to(dev, non_blocking=True)
-        p_times = d_in.data_ptr()
-        p_thr, p_gt, p_off = p_times + 8 * W, p_times + 8 * (W + T), p_times + 8 * (W + T + gt.size)
-        cap = event_capacity(times, suppression_ms, fired_only=True)
-        d_events = torch.empty(2 * N * T * cap, dtype=torch.int64, device=dev)
-        d_counts = torch.empty(N * T, dtype=torch.int32, device=dev)
-        d_tally = torch.empty((N, T, 4), dtype=torch.int32, device=dev)
-        stream = _lib.current_stream_ptr()
-        _lib.check(L.mkws_detect_stream(
-            probs.data_ptr(), int(probs.dtype == torch.float64), N, W, C, int(target_id), p_times, p_thr, T,
-            float(average_window_duration_ms), float(suppression_ms), int(minimum_count), 1, d_events.data_ptr(), cap, d_counts.data_ptr(),
-            None, None, stream))
-        _lib.check(L.mkws_detect_score(d_events.data_ptr(), d_counts.data_ptr(), N, T, cap, p_times, W, p_gt, p_off, tol, d_tally.data_ptr(), stream))
-        tally = d_tally.cpu().numpy()                                  # the call's one synchronisation: 16 bytes per lane
-    if tally[:, :, 3].any():
-        n, k = (int(x[0]) for x in np.nonzero(tally[:, :, 3]))
-        raise RuntimeError(f"head {n}, threshold {k}: {int(tally[n, k, 0])} fires for an event list of {cap}; the list was cut and cannot be scored")
-    return np.ascontiguousarray(tally[:, :, :3])
+    return _score_round(probs, [times, thr, gt, gt_off], launch,
+                        lambda L, ptrs, events, counts, cap, tally, stream: L.mkws_detect_score(
+                            events, counts, N, T, cap, ptrs[0], W, ptrs[2], ptrs[3], tol, tally, stream),
+                        N, T, event_capacity(times, suppression_ms, fired_only=True), "head")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -230,132 +263,63 @@ class SegmentDetectResult(DetectResult):
     trace=True scores is a list of S float64 [len_s] and flags a list of S uint8 [T, len_s], else None."""
 
 
-def _segment_probs(probs, rows):
-    import torch
-    if not torch.is_tensor(probs):
-        a = np.asarray(probs)
-        probs = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)).cuda()
-    if probs.dim() != 2 or not probs.is_cuda or probs.dtype not in (torch.float32, torch.float64):
-        raise ValueError("probs must be a CUDA tensor or numpy array [rows, classes] of float32 or float64")
-    if probs.shape[0] != rows:
-        raise ValueError(f"{probs.shape[0]} rows of probabilities but {rows} timestamps")
-    return probs.contiguous()
-
-
-def _segment_capacity(times, off, suppression_ms, fired_only):
+def _segment_capacity(times, spans, suppression_ms, fired_only):
     """The largest event_capacity over the segments, and the longest segment."""
-    spans = list(zip(off[:-1].tolist(), off[1:].tolist()))
     return (max([event_capacity(times[a:b], suppression_ms, fired_only) for a, b in spans], default=0),
             max([b - a for a, b in spans], default=0))
+
+
+def _segments_form(probs, times, S, T, average_window_duration_ms, suppression_ms, minimum_count, target_id):
+    """The segmented form: -> (probs [R, C] as checked by _device_probs, the `launch` of the two rounds = mkws_detect_segments, for parts
+    that begin with times, thresholds and segment offsets)."""
+    import torch
+    probs = _device_probs(probs, 2, "[rows, classes]", times.shape[0], "{} rows of probabilities but {} timestamps", target_id)
+    R, C = probs.shape
+    return probs, lambda L, ptrs, *out: L.mkws_detect_segments(
+        probs.data_ptr(), int(probs.dtype == torch.float64), ptrs[2], S, R, C, int(target_id), ptrs[0], ptrs[1], T,
+        float(average_window_duration_ms), float(suppression_ms), int(minimum_count), *out)
 
 
 def detect_segments_on_device(probs, seg_offsets, times_ms, thresholds, average_window_duration_ms, suppression_ms, minimum_count, target_id=2,
                               trace=False, fired_only=False):
     """detect_on_device for S concatenated recordings: probs CUDA tensor (or numpy array, which is uploaded) [rows, C], float32 or
     float64; segment s = rows seg_offsets[s] .. seg_offsets[s + 1] with its own non-decreasing times_ms[those rows]; thresholds: T
-    floats.  -> SegmentDetectResult whose segment s equals detect_on_device on that slice alone; never a cut event list.  One upload,
-    one launch and one device-to-host copy per call; a second round at the longest segment's length only if a lane had more events
-    than the largest event_capacity() over the segments allows for."""
-    import torch
+    floats.  -> SegmentDetectResult whose segment s equals detect_on_device on that slice alone; never a cut event list.  One upload
+    (times, thresholds and offsets), one launch and one device-to-host copy (= one synchronisation) per call; a second round at the
+    longest segment's length only if a lane had more events than the largest event_capacity() over the segments allows for."""
     off, times = check_segments(seg_offsets, times_ms)                 # before anything touches the device
-    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    if thr.size < 1:
-        raise ValueError("at least one threshold")
-    if not average_window_duration_ms >= 0:
-        raise ValueError("average_window_duration_ms must be >= 0")
-    R, S, T = int(times.shape[0]), int(off.shape[0]) - 1, int(thr.size)
-    probs = _segment_probs(probs, R)
-    C = probs.shape[1]
-    if not 0 <= int(target_id) < C:
-        raise ValueError(f"target_id {target_id} outside [0, {C})")
-    spans = list(zip(off[:-1].tolist(), off[1:].tolist()))
+    thr = _check_thresholds(thresholds, average_window_duration_ms)
+    S, T = int(off.shape[0]) - 1, int(thr.size)
+    probs, launch = _segments_form(probs, times, S, T, average_window_duration_ms, suppression_ms, minimum_count, target_id)
     if S == 0:
         return SegmentDetectResult(np.zeros((0, T), np.int32), np.zeros((0, T, 0), EVENT_DTYPE), [] if trace else None, [] if trace else None)
-    L = _lib.lib()
-    dev = probs.device
-    with torch.cuda.device(dev):
-        # times, thresholds and offsets travel in one upload of 8-byte words
-        off_words = np.zeros((S + 2) // 2 * 2, np.int32)
-        off_words[:S + 1] = off
-        d_in = torch.from_numpy(np.concatenate([times, thr.view(np.int64), off_words.view(np.int64)])).to(dev, non_blocking=True)
-        p_times = d_in.data_ptr()
-        p_thr, p_off = p_times + 8 * R, p_times + 8 * (R + T)
-        d_scores = torch.empty(R, dtype=torch.float64, device=dev) if trace else None
-        d_flags = torch.empty(T * R, dtype=torch.uint8, device=dev) if trace else None
-        cap, longest = _segment_capacity(times, off, suppression_ms, fired_only)
-        while True:
-            cwords = (S * T + 1) // 2
-            d_out = torch.empty(cwords + 2 * S * T * cap, dtype=torch.int64, device=dev)
-            base = d_out.data_ptr()
-            _lib.check(L.mkws_detect_segments(
-                probs.data_ptr(), int(probs.dtype == torch.float64), p_off, S, R, C, int(target_id), p_times, p_thr, T,
-                float(average_window_duration_ms), float(suppression_ms), int(minimum_count), int(bool(fired_only)),
-                base + 8 * cwords, cap, base, d_scores.data_ptr() if trace else None, d_flags.data_ptr() if trace else None,
-                _lib.current_stream_ptr()))
-            out = d_out.cpu().numpy()                                  # the call's one synchronisation
-            counts = out[:cwords].view(np.int32)[:S * T].reshape(S, T)
-            if int(counts.max()) <= cap:
-                break
-            cap = longest                                              # a lane cannot have more events than its segment has windows
-        events = out[cwords:].view(EVENT_DTYPE).reshape(S, T, cap)
-        scores = flags = None
-        if trace:
-            h_scores, h_flags = d_scores.cpu().numpy(), d_flags.cpu().numpy()
-            scores = [h_scores[a:b] for a, b in spans]
-            flags = [h_flags[T * a:T * b].reshape(T, b - a) for a, b in spans]
-        return SegmentDetectResult(counts, events, scores, flags)
+    spans = list(zip(off[:-1].tolist(), off[1:].tolist()))
+    # a lane cannot have more events than its segment has windows
+    cap, longest = _segment_capacity(times, spans, suppression_ms, fired_only)
+    counts, events, scores, flags = _detect_round(probs, [times, thr, off], launch, S, T, cap, longest, fired_only,
+                                                  times.shape[0] if trace else None)
+    if trace:
+        scores, flags = [scores[a:b] for a, b in spans], [flags[T * a:T * b].reshape(T, b - a) for a, b in spans]
+    return SegmentDetectResult(counts, events, scores, flags)
 
 
 def score_segments_on_device(probs, seg_offsets, times_ms, thresholds, gt_times_per_segment, time_tolerance_ms, average_window_duration_ms,
                              suppression_ms, minimum_count, target_id=2):
     """score_on_device for S concatenated recordings (mkws_detect_segments + mkws_detect_score_segments): -> int32 [S, T, 3] = (found,
     true_positives_raw, false_negatives) per (segment, threshold) lane; segment s equals score_on_device on that slice with
-    gt_times_per_segment[s].  One upload, two launches, one copy of 16 * S * T bytes; RuntimeError if a lane's event list was cut."""
-    import torch
+    gt_times_per_segment[s].  One upload, two launches, one copy of 16 * S * T bytes (= one synchronisation); RuntimeError if a lane's
+    event list was cut."""
     off, times = check_segments(seg_offsets, times_ms)
-    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    if thr.size < 1:
-        raise ValueError("at least one threshold")
-    if not average_window_duration_ms >= 0:
-        raise ValueError("average_window_duration_ms must be >= 0")
-    tol = float(time_tolerance_ms)
-    if not tol >= 0:
-        raise ValueError("time_tolerance_ms must be >= 0")
-    span = int(np.abs(times).max()) if times.size else 0
-    if span > 2 ** 53 or (np.isfinite(tol) and span + tol > 2 ** 53):
-        raise ValueError("times_ms (and times_ms +- time_tolerance_ms) must lie within +-2**53 milliseconds: they are compared as float64")
-    R, S, T = int(times.shape[0]), int(off.shape[0]) - 1, int(thr.size)
+    thr = _check_thresholds(thresholds, average_window_duration_ms)
+    tol = _check_tolerance(time_tolerance_ms, int(np.abs(times).max()) if times.size else 0)
+    S, T = int(off.shape[0]) - 1, int(thr.size)
     gt, gt_off = pack_groundtruth(gt_times_per_segment, S)             # refused before anything is uploaded
-    probs = _segment_probs(probs, R)
-    C = probs.shape[1]
-    if not 0 <= int(target_id) < C:
-        raise ValueError(f"target_id {target_id} outside [0, {C})")
+    probs, launch = _segments_form(probs, times, S, T, average_window_duration_ms, suppression_ms, minimum_count, target_id)
     if S == 0:
         return np.zeros((0, T, 3), np.int32)
-    L = _lib.lib()
-    dev = probs.device
-    with torch.cuda.device(dev):
-        words = np.zeros((2, (S + 2) // 2 * 2), np.int32)
-        words[0, :S + 1], words[1, :S + 1] = off, gt_off
-        host_in = np.concatenate([times, thr.view(np.int64), gt.view(np.int64), words[0].view(np.int64), words[1].view(np.int64)])
-        d_in = torch.from_numpy(host_in).to(dev, non_blocking=True)
-        p_times = d_in.data_ptr()
-        p_thr, p_gt = p_times + 8 * R, p_times + 8 * (R + T)
-        p_off = p_gt + 8 * gt.size
-        p_gt_off = p_off + 4 * words.shape[1]
-        cap, _ = _segment_capacity(times, off, suppression_ms, True)
-        d_events = torch.empty(2 * S * T * cap, dtype=torch.int64, device=dev)
-        d_counts = torch.empty(S * T, dtype=torch.int32, device=dev)
-        d_tally = torch.empty((S, T, 4), dtype=torch.int32, device=dev)
-        stream = _lib.current_stream_ptr()
-        _lib.check(L.mkws_detect_segments(
-            probs.data_ptr(), int(probs.dtype == torch.float64), p_off, S, R, C, int(target_id), p_times, p_thr, T,
-            float(average_window_duration_ms), float(suppression_ms), int(minimum_count), 1, d_events.data_ptr(), cap, d_counts.data_ptr(),
-            None, None, stream))
-        _lib.check(L.mkws_detect_score_segments(d_events.data_ptr(), d_counts.data_ptr(), p_off, S, R, T, cap, p_times, p_gt, p_gt_off, tol,
-                                                d_tally.data_ptr(), stream))
-        tally = d_tally.cpu().numpy()                                  # the call's one synchronisation: 16 bytes per lane
-    if tally[:, :, 3].any():
-        s, k = (int(x[0]) for x in np.nonzero(tally[:, :, 3]))
-        raise RuntimeError(f"segment {s}, threshold {k}: {int(tally[s, k, 0])} fires for an event list of {cap}; the list was cut and cannot be scored")
-    return np.ascontiguousarray(tally[:, :, :3])
+    R = int(times.shape[0])
+    spans = list(zip(off[:-1].tolist(), off[1:].tolist()))
+    return _score_round(probs, [times, thr, off, gt, gt_off], launch,
+                        lambda L, ptrs, events, counts, cap, tally, stream: L.mkws_detect_score_segments(
+                            events, counts, ptrs[2], S, R, T, cap, ptrs[0], ptrs[3], ptrs[4], tol, tally, stream),
+                        S, T, _segment_capacity(times, spans, suppression_ms, True)[0], "segment")

@@ -412,16 +412,10 @@ def detect(inferences, flags: StreamFlags, threshold, sample_rate=16000, data_sa
     return found, found_conf
 
 
-def detect_many(inferences, flags: StreamFlags, thresholds, sample_rate=16000, data_samples=None, keywords=None):
-    """detect() for every keyword and every threshold of a stream at once.  inferences: [W, 3] for one keyword, or [N, W, 3] / a list
-    of N [W, 3] for several (numpy arrays or CUDA tensors); keywords: the N target words (default: flags.target_keyword for each).
-    -> {threshold: (found_words, found_words_w_confidences)} for [W, 3] input, a list of N such dicts otherwise, holding exactly the
-    lists detect() builds.  CUDA tensors, and numpy input on a host with a GPU, take ONE device launch for all keywords and thresholds
-    (..detector.detect_on_device); numpy input on a host without a GPU loops over detect().  More inference rows than window offsets
-    are cut to the offsets (chunk_audio as shipped can return more); fewer raise IndexError, as detect() does."""
-    import dataclasses
+def _keyword_planes(inferences, flags, keywords):
+    """What detect_many and operating_curves accept as inferences -> (one array or tensor [N, W, classes], whether it is a tensor,
+    whether the caller gave [W, classes], the N keywords)."""
     import torch
-    thresholds = list(thresholds)
     as_list = isinstance(inferences, (list, tuple))
     on_device = torch.is_tensor(inferences[0] if as_list and len(inferences) else inferences)
     if as_list:
@@ -438,11 +432,44 @@ def detect_many(inferences, flags: StreamFlags, thresholds, sample_rate=16000, d
     keywords = [flags.target_keyword] * N if keywords is None else list(keywords)
     if len(keywords) != N:
         raise ValueError(f"{len(keywords)} keywords for {N} rows of inferences")
+    return inferences, on_device, single, keywords
+
+
+def _stream_windows(inferences, flags, sample_rate, data_samples):
+    """-> (clip and stride in samples, the start sample of every window detect() would step over); IndexError, as there, for fewer
+    rows of inferences [N, W, classes] than windows."""
     clip = int(flags.clip_duration_ms * sample_rate / 1000)
     stride = int(flags.clip_stride_ms * sample_rate / 1000)
     offsets = window_offsets(data_samples, clip, stride) if data_samples is not None else [i * stride for i in range(inferences.shape[1])]
     if inferences.shape[1] < len(offsets):
         raise IndexError(f"index {inferences.shape[1]} is out of bounds: {inferences.shape[1]} rows of inferences for {len(offsets)} windows")
+    return clip, stride, offsets
+
+
+def _found_by_threshold(keyword, t_ms, thresholds, events, counts):
+    """The fired-only events [T, capacity] and their counts [T] of one detector plane, t_ms being the times of its windows
+    -> {threshold: (found_words, found_words_w_confidences)}, the lists detect() builds."""
+    found = {}
+    for k, thr in enumerate(thresholds):
+        ev = events[k, :counts[k]]
+        when = [t_ms[w] for w in ev["window"].tolist()]
+        found[thr] = ([[keyword, t] for t in when], [[keyword, t, s] for t, s in zip(when, ev["score"].tolist())])
+    return found
+
+
+def detect_many(inferences, flags: StreamFlags, thresholds, sample_rate=16000, data_samples=None, keywords=None):
+    """detect() for every keyword and every threshold of a stream at once.  inferences: [W, 3] for one keyword, or [N, W, 3] / a list
+    of N [W, 3] for several (numpy arrays or CUDA tensors); keywords: the N target words (default: flags.target_keyword for each).
+    -> {threshold: (found_words, found_words_w_confidences)} for [W, 3] input, a list of N such dicts otherwise, holding exactly the
+    lists detect() builds.  CUDA tensors, and numpy input on a host with a GPU, take ONE device launch for all keywords and thresholds
+    (..detector.detect_on_device); numpy input on a host without a GPU loops over detect().  More inference rows than window offsets
+    are cut to the offsets (chunk_audio as shipped can return more); fewer raise IndexError, as detect() does."""
+    import dataclasses
+    import torch
+    thresholds = list(thresholds)
+    inferences, on_device, single, keywords = _keyword_planes(inferences, flags, keywords)
+    N = inferences.shape[0]
+    offsets = _stream_windows(inferences, flags, sample_rate, data_samples)[2]
     if not on_device and not torch.cuda.is_available():
         out = [{thr: detect(inferences[n], dataclasses.replace(flags, target_keyword=keywords[n]), thr, sample_rate, data_samples)
                 for thr in thresholds} for n in range(N)]
@@ -457,12 +484,7 @@ def detect_many(inferences, flags: StreamFlags, thresholds, sample_rate=16000, d
         res = detect_on_device(inferences[:, :len(offsets)], t_ms, thresholds, flags.average_window_duration_ms, flags.suppression_ms,
                                flags.minimum_count, target_id=2, fired_only=True)
         counts = res.counts.tolist()
-        for n in range(N):
-            kw = keywords[n]
-            for k, thr in enumerate(thresholds):
-                ev = res.event_buffer[n, k, :counts[n][k]]
-                times = [t_ms[w] for w in ev["window"].tolist()]
-                out[n][thr] = ([[kw, t] for t in times], [[kw, t, s] for t, s in zip(times, ev["score"].tolist())])
+        out = [_found_by_threshold(keywords[n], t_ms, thresholds, res.event_buffer[n], counts[n]) for n in range(N)]
     return out[0] if single else out
 
 
@@ -498,6 +520,23 @@ def summary_from_tally(keyword, thresh, found, true_positives_raw, false_negativ
     return result, capped
 
 
+def _curve_from_tally(keyword, thresholds, tally, n_gt, duration_s, num_nontarget_words):
+    """The tally [T][3] of one scored plane -> (summary_from_tally's dict per threshold, how many of them had their count capped)."""
+    curve, capped = [], 0
+    for thr, lane in zip(thresholds, tally):
+        result, was_capped = summary_from_tally(keyword, thr, *lane, n_gt, duration_s, num_nontarget_words)
+        capped += was_capped
+        curve.append(result)
+    return curve, capped
+
+
+def _read_groundtruth(path):
+    """run.py's ground-truth file: rows `keyword,time_ms`."""
+    import csv
+    with open(path, "r") as fh:
+        return [(row[0], float(row[1])) for row in csv.reader(fh) if row]
+
+
 def operating_curves(inferences, flags: StreamFlags, thresholds, groundtruth, keywords=None, sample_rate=16000, data_samples=None,
                      duration_s=None, num_nontarget_words=None):
     """The operating curve of every keyword of a stream: tpr_fpr.tpr_fpr's summary dict (true-positive rate, false accepts per hour, ...)
@@ -517,33 +556,15 @@ def operating_curves(inferences, flags: StreamFlags, thresholds, groundtruth, ke
     import torch
     from .tpr_fpr import tpr_fpr
     thresholds = list(thresholds)
-    as_list = isinstance(inferences, (list, tuple))
-    on_device = torch.is_tensor(inferences[0] if as_list and len(inferences) else inferences)
-    if as_list:
-        inferences = (torch.stack(list(inferences)) if on_device else np.stack([np.asarray(x) for x in inferences])) if len(inferences) \
-            else np.zeros((0, 0, 3), np.float32)
-    elif not on_device:
-        inferences = np.asarray(inferences)
-    single = not as_list and inferences.ndim == 2
-    if single:
-        inferences = inferences[None]
-    if inferences.ndim != 3:
-        raise ValueError("inferences must be [windows, classes] or [keywords, windows, classes]")
+    inferences, on_device, single, keywords = _keyword_planes(inferences, flags, keywords)
     N = inferences.shape[0]
-    keywords = [flags.target_keyword] * N if keywords is None else list(keywords)
-    if len(keywords) != N:
-        raise ValueError(f"{len(keywords)} keywords for {N} rows of inferences")
     tol = flags.time_tolerance_ms
     if not tol >= 0:
         raise ValueError("time_tolerance_ms must be >= 0")
     gt = _groundtruth_times(groundtruth, keywords)
     if not all(np.isfinite(np.asarray(g, dtype=np.float64)).all() for g in gt):
         raise ValueError("ground-truth times must be finite")
-    clip = int(flags.clip_duration_ms * sample_rate / 1000)
-    stride = int(flags.clip_stride_ms * sample_rate / 1000)
-    offsets = window_offsets(data_samples, clip, stride) if data_samples is not None else [i * stride for i in range(inferences.shape[1])]
-    if inferences.shape[1] < len(offsets):
-        raise IndexError(f"index {inferences.shape[1]} is out of bounds: {inferences.shape[1]} rows of inferences for {len(offsets)} windows")
+    clip, stride, offsets = _stream_windows(inferences, flags, sample_rate, data_samples)
     if duration_s is None:
         duration_s = (data_samples if data_samples is not None else (inferences.shape[1] - 1) * stride + clip) / sample_rate
     capped = 0
@@ -573,14 +594,39 @@ def operating_curves(inferences, flags: StreamFlags, thresholds, groundtruth, ke
             tally = score_on_device(inferences[:, :len(offsets)], t_ms, thresholds, gt, tol, flags.average_window_duration_ms,
                                     flags.suppression_ms, flags.minimum_count, target_id=2).tolist()
             for n in range(N):
-                n_gt = len(gt[n])
-                for k, thr in enumerate(thresholds):
-                    result, was_capped = summary_from_tally(keywords[n], thr, *tally[n][k], n_gt, duration_s, num_nontarget_words)
-                    capped += was_capped
-                    curves[n].append(result)
+                curves[n], was_capped = _curve_from_tally(keywords[n], thresholds, tally[n], len(gt[n]), duration_s, num_nontarget_words)
+                capped += was_capped
     if capped:
         print(f"WARNING: weird timing issue ({capped} of {N * len(thresholds)} keyword x threshold lanes: true positives capped to the ground-truth count)")
     return curves[0] if single else curves
+
+
+def _shared_embedding_passes(keywords, models, wav, groundtruth, thresholds, inference_chunk_len_seconds, average_window_duration_ms,
+                             suppression_ms, time_tolerance_ms):
+    """What multi_keyword_detections and multi_keyword_operating_curves do with a recording before their detector runs: the argument
+    checks and the wav are done when this returns -> (keywords as a list, the StreamFlags of the run, sample rate, samples of the
+    recording, an iterator over the distinct embeddings of `models` that yields (indices of the models on it, their softmax outputs
+    [len(indices), windows, 3] on the device): one streaming_inferences pass each)."""
+    keywords, models = list(keywords), list(models)
+    if len(models) != len(keywords) or len(set(keywords)) != len(keywords):
+        raise ValueError(f"discrepancy: {len(models)} models provided for {len(set(keywords))} keywords")
+    if inference_chunk_len_seconds <= 0:
+        raise ValueError("inference_chunk_len_seconds must be positive")
+    with open(wav, "rb") as f:
+        audio, sample_rate = input_data.decode_wav(f.read())
+    model_settings = input_data.standard_microspeech_model_settings(label_count=3)
+    flags = StreamFlags(wav=wav, ground_truth=groundtruth, target_keyword=keywords[0] if keywords else "", detection_thresholds=thresholds,
+                        average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms,
+                        time_tolerance_ms=time_tolerance_ms, max_chunk_length_sec=inference_chunk_len_seconds)
+    by_embedding = {}
+    for i, m in enumerate(models):                                  # one pass per distinct embedding (normally one)
+        by_embedding.setdefault(id(m.embedding), []).append(i)
+
+    def passes():
+        for idxs in by_embedding.values():
+            yield idxs, streaming_inferences([models[i] for i in idxs], model_settings, audio, sample_rate, 1000, 20,
+                                             max_chunk_length_sec=inference_chunk_len_seconds, as_device=True)
+    return keywords, flags, sample_rate, audio.shape[0], passes()
 
 
 def multi_keyword_operating_curves(keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds=1200,
@@ -589,40 +635,30 @@ def multi_keyword_operating_curves(keywords, models, wav, groundtruth_csv, thres
     (streaming_inferences(as_device=True), as multi_keyword_detections), then operating_curves on the device tensor -- the probabilities,
     the detections and the matching never visit the host.  groundtruth_csv: rows `keyword,time_ms` (run.py's ground-truth file).  The
     other arguments are multi_keyword_detections' flags; the recording's duration is its sample count over its sample rate."""
-    import csv
-    keywords, models, thresholds = list(keywords), list(models), list(thresholds)
-    if len(models) != len(keywords) or len(set(keywords)) != len(keywords):
-        raise ValueError(f"discrepancy: {len(models)} models provided for {len(set(keywords))} keywords")
-    if inference_chunk_len_seconds <= 0:
-        raise ValueError("inference_chunk_len_seconds must be positive")
-    with open(wav, "rb") as f:
-        audio, sample_rate = input_data.decode_wav(f.read())
-    with open(groundtruth_csv, "r") as fh:
-        groundtruth_data = [(row[0], float(row[1])) for row in csv.reader(fh) if row]
-    model_settings = input_data.standard_microspeech_model_settings(label_count=3)
-    flags = StreamFlags(wav=wav, ground_truth=groundtruth_csv, target_keyword=keywords[0] if keywords else "", detection_thresholds=thresholds,
-                        average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms,
-                        time_tolerance_ms=time_tolerance_ms, max_chunk_length_sec=inference_chunk_len_seconds)
-    by_embedding = {}
-    for i, m in enumerate(models):                                  # one pass per distinct embedding (normally one)
-        by_embedding.setdefault(id(m.embedding), []).append(i)
+    thresholds = list(thresholds)
+    keywords, flags, sample_rate, data_samples, passes = _shared_embedding_passes(
+        keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, time_tolerance_ms)
+    groundtruth_data = _read_groundtruth(groundtruth_csv)
     curves = {}
-    for idxs in by_embedding.values():
-        got = streaming_inferences([models[i] for i in idxs], model_settings, audio, sample_rate, 1000, 20,
-                                   max_chunk_length_sec=inference_chunk_len_seconds, as_device=True)
+    for idxs, got in passes:
         per = operating_curves(got, flags, thresholds, groundtruth_data, keywords=[keywords[i] for i in idxs], sample_rate=sample_rate,
-                               data_samples=audio.shape[0], num_nontarget_words=num_nontarget_words)
+                               data_samples=data_samples, num_nontarget_words=num_nontarget_words)
         for i, curve in zip(idxs, per):
             curves[keywords[i]] = curve
     return {kw: curves[kw] for kw in keywords}
 
 
-def calculate_streaming_accuracy(model, model_settings, flag_list, existing_inferences=None):
-    """Reference signature (:50-179): one wav, several StreamFlags; returns (results, inferences) with
-    results = [(FLAGS, {threshold: (found_words, found_words_w_confidences)})]."""
+def _one_recording(flag_list):
+    """What the StreamFlags of one target must share: one wav, one clip length, one stride."""
     assert len(set([f.wav for f in flag_list])) == 1, "can only process one wav"
     assert len(set([f.clip_duration_ms for f in flag_list])) == 1, "cannot vary"
     assert len(set([f.clip_stride_ms for f in flag_list])) == 1, "cannot vary"
+
+
+def calculate_streaming_accuracy(model, model_settings, flag_list, existing_inferences=None):
+    """Reference signature (:50-179): one wav, several StreamFlags; returns (results, inferences) with
+    results = [(FLAGS, {threshold: (found_words, found_words_w_confidences)})]."""
+    _one_recording(flag_list)
     with open(flag_list[0].wav, "rb") as f:
         audio, sample_rate = input_data.decode_wav(f.read())
     if existing_inferences is not None:
@@ -702,25 +738,11 @@ def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inf
     confidence, groundtruth)], min_threshold=...): groundtruth "ng" without a ground-truth file, otherwise tpr_fpr.get_groundtruth's
     classification against its rows `keyword,time_ms` (as shipped: first keyword only).  Also written as JSON to write_detections."""
     import json
-    keywords, models = list(keywords), list(models)
-    if len(models) != len(keywords) or len(set(keywords)) != len(keywords):
-        raise ValueError(f"discrepancy: {len(models)} models provided for {len(set(keywords))} keywords")
-    if inference_chunk_len_seconds <= 0:
-        raise ValueError("inference_chunk_len_seconds must be positive")
-    with open(wav, "rb") as f:
-        audio, sample_rate = input_data.decode_wav(f.read())
-    model_settings = input_data.standard_microspeech_model_settings(label_count=3)
-    per_keyword = [None] * len(models)                              # keyword -> its found_words_w_confidences
-    flags = StreamFlags(wav=wav, ground_truth=groundtruth, target_keyword=keywords[0] if keywords else "", detection_thresholds=[detection_threshold],
-                        average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms, time_tolerance_ms=750,
-                        max_chunk_length_sec=inference_chunk_len_seconds)
-    by_embedding = {}
-    for i, m in enumerate(models):                                  # one pass per distinct embedding (normally one)
-        by_embedding.setdefault(id(m.embedding), []).append(i)
-    for idxs in by_embedding.values():
-        got = streaming_inferences([models[i] for i in idxs], model_settings, audio, sample_rate, 1000, 20,
-                                   max_chunk_length_sec=inference_chunk_len_seconds, as_device=True)
-        found = detect_many(got, flags, [detection_threshold], sample_rate, data_samples=audio.shape[0], keywords=[keywords[i] for i in idxs])
+    keywords, flags, sample_rate, data_samples, passes = _shared_embedding_passes(
+        keywords, models, wav, groundtruth, [detection_threshold], inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, 750)
+    per_keyword = [None] * len(keywords)                            # keyword -> its found_words_w_confidences
+    for idxs, got in passes:
+        found = detect_many(got, flags, [detection_threshold], sample_rate, data_samples=data_samples, keywords=[keywords[i] for i in idxs])
         for i, by_threshold in zip(idxs, found):
             per_keyword[i] = by_threshold[detection_threshold][1]
     unsorted_detections = []
@@ -730,11 +752,8 @@ def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inf
     if groundtruth is None:
         detections_with_confidence = [dict(keyword=d[0], time_ms=d[1], confidence=d[2], groundtruth="ng") for d in detections_with_confidence]
     else:
-        import csv
         from .tpr_fpr import get_groundtruth
-        with open(groundtruth, "r") as fh:
-            groundtruth_data = [(row[0], float(row[1])) for row in csv.reader(fh) if row]
-        detections_with_confidence = get_groundtruth(detections_with_confidence, keywords, groundtruth_data)
+        detections_with_confidence = get_groundtruth(detections_with_confidence, keywords, _read_groundtruth(groundtruth))
     detections = dict(keywords=keywords, detections=detections_with_confidence, min_threshold=detection_threshold)
     if write_detections is not None:
         with open(write_detections, "w") as fh:
@@ -761,9 +780,7 @@ class _Prepared:
 def _read_target(p, live_model):
     """What calculate_streaming_accuracy establishes before it runs anything: one wav, one clip length, one stride."""
     flag_list = p.st.stream_flags
-    assert len(set([f.wav for f in flag_list])) == 1, "can only process one wav"
-    assert len(set([f.clip_duration_ms for f in flag_list])) == 1, "cannot vary"
-    assert len(set([f.clip_stride_ms for f in flag_list])) == 1, "cannot vary"
+    _one_recording(flag_list)
     with open(flag_list[0].wav, "rb") as f:
         p.audio, p.sample_rate = input_data.decode_wav(f.read())
     p.model = live_model
@@ -961,12 +978,8 @@ def eval_stream_tests(stream_targets, live_models=None):
             res = detect_segments_on_device(probs, off, times, thresholds, key[0], key[1], key[2], target_id=2, fired_only=True)
             counts = res.counts.tolist()
             for s, (p, flags) in enumerate(pairs):
-                kw, t_ms, found = flags.target_keyword, times[off[s]:off[s + 1]].tolist(), {}
-                for k, thr in enumerate(thresholds):
-                    ev = res.event_buffer[s, k, :counts[s][k]]
-                    when = [t_ms[w] for w in ev["window"].tolist()]
-                    found[thr] = ([[kw, t] for t in when], [[kw, t, sc] for t, sc in zip(when, ev["score"].tolist())])
-                by_pair[(p.index, id(flags))] = found
+                by_pair[(p.index, id(flags))] = _found_by_threshold(flags.target_keyword, times[off[s]:off[s + 1]].tolist(), thresholds,
+                                                                    res.event_buffer[s], counts[s])
     for p in prepared:
         per_flags = []
         for flags in p.st.stream_flags:
@@ -990,7 +1003,6 @@ def stream_operating_curves(stream_targets, live_models=None, num_nontarget_word
     sample rate) -- from the pass of eval_stream_tests (stored inferences re-used, new ones saved; result pickles are neither read nor
     written) and ONE detector.score_segments_on_device call per distinct detector setting, thresholds and tolerance, summary_from_tally
     on three integers per lane.  A host without a GPU takes operating_curves' host route per target."""
-    import csv
     from ..detector import score_segments_on_device
     targets, prepared = _prepare(stream_targets, live_models, skip_done=False)
     d_all = _batch_inferences(prepared)
@@ -999,8 +1011,7 @@ def stream_operating_curves(stream_targets, live_models=None, num_nontarget_word
     def groundtruth(flags):
         path = os.fspath(flags.ground_truth)
         if path not in gt_cache:
-            with open(path, "r") as fh:
-                gt_cache[path] = [(row[0], float(row[1])) for row in csv.reader(fh) if row]
+            gt_cache[path] = _read_groundtruth(path)
         return gt_cache[path]
     by_pair, capped, lanes = {}, 0, 0
     if d_all is not None:
@@ -1010,14 +1021,10 @@ def stream_operating_curves(stream_targets, live_models=None, num_nontarget_word
             gts = [_groundtruth_times(groundtruth(flags), [flags.target_keyword])[0] for _, flags in pairs]
             tally = score_segments_on_device(probs, off, times, thresholds, gts, key[4], key[0], key[1], key[2], target_id=2).tolist()
             for s, (p, flags) in enumerate(pairs):
-                curve = []
-                for k, thr in enumerate(thresholds):
-                    result, was_capped = summary_from_tally(flags.target_keyword, thr, *tally[s][k], len(gts[s]), p.audio.shape[0] / p.sample_rate,
-                                                            num_nontarget_words)
-                    capped += was_capped
-                    curve.append(result)
+                by_pair[(p.index, id(flags))], was_capped = _curve_from_tally(flags.target_keyword, thresholds, tally[s], len(gts[s]),
+                                                                              p.audio.shape[0] / p.sample_rate, num_nontarget_words)
+                capped += was_capped
                 lanes += len(thresholds)
-                by_pair[(p.index, id(flags))] = curve
     if capped:
         print(f"WARNING: weird timing issue ({capped} of {lanes} keyword x threshold lanes: true positives capped to the ground-truth count)")
     out = [None] * len(targets)

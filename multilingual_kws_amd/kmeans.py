@@ -194,10 +194,7 @@ def kmeans_fit_on_device(x, offsets, n_clusters, seeds, max_iter=300, tol=1e-4, 
     dev = x.device
     with torch.cuda.device(dev):
         # one upload of 8-byte words: the draws, then the offsets in pairs
-        words = np.zeros((off.size + 1) // 2 * 2, np.int32)
-        words[:off.size] = off
-        d_in = torch.from_numpy(np.concatenate([draws.reshape(-1).view(np.int64), words.view(np.int64)])).to(dev, non_blocking=True)
-        p_draws, p_off = d_in.data_ptr(), d_in.data_ptr() + 8 * draws.size
+        d_in, (p_draws, p_off) = _lib.upload_words([draws, off], dev)
         # every output in ONE buffer of 4-byte words, so that they cross in one copy: [f64 centres] centres, labels, init, info
         n64 = 2 * G * k * dim if want_f64 else 0
         at = np.cumsum([0, n64, G * k * dim, rows, G * k, G * 4])

@@ -47,13 +47,6 @@ def sorted_thresholds(thresholds):
     return thr, distinct, where
 
 
-def _words(a):
-    """int32 values padded to whole 8-byte words."""
-    w = np.zeros((a.size + 1) // 2 * 2, np.int32)
-    w[:a.size] = a
-    return w.view(np.int64)
-
-
 def roc_counts_on_device(probs, positives, negatives, thresholds, target_id=2, multiclass=False, negative_class=1):
     """probs: CUDA tensor or numpy array [K, N, C] float32 (what Head.forward_many returns); positives / negatives: K lists of row
     indices into a head's own plane (a row listed twice counts twice); thresholds: T floats in any order.
@@ -90,13 +83,7 @@ def roc_counts_on_device(probs, positives, negatives, thresholds, target_id=2, m
     dev = probs.device
     with torch.cuda.device(dev):
         # one upload of 8-byte words: the bit patterns of the float64 thresholds, then the int32 offsets and row lists in pairs
-        parts = [distinct.view(np.int64), _words(pos_off), _words(neg_off), _words(pos), _words(neg)]
-        d_in = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=True)
-        ptrs, p = [], d_in.data_ptr()
-        for part in parts:
-            ptrs.append(p)
-            p += 8 * part.size
-        p_thr, p_pos_off, p_neg_off, p_pos, p_neg = ptrs
+        d_in, (p_thr, p_pos_off, p_neg_off, p_pos, p_neg) = _lib.upload_words([distinct, pos_off, neg_off, pos, neg], dev)
         # counts of every piece of thresholds and the invalid-entry counters in ONE buffer, so that they cross in one copy
         d_out = torch.empty(K * D * 2 + K, dtype=torch.int32, device=dev)
         base, stream, done = d_out.data_ptr(), _lib.current_stream_ptr(), 0

@@ -346,3 +346,28 @@ def test_shared_embedding_key_is_the_base_weights_content_for_files_too(tmp_path
     assert len(loads) == 3
     with pytest.raises(FileNotFoundError, match="does not exist"):
         transfer_learning.load_models_shared(paths[4:])
+
+
+def test_pack_words_lays_parts_out_in_whole_8_byte_words():
+    from multilingual_kws_amd._lib import pack_words
+    # an int32 part of odd length is padded with a zero, and what follows still starts on a word
+    words, offsets = pack_words([np.array([7, -1, 3], np.int32), np.array([5], np.int64)])
+    assert words.dtype == np.int64 and offsets == [0, 16]
+    assert words[:2].view(np.int32).tolist() == [7, -1, 3, 0] and words[2] == 5
+    # float64 parts cross as their bit patterns
+    nan = np.array([0x7FF8_0000_DEAD_BEEF], np.uint64).view(np.float64)[0]
+    values = np.array([-0.0, np.inf, -np.inf, nan, 1.5], np.float64)
+    words, offsets = pack_words([values])
+    assert offsets == [0] and words.view(np.uint64).tolist() == values.view(np.uint64).tolist()
+    assert words.view(np.uint64)[0] == 1 << 63 and words.view(np.uint64)[3] == 0x7FF8_0000_DEAD_BEEF
+    # an empty part in the middle gets the offset of the part after it
+    words, offsets = pack_words([np.arange(2, dtype=np.int64), np.zeros(0, np.float64), np.zeros(0, np.int32), np.array([9, 8], np.int32)])
+    assert offsets == [0, 16, 16, 16] and words.size == 3 and words[2:].view(np.int32).tolist() == [9, 8]
+    # int64 + float64 + odd int32: 2 + 3 + 2 words
+    words, offsets = pack_words([np.array([1, 2], np.int64), np.array([0.5, 0.25, 0.125]), np.array([4, 5, 6], np.int32)])
+    assert words.size == 7 and offsets == [0, 16, 40] and all(o % 8 == 0 for o in offsets)
+    assert words[:2].tolist() == [1, 2] and words[2:5].view(np.float64).tolist() == [0.5, 0.25, 0.125]
+    assert words[5:].view(np.int32).tolist() == [4, 5, 6, 0]
+    assert pack_words([])[0].shape == (0,) and pack_words([])[1] == []
+    with pytest.raises(TypeError):
+        pack_words([np.zeros(2, np.float32)])
