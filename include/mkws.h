@@ -123,6 +123,26 @@ int mkws_frontend_stream_f32(mkws_frontend* fe, const float* d_audio, int n_samp
                              int window_samples, int hop_samples, float* d_spec, uint16_t* d_raw,
                              int max_windows, void* stream);
 
+/* Live form of mkws_frontend_stream_f32: the same stream fed push by push.  A push is hops_per_push * hop_samples NEW samples (d_audio,
+ * float32); what the stream has to remember between pushes -- its position, the audio of the frame that is not complete yet and a ring
+ * of per-frame filterbank outputs -- lives in d_state, a caller-owned device block of mkws_frontend_live_state_bytes() bytes, 8-byte
+ * aligned.  A zero-filled block is a fresh stream (reset = memset, snapshot / restore = copies; the handle holds nothing of the stream,
+ * so one handle serves any number of them).  Its first int64 is the number of samples pushed so far.
+ * After pushes totalling n samples the windows w < W(n) exist, W(n) = 0 for n < window_samples, else 1 + (n - window_samples) /
+ * hop_samples (the num_windows of mkws_frontend_stream_f32).  A push emits the windows it completed, in order, into rows 0 .. count-1
+ * of d_spec [hops_per_push, frames, channels] and d_raw (either may be NULL, not both): count = W(n + push) - W(n), i.e. 0 while the
+ * first window fills, then hops_per_push.  Rows from count on are left untouched.  Row of window w = row w of
+ * mkws_frontend_stream_f32 over the whole recording, bit for bit.
+ * d_meta int64 [2 + hops_per_push] = {count, index of the first new window, time_ms of each new window}; the time of window w is
+ * (w * hop_samples * 1000) / sample_rate in integers, the start of the window; entries from 2 + count on are left untouched.
+ * MKWS_ERR_INVALID_ARG for NULL pointers, non-positive sizes and a window shorter than one frame; MKWS_ERR_UNSUPPORTED for a hop that is
+ * not a multiple of the frame step.  mkws_frontend_live_state_bytes returns 0 for what the push would refuse.  Two launches,
+ * asynchronous on `stream`, allocates nothing, never synchronises: capturable like every other call (a replayed graph advances the
+ * stream by itself: the position is device state). */
+size_t mkws_frontend_live_state_bytes(const mkws_frontend* fe, int window_samples, int hop_samples, int hops_per_push);
+int mkws_frontend_live_push_f32(mkws_frontend* fe, void* d_state, const float* d_audio, int window_samples, int hop_samples,
+                                int hops_per_push, float* d_spec, uint16_t* d_raw, int64_t* d_meta, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Embedding model.  Replaces `embedding.predict(x)` on the Keras model
  *   EfficientNetB0(include_top=False, weights=None, input_shape=(49,40,1)) -> GAP ->
@@ -380,6 +400,31 @@ int mkws_detect_stream(const void* d_probs, int probs_f64, int n_heads, int n_wi
                        const int64_t* d_times_ms, const double* d_thresholds, int n_thr, double average_window_duration_ms,
                        double suppression_ms, int minimum_count, int fired_only, mkws_detect_event* d_events, int event_cap,
                        int32_t* d_counts, double* d_scores, uint8_t* d_flags, void* stream);
+
+/* Live form of mkws_detect_stream: the detector stepped over the few windows a push completed, its state kept between calls in
+ * d_state, a caller-owned device block of mkws_detect_live_state_bytes() bytes, 8-byte aligned.  A zero-filled block is a fresh stream
+ * (reset = memset, snapshot / restore = copies).  It holds, per head, the last `history` (time, target probability) pairs and the
+ * {label of the last event, time after which it may change} of each threshold's lane.
+ * d_probs float32 [n_heads, max_new, classes]; d_meta int64 [2 + max_new] as mkws_frontend_live_push_f32 writes it: {count, (index of
+ * the first new window: not read), time_ms of each new window}; rows and times from count on are not read; count is clamped into
+ * [0, max_new].  Times must not decrease, from call to call either (the caller checks).
+ * The specification is mkws_detect_stream's: calls whose windows add up to a stream leave, concatenated, that call's events, counts
+ * and scores on the whole stream, byte for byte -- provided `history` is at least the largest number of windows an average spans
+ * (the windows within average_window_duration_ms of each other; multilingual_kws_amd/detector.py, live_history).  Above
+ * MKWS_DETECT_LIVE_MAX_HISTORY the call returns MKWS_ERR_UNSUPPORTED.
+ * d_events [n_heads, n_thr, max_new]: event.window is the index inside this push (0 .. count-1; the caller adds d_meta[1]); a lane has
+ * at most one event per window, so the lists are never cut.  d_counts int32 [n_heads, n_thr]: events of THIS push.  d_scores (optional)
+ * double [n_heads, max_new].  count == 0: the state is left as it is and zero counts are written.
+ * MKWS_ERR_INVALID_ARG as mkws_detect_stream, and for history < 1; MKWS_ERR_UNSUPPORTED for n_thr above 1024 and max_new above
+ * MKWS_DETECT_LIVE_MAX_NEW; n_heads == 0 or max_new == 0 returns MKWS_OK with nothing launched.  mkws_detect_live_state_bytes returns 0
+ * for sizes the step would refuse.  One launch, asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+#define MKWS_DETECT_LIVE_MAX_HISTORY 256
+#define MKWS_DETECT_LIVE_MAX_NEW 1024
+size_t mkws_detect_live_state_bytes(int n_heads, int n_thr, int history);
+int mkws_detect_live_step(void* d_state, const float* d_probs, const int64_t* d_meta, int max_new, int n_heads, int classes, int target_id,
+                          const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+                          int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
+                          double* d_scores, void* stream);
 
 /* Scoring against ground truth: tpr_fpr's counts (multilingual_kws/embedding/tpr_fpr.py:72-107) for every (head, threshold) lane in
  * one launch, on what mkws_detect_stream(..., fired_only = 1, ...) left on the same stream: d_events [n_heads, n_thr, event_cap] and

@@ -39,6 +39,43 @@ struct DetectArgs {
   const int32_t* seg_off;   // SEG only: [gridDim.x + 1] row offsets into a concatenation of n_windows rows
 };
 
+// The decision step of one (head, threshold) lane for one window: what SingleTargetRecognizeCommands does once it has the window's score.
+// Compares only; shared by the stateless kernel below and the live step (detect_live_kernel), which keeps LaneState between calls.
+struct LaneState {
+  bool prev_kw;        // the previous top label is the keyword ("_silence_" before anything has fired)
+  int64_t deadline;    // time of the event that made it so + suppression: the label may change after it; read only while prev_kw
+  int n_events;
+};
+struct LaneRule {
+  double thr;
+  int64_t suppression;
+  bool can_change, fired_only;
+  int event_cap;
+};
+__device__ __forceinline__ void lane_step(LaneState& s, const LaneRule& r, double score, int64_t tw, bool evaluated, int window,
+                                          mkws_detect_event* __restrict__ ev, uint8_t* __restrict__ fl) {
+  const bool above = evaluated & (score > r.thr);
+  const bool below = evaluated & (score < r.thr);                    // a NaN score is neither above nor below
+  const bool may = r.can_change & (!s.prev_kw | (tw > s.deadline));  // `since` is infinite while the label is silence
+  const bool fire = above & !s.prev_kw & may;
+  const bool release = below & may;
+  const bool is_new = fire | release;
+  const bool is_kw = evaluated ? above : s.prev_kw;                  // not evaluated: the label of the last event
+  if (fire | (release & !r.fired_only)) {
+    if (s.n_events < r.event_cap) {
+      mkws_detect_event e;
+      e.window = window;
+      e.fired = fire ? 1 : 0;
+      e.score = score;
+      ev[s.n_events] = e;
+    }
+    ++s.n_events;
+  }
+  s.prev_kw = is_new ? above : s.prev_kw;
+  s.deadline = is_new ? tw + r.suppression : s.deadline;
+  if (fl) fl[window] = (uint8_t)((is_kw ? 1 : 0) | (is_new ? 2 : 0));   // (trace: indexed by the window, like the events)
+}
+
 // SEG (mkws_detect_segments): blockIdx.x is a segment of a concatenated stream instead of a head over a shared one.  Its windows are
 // rows [base, base + W) of probs AND of times (both clamped into [0, n_windows], so a bad offset list reads nothing outside them); the
 // lookback search below runs over [0, w] of the segment's own slice and so never leaves it; window indices are those inside the segment.
@@ -68,10 +105,8 @@ __global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
   mkws_detect_event* __restrict__ ev = a.events + lane_row * (size_t)a.event_cap;
   uint8_t* __restrict__ fl = a.flags ? a.flags + (SEG ? (size_t)a.n_thr * base + (size_t)(walker ? ti : 0) * W : lane_row * (size_t)W) : nullptr;
   const double quarter = a.avg_ms / 4;
-  const bool can_change = !a.never;
-  bool prev_kw = false;           // the previous top label is the keyword ("_silence_" before anything has fired)
-  int64_t deadline = 0;           // time of the event that made it so + suppression: the label may change after it; read only while prev_kw
-  int n_events = 0;
+  const LaneRule rule = {thr, a.suppression, !a.never, a.fired_only != 0, a.event_cap};
+  LaneState lane = {false, 0, 0};
 
   for (int w0 = 0; w0 < W; w0 += kDetectTile) {
     const int nw = min(kDetectTile, W - w0);
@@ -116,36 +151,119 @@ __global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < kDetectChunk; ++u) {
-          if (i0 + u < nw) {
-            const double score = c_score[u];
-            const int64_t tw = c_time[u];
-            const bool above = c_eval[u] & (score > thr);
-            const bool below = c_eval[u] & (score < thr);            // a NaN score is neither above nor below
-            const bool may = can_change & (!prev_kw | (tw > deadline));   // `since` is infinite while the label is silence
-            const bool fire = above & !prev_kw & may;
-            const bool release = below & may;
-            const bool is_new = fire | release;
-            const bool is_kw = c_eval[u] ? above : prev_kw;          // not evaluated: the label of the last event
-            if (fire | (release & !a.fired_only)) {
-              if (n_events < a.event_cap) {
-                mkws_detect_event e;
-                e.window = w0 + i0 + u;
-                e.fired = fire ? 1 : 0;
-                e.score = score;
-                ev[n_events] = e;
-              }
-              ++n_events;
-            }
-            prev_kw = is_new ? above : prev_kw;
-            deadline = is_new ? tw + a.suppression : deadline;
-            if (fl) fl[w0 + i0 + u] = (uint8_t)((is_kw ? 1 : 0) | (is_new ? 2 : 0));
-          }
+          if (i0 + u < nw) lane_step(lane, rule, c_score[u], c_time[u], c_eval[u], w0 + i0 + u, ev, fl);
         }
       }
     }
     __syncthreads();
   }
-  if (walker) a.counts[lane_row] = n_events;
+  if (walker) a.counts[lane_row] = lane.n_events;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Live step (mkws_detect_live_step, include/mkws.h): the same detector fed a few windows at a time, with what it has to remember in a
+// caller-owned state block, all zeros for a fresh stream.  Per head, back to back:
+//   int64 seen (windows so far) | pad to 16 B | {int64 time, double target probability}[history] | {int64 deadline, int64 prev_kw}[n_thr]
+// The ring (window k of the head in slot k % history) replaces the stateless kernel's re-read of earlier windows: a workgroup lays the
+// min(seen, history) newest old entries and the push's windows out in LDS in stream order, and from there on phase 1 (scores) and phase
+// 2 (lane_step) are the stateless kernel's, on indices into that line.  One workgroup per head -- it is the only reader and writer of
+// its head's state, it reads the ring before its first barrier and writes it after -- so one launch per step, thresholds <= its threads.
+constexpr int kLiveMaxNew = MKWS_DETECT_LIVE_MAX_NEW;     // windows per step: 30 KB of LDS with the longest history
+
+struct LiveEntry { int64_t time; double prob; };
+struct LiveLane { int64_t deadline, prev_kw; };
+
+struct LiveArgs {
+  unsigned char* state;
+  const float* probs;
+  const int64_t* meta;
+  const double* thr;
+  mkws_detect_event* events;
+  int32_t* counts;
+  double* scores;
+  double avg_ms;
+  int64_t suppression;
+  int max_new, classes, target, n_thr, min_count, fired_only, never, history;
+};
+
+__host__ __device__ inline size_t live_head_bytes(int n_thr, int history) { return 16 + (size_t)history * sizeof(LiveEntry) + (size_t)n_thr * sizeof(LiveLane); }
+
+__global__ __launch_bounds__(kDetectThreads) void detect_live_kernel(LiveArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char live_smem[];
+  const int line = a.history + a.max_new;
+  int64_t* s_time = reinterpret_cast<int64_t*>(live_smem);             // [line]
+  double* s_prob = reinterpret_cast<double*>(s_time + line);            // [line]
+  double* s_score = s_prob + line;                                      // [max_new]
+  uint8_t* s_eval = reinterpret_cast<uint8_t*>(s_score + a.max_new);    // [max_new]
+  const int head = blockIdx.x, tid = threadIdx.x;
+  unsigned char* hs = a.state + head * live_head_bytes(a.n_thr, a.history);
+  int64_t* p_seen = reinterpret_cast<int64_t*>(hs);
+  LiveEntry* ring = reinterpret_cast<LiveEntry*>(hs + 16);
+  LiveLane* lanes = reinterpret_cast<LiveLane*>(hs + 16 + (size_t)a.history * sizeof(LiveEntry));
+  const bool walker = tid < a.n_thr;
+  const size_t lane_row = (size_t)head * a.n_thr + (walker ? tid : 0);
+  const int count = (int)min(max(a.meta[0], (int64_t)0), (int64_t)a.max_new);
+  if (count == 0) {                                                    // an empty push changes nothing
+    if (walker) a.counts[lane_row] = 0;
+    return;
+  }
+  const int64_t seen = max(*p_seen, (int64_t)0);
+  const int nh = (int)min(seen, (int64_t)a.history);                   // old entries still held
+  for (int k = tid; k < nh + count; k += blockDim.x) {
+    if (k < nh) {
+      const LiveEntry e = ring[(seen - nh + k) % a.history];
+      s_time[k] = e.time;
+      s_prob[k] = e.prob;
+    } else {
+      s_time[k] = a.meta[2 + (k - nh)];
+      s_prob[k] = (double)a.probs[((size_t)head * a.max_new + (k - nh)) * a.classes + a.target];
+    }
+  }
+  __syncthreads();
+  // phase 1 of detect_kernel over the line; w = nh + i.  The search runs over [0, w] of the line: the caller's history holds every
+  // window an average can reach, so what fell out of the ring is older than t[w] - avg
+  const double quarter = a.avg_ms / 4;
+  for (int i = tid; i < count; i += blockDim.x) {
+    const int w = nh + i;
+    const int64_t tw = s_time[w];
+    const double limit = (double)tw - a.avg_ms;
+    int lo = 0, hi = w;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if ((double)s_time[mid] >= limit) hi = mid; else lo = mid + 1;
+    }
+    const int how_many = w - lo + 1;
+    const double duration = (double)(tw - s_time[lo]);
+    const bool evaluated = !(how_many < a.min_count || duration < quarter);
+    double score = 0.0;
+    if (evaluated) {
+      const double n = (double)how_many;
+      for (int j = lo; j <= w; ++j) score += s_prob[j] / n;            // one IEEE division, one IEEE addition per term, in order
+    }
+    s_score[i] = score;
+    s_eval[i] = evaluated;
+    if (a.scores) a.scores[(size_t)head * a.max_new + i] = score;
+    if (i >= count - a.history) {                                      // the newest `history` windows go into the ring
+      LiveEntry e;
+      e.time = tw;
+      e.prob = s_prob[w];
+      ring[(seen + i) % a.history] = e;
+    }
+  }
+  __syncthreads();
+  if (walker) {
+    const LiveLane was = lanes[tid];
+    const LaneRule rule = {a.thr[tid], a.suppression, !a.never, a.fired_only != 0, a.max_new};
+    LaneState lane = {was.prev_kw != 0, was.deadline, 0};
+    mkws_detect_event* __restrict__ ev = a.events + lane_row * (size_t)a.max_new;
+    for (int i = 0; i < count; ++i) lane_step(lane, rule, s_score[i], s_time[nh + i], s_eval[i] != 0, i, ev, nullptr);
+    LiveLane now;
+    now.deadline = lane.deadline;
+    now.prev_kw = lane.prev_kw ? 1 : 0;
+    lanes[tid] = now;
+    a.counts[lane_row] = lane.n_events;
+  }
+  if (tid == 0) *p_seen = seen + count;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -279,6 +397,13 @@ static int check_score_args(int n_planes, int n_windows, int event_cap, int n_th
   return MKWS_OK;
 }
 
+// since > suppression_ms with integer times: since > floor(suppression_ms).  Negative: every difference (>= 0) exceeds it.  Not below
+// 2^62 (+inf included): no difference of two times does (the host class then never reports an event, `inf > inf` being false)
+static void suppression_words(double suppression_ms, int* never, int64_t* suppression) {
+  *never = suppression_ms >= 4611686018427387904.0;
+  *suppression = suppression_ms < 0 ? -1 : *never ? 0 : (int64_t)std::floor(suppression_ms);
+}
+
 // the launch behind mkws_detect_stream (seg_off NULL: n_planes heads over n_windows shared windows) and mkws_detect_segments (n_planes
 // segments of a concatenation of n_windows rows); the arguments have been checked
 static int launch_detect(const void* d_probs, int probs_f64, int n_planes, int n_windows, const int32_t* seg_off, int classes, int target_id,
@@ -296,10 +421,7 @@ static int launch_detect(const void* d_probs, int probs_f64, int n_planes, int n
   a.scores = d_scores;
   a.flags = d_flags;
   a.avg_ms = average_window_duration_ms;
-  // since > suppression_ms with integer times: since > floor(suppression_ms).  Negative: every difference (>= 0) exceeds it.  Not below
-  // 2^62 (+inf included): no difference of two times does (the host class then never reports an event, `inf > inf` being false)
-  a.never = suppression_ms >= 4611686018427387904.0;
-  a.suppression = suppression_ms < 0 ? -1 : a.never ? 0 : (int64_t)std::floor(suppression_ms);
+  suppression_words(suppression_ms, &a.never, &a.suppression);
   a.n_windows = n_windows;
   a.classes = classes;
   a.target = target_id;
@@ -390,4 +512,48 @@ extern "C" int mkws_detect_score_segments(const mkws_detect_event* d_events, con
     return rc;
   if (n_seg == 0) return MKWS_OK;
   return launch_score(d_events, d_counts, n_seg, n_thr, event_cap, d_times_ms, n_rows, d_seg_offsets, d_gt_ms, d_gt_offsets, time_tolerance_ms, d_tally, stream);
+}
+
+extern "C" size_t mkws_detect_live_state_bytes(int n_heads, int n_thr, int history) {
+  if (n_heads < 0 || n_thr < 1 || n_thr > kDetectThreads || history < 1 || history > MKWS_DETECT_LIVE_MAX_HISTORY) return 0;
+  return (size_t)n_heads * live_head_bytes(n_thr, history);
+}
+
+extern "C" int mkws_detect_live_step(void* d_state, const float* d_probs, const int64_t* d_meta, int max_new, int n_heads, int classes, int target_id,
+                                     const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+                                     int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
+                                     double* d_scores, void* stream) {
+  if (int rc = check_detect_args(n_heads, max_new, 0, n_thr, classes, target_id, average_window_duration_ms, suppression_ms,
+                                 d_state && d_probs && d_meta && d_thresholds && d_counts && (d_events || max_new == 0)))
+    return rc;
+  if (history < 1) return fail(MKWS_ERR_INVALID_ARG, "history = %d: at least one window", history);
+  if (reinterpret_cast<uintptr_t>(d_state) % 8 != 0) return fail(MKWS_ERR_INVALID_ARG, "d_state must be 8-byte aligned");
+  if (history > MKWS_DETECT_LIVE_MAX_HISTORY)
+    return fail(MKWS_ERR_UNSUPPORTED, "history of %d windows: at most %d (an average over fewer windows than the host class holds is never computed)", history,
+                MKWS_DETECT_LIVE_MAX_HISTORY);
+  if (n_thr > kDetectThreads) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per live step", n_thr, kDetectThreads);
+  if (max_new > kLiveMaxNew) return fail(MKWS_ERR_UNSUPPORTED, "%d windows per step: at most %d", max_new, kLiveMaxNew);
+  if (n_heads == 0 || max_new == 0) return MKWS_OK;
+  LiveArgs a;
+  a.state = static_cast<unsigned char*>(d_state);
+  a.probs = d_probs;
+  a.meta = d_meta;
+  a.thr = d_thresholds;
+  a.events = d_events;
+  a.counts = d_counts;
+  a.scores = d_scores;
+  a.avg_ms = average_window_duration_ms;
+  suppression_words(suppression_ms, &a.never, &a.suppression);
+  a.max_new = max_new;
+  a.classes = classes;
+  a.target = target_id;
+  a.n_thr = n_thr;
+  a.min_count = minimum_count;
+  a.fired_only = fired_only != 0;
+  a.history = history;
+  const int threads = (n_thr + 63) / 64 * 64;
+  const size_t lds = (size_t)(history + max_new) * 16 + (size_t)max_new * 8 + (size_t)((max_new + 15) & ~15);
+  hipLaunchKernelGGL(detect_live_kernel, dim3(n_heads), dim3(threads), lds, static_cast<hipStream_t>(stream), a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
 }

@@ -535,6 +535,31 @@ __global__ __launch_bounds__(256) void frontend_frames_kernel(FrontendParams p, 
   }
 }
 
+// scan + finish of ONE window whose frames_per_window x C filterbank outputs are staged in s_sig (the caller has passed a barrier since);
+// row = the window's row of the outputs
+__device__ __forceinline__ void window_scan_finish(const FrontendParams& p, const uint32_t* s_sig, uint32_t* s_est, const int16_t* s_pcan,
+                                                   const uint16_t* s_log, int frames_per_window, int tid, size_t row,
+                                                   float* __restrict__ spec, uint16_t* __restrict__ raw) {
+  const int C = p.num_channels, FC = frames_per_window * C;
+  if (tid < C) {
+    const uint32_t sm = (tid & 1) ? p.odd_smoothing : p.even_smoothing;
+    const uint32_t om = (1u << 14) - sm;
+    uint32_t est = 0;
+    for (int t = 0; t < frames_per_window; ++t) {
+      const uint32_t su = s_sig[t * C + tid] << p.smoothing_bits;
+      est = (uint32_t)((((uint64_t)su * sm) + ((uint64_t)est * om)) >> 14);
+      s_est[t * C + tid] = est;
+    }
+  }
+  __syncthreads();
+  const float scale = 10.0f / 256.0f;
+  for (int i = tid; i < FC; i += 256) {
+    const uint32_t v = finish_element(p, s_sig[i], s_est[i], s_pcan, s_log);
+    if (spec) spec[row * FC + i] = (float)v * scale;
+    if (raw) raw[row * FC + i] = (uint16_t)v;
+  }
+}
+
 // one workgroup (256 threads) per window: scan + finish over frames [w*hop_frames, +frames_per_window)
 __global__ __launch_bounds__(256) void frontend_windows_kernel(FrontendParams p, const uint32_t* __restrict__ sig, int hop_frames,
                                                                int frames_per_window, float* __restrict__ spec,
@@ -552,23 +577,131 @@ __global__ __launch_bounds__(256) void frontend_windows_kernel(FrontendParams p,
   for (int i = tid; i < 128; i += 256) s_pcan[i] = p.pcan_lut[i];
   for (int i = tid; i < 132; i += 256) s_log[i] = p.log_lut[i];
   __syncthreads();
-  if (tid < C) {
-    const uint32_t sm = (tid & 1) ? p.odd_smoothing : p.even_smoothing;
-    const uint32_t om = (1u << 14) - sm;
-    uint32_t est = 0;
-    for (int t = 0; t < frames_per_window; ++t) {
-      const uint32_t su = s_sig[t * C + tid] << p.smoothing_bits;
-      est = (uint32_t)((((uint64_t)su * sm) + ((uint64_t)est * om)) >> 14);
-      s_est[t * C + tid] = est;
-    }
+  window_scan_finish(p, s_sig, s_est, s_pcan, s_log, frames_per_window, tid, win, spec, raw);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Live form (mkws_frontend_live_push_f32): the streaming split fed push by push.  What a stream needs from one push to the next lives
+// in a caller-owned state block, all zeros for a fresh stream:
+//   int64 pos (samples pushed so far) | pad to kLiveHeader bytes | float tail[kLiveTail] | uint32 ring[ring_frames][C]
+// tail  = the samples from the start of the first frame that is not complete yet up to pos (fewer than window_size of them);
+// ring  = the filterbank outputs (frame_to_sig) of the newest frames, global frame f in slot f % ring_frames.
+// A push of P = hops_per_push * hop_samples samples is two launches:
+//   live_frames_kernel   every frame the push completed, one wave each, from the VIRTUAL buffer tail ++ d_audio (a frame may begin in
+//                        the tail and end in the new audio: samples are fetched one by one, each from its side), into the ring; it
+//                        changes neither tail nor pos, and its first workgroup writes d_meta from the old pos;
+//   live_windows_kernel  workgroup b < count: scan + finish of window first + b over its ring slots; workgroup 0 first moves the new
+//                        tail into place (every thread reads its samples, a barrier, then the writes: source and destination overlap)
+//                        and advances pos -- it is the only reader of either in this launch, and the launch before has finished.
+// Ring size: the windows of one push span frames [W0 * hop_frames, F1) with F1 the frames complete after it; F1 - W0 * hop_frames <=
+// hops_per_push * hop_frames + frames_per_window (W0 * hop > pos - window_samples, F1 <= (pos + P - window_size) / step + 1), so a ring
+// of that many slots -- live_geom adds hop_frames -- holds every frame a push reads and a push never overwrites one it still needs.
+constexpr int kLiveHeader = 64;
+constexpr int kLiveTail = 512;       // floats; >= window_size (the handle implements the 512-point FFT only)
+
+struct LiveGeom {
+  int window_samples, hop_samples, hops_per_push, hop_frames, frames_per_window, ring_frames, sample_rate;
+};
+
+__device__ __forceinline__ int64_t live_count(int64_t n, int size, int step) { return n < size ? 0 : (n - size) / step + 1; }
+
+struct LivePos {
+  int64_t pos, F0, F1;   // samples before this push; frames complete before and after it
+  int T;                 // samples in the tail: pos - F0 * window_step, in [0, window_size)
+};
+__device__ __forceinline__ LivePos live_pos(const FrontendParams& p, const LiveGeom& g, const unsigned char* state) {
+  LivePos q;
+  q.pos = max(*reinterpret_cast<const int64_t*>(state), (int64_t)0);      // (a negative count is not a stream: read as its start)
+  q.F0 = live_count(q.pos, p.window_size, p.window_step);
+  q.F1 = live_count(q.pos + (int64_t)g.hop_samples * g.hops_per_push, p.window_size, p.window_step);
+  q.T = (int)(q.pos - q.F0 * p.window_step);
+  return q;
+}
+// sample i of tail ++ audio, as load_frame converts it
+__device__ __forceinline__ float live_sample(const float* tail, const float* audio, int T, int i) {
+  return i < T ? tail[i] : audio[i - T];
+}
+
+__global__ __launch_bounds__(256) void frontend_live_frames_kernel(FrontendParams p, LiveGeom g, const float* __restrict__ audio,
+                                                                   unsigned char* __restrict__ state, int64_t* __restrict__ meta) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t* s_fft = reinterpret_cast<uint32_t*>(smem);
+  int16_t* s_coef = reinterpret_cast<int16_t*>(s_fft + 4 * 512);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const LivePos q = live_pos(p, g, state);
+  const float* tail = reinterpret_cast<const float*>(state + kLiveHeader);
+  uint32_t* ring = reinterpret_cast<uint32_t*>(state + kLiveHeader + kLiveTail * sizeof(float));
+  if (blockIdx.x == 0) {
+    const int64_t W0 = live_count(q.pos, g.window_samples, g.hop_samples);
+    const int64_t W1 = live_count(q.pos + (int64_t)g.hop_samples * g.hops_per_push, g.window_samples, g.hop_samples);
+    const int count = (int)min(W1 - W0, (int64_t)g.hops_per_push);
+    if (tid == 0) { meta[0] = count; meta[1] = W0; }
+    for (int k = tid; k < count; k += 256) meta[2 + k] = ((W0 + k) * g.hop_samples * 1000) / g.sample_rate;   // (a push may hold more hops than the workgroup has threads)
   }
+  for (int i = tid; i < p.ncoef; i += 256) s_coef[i] = p.out_coef[i];
+  LaneConst L;
+  init_lane_const(p, lane, L);
   __syncthreads();
-  const float scale = 10.0f / 256.0f;
-  for (int i = tid; i < FC; i += 256) {
-    const uint32_t v = finish_element(p, s_sig[i], s_est[i], s_pcan, s_log);
-    if (spec) spec[win * FC + i] = (float)v * scale;
-    if (raw) raw[win * FC + i] = (uint16_t)v;
+  uint32_t* fftbuf = s_fft + wave * 512;
+  const int nf = (int)(q.F1 - q.F0);                     // <= hops_per_push * hop_frames
+  for (int f = blockIdx.x * 4 + wave; f < nf; f += gridDim.x * 4) {
+    // load_frame's selects on samples fetched one by one: the frame's last sample is f * step + window_size - 1 < T + P
+    const int base = f * p.window_step;
+    int x[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int a = AudioLoad<float>::cvt(live_sample(tail, audio, q.T, base + L.toff[j]));
+      const int b = AudioLoad<float>::cvt(live_sample(tail, audio, q.T, base + L.toff[j] + 1));
+      x[2 * j] = (L.tsel[j] == 2) ? a : (L.tsel[j] == 1 ? b : 0);
+      x[2 * j + 1] = (L.tsel[j] == 2) ? b : 0;
+    }
+    frame_to_sig(p, L, lane, x, fftbuf, fftbuf + 256, s_coef, ring + (size_t)((q.F0 + f) % g.ring_frames) * p.num_channels);
   }
+}
+
+__global__ __launch_bounds__(256) void frontend_live_windows_kernel(FrontendParams p, LiveGeom g, const float* __restrict__ audio,
+                                                                    unsigned char* __restrict__ state, const int64_t* __restrict__ meta,
+                                                                    float* __restrict__ spec, uint16_t* __restrict__ raw) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int C = p.num_channels, FC = g.frames_per_window * C;
+  uint32_t* s_sig = reinterpret_cast<uint32_t*>(smem);
+  uint32_t* s_est = s_sig + FC;
+  int16_t* s_pcan = reinterpret_cast<int16_t*>(s_est + FC);
+  uint16_t* s_log = reinterpret_cast<uint16_t*>(s_pcan + 128);
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0) {
+    const LivePos q = live_pos(p, g, state);
+    float* tail = reinterpret_cast<float*>(state + kLiveHeader);
+    const int P = g.hop_samples * g.hops_per_push;
+    const int shift = (int)(q.F1 - q.F0) * p.window_step;                // where the first incomplete frame begins in tail ++ audio
+    const int Tn = (int)(q.pos + P - q.F1 * p.window_step);              // in [0, window_size): at most kLiveTail = 2 x 256 samples
+    float keep[kLiveTail / 256];
+#pragma unroll
+    for (int k = 0; k < kLiveTail / 256; ++k) {
+      const int i = tid + 256 * k;
+      keep[k] = i < Tn ? live_sample(tail, audio, q.T, shift + i) : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kLiveTail / 256; ++k) {
+      const int i = tid + 256 * k;
+      if (i < Tn) tail[i] = keep[k];
+    }
+    if (tid == 0) *reinterpret_cast<int64_t*>(state) = q.pos + P;
+  }
+  const int count = (int)min(max(meta[0], (int64_t)0), (int64_t)g.hops_per_push);
+  if ((int)blockIdx.x >= count) return;
+  const uint32_t* ring = reinterpret_cast<const uint32_t*>(state + kLiveHeader + kLiveTail * sizeof(float));
+  const int64_t first = (max(meta[1], (int64_t)0) + blockIdx.x) * g.hop_frames;   // the window's first frame
+  for (int i = tid; i < FC; i += 256) {
+    const int t = i / C;
+    s_sig[i] = ring[(size_t)((first + t) % g.ring_frames) * C + (i - t * C)];
+  }
+  for (int i = tid; i < 128; i += 256) s_pcan[i] = p.pcan_lut[i];
+  for (int i = tid; i < 132; i += 256) s_log[i] = p.log_lut[i];
+  __syncthreads();
+  window_scan_finish(p, s_sig, s_est, s_pcan, s_log, g.frames_per_window, tid, blockIdx.x, spec, raw);
 }
 
 }  // namespace mkws
@@ -857,6 +990,55 @@ int mkws_frontend_stream_f32(mkws_frontend* fe, const float* d_audio, int n_samp
   hipLaunchKernelGGL(frontend_windows_kernel, dim3(num_windows), dim3(256), lds2, s, p, fe->d_stream_sig, hop_frames, fpw, d_spec, d_raw);
   MKWS_HIP(hipGetLastError());
   return num_windows;
+}
+
+// the geometry of a live stream, checked; 0 bytes / a status for what the live calls refuse
+static int live_geom(const mkws_frontend* fe, int window_samples, int hop_samples, int hops_per_push, LiveGeom* g) {
+  if (!fe) return fail(MKWS_ERR_INVALID_ARG, "frontend handle is NULL");
+  if (window_samples <= 0 || hop_samples <= 0 || hops_per_push <= 0) return fail(MKWS_ERR_INVALID_ARG, "bad sample counts");
+  const FrontendParams& p = fe->prm;
+  if (hop_samples % p.window_step != 0)
+    return fail(MKWS_ERR_UNSUPPORTED, "hop of %d samples is not a multiple of the %d-sample frame step (frame sharing needs that)", hop_samples, p.window_step);
+  const int fpw = mkws_frontend_num_frames(&fe->cfg, window_samples);
+  if (fpw <= 0) return fail(MKWS_ERR_INVALID_ARG, "window of %d samples is shorter than one frame", window_samples);
+  if ((int64_t)hop_samples * hops_per_push > (1 << 24)) return fail(MKWS_ERR_UNSUPPORTED, "%d hops of %d samples per push", hops_per_push, hop_samples);
+  if (p.window_size > kLiveTail) return fail(MKWS_ERR_UNSUPPORTED, "frame of %d samples", p.window_size);
+  const size_t lds2 = 2 * (size_t)fpw * p.num_channels * 4 + 128 * 2 + 132 * 2 + 16;
+  if (lds2 > 64 * 1024) return fail(MKWS_ERR_UNSUPPORTED, "window of %d frames needs %zu B LDS", fpw, lds2);
+  g->window_samples = window_samples;
+  g->hop_samples = hop_samples;
+  g->hops_per_push = hops_per_push;
+  g->hop_frames = hop_samples / p.window_step;
+  g->frames_per_window = fpw;
+  g->ring_frames = fpw + (hops_per_push + 1) * g->hop_frames;
+  g->sample_rate = fe->cfg.sample_rate;
+  return MKWS_OK;
+}
+
+size_t mkws_frontend_live_state_bytes(const mkws_frontend* fe, int window_samples, int hop_samples, int hops_per_push) {
+  LiveGeom g;
+  if (live_geom(fe, window_samples, hop_samples, hops_per_push, &g) != MKWS_OK) return 0;
+  return kLiveHeader + kLiveTail * sizeof(float) + (size_t)g.ring_frames * fe->prm.num_channels * sizeof(uint32_t);
+}
+
+int mkws_frontend_live_push_f32(mkws_frontend* fe, void* d_state, const float* d_audio, int window_samples, int hop_samples, int hops_per_push,
+                                float* d_spec, uint16_t* d_raw, int64_t* d_meta, void* stream) {
+  LiveGeom g;
+  if (int rc = live_geom(fe, window_samples, hop_samples, hops_per_push, &g)) return rc;
+  if (!d_state || !d_audio || !d_meta || (!d_spec && !d_raw)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (reinterpret_cast<uintptr_t>(d_state) % 8 != 0) return fail(MKWS_ERR_INVALID_ARG, "d_state must be 8-byte aligned");
+  const FrontendParams& p = fe->prm;
+  const size_t lds1 = 4 * 512 * 4 + ((p.ncoef + 7) & ~7) * 2 + 16;
+  const size_t lds2 = 2 * (size_t)g.frames_per_window * p.num_channels * 4 + 128 * 2 + 132 * 2 + 16;
+  int grid1 = (hops_per_push * g.hop_frames + 3) / 4;                     // a push completes at most that many frames
+  if (grid1 > 4096) grid1 = 4096;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned char* st = static_cast<unsigned char*>(d_state);
+  hipLaunchKernelGGL(frontend_live_frames_kernel, dim3(grid1), dim3(256), lds1, s, p, g, d_audio, st, d_meta);
+  MKWS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(frontend_live_windows_kernel, dim3(hops_per_push), dim3(256), lds2, s, p, g, d_audio, st, static_cast<const int64_t*>(d_meta), d_spec, d_raw);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
 }
 
 }  // extern "C"

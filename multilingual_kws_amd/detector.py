@@ -323,3 +323,116 @@ def score_segments_on_device(probs, seg_offsets, times_ms, thresholds, gt_times_
                         lambda L, ptrs, events, counts, cap, tally, stream: L.mkws_detect_score_segments(
                             events, counts, ptrs[2], S, R, T, cap, ptrs[0], ptrs[3], ptrs[4], tol, tally, stream),
                         S, T, _segment_capacity(times, spans, suppression_ms, True)[0], "segment")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Live form (mkws_detect_live_step): the detector stepped over the few windows a push completed, its state in a device block of the
+# caller's.  LiveDetectorHost is the host restatement -- the specification, and what runs without a GPU.
+
+LIVE_MAX_HISTORY = 256    # MKWS_DETECT_LIVE_MAX_HISTORY
+LIVE_MAX_NEW = 1024       # MKWS_DETECT_LIVE_MAX_NEW
+
+
+def live_history(average_window_duration_ms, hop_samples, sample_rate=16000):
+    """The `history` a live detector needs: the most windows an average can span.  Window w is at floor(w * hop_ms) with hop_ms =
+    hop_samples * 1000 / sample_rate, so two windows k apart are more than k * hop_ms - 1 ms apart; the host deque keeps those within
+    average_window_duration_ms of the newest: k < (avg + 1) / hop_ms, i.e. at most floor((avg + 1) / hop_ms) + 1 windows.  ValueError
+    above LIVE_MAX_HISTORY (the C call refuses it too, rather than ever averaging over too few windows)."""
+    if not average_window_duration_ms >= 0:
+        raise ValueError("average_window_duration_ms must be >= 0")
+    if hop_samples <= 0 or sample_rate <= 0 or hop_samples * 1000 < sample_rate:
+        raise ValueError("the hop must be at least one millisecond")
+    avg = float(average_window_duration_ms)
+    history = (int(np.floor((avg + 1) * sample_rate / (hop_samples * 1000))) if np.isfinite(avg) else LIVE_MAX_HISTORY) + 1
+    if history > LIVE_MAX_HISTORY:
+        raise ValueError(f"an average over {average_window_duration_ms} ms spans {history} windows of {hop_samples} samples; "
+                         f"the live detector keeps at most {LIVE_MAX_HISTORY}")
+    return history
+
+
+def live_detector_state(n_heads, n_thr, history, device=None):
+    """A zero-filled state block (int64 CUDA tensor) = a fresh stream.  Reset is .zero_(), snapshot .clone(), restore .copy_()."""
+    import torch
+    n = _lib.lib().mkws_detect_live_state_bytes(int(n_heads), int(n_thr), int(history))
+    if n == 0 and n_heads:
+        raise ValueError(f"no live detector state for {n_heads} heads x {n_thr} thresholds with a history of {history} "
+                         f"(thresholds: 1 .. 1024, history: 1 .. {LIVE_MAX_HISTORY})")
+    return torch.zeros(max(1, n // 8), dtype=torch.int64, device=device if device is not None else "cuda")
+
+
+def live_out_words(n_heads, n_thr, max_new):
+    """int64 words of detect_live_step's output buffer: the counts (int32 pairs padded to whole words), then the events."""
+    return (n_heads * n_thr + 1) // 2 + 2 * n_heads * n_thr * max_new
+
+
+def live_unpack(words, n_heads, n_thr, max_new):
+    """The host copy (numpy int64) of that buffer -> (counts int32 [N, T], events EVENT_DTYPE [N, T, max_new]; `window` counts inside the push)."""
+    cwords = (n_heads * n_thr + 1) // 2
+    return (words[:cwords].view(np.int32)[:n_heads * n_thr].reshape(n_heads, n_thr),
+            words[cwords:].view(EVENT_DTYPE).reshape(n_heads, n_thr, max_new))
+
+
+def detect_live_step(state, probs, meta, d_thresholds, average_window_duration_ms, suppression_ms, minimum_count, history, target_id=2,
+                     fired_only=False, out=None, scores=None):
+    """One step of the live detector.  state: live_detector_state(N, T, history); probs CUDA float32 [N, max_new, C]; meta CUDA int64
+    [2 + max_new] = {count, first new window, time_ms of each new window} (what Frontend.live_push writes); d_thresholds CUDA float64
+    [T].  -> out, a CUDA int64 tensor of live_out_words(N, T, max_new) words (live_unpack reads its host copy): the events and counts of
+    THIS push.  scores: optional CUDA float64 [N, max_new].  Steps whose windows add up to a stream give, concatenated, detect_on_device
+    on the whole stream byte for byte.  Asynchronous, allocation-free when `out` is passed in, one launch: capturable."""
+    import torch
+    if probs.dim() != 3 or not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise ValueError("probs must be a contiguous CUDA float32 tensor [heads, max_new, classes]")
+    N, max_new, C = probs.shape
+    T = int(d_thresholds.numel())
+    if d_thresholds.dtype != torch.float64 or not d_thresholds.is_cuda or meta.dtype != torch.int64 or meta.numel() < 2 + max_new:
+        raise ValueError("d_thresholds must be CUDA float64 [T] and meta CUDA int64 [2 + max_new]")
+    if out is None:
+        out = torch.zeros(live_out_words(N, T, max_new), dtype=torch.int64, device=probs.device)
+    base = out.data_ptr()
+    with torch.cuda.device(probs.device):
+        _lib.check(_lib.lib().mkws_detect_live_step(
+            state.data_ptr(), probs.data_ptr(), meta.data_ptr(), max_new, N, C, int(target_id), d_thresholds.data_ptr(), T,
+            float(average_window_duration_ms), float(suppression_ms), int(minimum_count), int(bool(fired_only)), int(history),
+            base + 8 * ((N * T + 1) // 2), base, scores.data_ptr() if scores is not None else None, _lib.current_stream_ptr()))
+    return out
+
+
+class LiveDetectorHost:
+    """The host restatement of the live detector: K x T SingleTargetRecognizeCommands (one per keyword head and threshold) fed push by
+    push.  step() returns what one mkws_detect_live_step leaves behind, and is the specification it is held to bit for bit."""
+
+    def __init__(self, n_heads, thresholds, average_window_duration_ms, suppression_ms, minimum_count, target_id=2, fired_only=False, classes=3):
+        self.n_heads, self.thresholds = int(n_heads), [float(t) for t in thresholds]
+        self.settings = (average_window_duration_ms, suppression_ms, minimum_count)
+        self.target_id, self.fired_only, self.classes = int(target_id), bool(fired_only), int(classes)
+        self.reset()
+
+    def reset(self):
+        from .embedding.single_target_recognize_commands import SingleTargetRecognizeCommands
+        avg, sup, minc = self.settings
+        labels = ["_class_%d" % c for c in range(self.classes)]       # (the class reports "_silence_" for everything but the target)
+        labels[self.target_id] = self._keyword = "_keyword_"
+        self.lanes = [[SingleTargetRecognizeCommands(labels, avg, thr, sup, minc, self.target_id) for thr in self.thresholds]
+                      for _ in range(self.n_heads)]
+
+    def step(self, probs, times_ms):
+        """probs [K, n, classes], times_ms [n]: the windows of one push (n may be 0) -> (counts int32 [K, T], events: [K][T] arrays of
+        EVENT_DTYPE with `window` counted inside the push, scores float64 [K, n])."""
+        from .embedding.single_target_recognize_commands import RecognizeResult
+        probs = np.asarray(probs)
+        K, T, n = self.n_heads, len(self.thresholds), len(times_ms)
+        counts, scores = np.zeros((K, T), np.int32), np.zeros((K, n), np.float64)
+        events = [[[] for _ in range(T)] for _ in range(K)]
+        el = RecognizeResult()
+        for k in range(K):
+            for j in range(T):
+                rc = self.lanes[k][j]
+                for i in range(n):
+                    rc.process_latest_result(probs[k, i], int(times_ms[i]), el)
+                    scores[k, i] = el.score
+                    fired = el.is_new_command and el.found_command == self._keyword
+                    if el.is_new_command and (fired or not self.fired_only):
+                        events[k][j].append((i, int(fired), el.score))
+                counts[k, j] = len(events[k][j])
+        return counts, [[np.asarray(e, dtype=EVENT_DTYPE) for e in row] for row in events], scores
+

@@ -392,6 +392,195 @@ class StreamingSession:
         return self.probs
 
 
+class LivePushCutter:
+    """The host part of LiveSession.feed: chunks of any length -> whole pushes of `push_samples` samples; what does not fill a push
+    waits for the next chunk.  The pushes depend on the samples fed so far only, not on how they were cut into chunks."""
+
+    def __init__(self, push_samples):
+        self.push_samples = int(push_samples)
+        self.reset()
+
+    def reset(self):
+        self.rest = np.zeros(0, np.float32)
+
+    def cut(self, chunk):
+        """float32 samples -> [full pushes, push_samples] (a view of a fresh array; may have zero rows)."""
+        a = np.asarray(chunk, dtype=np.float32).reshape(-1)
+        if self.rest.size:
+            a = np.concatenate([self.rest, a])
+        full = a.size // self.push_samples
+        self.rest = a[full * self.push_samples:].copy()
+        return a[:full * self.push_samples].reshape(full, self.push_samples)
+
+
+def default_live_flags(thresholds):
+    return StreamFlags(wav="", ground_truth="", target_keyword="", detection_thresholds=list(thresholds))
+
+
+class LiveSession:
+    """A live keyword spotter: fed audio chunks of any length, returns the detections those chunks completed.
+
+    Where StreamingSession leaves the audio ring, 48 of every window's 49 frames and the detector to the caller, this session keeps the
+    frontend's per-frame results and the detector's state in device memory between calls (include/mkws.h: mkws_frontend_live_push_f32,
+    mkws_detect_live_step).  One push -- hops_per_push hops of NEW audio -- is one chain on one stream,
+        frontend push (2 launches) -> mkws_embed_forward -> mkws_heads_forward -> detector step (1 launch),
+    replayed as one hipGraph; per push the host uploads the new samples only and reads back one small buffer of counts and events.
+    Every piece is bit-equal to its offline form: a push's spectrogram rows to Frontend.stream, its probabilities to
+    StreamingSession.infer on that window (same launches on the same handle), its events to detect_on_device over the stream so far.
+
+    models: TransferLearnedModel(s) sharing one embedding (or embedding= and heads=); keywords: their target words (default
+    flags.target_keyword, or "keyword_<i>"); flags: a StreamFlags, of which average_window_duration_ms, suppression_ms, minimum_count,
+    clip_duration_ms and clip_stride_ms are used; fired_only=False also reports the class's releases (label "_silence_")."""
+
+    def __init__(self, models=None, thresholds=(0.9,), flags=None, model_settings=None, hops_per_push=1, embedding=None, heads=None,
+                 keywords=None, fired_only=True, use_graph=True):
+        import torch
+        from ..detector import live_detector_state, live_history, live_out_words
+        from ..head import Head
+        if models is not None:
+            mlist = list(models) if isinstance(models, (list, tuple)) else [models]
+            embedding, heads = mlist[0].embedding, [m.head for m in mlist]
+        self.embedding, self.heads, self.hops = embedding, list(heads), int(hops_per_push)
+        if not 1 <= self.hops <= embedding.max_batch:
+            raise ValueError(f"LiveSession(hops_per_push={hops_per_push}): from 1 to the embedding handle's max_batch={embedding.max_batch}")
+        self.thresholds = [float(t) for t in thresholds]
+        if not self.thresholds:
+            raise ValueError("at least one threshold")
+        self.flags = flags if flags is not None else default_live_flags(self.thresholds)
+        N = len(self.heads)
+        if keywords is None:
+            keywords = [self.flags.target_keyword or f"keyword_{i}" for i in range(N)]
+        self.keywords = list(keywords)
+        if len(self.keywords) != N:
+            raise ValueError(f"{len(self.keywords)} keywords for {N} heads")
+        if self.heads[0].classes != len(self.flags.labels()):
+            raise ValueError("The results for recognition should contain {} elements, but there are {} produced".format(
+                len(self.flags.labels()), self.heads[0].classes))
+        self.fired_only = bool(fired_only)
+        ms = model_settings or input_data.standard_microspeech_model_settings(3)
+        self.sample_rate = ms["sample_rate"]
+        self.window_samples = int(self.flags.clip_duration_ms * self.sample_rate / 1000)
+        self.hop_samples = int(self.flags.clip_stride_ms * self.sample_rate / 1000)
+        self.push_samples = self.hops * self.hop_samples
+        self.history = live_history(self.flags.average_window_duration_ms, self.hop_samples, self.sample_rate)
+        self.fe = input_data._frontend_for(ms, self.window_samples)
+        self.cutter = LivePushCutter(self.push_samples)
+        dev = embedding.device
+        T, h = len(self.thresholds), self.hops
+        with torch.cuda.device(dev):
+            self.audio = torch.zeros(self.push_samples, dtype=torch.float32, device=dev)        # static graph input: the NEW samples
+            self.fstate = self.fe.live_state(self.window_samples, self.hop_samples, h, device=dev)
+            self.dstate = live_detector_state(N, T, self.history, device=dev)
+            self.spec = torch.zeros((h, ms["spectrogram_length"], ms["fingerprint_width"]), dtype=torch.float32, device=dev)
+            self.meta = torch.zeros(2 + h, dtype=torch.int64, device=dev)
+            self.d_thr = torch.tensor(self.thresholds, dtype=torch.float64, device=dev)
+            self.out = torch.zeros(live_out_words(N, T, h), dtype=torch.int64, device=dev)      # counts and events: the one D2H per push
+            self.h_audio = torch.zeros(self.push_samples, dtype=torch.float32).pin_memory()
+            self.h_out = torch.zeros(self.out.numel(), dtype=torch.int64).pin_memory()
+        self._Head = Head
+        self.graph = None
+        self.recaptures = 0
+        self.last_records = []
+        self.probs = self._chain()                      # eager pass: creates every lazily-built table / attribute
+        if use_graph:
+            self._capture()
+        self.reset()
+
+    def _chain(self):
+        from ..detector import detect_live_step
+        f = self.flags
+        self.fe.live_push(self.fstate, self.audio, self.window_samples, self.hop_samples, self.hops, spec=self.spec, meta=self.meta)
+        probs = self._Head.forward_many(self.heads, self.embedding.forward(self.spec))
+        detect_live_step(self.dstate, probs, self.meta, self.d_thr, f.average_window_duration_ms, f.suppression_ms, f.minimum_count,
+                         self.history, target_id=2, fired_only=self.fired_only, out=self.out)
+        return probs
+
+    def _capture(self):
+        """Warm-up (which heals a handle with a recorded exchange failure) and capture, on a single stream: the chain is one branch.  The
+        chain is stateful and the warm-up runs it: both state blocks are put back afterwards, so capturing does not advance the stream."""
+        import torch
+        dev = self.embedding.device
+        kept = (self.fstate.clone(), self.dstate.clone())
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._chain()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.probs = self._chain()
+        self.graph = g
+        self.fstate.copy_(kept[0])
+        self.dstate.copy_(kept[1])
+
+    def reset(self):
+        """Starts a new stream: both state blocks zeroed, the unfinished push dropped."""
+        self.fstate.zero_()
+        self.dstate.zero_()
+        self.cutter.reset()
+        self.samples_pushed = 0                         # the host's mirror of the state block's first int64
+        self.last_records = []
+
+    @property
+    def samples_seen(self):
+        return self.samples_pushed + int(self.cutter.rest.size)
+
+    @property
+    def windows_seen(self):
+        from ..frontend import live_windows
+        return live_windows(self.samples_pushed, self.window_samples, self.hop_samples)
+
+    def close(self):
+        self.graph = None
+        self.probs = self.audio = self.fstate = self.dstate = self.spec = self.meta = self.out = None
+
+    def _push(self, samples):
+        """One push of push_samples new samples (numpy) -> records (window, head, threshold index, fired, score) of the events it completed."""
+        import torch
+        from ..detector import live_unpack
+        dev = self.embedding.device
+        self.h_audio.numpy()[:] = samples
+        with torch.cuda.device(dev):
+            self.audio.copy_(self.h_audio, non_blocking=True)
+            if self.graph is not None:
+                if self.embedding.get_option("exchange_error"):
+                    # StreamingSession's protocol: the PREVIOUS replay ran a failed exchange (all-NaN probabilities: the detector scored
+                    # NaN and reported no event; the frontend ring is unaffected): heal the handle and capture the single-workgroup kernels
+                    self._capture()
+                    self.recaptures += 1
+                self.graph.replay()
+            else:
+                self.probs = self._chain()
+            self.h_out.copy_(self.out, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+        first = self.windows_seen
+        self.samples_pushed += self.push_samples
+        counts, events = live_unpack(self.h_out.numpy(), len(self.heads), len(self.thresholds), self.hops)
+        records = []
+        if counts.any():
+            for n, k in zip(*np.nonzero(counts)):
+                for w, fired, score in events[n, k, :counts[n, k]].tolist():
+                    records.append((first + w, int(n), int(k), fired, score))
+            records.sort(key=lambda r: r[:3])
+        return records
+
+    def feed(self, chunk):
+        """chunk: float32 samples of any length (numpy, CPU tensor or CUDA tensor, which is brought to the host: the pushes are cut
+        there) -> [[keyword, time_ms, score, threshold], ...] for the events the chunk completed, ordered by window, keyword and
+        threshold.  time_ms is the start of the window, as detect() reports it.  The same events as records (window, head index,
+        threshold index, fired, score) are kept in .last_records."""
+        import torch
+        from ..frontend import live_window_time_ms
+        if torch.is_tensor(chunk):
+            chunk = chunk.detach().reshape(-1).to("cpu", torch.float32).numpy()
+        records = []
+        for samples in self.cutter.cut(chunk):
+            records.extend(self._push(samples))
+        self.last_records = records
+        return [[self.keywords[n] if fired else input_data.SILENCE_LABEL, live_window_time_ms(w, self.hop_samples, self.sample_rate), score,
+                 self.thresholds[k]] for w, n, k, fired, score in records]
+
+
 def detect(inferences, flags: StreamFlags, threshold, sample_rate=16000, data_samples=None):
     """Runs the detector over per-window softmax outputs; returns (found_words, found_words_w_confidences)
     exactly as the reference collects them (:143-167)."""

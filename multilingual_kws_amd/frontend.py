@@ -109,3 +109,48 @@ class Frontend:
                     nw, _lib.current_stream_ptr()))
             assert got == nw
         return (spec, raw) if want_raw else spec
+
+    # -- live form (mkws_frontend_live_push_f32): the stream fed push by push, its state in a device block of the caller's ------------
+    def live_state(self, window_samples, hop_samples, hops_per_push=1, device=None):
+        """A zero-filled state block (int64 CUDA tensor) = a fresh stream of pushes of hops_per_push * hop_samples samples.  Reset is
+        .zero_(), snapshot .clone(), restore .copy_(); its first element is the number of samples pushed so far.  ValueError for a geometry
+        the push refuses (a hop that is not a multiple of the frame step, ...)."""
+        import torch
+        n = self.L.mkws_frontend_live_state_bytes(self.h, int(window_samples), int(hop_samples), int(hops_per_push))
+        if n == 0:                 # (a size carries no status: what the push would refuse, in the library's own words)
+            raise ValueError("no live frontend state: " + self.L.mkws_last_error().decode("utf-8", "replace"))
+        return torch.zeros((n + 7) // 8, dtype=torch.int64, device=device if device is not None else "cuda")
+
+    def live_push(self, state, audio, window_samples, hop_samples, hops_per_push=1, spec=None, raw=None, meta=None, want_raw=False):
+        """One push: audio CUDA float32 [hops_per_push * hop_samples], the NEW samples -> (spec float32 [hops_per_push, frames, channels],
+        raw, meta int64 [2 + hops_per_push] = {count, index of the first new window, time_ms of each}); raw holds the op's raw integers
+        with want_raw (or raw=) and is None otherwise.  Rows 0 .. count-1 hold the windows the push completed, bit-equal to the same rows of stream() over
+        the whole recording; the others are left as they were.  Asynchronous, allocation-free when spec / raw / meta are passed in
+        (static buffers of a captured graph), and the state advances on the device: a replay is a push."""
+        import torch
+        h = int(hops_per_push)
+        if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.numel() != h * int(hop_samples):
+            raise ValueError(f"live_push takes a contiguous CUDA float32 tensor of {h} x {int(hop_samples)} new samples")
+        F = num_frames(self.cfg, window_samples)
+        if spec is None:
+            spec = torch.zeros((h, F, self.num_channels), dtype=torch.float32, device=audio.device)
+        if raw is None and want_raw:
+            raw = torch.zeros((h, F, self.num_channels), dtype=torch.int16, device=audio.device)
+        if meta is None:
+            meta = torch.zeros(2 + h, dtype=torch.int64, device=audio.device)
+        with torch.cuda.device(audio.device):
+            _lib.check(self.L.mkws_frontend_live_push_f32(
+                self.h, ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(audio.data_ptr()), int(window_samples), int(hop_samples), h,
+                ctypes.c_void_p(spec.data_ptr()), ctypes.c_void_p(raw.data_ptr()) if raw is not None else None,
+                ctypes.c_void_p(meta.data_ptr()), _lib.current_stream_ptr()))
+        return spec, raw, meta
+
+
+def live_windows(n_samples, window_samples, hop_samples):
+    """W(n): the windows that exist after n samples of a live stream (the num_windows of Frontend.stream)."""
+    return 0 if n_samples < window_samples else 1 + (n_samples - window_samples) // hop_samples
+
+
+def live_window_time_ms(w, hop_samples, sample_rate=16000):
+    """Time of live window w, the start of the window: the int(offset * 1000 / sample_rate) of batch_streaming_analysis.detect()."""
+    return (w * hop_samples * 1000) // sample_rate
