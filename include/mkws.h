@@ -143,6 +143,20 @@ size_t mkws_frontend_live_state_bytes(const mkws_frontend* fe, int window_sample
 int mkws_frontend_live_push_f32(mkws_frontend* fe, void* d_state, const float* d_audio, int window_samples, int hop_samples,
                                 int hops_per_push, float* d_spec, uint16_t* d_raw, int64_t* d_meta, void* stream);
 
+/* n_streams live streams advanced by one push each, in the same two launches.  Stream s's state block is d_states + s *
+ * state_stride_bytes (a multiple of 8, at least mkws_frontend_live_state_bytes(); MKWS_ERR_INVALID_ARG otherwise) and is exactly the
+ * block the one-stream call takes: a slice may be copied out, pushed with mkws_frontend_live_push_f32 and copied back.  The call is
+ * that call applied to every ACTIVE stream's slice, byte for byte: d_active int32 [n_streams] (NULL = all active); d_audio
+ * [n_streams, hops_per_push * hop_samples]; stream s owns rows s * hops_per_push .. + count_s - 1 of d_spec / d_raw
+ * [n_streams * hops_per_push, frames, channels] (the rows of one embedding batch) and row s of d_meta [n_streams, 2 + hops_per_push].
+ * A stream with d_active[s] == 0 is not advanced: its state slice and its spec / raw rows are untouched (its audio row is not read) and
+ * its meta row gets count = 0 and the index of the window it is at.  The streams are independent: each is wherever its own pushes
+ * have brought it.  Refusals as the one-stream call, and n_streams < 0; n_streams == 0 returns MKWS_OK with nothing launched.  Two
+ * launches for any n_streams, asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_frontend_live_push_many_f32(mkws_frontend* fe, void* d_states, size_t state_stride_bytes, int n_streams, const int32_t* d_active,
+                                     const float* d_audio, int window_samples, int hop_samples, int hops_per_push, float* d_spec,
+                                     uint16_t* d_raw, int64_t* d_meta, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Embedding model.  Replaces `embedding.predict(x)` on the Keras model
  *   EfficientNetB0(include_top=False, weights=None, input_shape=(49,40,1)) -> GAP ->
@@ -425,6 +439,19 @@ int mkws_detect_live_step(void* d_state, const float* d_probs, const int64_t* d_
                           const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
                           int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
                           double* d_scores, void* stream);
+
+/* n_streams live detectors stepped in one launch.  Stream s's state block is d_states + s * state_stride_bytes (a multiple of 8, at
+ * least mkws_detect_live_state_bytes(); MKWS_ERR_INVALID_ARG otherwise), exactly the block of the one-stream call, and the call is
+ * that call applied to every stream's slice, byte for byte, on: rows s * max_new .. of every head's plane of d_probs
+ * [n_heads, n_streams * max_new, classes] (what mkws_heads_forward writes for the batch mkws_frontend_live_push_many_f32 filled), row s
+ * of d_meta [n_streams, 2 + max_new], d_events [n_streams, n_heads, n_thr, max_new], d_counts [n_streams, n_heads, n_thr] and the
+ * optional d_scores [n_streams, n_heads, max_new].  There is no activity mask: a meta row with count == 0 leaves that stream's state as
+ * it is and writes zero counts.  Refusals and limits as the one-stream call, and n_streams < 0; n_streams == 0 returns MKWS_OK with
+ * nothing launched.  One launch for any n_streams, asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_detect_live_step_many(void* d_states, size_t state_stride_bytes, int n_streams, const float* d_probs, const int64_t* d_meta,
+                               int max_new, int n_heads, int classes, int target_id, const double* d_thresholds, int n_thr,
+                               double average_window_duration_ms, double suppression_ms, int minimum_count, int fired_only, int history,
+                               mkws_detect_event* d_events, int32_t* d_counts, double* d_scores, void* stream);
 
 /* Scoring against ground truth: tpr_fpr's counts (multilingual_kws/embedding/tpr_fpr.py:72-107) for every (head, threshold) lane in
  * one launch, on what mkws_detect_stream(..., fired_only = 1, ...) left on the same stream: d_events [n_heads, n_thr, event_cap] and

@@ -56,6 +56,7 @@ SYMBOLS = [
     ("mkws_frontend_stream_f32", _I, [_P, _P, _I, _I, _I, _P, _P, _I, _P]),
     ("mkws_frontend_live_state_bytes", _SZ, [_P, _I, _I, _I]),
     ("mkws_frontend_live_push_f32", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    ("mkws_frontend_live_push_many_f32", _I, [_P, _P, _SZ, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     ("mkws_embed_weight_count", _SZ, []),
     ("mkws_embed_weight_manifest", _I, [ctypes.c_char_p, _SZ]),
     ("mkws_embed_create", _I, [_P, _SZ, _I, ctypes.POINTER(_P)]),
@@ -68,6 +69,7 @@ SYMBOLS = [
     ("mkws_detect_stream", _I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
     ("mkws_detect_live_state_bytes", _SZ, [_I, _I, _I]),
     ("mkws_detect_live_step", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),
+    ("mkws_detect_live_step_many", _I, [_P, _SZ, _I, _P, _P, _I, _I, _I, _I, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),
     ("mkws_detect_score", _I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, ctypes.c_double, _P, _P]),
     ("mkws_detect_segments", _I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
     ("mkws_detect_score_segments", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_double, _P, _P]),

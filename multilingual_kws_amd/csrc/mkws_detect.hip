@@ -168,6 +168,10 @@ __global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
 // min(seen, history) newest old entries and the push's windows out in LDS in stream order, and from there on phase 1 (scores) and phase
 // 2 (lane_step) are the stateless kernel's, on indices into that line.  One workgroup per head -- it is the only reader and writer of
 // its head's state, it reads the ring before its first barrier and writes it after -- so one launch per step, thresholds <= its threads.
+// Many streams (mkws_detect_live_step_many): one workgroup per (head, stream), blockIdx.x = s * n_heads + head.  Stream s's block is
+// state + s * state_stride and a head sits inside it where it sits in a one-stream block; its meta row is meta + s * (2 + max_new), its
+// probability rows are s * max_new .. of every head's plane of n_streams * max_new rows, its events / counts / scores the s-th
+// [n_heads, ...] slab.  The one-stream call is n_streams = 1.
 constexpr int kLiveMaxNew = MKWS_DETECT_LIVE_MAX_NEW;     // windows per step: 30 KB of LDS with the longest history
 
 struct LiveEntry { int64_t time; double prob; };
@@ -175,6 +179,8 @@ struct LiveLane { int64_t deadline, prev_kw; };
 
 struct LiveArgs {
   unsigned char* state;
+  size_t state_stride;
+  int n_streams, n_heads;
   const float* probs;
   const int64_t* meta;
   const double* thr;
@@ -195,14 +201,17 @@ __global__ __launch_bounds__(kDetectThreads) void detect_live_kernel(LiveArgs a)
   double* s_prob = reinterpret_cast<double*>(s_time + line);            // [line]
   double* s_score = s_prob + line;                                      // [max_new]
   uint8_t* s_eval = reinterpret_cast<uint8_t*>(s_score + a.max_new);    // [max_new]
-  const int head = blockIdx.x, tid = threadIdx.x;
-  unsigned char* hs = a.state + head * live_head_bytes(a.n_thr, a.history);
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x / a.n_heads, head = blockIdx.x - s * a.n_heads;
+  unsigned char* hs = a.state + (size_t)s * a.state_stride + head * live_head_bytes(a.n_thr, a.history);
+  const int64_t* meta = a.meta + (size_t)s * (2 + a.max_new);
+  const float* probs = a.probs + ((size_t)head * a.n_streams + s) * a.max_new * a.classes + a.target;   // row 0 of this stream in the head's plane
   int64_t* p_seen = reinterpret_cast<int64_t*>(hs);
   LiveEntry* ring = reinterpret_cast<LiveEntry*>(hs + 16);
   LiveLane* lanes = reinterpret_cast<LiveLane*>(hs + 16 + (size_t)a.history * sizeof(LiveEntry));
   const bool walker = tid < a.n_thr;
-  const size_t lane_row = (size_t)head * a.n_thr + (walker ? tid : 0);
-  const int count = (int)min(max(a.meta[0], (int64_t)0), (int64_t)a.max_new);
+  const size_t lane_row = (size_t)blockIdx.x * a.n_thr + (walker ? tid : 0);
+  const int count = (int)min(max(meta[0], (int64_t)0), (int64_t)a.max_new);
   if (count == 0) {                                                    // an empty push changes nothing
     if (walker) a.counts[lane_row] = 0;
     return;
@@ -215,8 +224,8 @@ __global__ __launch_bounds__(kDetectThreads) void detect_live_kernel(LiveArgs a)
       s_time[k] = e.time;
       s_prob[k] = e.prob;
     } else {
-      s_time[k] = a.meta[2 + (k - nh)];
-      s_prob[k] = (double)a.probs[((size_t)head * a.max_new + (k - nh)) * a.classes + a.target];
+      s_time[k] = meta[2 + (k - nh)];
+      s_prob[k] = (double)probs[(size_t)(k - nh) * a.classes];
     }
   }
   __syncthreads();
@@ -242,7 +251,7 @@ __global__ __launch_bounds__(kDetectThreads) void detect_live_kernel(LiveArgs a)
     }
     s_score[i] = score;
     s_eval[i] = evaluated;
-    if (a.scores) a.scores[(size_t)head * a.max_new + i] = score;
+    if (a.scores) a.scores[(size_t)blockIdx.x * a.max_new + i] = score;
     if (i >= count - a.history) {                                      // the newest `history` windows go into the ring
       LiveEntry e;
       e.time = tw;
@@ -519,10 +528,10 @@ extern "C" size_t mkws_detect_live_state_bytes(int n_heads, int n_thr, int histo
   return (size_t)n_heads * live_head_bytes(n_thr, history);
 }
 
-extern "C" int mkws_detect_live_step(void* d_state, const float* d_probs, const int64_t* d_meta, int max_new, int n_heads, int classes, int target_id,
-                                     const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
-                                     int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
-                                     double* d_scores, void* stream) {
+static int live_step_many(void* d_state, size_t stride, int n_streams, const float* d_probs, const int64_t* d_meta, int max_new, int n_heads, int classes,
+                          int target_id, const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+                          int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts, double* d_scores,
+                          void* stream) {
   if (int rc = check_detect_args(n_heads, max_new, 0, n_thr, classes, target_id, average_window_duration_ms, suppression_ms,
                                  d_state && d_probs && d_meta && d_thresholds && d_counts && (d_events || max_new == 0)))
     return rc;
@@ -533,9 +542,19 @@ extern "C" int mkws_detect_live_step(void* d_state, const float* d_probs, const 
                 MKWS_DETECT_LIVE_MAX_HISTORY);
   if (n_thr > kDetectThreads) return fail(MKWS_ERR_UNSUPPORTED, "%d thresholds: at most %d per live step", n_thr, kDetectThreads);
   if (max_new > kLiveMaxNew) return fail(MKWS_ERR_UNSUPPORTED, "%d windows per step: at most %d", max_new, kLiveMaxNew);
-  if (n_heads == 0 || max_new == 0) return MKWS_OK;
+  if (n_streams < 0) return fail(MKWS_ERR_INVALID_ARG, "n_streams = %d", n_streams);
+  if (n_streams > 1 || stride != 0) {                                   // (the one-stream call has no stride)
+    const size_t need = mkws_detect_live_state_bytes(n_heads, n_thr, history);
+    if (stride % 8 != 0 || stride < need) return fail(MKWS_ERR_INVALID_ARG, "state stride of %zu bytes: a multiple of 8, at least %zu", stride, need);
+  }
+  if ((int64_t)n_streams * n_heads > INT32_MAX || (int64_t)n_streams * max_new > INT32_MAX)
+    return fail(MKWS_ERR_UNSUPPORTED, "%d streams of %d heads and %d windows per step", n_streams, n_heads, max_new);
+  if (n_heads == 0 || max_new == 0 || n_streams == 0) return MKWS_OK;
   LiveArgs a;
   a.state = static_cast<unsigned char*>(d_state);
+  a.state_stride = stride;
+  a.n_streams = n_streams;
+  a.n_heads = n_heads;
   a.probs = d_probs;
   a.meta = d_meta;
   a.thr = d_thresholds;
@@ -553,7 +572,24 @@ extern "C" int mkws_detect_live_step(void* d_state, const float* d_probs, const 
   a.history = history;
   const int threads = (n_thr + 63) / 64 * 64;
   const size_t lds = (size_t)(history + max_new) * 16 + (size_t)max_new * 8 + (size_t)((max_new + 15) & ~15);
-  hipLaunchKernelGGL(detect_live_kernel, dim3(n_heads), dim3(threads), lds, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(detect_live_kernel, dim3(n_streams * n_heads), dim3(threads), lds, static_cast<hipStream_t>(stream), a);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
+}
+
+extern "C" int mkws_detect_live_step(void* d_state, const float* d_probs, const int64_t* d_meta, int max_new, int n_heads, int classes, int target_id,
+                                     const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+                                     int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
+                                     double* d_scores, void* stream) {
+  return live_step_many(d_state, 0, 1, d_probs, d_meta, max_new, n_heads, classes, target_id, d_thresholds, n_thr, average_window_duration_ms,
+                        suppression_ms, minimum_count, fired_only, history, d_events, d_counts, d_scores, stream);
+}
+
+extern "C" int mkws_detect_live_step_many(void* d_states, size_t state_stride_bytes, int n_streams, const float* d_probs, const int64_t* d_meta,
+                                          int max_new, int n_heads, int classes, int target_id, const double* d_thresholds, int n_thr,
+                                          double average_window_duration_ms, double suppression_ms, int minimum_count, int fired_only,
+                                          int history, mkws_detect_event* d_events, int32_t* d_counts, double* d_scores, void* stream) {
+  if (state_stride_bytes == 0) return fail(MKWS_ERR_INVALID_ARG, "state stride of 0 bytes");
+  return live_step_many(d_states, state_stride_bytes, n_streams, d_probs, d_meta, max_new, n_heads, classes, target_id, d_thresholds, n_thr,
+                        average_window_duration_ms, suppression_ms, minimum_count, fired_only, history, d_events, d_counts, d_scores, stream);
 }

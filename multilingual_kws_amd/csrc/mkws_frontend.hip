@@ -589,9 +589,9 @@ __global__ __launch_bounds__(256) void frontend_windows_kernel(FrontendParams p,
 // A push of P = hops_per_push * hop_samples samples is two launches:
 //   live_frames_kernel   every frame the push completed, one wave each, from the VIRTUAL buffer tail ++ d_audio (a frame may begin in
 //                        the tail and end in the new audio: samples are fetched one by one, each from its side), into the ring; it
-//                        changes neither tail nor pos, and its first workgroup writes d_meta from the old pos;
-//   live_windows_kernel  workgroup b < count: scan + finish of window first + b over its ring slots; workgroup 0 first moves the new
-//                        tail into place (every thread reads its samples, a barrier, then the writes: source and destination overlap)
+//                        changes neither tail nor pos, and the wave of the stream's first frame writes d_meta from the old pos;
+//   live_windows_kernel  workgroup row < count: scan + finish of window first + row over its ring slots; workgroup row 0 first moves the
+//                        new tail into place (every thread reads its samples, a barrier, then the writes: source and destination overlap)
 //                        and advances pos -- it is the only reader of either in this launch, and the launch before has finished.
 // Ring size: the windows of one push span frames [W0 * hop_frames, F1) with F1 the frames complete after it; F1 - W0 * hop_frames <=
 // hops_per_push * hop_frames + frames_per_window (W0 * hop > pos - window_samples, F1 <= (pos + P - window_size) / step + 1), so a ring
@@ -622,46 +622,69 @@ __device__ __forceinline__ float live_sample(const float* tail, const float* aud
   return i < T ? tail[i] : audio[i - T];
 }
 
-__global__ __launch_bounds__(256) void frontend_live_frames_kernel(FrontendParams p, LiveGeom g, const float* __restrict__ audio,
-                                                                   unsigned char* __restrict__ state, int64_t* __restrict__ meta) {
+// Many streams (mkws_frontend_live_push_many_f32): stream s's state block is states + s * stride, its new samples audio + s * P, its
+// meta row meta + s * (2 + hops_per_push); `active` (or NULL = all) names the streams this push advances.  The one-stream call is
+// n_streams = 1, active = NULL of the same two kernels.
+struct LiveMany {
+  unsigned char* states;
+  size_t stride;            // bytes from one stream's state block to the next
+  int n_streams;
+  const int32_t* active;
+};
+__device__ __forceinline__ bool live_active(const LiveMany& m, int s) { return m.active == nullptr || m.active[s] != 0; }
+
+// Items j = s * M + f, M = hops_per_push * hop_frames (the most frames a push completes), one wave each: at the reference's geometry
+// M = 1 and a workgroup serves four streams with one load of the window coefficients.  The item f = 0 of a stream -- there always is
+// one -- writes that stream's meta row from the OLD position, count = 0 for a stream that is not advanced.
+__global__ __launch_bounds__(256) void frontend_live_frames_kernel(FrontendParams p, LiveGeom g, LiveMany m, const float* __restrict__ audio,
+                                                                   int64_t* __restrict__ meta) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t* s_fft = reinterpret_cast<uint32_t*>(smem);
   int16_t* s_coef = reinterpret_cast<int16_t*>(s_fft + 4 * 512);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const LivePos q = live_pos(p, g, state);
-  const float* tail = reinterpret_cast<const float*>(state + kLiveHeader);
-  uint32_t* ring = reinterpret_cast<uint32_t*>(state + kLiveHeader + kLiveTail * sizeof(float));
-  if (blockIdx.x == 0) {
-    const int64_t W0 = live_count(q.pos, g.window_samples, g.hop_samples);
-    const int64_t W1 = live_count(q.pos + (int64_t)g.hop_samples * g.hops_per_push, g.window_samples, g.hop_samples);
-    const int count = (int)min(W1 - W0, (int64_t)g.hops_per_push);
-    if (tid == 0) { meta[0] = count; meta[1] = W0; }
-    for (int k = tid; k < count; k += 256) meta[2 + k] = ((W0 + k) * g.hop_samples * 1000) / g.sample_rate;   // (a push may hold more hops than the workgroup has threads)
-  }
   for (int i = tid; i < p.ncoef; i += 256) s_coef[i] = p.out_coef[i];
   LaneConst L;
   init_lane_const(p, lane, L);
   __syncthreads();
   uint32_t* fftbuf = s_fft + wave * 512;
-  const int nf = (int)(q.F1 - q.F0);                     // <= hops_per_push * hop_frames
-  for (int f = blockIdx.x * 4 + wave; f < nf; f += gridDim.x * 4) {
+  const int M = g.hops_per_push * g.hop_frames;
+  const int P = g.hop_samples * g.hops_per_push;
+  const int64_t items = (int64_t)m.n_streams * M;
+  for (int64_t j = (int64_t)blockIdx.x * 4 + wave; j < items; j += (int64_t)gridDim.x * 4) {
+    const int s = (int)(j / M), f = (int)(j - (int64_t)s * M);
+    unsigned char* state = m.states + (size_t)s * m.stride;
+    const bool on = live_active(m, s);
+    const LivePos q = live_pos(p, g, state);
+    if (f == 0) {
+      int64_t* row = meta + (size_t)s * (2 + g.hops_per_push);
+      const int64_t W0 = live_count(q.pos, g.window_samples, g.hop_samples);
+      const int64_t W1 = live_count(q.pos + P, g.window_samples, g.hop_samples);
+      const int count = on ? (int)min(W1 - W0, (int64_t)g.hops_per_push) : 0;
+      if (lane == 0) { row[0] = count; row[1] = W0; }
+      for (int k = lane; k < count; k += 64) row[2 + k] = ((W0 + k) * g.hop_samples * 1000) / g.sample_rate;
+    }
+    if (!on || f >= (int)(q.F1 - q.F0)) continue;          // (F1 - F0 <= M)
+    const float* tail = reinterpret_cast<const float*>(state + kLiveHeader);
+    const float* au = audio + (size_t)s * P;
+    uint32_t* ring = reinterpret_cast<uint32_t*>(state + kLiveHeader + kLiveTail * sizeof(float));
     // load_frame's selects on samples fetched one by one: the frame's last sample is f * step + window_size - 1 < T + P
     const int base = f * p.window_step;
     int x[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int a = AudioLoad<float>::cvt(live_sample(tail, audio, q.T, base + L.toff[j]));
-      const int b = AudioLoad<float>::cvt(live_sample(tail, audio, q.T, base + L.toff[j] + 1));
-      x[2 * j] = (L.tsel[j] == 2) ? a : (L.tsel[j] == 1 ? b : 0);
-      x[2 * j + 1] = (L.tsel[j] == 2) ? b : 0;
+    for (int u = 0; u < 4; ++u) {
+      const int a = AudioLoad<float>::cvt(live_sample(tail, au, q.T, base + L.toff[u]));
+      const int b = AudioLoad<float>::cvt(live_sample(tail, au, q.T, base + L.toff[u] + 1));
+      x[2 * u] = (L.tsel[u] == 2) ? a : (L.tsel[u] == 1 ? b : 0);
+      x[2 * u + 1] = (L.tsel[u] == 2) ? b : 0;
     }
     frame_to_sig(p, L, lane, x, fftbuf, fftbuf + 256, s_coef, ring + (size_t)((q.F0 + f) % g.ring_frames) * p.num_channels);
   }
 }
 
-__global__ __launch_bounds__(256) void frontend_live_windows_kernel(FrontendParams p, LiveGeom g, const float* __restrict__ audio,
-                                                                    unsigned char* __restrict__ state, const int64_t* __restrict__ meta,
+// One workgroup per (stream, window row): blockIdx.x = s * hops_per_push + row, which is also the row of spec / raw it writes.
+__global__ __launch_bounds__(256) void frontend_live_windows_kernel(FrontendParams p, LiveGeom g, LiveMany m, const float* __restrict__ audio,
+                                                                    const int64_t* __restrict__ meta,
                                                                     float* __restrict__ spec, uint16_t* __restrict__ raw) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int C = p.num_channels, FC = g.frames_per_window * C;
@@ -670,17 +693,21 @@ __global__ __launch_bounds__(256) void frontend_live_windows_kernel(FrontendPara
   int16_t* s_pcan = reinterpret_cast<int16_t*>(s_est + FC);
   uint16_t* s_log = reinterpret_cast<uint16_t*>(s_pcan + 128);
   const int tid = threadIdx.x;
-  if (blockIdx.x == 0) {
+  const int s = blockIdx.x / g.hops_per_push, row = blockIdx.x - s * g.hops_per_push;
+  unsigned char* state = m.states + (size_t)s * m.stride;
+  const int64_t* mrow = meta + (size_t)s * (2 + g.hops_per_push);
+  if (row == 0 && live_active(m, s)) {
     const LivePos q = live_pos(p, g, state);
     float* tail = reinterpret_cast<float*>(state + kLiveHeader);
     const int P = g.hop_samples * g.hops_per_push;
+    const float* au = audio + (size_t)s * P;
     const int shift = (int)(q.F1 - q.F0) * p.window_step;                // where the first incomplete frame begins in tail ++ audio
     const int Tn = (int)(q.pos + P - q.F1 * p.window_step);              // in [0, window_size): at most kLiveTail = 2 x 256 samples
     float keep[kLiveTail / 256];
 #pragma unroll
     for (int k = 0; k < kLiveTail / 256; ++k) {
       const int i = tid + 256 * k;
-      keep[k] = i < Tn ? live_sample(tail, audio, q.T, shift + i) : 0.0f;
+      keep[k] = i < Tn ? live_sample(tail, au, q.T, shift + i) : 0.0f;
     }
     __syncthreads();
 #pragma unroll
@@ -690,10 +717,10 @@ __global__ __launch_bounds__(256) void frontend_live_windows_kernel(FrontendPara
     }
     if (tid == 0) *reinterpret_cast<int64_t*>(state) = q.pos + P;
   }
-  const int count = (int)min(max(meta[0], (int64_t)0), (int64_t)g.hops_per_push);
-  if ((int)blockIdx.x >= count) return;
+  const int count = (int)min(max(mrow[0], (int64_t)0), (int64_t)g.hops_per_push);
+  if (row >= count) return;
   const uint32_t* ring = reinterpret_cast<const uint32_t*>(state + kLiveHeader + kLiveTail * sizeof(float));
-  const int64_t first = (max(meta[1], (int64_t)0) + blockIdx.x) * g.hop_frames;   // the window's first frame
+  const int64_t first = (max(mrow[1], (int64_t)0) + row) * g.hop_frames;   // the window's first frame
   for (int i = tid; i < FC; i += 256) {
     const int t = i / C;
     s_sig[i] = ring[(size_t)((first + t) % g.ring_frames) * C + (i - t * C)];
@@ -1021,24 +1048,48 @@ size_t mkws_frontend_live_state_bytes(const mkws_frontend* fe, int window_sample
   return kLiveHeader + kLiveTail * sizeof(float) + (size_t)g.ring_frames * fe->prm.num_channels * sizeof(uint32_t);
 }
 
-int mkws_frontend_live_push_f32(mkws_frontend* fe, void* d_state, const float* d_audio, int window_samples, int hop_samples, int hops_per_push,
-                                float* d_spec, uint16_t* d_raw, int64_t* d_meta, void* stream) {
+static int live_push_many(mkws_frontend* fe, void* d_states, size_t stride, int n_streams, const int32_t* d_active, const float* d_audio,
+                          int window_samples, int hop_samples, int hops_per_push, float* d_spec, uint16_t* d_raw, int64_t* d_meta, void* stream) {
   LiveGeom g;
   if (int rc = live_geom(fe, window_samples, hop_samples, hops_per_push, &g)) return rc;
-  if (!d_state || !d_audio || !d_meta || (!d_spec && !d_raw)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
-  if (reinterpret_cast<uintptr_t>(d_state) % 8 != 0) return fail(MKWS_ERR_INVALID_ARG, "d_state must be 8-byte aligned");
+  if (n_streams < 0) return fail(MKWS_ERR_INVALID_ARG, "n_streams = %d", n_streams);
+  if (!d_states || !d_audio || !d_meta || (!d_spec && !d_raw)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (reinterpret_cast<uintptr_t>(d_states) % 8 != 0) return fail(MKWS_ERR_INVALID_ARG, "d_state must be 8-byte aligned");
   const FrontendParams& p = fe->prm;
+  if ((int64_t)n_streams * hops_per_push > INT32_MAX)
+    return fail(MKWS_ERR_UNSUPPORTED, "%d streams of %d hops per push", n_streams, hops_per_push);
+  if (n_streams == 0) return MKWS_OK;
   const size_t lds1 = 4 * 512 * 4 + ((p.ncoef + 7) & ~7) * 2 + 16;
   const size_t lds2 = 2 * (size_t)g.frames_per_window * p.num_channels * 4 + 128 * 2 + 132 * 2 + 16;
-  int grid1 = (hops_per_push * g.hop_frames + 3) / 4;                     // a push completes at most that many frames
-  if (grid1 > 4096) grid1 = 4096;
+  const int64_t items = (int64_t)n_streams * hops_per_push * g.hop_frames;   // a push completes at most that many frames
+  const int grid1 = (int)std::min<int64_t>((items + 3) / 4, 4096);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  unsigned char* st = static_cast<unsigned char*>(d_state);
-  hipLaunchKernelGGL(frontend_live_frames_kernel, dim3(grid1), dim3(256), lds1, s, p, g, d_audio, st, d_meta);
+  LiveMany m;
+  m.states = static_cast<unsigned char*>(d_states);
+  m.stride = stride;
+  m.n_streams = n_streams;
+  m.active = d_active;
+  hipLaunchKernelGGL(frontend_live_frames_kernel, dim3(grid1), dim3(256), lds1, s, p, g, m, d_audio, d_meta);
   MKWS_HIP(hipGetLastError());
-  hipLaunchKernelGGL(frontend_live_windows_kernel, dim3(hops_per_push), dim3(256), lds2, s, p, g, d_audio, st, static_cast<const int64_t*>(d_meta), d_spec, d_raw);
+  hipLaunchKernelGGL(frontend_live_windows_kernel, dim3(n_streams * hops_per_push), dim3(256), lds2, s, p, g, m, d_audio,
+                     static_cast<const int64_t*>(d_meta), d_spec, d_raw);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
+}
+
+int mkws_frontend_live_push_f32(mkws_frontend* fe, void* d_state, const float* d_audio, int window_samples, int hop_samples, int hops_per_push,
+                                float* d_spec, uint16_t* d_raw, int64_t* d_meta, void* stream) {
+  return live_push_many(fe, d_state, 0, 1, nullptr, d_audio, window_samples, hop_samples, hops_per_push, d_spec, d_raw, d_meta, stream);
+}
+
+int mkws_frontend_live_push_many_f32(mkws_frontend* fe, void* d_states, size_t state_stride_bytes, int n_streams, const int32_t* d_active,
+                                     const float* d_audio, int window_samples, int hop_samples, int hops_per_push, float* d_spec,
+                                     uint16_t* d_raw, int64_t* d_meta, void* stream) {
+  const size_t need = mkws_frontend_live_state_bytes(fe, window_samples, hop_samples, hops_per_push);
+  if (need && (state_stride_bytes % 8 != 0 || state_stride_bytes < need))
+    return fail(MKWS_ERR_INVALID_ARG, "state stride of %zu bytes: a multiple of 8, at least %zu", state_stride_bytes, need);
+  return live_push_many(fe, d_states, state_stride_bytes, n_streams, d_active, d_audio, window_samples, hop_samples, hops_per_push, d_spec,
+                        d_raw, d_meta, stream);
 }
 
 }  // extern "C"

@@ -397,6 +397,72 @@ def detect_live_step(state, probs, meta, d_thresholds, average_window_duration_m
     return out
 
 
+# Many streams in lockstep (mkws_detect_live_step_many): S detectors stepped in one launch.  The host specification is one
+# LiveDetectorHost per stream.
+
+def live_detector_state_many(streams, n_heads, n_thr, history, device=None):
+    """Zero-filled state blocks of `streams` fresh streams: an int64 CUDA tensor [streams, words]; the row stride is the state stride, so
+    row s viewed flat is a valid one-stream state (detect_live_step takes it, .zero_() resets that stream alone)."""
+    import torch
+    if int(streams) < 0:
+        raise ValueError(f"live_detector_state_many: {streams} streams")
+    words = live_detector_state(n_heads, n_thr, history, device=device).numel()
+    return torch.zeros((int(streams), words), dtype=torch.int64, device=device if device is not None else "cuda")
+
+
+def live_out_words_many(streams, n_heads, n_thr, max_new):
+    """int64 words of detect_live_step_many's output buffer: ALL counts [S, N, T] (int32 pairs padded to whole words), then ALL events
+    [S, N, T, max_new]."""
+    return (streams * n_heads * n_thr + 1) // 2 + 2 * streams * n_heads * n_thr * max_new
+
+
+def live_unpack_many(words, streams, n_heads, n_thr, max_new):
+    """The host copy (numpy int64) of that buffer -> (counts int32 [S, N, T], events EVENT_DTYPE [S, N, T, max_new]); [s] of each is what
+    live_unpack gives for stream s alone."""
+    cwords = (streams * n_heads * n_thr + 1) // 2
+    return (words[:cwords].view(np.int32)[:streams * n_heads * n_thr].reshape(streams, n_heads, n_thr),
+            words[cwords:].view(EVENT_DTYPE).reshape(streams, n_heads, n_thr, max_new))
+
+
+def detect_live_step_many(states, probs, meta, d_thresholds, average_window_duration_ms, suppression_ms, minimum_count, history, target_id=2,
+                          fired_only=False, out=None, scores=None):
+    """One step of S live detectors.  states: live_detector_state_many(S, N, T, history); probs CUDA float32 [N, S * max_new, C], stream
+    s's windows in rows s * max_new .. of every head's plane (what Head.forward_many gives for the batch Frontend.live_push_many filled);
+    meta CUDA int64 [S, 2 + max_new] as live_push_many writes it; d_thresholds CUDA float64 [T].  -> out, a CUDA int64 tensor of
+    live_out_words_many(S, N, T, max_new) words (live_unpack_many reads its host copy).  scores: optional CUDA float64 [S, N, max_new].
+    For every stream this is detect_live_step on its own slice, byte for byte; a meta row with count == 0 leaves its stream as it is.
+    Asynchronous, allocation-free when `out` is passed in, one launch for any S: capturable."""
+    import torch
+    from .frontend import check_live_many
+    if meta.dim() != 2 or meta.shape[1] < 2:
+        raise ValueError("meta must be an int64 tensor [streams, 2 + max_new]")
+    max_new = int(meta.shape[1]) - 2
+    check_live_many(states, meta.shape, 2 + max_new, "meta")
+    S = int(states.shape[0])
+    if probs.dim() != 3 or probs.shape[1] != S * max_new:
+        raise ValueError(f"probs must have the shape [heads, {S} x {max_new}, classes]: max_new rows per stream in every head's plane")
+    if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise ValueError("probs must be a contiguous CUDA float32 tensor [heads, streams * max_new, classes]")
+    N, _, C = probs.shape
+    T = int(d_thresholds.numel())
+    if d_thresholds.dtype != torch.float64 or not d_thresholds.is_cuda or meta.dtype != torch.int64 or not meta.is_cuda or not meta.is_contiguous():
+        raise ValueError("d_thresholds must be CUDA float64 [T] and meta contiguous CUDA int64 [streams, 2 + max_new]")
+    words = live_out_words_many(S, N, T, max_new)
+    if out is None:
+        out = torch.zeros(words, dtype=torch.int64, device=probs.device)
+    elif out.numel() != words or out.dtype != torch.int64 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int64 tensor of {words} words (live_out_words_many)")
+    if scores is not None and (scores.numel() != S * N * max_new or scores.dtype != torch.float64 or not scores.is_contiguous()):
+        raise ValueError(f"scores must be a contiguous float64 tensor [{S}, {N}, {max_new}]")
+    base = out.data_ptr()
+    with torch.cuda.device(probs.device):
+        _lib.check(_lib.lib().mkws_detect_live_step_many(
+            states.data_ptr(), 8 * int(states.stride(0)), S, probs.data_ptr(), meta.data_ptr(), max_new, N, C, int(target_id),
+            d_thresholds.data_ptr(), T, float(average_window_duration_ms), float(suppression_ms), int(minimum_count), int(bool(fired_only)),
+            int(history), base + 8 * ((S * N * T + 1) // 2), base, scores.data_ptr() if scores is not None else None, _lib.current_stream_ptr()))
+    return out
+
+
 class LiveDetectorHost:
     """The host restatement of the live detector: K x T SingleTargetRecognizeCommands (one per keyword head and threshold) fed push by
     push.  step() returns what one mkws_detect_live_step leaves behind, and is the specification it is held to bit for bit."""

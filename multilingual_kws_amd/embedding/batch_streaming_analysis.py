@@ -413,8 +413,94 @@ class LivePushCutter:
         return a[:full * self.push_samples].reshape(full, self.push_samples)
 
 
+class LiveGroupScheduler:
+    """The host part of LiveSessionGroup.feed: chunks of any length for some of `streams` slots -> ticks.  One LivePushCutter per slot;
+    a tick is (active int32 [S], audio float32 [S, push_samples]): slot s is active in a tick if it has a whole push pending, and its row
+    then holds that push (the rows of the others are zeros and are not read).  feed() emits ticks while any slot has a push, so nothing
+    but the cutters' unfinished pushes waits between calls: tick t of a feed holds the t-th push each slot completed in it.  What a slot
+    pushes depends only on the samples fed to THAT slot so far, never on how they were cut into chunks or on the other slots."""
+
+    def __init__(self, streams, push_samples):
+        self.streams, self.push_samples = int(streams), int(push_samples)
+        if self.streams < 1 or self.push_samples < 1:
+            raise ValueError(f"LiveGroupScheduler({streams}, {push_samples}): at least one slot and one sample per push")
+        self.cutters = [LivePushCutter(self.push_samples) for _ in range(self.streams)]
+
+    def reset(self, slot=None):
+        for c in (self.cutters if slot is None else [self.cutters[self.slot(slot)]]):
+            c.reset()
+
+    def slot(self, slot):
+        if not 0 <= int(slot) < self.streams:
+            raise ValueError(f"slot {slot}: from 0 to {self.streams - 1}")
+        return int(slot)
+
+    def pending(self, slot):
+        """Samples of the slot's unfinished push."""
+        return int(self.cutters[self.slot(slot)].rest.size)
+
+    def chunks(self, chunks):
+        """{slot: samples} or a length-S sequence with None for silent slots -> [(slot, samples)] in slot order."""
+        if isinstance(chunks, dict):
+            items = sorted((self.slot(k), v) for k, v in chunks.items())
+        else:
+            chunks = list(chunks)
+            if len(chunks) != self.streams:
+                raise ValueError(f"{len(chunks)} chunks for {self.streams} slots (a dict {{slot: samples}} names some of them)")
+            items = list(enumerate(chunks))
+        return [(k, v) for k, v in items if v is not None]
+
+    def feed(self, chunks):
+        """-> the list of ticks these chunks complete (may be empty)."""
+        pushes = {k: self.cutters[k].cut(v) for k, v in self.chunks(chunks)}
+        ticks = []
+        for t in range(max([len(v) for v in pushes.values()], default=0)):
+            active = np.zeros(self.streams, np.int32)
+            audio = np.zeros((self.streams, self.push_samples), np.float32)
+            for k, v in pushes.items():
+                if t < len(v):
+                    active[k], audio[k] = 1, v[t]
+            ticks.append((active, audio))
+        return ticks
+
+
 def default_live_flags(thresholds):
     return StreamFlags(wav="", ground_truth="", target_keyword="", detection_thresholds=list(thresholds))
+
+
+def _live_setup(self, thresholds, flags, model_settings, keywords, fired_only):
+    """What LiveSession and LiveSessionGroup derive from their arguments once embedding, heads and hops are set: thresholds, flags,
+    keywords, the stream's geometry, the detector's history and the frontend handle.  -> the model settings."""
+    from ..detector import live_history
+    self.thresholds = [float(t) for t in thresholds]
+    if not self.thresholds:
+        raise ValueError("at least one threshold")
+    self.flags = flags if flags is not None else default_live_flags(self.thresholds)
+    N = len(self.heads)
+    if keywords is None:
+        keywords = [self.flags.target_keyword or f"keyword_{i}" for i in range(N)]
+    self.keywords = list(keywords)
+    if len(self.keywords) != N:
+        raise ValueError(f"{len(self.keywords)} keywords for {N} heads")
+    if self.heads[0].classes != len(self.flags.labels()):
+        raise ValueError("The results for recognition should contain {} elements, but there are {} produced".format(
+            len(self.flags.labels()), self.heads[0].classes))
+    self.fired_only = bool(fired_only)
+    ms = model_settings or input_data.standard_microspeech_model_settings(3)
+    self.sample_rate = ms["sample_rate"]
+    self.window_samples = int(self.flags.clip_duration_ms * self.sample_rate / 1000)
+    self.hop_samples = int(self.flags.clip_stride_ms * self.sample_rate / 1000)
+    self.push_samples = self.hops * self.hop_samples
+    self.history = live_history(self.flags.average_window_duration_ms, self.hop_samples, self.sample_rate)
+    self.fe = input_data._frontend_for(ms, self.window_samples)
+    return ms
+
+
+def _live_rows(self, records):
+    """records (window, head, threshold index, fired, score) -> feed()'s rows [keyword, time_ms, score, threshold]."""
+    from ..frontend import live_window_time_ms
+    return [[self.keywords[n] if fired else input_data.SILENCE_LABEL, live_window_time_ms(w, self.hop_samples, self.sample_rate), score,
+             self.thresholds[k]] for w, n, k, fired, score in records]
 
 
 class LiveSession:
@@ -435,7 +521,7 @@ class LiveSession:
     def __init__(self, models=None, thresholds=(0.9,), flags=None, model_settings=None, hops_per_push=1, embedding=None, heads=None,
                  keywords=None, fired_only=True, use_graph=True):
         import torch
-        from ..detector import live_detector_state, live_history, live_out_words
+        from ..detector import live_detector_state, live_out_words
         from ..head import Head
         if models is not None:
             mlist = list(models) if isinstance(models, (list, tuple)) else [models]
@@ -443,30 +529,10 @@ class LiveSession:
         self.embedding, self.heads, self.hops = embedding, list(heads), int(hops_per_push)
         if not 1 <= self.hops <= embedding.max_batch:
             raise ValueError(f"LiveSession(hops_per_push={hops_per_push}): from 1 to the embedding handle's max_batch={embedding.max_batch}")
-        self.thresholds = [float(t) for t in thresholds]
-        if not self.thresholds:
-            raise ValueError("at least one threshold")
-        self.flags = flags if flags is not None else default_live_flags(self.thresholds)
-        N = len(self.heads)
-        if keywords is None:
-            keywords = [self.flags.target_keyword or f"keyword_{i}" for i in range(N)]
-        self.keywords = list(keywords)
-        if len(self.keywords) != N:
-            raise ValueError(f"{len(self.keywords)} keywords for {N} heads")
-        if self.heads[0].classes != len(self.flags.labels()):
-            raise ValueError("The results for recognition should contain {} elements, but there are {} produced".format(
-                len(self.flags.labels()), self.heads[0].classes))
-        self.fired_only = bool(fired_only)
-        ms = model_settings or input_data.standard_microspeech_model_settings(3)
-        self.sample_rate = ms["sample_rate"]
-        self.window_samples = int(self.flags.clip_duration_ms * self.sample_rate / 1000)
-        self.hop_samples = int(self.flags.clip_stride_ms * self.sample_rate / 1000)
-        self.push_samples = self.hops * self.hop_samples
-        self.history = live_history(self.flags.average_window_duration_ms, self.hop_samples, self.sample_rate)
-        self.fe = input_data._frontend_for(ms, self.window_samples)
+        ms = _live_setup(self, thresholds, flags, model_settings, keywords, fired_only)
         self.cutter = LivePushCutter(self.push_samples)
         dev = embedding.device
-        T, h = len(self.thresholds), self.hops
+        N, T, h = len(self.heads), len(self.thresholds), self.hops
         with torch.cuda.device(dev):
             self.audio = torch.zeros(self.push_samples, dtype=torch.float32, device=dev)        # static graph input: the NEW samples
             self.fstate = self.fe.live_state(self.window_samples, self.hop_samples, h, device=dev)
@@ -570,15 +636,175 @@ class LiveSession:
         threshold.  time_ms is the start of the window, as detect() reports it.  The same events as records (window, head index,
         threshold index, fired, score) are kept in .last_records."""
         import torch
-        from ..frontend import live_window_time_ms
         if torch.is_tensor(chunk):
             chunk = chunk.detach().reshape(-1).to("cpu", torch.float32).numpy()
         records = []
         for samples in self.cutter.cut(chunk):
             records.extend(self._push(samples))
         self.last_records = records
-        return [[self.keywords[n] if fired else input_data.SILENCE_LABEL, live_window_time_ms(w, self.hop_samples, self.sample_rate), score,
-                 self.thresholds[k]] for w, n, k, fired, score in records]
+        return _live_rows(self, records)
+
+
+class LiveSessionGroup:
+    """`streams` live keyword spotters served in lockstep: slot s is fed chunks of any length and gets back the detections they completed,
+    as from a LiveSession of its own, but a tick -- one push of every slot that has a whole push pending -- is ONE chain on one stream,
+        frontend push of all slots (2 launches) -> mkws_embed_forward at batch streams * hops_per_push -> mkws_heads_forward
+        -> detector step of all slots (1 launch),
+    replayed as one hipGraph: per tick one pinned upload (the [S, push] audio and the active mask), one replay, one download of the packed
+    counts and events, one synchronise.  The slots share the heads, thresholds and flags; their states are the rows of two device
+    tensors (fstates, dstates: a row is a one-stream state block), and a slot that is not active in a tick is not touched by it.
+
+    What is promised, piece by piece:
+      * a slot's spectrogram rows are bit-equal to Frontend.stream over that slot's audio;
+      * a tick's probabilities (.probs [N, S * h, 3], slot s in rows s * h ..) are torch.equal to the eager
+        Head.forward_many(heads, embedding.forward(group.spec)) on the same handle;
+      * a slot's events are byte-equal to detect_on_device over the probability rows that slot received;
+      * LiveSessionGroup(streams=1, hops_per_push=h) returns exactly what LiveSession(hops_per_push=h) returns on the same handle (the
+        embedding batch is the same and so is the plan).
+    NOT promised: equality of a slot's probabilities with those of its own batch-1 LiveSession -- the embedding handle picks another plan
+    at another batch size (equal up to its rounding; tools/bench_live_group.py measures the difference).
+
+    Arguments as LiveSession's; streams * hops_per_push must not exceed the embedding handle's max_batch."""
+
+    def __init__(self, models=None, streams=1, thresholds=(0.9,), flags=None, model_settings=None, hops_per_push=1, embedding=None, heads=None,
+                 keywords=None, fired_only=True, use_graph=True):
+        import torch
+        from ..detector import live_detector_state_many, live_out_words_many
+        from ..head import Head
+        if models is not None:
+            mlist = list(models) if isinstance(models, (list, tuple)) else [models]
+            embedding, heads = mlist[0].embedding, [m.head for m in mlist]
+        self.embedding, self.heads, self.hops, self.streams = embedding, list(heads), int(hops_per_push), int(streams)
+        if self.streams < 1 or not 1 <= self.hops or self.streams * self.hops > embedding.max_batch:
+            raise ValueError(f"LiveSessionGroup(streams={streams}, hops_per_push={hops_per_push}): streams * hops_per_push from 1 to the "
+                             f"embedding handle's max_batch={embedding.max_batch}")
+        ms = _live_setup(self, thresholds, flags, model_settings, keywords, fired_only)
+        self.scheduler = LiveGroupScheduler(self.streams, self.push_samples)
+        dev = embedding.device
+        S, N, T, h, P = self.streams, len(self.heads), len(self.thresholds), self.hops, self.push_samples
+        with torch.cuda.device(dev):
+            # the static graph input, ONE buffer so that a tick is one upload: the NEW samples [S, push] (float32), then the active mask [S] (int32)
+            self.d_in = torch.zeros(S * P + S, dtype=torch.float32, device=dev)
+            self.audio, self.active = self.d_in[:S * P].view(S, P), self.d_in[S * P:].view(torch.int32)
+            self.fstates = self.fe.live_state_many(S, self.window_samples, self.hop_samples, h, device=dev)
+            self.dstates = live_detector_state_many(S, N, T, self.history, device=dev)
+            self.spec = torch.zeros((S * h, ms["spectrogram_length"], ms["fingerprint_width"]), dtype=torch.float32, device=dev)
+            self.meta = torch.zeros((S, 2 + h), dtype=torch.int64, device=dev)
+            self.d_thr = torch.tensor(self.thresholds, dtype=torch.float64, device=dev)
+            self.out = torch.zeros(live_out_words_many(S, N, T, h), dtype=torch.int64, device=dev)   # counts and events: the one D2H per tick
+            self.h_in = torch.zeros(S * P + S, dtype=torch.float32).pin_memory()
+            self.h_out = torch.zeros(self.out.numel(), dtype=torch.int64).pin_memory()
+        self.h_audio, self.h_active = self.h_in[:S * P].view(S, P).numpy(), self.h_in[S * P:].view(torch.int32).numpy()
+        self._Head = Head
+        self.graph = None
+        self.recaptures = 0
+        self.last_records = {}
+        self.probs = self._chain()                      # eager pass: creates every lazily-built table / attribute
+        if use_graph:
+            self._capture()
+        self.reset()
+
+    def _chain(self):
+        from ..detector import detect_live_step_many
+        f = self.flags
+        self.fe.live_push_many(self.fstates, self.audio, self.window_samples, self.hop_samples, self.hops, active=self.active,
+                               spec=self.spec, meta=self.meta)
+        probs = self._Head.forward_many(self.heads, self.embedding.forward(self.spec))
+        detect_live_step_many(self.dstates, probs, self.meta, self.d_thr, f.average_window_duration_ms, f.suppression_ms, f.minimum_count,
+                              self.history, target_id=2, fired_only=self.fired_only, out=self.out)
+        return probs
+
+    def _capture(self):
+        """LiveSession._capture for the group: warm-up and capture on a single stream (the chain is one branch), BOTH state tensors put back
+        afterwards, so capturing advances no slot."""
+        import torch
+        dev = self.embedding.device
+        kept = (self.fstates.clone(), self.dstates.clone())
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._chain()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.probs = self._chain()
+        self.graph = g
+        self.fstates.copy_(kept[0])
+        self.dstates.copy_(kept[1])
+
+    def reset(self, slot=None):
+        """Starts a new stream in `slot` (None: in every slot): its two state slices zeroed, its unfinished push dropped."""
+        if slot is None:
+            self.fstates.zero_()
+            self.dstates.zero_()
+            self.spec.zero_()                           # (rows no slot has written yet ride along in the embedding batch: the same after every reset)
+            self.samples_pushed = [0] * self.streams    # the host's mirror of each state slice's first int64
+        else:
+            slot = self.scheduler.slot(slot)
+            self.fstates[slot].zero_()
+            self.dstates[slot].zero_()
+            self.samples_pushed[slot] = 0
+        self.scheduler.reset(slot)
+        self.last_records = {}
+
+    def samples_seen(self, slot):
+        return self.samples_pushed[self.scheduler.slot(slot)] + self.scheduler.pending(slot)
+
+    def windows_seen(self, slot):
+        from ..frontend import live_windows
+        return live_windows(self.samples_pushed[self.scheduler.slot(slot)], self.window_samples, self.hop_samples)
+
+    def close(self):
+        self.graph = None
+        self.probs = self.d_in = self.audio = self.active = self.fstates = self.dstates = self.spec = self.meta = self.out = None
+
+    def _tick(self, active, audio, records):
+        """One tick (LiveGroupScheduler's): appends the records (window, head, threshold index, fired, score) of the events it completed to
+        records[slot]."""
+        import torch
+        from ..detector import live_unpack_many
+        dev = self.embedding.device
+        self.h_audio[:] = audio
+        self.h_active[:] = active
+        with torch.cuda.device(dev):
+            self.d_in.copy_(self.h_in, non_blocking=True)
+            if self.graph is not None:
+                if self.embedding.get_option("exchange_error"):
+                    # LiveSession's protocol: the PREVIOUS replay ran a failed exchange (all-NaN probabilities: the detectors scored NaN and
+                    # reported no event; the frontend rings are unaffected): heal the handle and capture the single-workgroup kernels
+                    self._capture()
+                    self.recaptures += 1
+                self.graph.replay()
+            else:
+                self.probs = self._chain()
+            self.h_out.copy_(self.out, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+        on = np.flatnonzero(active).tolist()
+        first = {s: self.windows_seen(s) for s in on}
+        for s in on:
+            self.samples_pushed[s] += self.push_samples
+        counts, events = live_unpack_many(self.h_out.numpy(), self.streams, len(self.heads), len(self.thresholds), self.hops)
+        if counts.any():
+            fresh = {}
+            for s, n, k in zip(*np.nonzero(counts)):
+                for w, fired, score in events[s, n, k, :counts[s, n, k]].tolist():
+                    fresh.setdefault(int(s), []).append((first[int(s)] + w, int(n), int(k), fired, score))
+            for s, rec in fresh.items():
+                rec.sort(key=lambda r: r[:3])
+                records.setdefault(s, []).extend(rec)
+
+    def feed(self, chunks):
+        """chunks: {slot: samples} or a length-S sequence with None for silent slots; samples are float32 of any length (numpy, CPU or CUDA
+        tensor, which is brought to the host: the pushes are cut there).  Runs the ticks the chunks complete -> {slot: [[keyword, time_ms,
+        score, threshold], ...]} with one entry per slot fed, each slot's rows ordered as LiveSession.feed orders them.  The same events
+        as records (window, head index, threshold index, fired, score) are kept per slot in .last_records."""
+        import torch
+        fed = [(k, v.detach().reshape(-1).to("cpu", torch.float32).numpy() if torch.is_tensor(v) else v) for k, v in self.scheduler.chunks(chunks)]
+        records = {k: [] for k, _ in fed}
+        for active, audio in self.scheduler.feed(dict(fed)):
+            self._tick(active, audio, records)
+        self.last_records = records
+        return {k: _live_rows(self, rec) for k, rec in records.items()}
 
 
 def detect(inferences, flags: StreamFlags, threshold, sample_rate=16000, data_samples=None):

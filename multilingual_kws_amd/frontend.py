@@ -145,6 +145,62 @@ class Frontend:
                 ctypes.c_void_p(meta.data_ptr()), _lib.current_stream_ptr()))
         return spec, raw, meta
 
+    # -- many live streams in lockstep (mkws_frontend_live_push_many_f32): one push for all of them, two launches for any number -------
+    def live_state_many(self, streams, window_samples, hop_samples, hops_per_push=1, device=None):
+        """Zero-filled state blocks of `streams` fresh streams: an int64 CUDA tensor [streams, words] whose row stride is the state
+        stride, so row s viewed flat is a valid one-stream state (live_push takes it, .zero_() resets that stream alone)."""
+        import torch
+        if int(streams) < 0:
+            raise ValueError(f"live_state_many: {streams} streams")
+        words = self.live_state(window_samples, hop_samples, hops_per_push, device=device).numel()
+        return torch.zeros((int(streams), words), dtype=torch.int64, device=device if device is not None else "cuda")
+
+    def live_push_many(self, states, audio, window_samples, hop_samples, hops_per_push=1, active=None, spec=None, raw=None, meta=None,
+                       want_raw=False):
+        """One push of every active stream.  states: live_state_many(S, ...); audio CUDA float32 [S, hops_per_push * hop_samples], the
+        NEW samples of each stream; active: CUDA int32 [S] (None = all) -> (spec float32 [S * hops_per_push, frames, channels], raw,
+        meta int64 [S, 2 + hops_per_push]).  Stream s owns rows s * hops_per_push .. + meta[s, 0] - 1 of spec / raw -- the layout of one
+        embedding batch -- and what it gets is live_push on its own slice, bit for bit.  A stream with active[s] == 0 is not advanced:
+        its state and rows are untouched and its meta row says count = 0.  Asynchronous, allocation-free when spec / raw / meta are
+        passed in, two launches for any S."""
+        import torch
+        h = int(hops_per_push)
+        check_live_many(states, audio.shape if audio.dim() == 2 else None, h * int(hop_samples), "audio")
+        S = int(states.shape[0])
+        if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous():
+            raise ValueError(f"live_push_many takes a contiguous CUDA float32 tensor [{S}, {h} x {int(hop_samples)}] of new samples")
+        if active is not None and (not active.is_cuda or active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != S):
+            raise ValueError(f"active must be a contiguous CUDA int32 tensor [{S}]")
+        F = num_frames(self.cfg, window_samples)
+        if spec is None:
+            spec = torch.zeros((S * h, F, self.num_channels), dtype=torch.float32, device=audio.device)
+        if raw is None and want_raw:
+            raw = torch.zeros((S * h, F, self.num_channels), dtype=torch.int16, device=audio.device)
+        if meta is None:
+            meta = torch.zeros((S, 2 + h), dtype=torch.int64, device=audio.device)
+        for name, t, n in (("spec", spec, S * h * F * self.num_channels), ("raw", raw, S * h * F * self.num_channels), ("meta", meta, S * (2 + h))):
+            if t is not None and (t.numel() != n or not t.is_contiguous()):
+                raise ValueError(f"{name} must be contiguous with {n} elements")
+        with torch.cuda.device(audio.device):
+            _lib.check(self.L.mkws_frontend_live_push_many_f32(
+                self.h, ctypes.c_void_p(states.data_ptr()), 8 * int(states.stride(0)), S,
+                ctypes.c_void_p(active.data_ptr()) if active is not None else None, ctypes.c_void_p(audio.data_ptr()),
+                int(window_samples), int(hop_samples), h, ctypes.c_void_p(spec.data_ptr()),
+                ctypes.c_void_p(raw.data_ptr()) if raw is not None else None, ctypes.c_void_p(meta.data_ptr()), _lib.current_stream_ptr()))
+        return spec, raw, meta
+
+
+def check_live_many(states, shape, row, what):
+    """The rules of a many-stream call that are decided before any device call: states is an int64 tensor [S, words] with unit inner
+    stride (its row stride is the state stride), and the per-stream input has the shape [S, row].  ValueError otherwise."""
+    import torch
+    if states.dim() != 2 or states.dtype != torch.int64 or (states.shape[1] > 1 and states.stride(1) != 1) or \
+            (states.shape[0] > 1 and states.stride(0) < states.shape[1]):
+        raise ValueError("states must be an int64 tensor [streams, words] whose rows are contiguous and do not overlap "
+                         "(live_state_many / live_detector_state_many)")
+    if shape is None or tuple(shape) != (int(states.shape[0]), int(row)):
+        raise ValueError(f"{what} must have the shape [{int(states.shape[0])}, {int(row)}]: one row per stream of the state tensor")
+
 
 def live_windows(n_samples, window_samples, hop_samples):
     """W(n): the windows that exist after n samples of a live stream (the num_windows of Frontend.stream)."""
