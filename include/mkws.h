@@ -588,26 +588,37 @@ int mkws_kmeans_nearest(const float* d_x, int dim, int n_rows, const int32_t* d_
 typedef struct mkws_augment_item {
   int32_t mode;     /* 0: out = shift(fg)            (random_timeshift, :245-268)
                        1: out = bg_slice * bg_vol    (silence branch, :284-287 / :227-243)
-                       2: out = clip(shift(fg) + bg_slice * (rms(fg)/rms(bg) or 0) * bg_vol, -1, 1)
-                          (add_background, :141-157) */
+                       2: out = clip(shift(fg) + bg_slice * (rms(shift(fg))/rms(bg_slice) or 0) * bg_vol, -1, 1)
+                          (add_background, :141-157): both RMS values are taken over exactly the n_samples of the
+                          SHIFTED clip and of the slice; the ratio is 0 where rms(bg_slice) is 0 */
   int32_t bank;     /* foreground bank: 0 = d_bank0 (target clips), 1 = d_bank1 (unknown-word clips) */
   int32_t src;      /* row of the foreground clip in that bank */
-  int32_t shift;    /* out[t] = fg[t - shift], zero-filled (positive = delay) */
+  int32_t shift;    /* out[t] = fg[t - shift], zero-filled (positive = delay); |shift| >= n_samples yields zeros */
   int32_t bg_idx;   /* background track */
   int32_t bg_off;   /* first sample of the n_samples-long background slice */
   float bg_vol;
   int32_t reserved;
 } mkws_augment_item;
 
-/* d_bank0 [n0, n_samples], d_bank1 [n1, n_samples] (may be NULL), d_bg [tracks, bg_stride] float32;
- * d_items [B]; d_out [B, n_samples]. */
+/* d_bank0 [n0, n_samples], d_bank1 [n1, n_samples] (may be NULL when no item names bank 1), d_bg [tracks, bg_stride] float32;
+ * d_items [B]; d_out [B, n_samples].  d_bg may be NULL (with any bg_stride) only if EVERY item is mode 0: a mode 1 or mode 2 item
+ * reads its slice unconditionally.  The kernel checks nothing an item says: `src` must be a row of its bank, and
+ * [bg_off, bg_off + n_samples) must lie inside track `bg_idx` -- the slice may end on the track's last sample, and neither the rows
+ * nor bg_stride need any alignment beyond that of a float.  Nothing outside d_out [B, n_samples] is written.  B == 0 returns MKWS_OK
+ * with nothing launched; MKWS_ERR_INVALID_ARG for B < 0, n_samples <= 0 and a NULL d_bank0, d_items or d_out.
+ * (The cases: tests/util_assembly_cases.py.) */
 int mkws_augment_batch(const float* d_bank0, const float* d_bank1, const float* d_bg, int64_t bg_stride,
                        const mkws_augment_item* d_items, int B, int n_samples, float* d_out, void* stream);
 /* SpecAugment masking in place on d_spec [B, frames, channels]; d_masks int32 [B,8] =
- * {freq0 start, size, freq1 start, size, time0 start, size, time1 start, size}; size 0 = no mask. */
+ * {freq0 start, size, freq1 start, size, time0 start, size, time1 start, size}: element (frame f, channel c) is set to zero iff
+ * some freq mask has start <= c < start + size or some time mask has start <= f < start + size.  The masks are intersected with the
+ * image: a negative start and a mask that hangs over the last channel / frame are allowed, size <= 0 = no mask; every other element
+ * keeps its bits.  MKWS_ERR_INVALID_ARG for B < 0, frames <= 0, channels <= 0 and (B > 0) NULL buffers. */
 int mkws_specaug_apply(float* d_spec, const int32_t* d_masks, int B, int frames, int channels, void* stream);
 /* The same with ANY number of masks per axis (the reference loops frequency_n / time_n times for whatever SpecAugParams says,
- * input_data.py:317-362): d_masks int32 [B, 2*(n_freq + n_time)] = n_freq x {channel start, size} then n_time x {frame start, size}. */
+ * input_data.py:317-362): d_masks int32 [B, 2*(n_freq + n_time)] = n_freq x {channel start, size} then n_time x {frame start, size};
+ * the same mask semantics, and (2, 2) is mkws_specaug_apply's table byte for byte.  Negative counts are MKWS_ERR_INVALID_ARG;
+ * n_freq + n_time == 0 returns MKWS_OK with nothing launched (d_masks may then be NULL). */
 int mkws_specaug_apply_n(float* d_spec, const int32_t* d_masks, int n_freq, int n_time, int B, int frames, int channels, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -83,7 +83,7 @@ def test_full_finetune_step_512_matches_oracle_chain(data):
         assert spec.shape == (B, 49, 40, 1)
         audio, masks, lab = ds.last_audio.cpu().numpy(), ds.last_masks, labels.cpu().numpy()
         assert masks is not None and masks.any()
-        # frontend + SpecAugment: bit-exact against the C oracle + host masking (value-level check of mkws_specaug_apply)
+        # frontend + SpecAugment: bit-exact against the C oracle + host masking (the dataset's masking call is mkws_specaug_apply_n; the [B, 8] form has its own tests in test_assembly_kernels_gpu.py)
         ref_spec = _apply_masks(fo.run_batch_f32(audio), masks)
         assert np.array_equal(spec[..., 0].cpu().numpy(), ref_spec)
         # embedding: north_star tolerance 1e-3 relative (asserted tighter)
