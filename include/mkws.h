@@ -368,6 +368,24 @@ int mkws_head_group_size(const mkws_head_group* g);
  * `stream`, allocates nothing, never synchronises: capturable like every other call. */
 int mkws_head_group_forward_segments(mkws_head_group* g, const float* d_emb, int B, int64_t row_base, const int32_t* d_seg_offsets,
                                      const int32_t* d_seg_head, int n_seg, float* d_probs, int32_t* d_invalid, void* stream);
+/* Serving with the group as a head table and a ROUTE table in device memory: route r = (d_route_slot[r], d_route_head[r]) says "this slot
+ * listens for this keyword".  d_emb float32 [B, in] holds rows_per_slot rows per slot, slot s in rows s * rows_per_slot .. (the batch
+ * mkws_frontend_live_push_many_f32 filled, embedded); route r's rows_per_slot output rows, rows r * rows_per_slot .. of d_probs float32
+ * [n_routes, rows_per_slot, classes], are the outputs of member d_route_head[r] on its slot's rows -- work per route, not per
+ * (slot, head), and what mkws_detect_live_step_routes reads.  Both tables are int32 [n_routes] and are read by the kernel, so they may be
+ * rewritten between calls (or between replays of a captured call) without touching the launch.
+ * An output row is, bit for bit, what mkws_head_forward of that head writes for that embedding row: the kernel is that call's -- the K
+ * walk in ascending chunks of 16, the four-wave K split joined in wave order, the epilogue -- and only the mapping of a workgroup to
+ * (route, 16-row tile of the slot's rows) and an output row base different from the input row base are new.
+ * slot < 0 is a disabled route: nothing of it is read (not its head index either) or written.  A route whose slot is >= n_slots, whose
+ * head index is outside [0, mkws_head_group_size) or whose rows would pass B is invalid: it gets NaN in all its rows (the detector
+ * treats a NaN score as no event) and is counted once in *d_invalid (int32 [1], set by every call that launches, by a plain store of the
+ * kernel's: the call adds no memset and no atomic to a captured chain); the bad index is never dereferenced.
+ * MKWS_ERR_UNSUPPORTED unless in % 16 == 0 and hidden <= 32 (the matrix-core path only); MKWS_ERR_INVALID_ARG for NULL pointers and
+ * negative sizes; n_routes == 0 or rows_per_slot == 0 returns MKWS_OK with nothing launched and nothing written.  One launch, one
+ * workgroup per (route, tile), asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_head_group_forward_routes(mkws_head_group* g, const float* d_emb, int B, int rows_per_slot, int n_slots, const int32_t* d_route_slot,
+                                   const int32_t* d_route_head, int n_routes, float* d_probs, int32_t* d_invalid, void* stream);
 /* mkws_head_loss_grad of head h on the B rows at d_emb + h * emb_stride (stride in floats) with the labels at
  * d_labels + h * label_stride (in int32s), for every h; B at most the smallest max_batch of the group.
  * d_stats (optional, may be NULL): float32 [n_heads][2] = {sum of per-row loss, number of correct rows} of each head; the same
@@ -452,6 +470,24 @@ int mkws_detect_live_step_many(void* d_states, size_t state_stride_bytes, int n_
                                int max_new, int n_heads, int classes, int target_id, const double* d_thresholds, int n_thr,
                                double average_window_duration_ms, double suppression_ms, int minimum_count, int fired_only, int history,
                                mkws_detect_event* d_events, int32_t* d_counts, double* d_scores, void* stream);
+
+/* mkws_detect_live_step_many with "stream" replaced by "route", one head per route: n_routes live detectors, each listening to one slot
+ * with thresholds of its own, stepped in one launch.  Route r's state block is d_states + r * state_stride_bytes, exactly the block
+ * mkws_detect_live_step takes for n_heads = 1; its probability rows are r * max_new .. of d_probs [n_routes * max_new, classes] (what
+ * mkws_head_group_forward_routes writes); its meta row is row d_route_slot[r] of d_meta [n_slots, 2 + max_new] -- the SLOT's row, as
+ * mkws_frontend_live_push_many_f32 writes it, shared by the routes of that slot; its thresholds are row r of d_thresholds double
+ * [n_routes, n_thr].  d_events [n_routes, n_thr, max_new], d_counts int32 [n_routes, n_thr], optional d_scores [n_routes, max_new].
+ * Specification, byte for byte: route r is mkws_detect_live_step(n_heads = 1) on its own block, its own probability rows, its slot's
+ * meta row and its own threshold row.  A route whose slot is outside [0, n_slots) (d_route_slot int32 [n_routes]; -1 = disabled) leaves
+ * its state untouched, gets zero counts and never has a meta row read; a meta row with count == 0 behaves as in the one-stream call.
+ * The tables are read by the kernel, so they may be rewritten between calls (or replays of a captured call).
+ * Refusals and limits as mkws_detect_live_step_many, and a NULL d_route_slot or n_slots < 0; n_routes == 0 returns MKWS_OK with nothing
+ * launched.  One launch for any n_routes, asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_detect_live_step_routes(void* d_states, size_t state_stride_bytes, int n_routes, const int32_t* d_route_slot, int n_slots,
+                                 const float* d_probs, const int64_t* d_meta, int max_new, int classes, int target_id,
+                                 const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+                                 int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
+                                 double* d_scores, void* stream);
 
 /* Scoring against ground truth: tpr_fpr's counts (multilingual_kws/embedding/tpr_fpr.py:72-107) for every (head, threshold) lane in
  * one launch, on what mkws_detect_stream(..., fired_only = 1, ...) left on the same stream: d_events [n_heads, n_thr, event_cap] and

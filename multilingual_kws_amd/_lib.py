@@ -70,6 +70,7 @@ SYMBOLS = [
     ("mkws_detect_live_state_bytes", _SZ, [_I, _I, _I]),
     ("mkws_detect_live_step", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),
     ("mkws_detect_live_step_many", _I, [_P, _SZ, _I, _P, _P, _I, _I, _I, _I, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),
+    ("mkws_detect_live_step_routes", _I, [_P, _SZ, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P]),
     ("mkws_detect_score", _I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, ctypes.c_double, _P, _P]),
     ("mkws_detect_segments", _I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
     ("mkws_detect_score_segments", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_double, _P, _P]),
@@ -99,6 +100,7 @@ SYMBOLS = [
     ("mkws_head_group_destroy", None, [_P]),
     ("mkws_head_group_size", _I, [_P]),
     ("mkws_head_group_forward_segments", _I, [_P, _P, _I, ctypes.c_int64, _P, _P, _I, _P, _P, _P]),
+    ("mkws_head_group_forward_routes", _I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     ("mkws_head_group_loss_grad", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _I, _P, _P]),
     ("mkws_head_group_adam_step", _I, [_P, _F, _F, _F, _F, _I, _F, _P]),
     # training operators (backprop_into_embedding)

@@ -172,6 +172,9 @@ __global__ __launch_bounds__(kDetectThreads) void detect_kernel(DetectArgs a) {
 // state + s * state_stride and a head sits inside it where it sits in a one-stream block; its meta row is meta + s * (2 + max_new), its
 // probability rows are s * max_new .. of every head's plane of n_streams * max_new rows, its events / counts / scores the s-th
 // [n_heads, ...] slab.  The one-stream call is n_streams = 1.
+// Routes (mkws_detect_live_step_routes, ROUTED): n_heads = 1 and a "stream" is a route; everything above holds with s = the route, but
+// its meta row is that of its SLOT (route_slot[s], one frontend stream shared by the routes listening to it) and its thresholds are row s
+// of thr.  A route whose slot is outside [0, n_slots) writes zero counts and returns before it reads anything else.
 constexpr int kLiveMaxNew = MKWS_DETECT_LIVE_MAX_NEW;     // windows per step: 30 KB of LDS with the longest history
 
 struct LiveEntry { int64_t time; double prob; };
@@ -190,10 +193,13 @@ struct LiveArgs {
   double avg_ms;
   int64_t suppression;
   int max_new, classes, target, n_thr, min_count, fired_only, never, history;
+  const int32_t* route_slot;   // ROUTED only: [n_streams]
+  int n_slots;
 };
 
 __host__ __device__ inline size_t live_head_bytes(int n_thr, int history) { return 16 + (size_t)history * sizeof(LiveEntry) + (size_t)n_thr * sizeof(LiveLane); }
 
+template <bool ROUTED>
 __global__ __launch_bounds__(kDetectThreads) void detect_live_kernel(LiveArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char live_smem[];
   const int line = a.history + a.max_new;
@@ -204,13 +210,22 @@ __global__ __launch_bounds__(kDetectThreads) void detect_live_kernel(LiveArgs a)
   const int tid = threadIdx.x;
   const int s = blockIdx.x / a.n_heads, head = blockIdx.x - s * a.n_heads;
   unsigned char* hs = a.state + (size_t)s * a.state_stride + head * live_head_bytes(a.n_thr, a.history);
-  const int64_t* meta = a.meta + (size_t)s * (2 + a.max_new);
+  const bool walker = tid < a.n_thr;
+  const size_t lane_row = (size_t)blockIdx.x * a.n_thr + (walker ? tid : 0);
+  int meta_row = s;
+  if (ROUTED) {
+    meta_row = a.route_slot[s];
+    if (meta_row < 0 || meta_row >= a.n_slots) {                       // a disabled route: nothing of it is read, its state stays
+      if (walker) a.counts[lane_row] = 0;
+      return;
+    }
+  }
+  const int64_t* meta = a.meta + (size_t)meta_row * (2 + a.max_new);
+  const double* thr = ROUTED ? a.thr + (size_t)s * a.n_thr : a.thr;
   const float* probs = a.probs + ((size_t)head * a.n_streams + s) * a.max_new * a.classes + a.target;   // row 0 of this stream in the head's plane
   int64_t* p_seen = reinterpret_cast<int64_t*>(hs);
   LiveEntry* ring = reinterpret_cast<LiveEntry*>(hs + 16);
   LiveLane* lanes = reinterpret_cast<LiveLane*>(hs + 16 + (size_t)a.history * sizeof(LiveEntry));
-  const bool walker = tid < a.n_thr;
-  const size_t lane_row = (size_t)blockIdx.x * a.n_thr + (walker ? tid : 0);
   const int count = (int)min(max(meta[0], (int64_t)0), (int64_t)a.max_new);
   if (count == 0) {                                                    // an empty push changes nothing
     if (walker) a.counts[lane_row] = 0;
@@ -262,7 +277,7 @@ __global__ __launch_bounds__(kDetectThreads) void detect_live_kernel(LiveArgs a)
   __syncthreads();
   if (walker) {
     const LiveLane was = lanes[tid];
-    const LaneRule rule = {a.thr[tid], a.suppression, !a.never, a.fired_only != 0, a.max_new};
+    const LaneRule rule = {thr[tid], a.suppression, !a.never, a.fired_only != 0, a.max_new};
     LaneState lane = {was.prev_kw != 0, was.deadline, 0};
     mkws_detect_event* __restrict__ ev = a.events + lane_row * (size_t)a.max_new;
     for (int i = 0; i < count; ++i) lane_step(lane, rule, s_score[i], s_time[nh + i], s_eval[i] != 0, i, ev, nullptr);
@@ -528,8 +543,9 @@ extern "C" size_t mkws_detect_live_state_bytes(int n_heads, int n_thr, int histo
   return (size_t)n_heads * live_head_bytes(n_thr, history);
 }
 
-static int live_step_many(void* d_state, size_t stride, int n_streams, const float* d_probs, const int64_t* d_meta, int max_new, int n_heads, int classes,
-                          int target_id, const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+// route_slot NULL: the streams form; else n_heads = 1, n_streams routes over n_slots meta rows
+static int live_step_many(void* d_state, size_t stride, int n_streams, const int32_t* route_slot, int n_slots, const float* d_probs,
+                          const int64_t* d_meta, int max_new, int n_heads, int classes, int target_id, const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
                           int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts, double* d_scores,
                           void* stream) {
   if (int rc = check_detect_args(n_heads, max_new, 0, n_thr, classes, target_id, average_window_duration_ms, suppression_ms,
@@ -570,9 +586,12 @@ static int live_step_many(void* d_state, size_t stride, int n_streams, const flo
   a.min_count = minimum_count;
   a.fired_only = fired_only != 0;
   a.history = history;
+  a.route_slot = route_slot;
+  a.n_slots = n_slots;
   const int threads = (n_thr + 63) / 64 * 64;
   const size_t lds = (size_t)(history + max_new) * 16 + (size_t)max_new * 8 + (size_t)((max_new + 15) & ~15);
-  hipLaunchKernelGGL(detect_live_kernel, dim3(n_streams * n_heads), dim3(threads), lds, static_cast<hipStream_t>(stream), a);
+  if (route_slot) hipLaunchKernelGGL(detect_live_kernel<true>, dim3(n_streams * n_heads), dim3(threads), lds, static_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL(detect_live_kernel<false>, dim3(n_streams * n_heads), dim3(threads), lds, static_cast<hipStream_t>(stream), a);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }
@@ -581,7 +600,7 @@ extern "C" int mkws_detect_live_step(void* d_state, const float* d_probs, const 
                                      const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
                                      int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
                                      double* d_scores, void* stream) {
-  return live_step_many(d_state, 0, 1, d_probs, d_meta, max_new, n_heads, classes, target_id, d_thresholds, n_thr, average_window_duration_ms,
+  return live_step_many(d_state, 0, 1, nullptr, 0, d_probs, d_meta, max_new, n_heads, classes, target_id, d_thresholds, n_thr, average_window_duration_ms,
                         suppression_ms, minimum_count, fired_only, history, d_events, d_counts, d_scores, stream);
 }
 
@@ -590,6 +609,18 @@ extern "C" int mkws_detect_live_step_many(void* d_states, size_t state_stride_by
                                           double average_window_duration_ms, double suppression_ms, int minimum_count, int fired_only,
                                           int history, mkws_detect_event* d_events, int32_t* d_counts, double* d_scores, void* stream) {
   if (state_stride_bytes == 0) return fail(MKWS_ERR_INVALID_ARG, "state stride of 0 bytes");
-  return live_step_many(d_states, state_stride_bytes, n_streams, d_probs, d_meta, max_new, n_heads, classes, target_id, d_thresholds, n_thr,
+  return live_step_many(d_states, state_stride_bytes, n_streams, nullptr, 0, d_probs, d_meta, max_new, n_heads, classes, target_id, d_thresholds, n_thr,
+                        average_window_duration_ms, suppression_ms, minimum_count, fired_only, history, d_events, d_counts, d_scores, stream);
+}
+
+extern "C" int mkws_detect_live_step_routes(void* d_states, size_t state_stride_bytes, int n_routes, const int32_t* d_route_slot, int n_slots,
+                                            const float* d_probs, const int64_t* d_meta, int max_new, int classes, int target_id,
+                                            const double* d_thresholds, int n_thr, double average_window_duration_ms, double suppression_ms,
+                                            int minimum_count, int fired_only, int history, mkws_detect_event* d_events, int32_t* d_counts,
+                                            double* d_scores, void* stream) {
+  if (state_stride_bytes == 0) return fail(MKWS_ERR_INVALID_ARG, "state stride of 0 bytes");
+  if (!d_route_slot) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_slots < 0) return fail(MKWS_ERR_INVALID_ARG, "n_slots = %d", n_slots);
+  return live_step_many(d_states, state_stride_bytes, n_routes, d_route_slot, n_slots, d_probs, d_meta, max_new, 1, classes, target_id, d_thresholds, n_thr,
                         average_window_duration_ms, suppression_ms, minimum_count, fired_only, history, d_events, d_counts, d_scores, stream);
 }

@@ -49,10 +49,12 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // The tile's work as a function of its own: the 16 rows from row0 under ONE head's parameters, stores masked to rows [store_lo, store_hi)
 // (the whole-batch kernels pass [0, B); the segmented kernel the rows of the tile that belong to the segment it is finishing).  Waves
-// 1..3 return after the barrier.
+// 1..3 return after the barrier.  out_shift: input row `row` is stored as output row `row + out_shift` (the routed kernel's output row base
+// differs from its input row base; 0 everywhere else).
 template <int NT>
 __device__ __forceinline__ void head_fwd_tile(const HeadDims& d, const float* __restrict__ params, const float* __restrict__ x, int B,
-                                              float* __restrict__ probs, int row0, int store_lo, int store_hi, float (&s_part)[3][NT][64][4]) {
+                                              float* __restrict__ probs, int row0, int store_lo, int store_hi, float (&s_part)[3][NT][64][4],
+                                              long long out_shift = 0) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c = lane & 15;
@@ -176,7 +178,7 @@ __device__ __forceinline__ void head_fwd_tile(const HeadDims& d, const float* __
   if (g == 0 && row >= store_lo && row < store_hi) {
 #pragma unroll
     for (int k = 0; k < kMaxClasses; ++k)
-      if (k < d.cls) probs[(size_t)row * d.cls + k] = e[k] * inv;
+      if (k < d.cls) probs[(size_t)(row + out_shift) * d.cls + k] = e[k] * inv;
   }
 }
 
@@ -234,6 +236,55 @@ __global__ __launch_bounds__(256) void head_fwd_segments_kernel(HeadDims d, cons
     const int n_bad = __popcll(__ballot(bad));
     if (threadIdx.x == 0 && n_bad) atomicAdd(invalid, n_bad);  // an integer count
   }
+}
+
+// Routed forward (mkws_head_group_forward_routes): route r = (slot, head) is the rows_per_slot embedding rows of its slot under member
+// `head` of the group's table, written to rows r * rows_per_slot .. of probs.  One workgroup per (route, 16-row tile of the slot's rows):
+// blockIdx.x = route * tiles + tile.  The tile is head_fwd_tile from the slot's input row, stores masked to the slot's rows and
+// shifted to the route's output rows; lanes past the slot's rows read the rows behind them (clamped at B - 1) and store nothing.  A
+// disabled route (slot < 0) returns before it reads or writes anything else; an invalid one gets NaN rows, and neither a bad slot nor a
+// bad head index is used as an index.  The count of invalid routes is workgroup 0's: it walks the two tables once and stores the sum, so
+// every launch sets *invalid, with a plain store and without a memset node or an atomic in a captured chain.  (Everything that steers
+// this is uniform over the workgroup.)
+__device__ __forceinline__ bool route_is_invalid(int slot, int head, int n_slots, int n_heads, int rows_per_slot, int B) {
+  return slot >= n_slots || head < 0 || head >= n_heads || ((long long)slot + 1) * rows_per_slot > B;
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void head_fwd_routes_kernel(HeadDims d, const HeadSlot* __restrict__ slots, int n_heads, const float* __restrict__ x,
+                                                              int B, int rows_per_slot, int n_slots, const int32_t* __restrict__ route_slot,
+                                                              const int32_t* __restrict__ route_head, int n_routes, float* __restrict__ probs,
+                                                              int32_t* __restrict__ invalid) {
+  __shared__ float s_part[3][NT][64][4];
+  __shared__ int s_bad[4];
+  if (blockIdx.x == 0) {
+    int bad = 0;
+    for (int i = threadIdx.x; i < n_routes; i += 256) {
+      const int sl = route_slot[i];
+      if (sl >= 0) bad += route_is_invalid(sl, route_head[i], n_slots, n_heads, rows_per_slot, B) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    if ((threadIdx.x & 63) == 0) s_bad[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) *invalid = s_bad[0] + s_bad[1] + s_bad[2] + s_bad[3];
+  }
+  const int tiles = (rows_per_slot + 15) / 16;
+  const int r = blockIdx.x / tiles;
+  const int slot = route_slot[r];
+  if (slot < 0) return;
+  const int h = route_head[r];
+  const int t0 = (blockIdx.x - r * tiles) * 16;                        // first row of the tile inside the slot
+  const long long out0 = (long long)r * rows_per_slot;                 // the route's first output row
+  if (route_is_invalid(slot, h, n_slots, n_heads, rows_per_slot, B)) {
+    const int row = t0 + (int)threadIdx.x;
+    if (threadIdx.x < 16 && row < rows_per_slot) {
+      for (int k = 0; k < d.cls; ++k) probs[(size_t)(out0 + row) * d.cls + k] = __builtin_nanf("");
+    }
+    return;
+  }
+  const int in0 = slot * rows_per_slot;                                // the slot's first input row (<= B - rows_per_slot: fits an int)
+  head_fwd_tile<NT>(d, slots[h].params, x, B, probs, in0 + t0, in0, in0 + rows_per_slot, s_part, out0 - in0);
 }
 
 // R rows per wave: every W1 value a lane loads is used for R rows (the 50-head serving launch re-read each head's 73 KB of W1 once
@@ -764,6 +815,28 @@ int mkws_head_group_forward_segments(mkws_head_group* g, const float* d_emb, int
   else
     hipLaunchKernelGGL((head_fwd_segments_kernel<2>), dim3((B + 15) / 16), dim3(256), 0, s, g->d, g->d_slots, g->n, d_emb, B, (long long)row_base,
                        d_seg_offsets, d_seg_head, n_seg, d_probs, d_invalid);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+int mkws_head_group_forward_routes(mkws_head_group* g, const float* d_emb, int B, int rows_per_slot, int n_slots, const int32_t* d_route_slot,
+                                   const int32_t* d_route_head, int n_routes, float* d_probs, int32_t* d_invalid, void* stream) {
+  if (!g) return fail(MKWS_ERR_INVALID_ARG, "head group handle is NULL");
+  if (B < 0 || rows_per_slot < 0 || n_slots < 0 || n_routes < 0) return fail(MKWS_ERR_INVALID_ARG, "negative batch, rows per slot, slot or route count");
+  if (g->d.in % 16 != 0 || g->d.hid > 32)
+    return fail(MKWS_ERR_UNSUPPORTED, "the routed forward runs on the matrix cores only: in %% 16 == 0 and hidden <= 32 (got %d, %d)", g->d.in, g->d.hid);
+  if (n_routes == 0 || rows_per_slot == 0) return MKWS_OK;
+  if (!d_emb || !d_route_slot || !d_route_head || !d_probs || !d_invalid) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  const int tiles = (rows_per_slot - 1) / 16 + 1;
+  if ((int64_t)n_routes * rows_per_slot > INT32_MAX || (int64_t)n_routes * tiles > INT32_MAX) return fail(MKWS_ERR_UNSUPPORTED, "%d routes of %d rows", n_routes, rows_per_slot);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(n_routes * tiles);
+  if (g->d.hid <= 16)
+    hipLaunchKernelGGL((head_fwd_routes_kernel<1>), grid, dim3(256), 0, s, g->d, g->d_slots, g->n, d_emb, B, rows_per_slot, n_slots, d_route_slot,
+                       d_route_head, n_routes, d_probs, d_invalid);
+  else
+    hipLaunchKernelGGL((head_fwd_routes_kernel<2>), grid, dim3(256), 0, s, g->d, g->d_slots, g->n, d_emb, B, rows_per_slot, n_slots, d_route_slot,
+                       d_route_head, n_routes, d_probs, d_invalid);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }

@@ -463,6 +463,84 @@ def detect_live_step_many(states, probs, meta, d_thresholds, average_window_dura
     return out
 
 
+# Routes (mkws_detect_live_step_routes): R detectors of one head each, route r listening to slot route_slot[r] with its own threshold row.
+# The host specification is one LiveDetectorHost(1, thresholds of the route) per route, fed its slot's pushes.
+
+def live_detector_state_routes(n_routes, n_thr, history, device=None):
+    """Zero-filled state blocks of `n_routes` fresh routes: an int64 CUDA tensor [n_routes, words]; row r viewed flat is the one-stream state
+    of one head (detect_live_step takes it, .zero_() resets that route alone)."""
+    return live_detector_state_many(n_routes, 1, n_thr, history, device=device)
+
+
+def live_out_words_routes(n_routes, n_thr, max_new):
+    """int64 words of detect_live_step_routes' output buffer: the many-stream layout with streams = n_routes, n_heads = 1."""
+    return live_out_words_many(n_routes, 1, n_thr, max_new)
+
+
+def live_unpack_routes(words, n_routes, n_thr, max_new):
+    """The host copy (numpy int64) of that buffer -> (counts int32 [R, T], events EVENT_DTYPE [R, T, max_new])."""
+    counts, events = live_unpack_many(words, n_routes, 1, n_thr, max_new)
+    return counts[:, 0], events[:, 0]
+
+
+def check_live_routes(states, probs, meta, route_slot, thresholds, out=None, scores=None):
+    """What detect_live_step_routes refuses, decided before any device call -> (R, n_slots, max_new, classes, T).  states int64
+    [R, words] with contiguous, non-overlapping rows; probs contiguous float32 [R * max_new, classes] (or [R, max_new, classes]); meta
+    contiguous int64 [n_slots, 2 + max_new]; route_slot contiguous int32 [R]; thresholds contiguous float64 [R, T]; out contiguous int64
+    of live_out_words_routes words; scores contiguous float64 of R * max_new values.  ValueError otherwise."""
+    import torch
+    from .frontend import check_live_many
+    if not torch.is_tensor(meta) or meta.dim() != 2 or meta.shape[1] < 2 or meta.dtype != torch.int64 or not meta.is_contiguous():
+        raise ValueError("meta must be a contiguous int64 tensor [slots, 2 + max_new]")
+    n_slots, max_new = int(meta.shape[0]), int(meta.shape[1]) - 2
+    if not torch.is_tensor(route_slot) or route_slot.dim() != 1 or route_slot.dtype != torch.int32 or not route_slot.is_contiguous():
+        raise ValueError("route_slot must be a contiguous int32 vector [routes]")
+    check_live_many(states, (int(states.shape[0]) if states.dim() == 2 else 0, 1), 1, "states")      # (the rules of the state tensor itself)
+    if int(route_slot.shape[0]) != int(states.shape[0]):
+        raise ValueError(f"route_slot has {int(route_slot.shape[0])} entries for the {int(states.shape[0])} rows of the state tensor: one per route")
+    R = int(states.shape[0])
+    if not torch.is_tensor(thresholds) or thresholds.dim() != 2 or int(thresholds.shape[0]) != R or thresholds.shape[1] < 1 or \
+            thresholds.dtype != torch.float64 or not thresholds.is_contiguous():
+        raise ValueError(f"thresholds must be a contiguous float64 tensor [{R}, T]: one row per route")
+    T = int(thresholds.shape[1])
+    if not torch.is_tensor(probs) or probs.dim() not in (2, 3) or probs.dtype != torch.float32 or not probs.is_contiguous() or \
+            int(probs.numel()) != R * max_new * int(probs.shape[-1]) or (probs.dim() == 3 and int(probs.shape[0]) != R):
+        raise ValueError(f"probs must be a contiguous float32 tensor [{R} x {max_new}, classes]: max_new rows per route")
+    C = int(probs.shape[-1])
+    words = live_out_words_routes(R, T, max_new)
+    if out is not None and (out.numel() != words or out.dtype != torch.int64 or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int64 tensor of {words} words (live_out_words_routes)")
+    if scores is not None and (scores.numel() != R * max_new or scores.dtype != torch.float64 or not scores.is_contiguous()):
+        raise ValueError(f"scores must be a contiguous float64 tensor [{R}, {max_new}]")
+    return R, n_slots, max_new, C, T
+
+
+def detect_live_step_routes(states, probs, meta, route_slot, d_thresholds, average_window_duration_ms, suppression_ms, minimum_count, history,
+                            target_id=2, fired_only=False, out=None, scores=None):
+    """One step of R routed live detectors.  states: live_detector_state_routes(R, T, history); probs CUDA float32 [R * max_new, C] (or
+    [R, max_new, C]), route r's windows in rows r * max_new .. (what HeadGroup.forward_routes writes); meta CUDA int64 [n_slots, 2 +
+    max_new] as Frontend.live_push_many writes it; route_slot CUDA int32 [R], the slot whose meta row a route follows (outside
+    [0, n_slots): the route is disabled, its state untouched, its counts zero); d_thresholds CUDA float64 [R, T], a row per route.
+    -> out, a CUDA int64 tensor of live_out_words_routes(R, T, max_new) words (live_unpack_routes, or live_unpack_many with streams = R
+    and n_heads = 1, reads its host copy).  scores: optional CUDA float64 [R, max_new].  For every route this is detect_live_step with one
+    head on its own state row, byte for byte.  Asynchronous, allocation-free when `out` is passed in, one launch for any R: capturable."""
+    import torch
+    R, n_slots, max_new, C, T = check_live_routes(states, probs, meta, route_slot, d_thresholds, out, scores)
+    for name, t in (("probs", probs), ("meta", meta), ("route_slot", route_slot), ("d_thresholds", d_thresholds), ("states", states)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a CUDA tensor")
+    if out is None:
+        out = torch.zeros(live_out_words_routes(R, T, max_new), dtype=torch.int64, device=probs.device)
+    base = out.data_ptr()
+    with torch.cuda.device(probs.device):
+        _lib.check(_lib.lib().mkws_detect_live_step_routes(
+            states.data_ptr(), 8 * int(states.stride(0)), R, route_slot.data_ptr(), n_slots, probs.data_ptr(), meta.data_ptr(), max_new, C,
+            int(target_id), d_thresholds.data_ptr(), T, float(average_window_duration_ms), float(suppression_ms), int(minimum_count),
+            int(bool(fired_only)), int(history), base + 8 * ((R * T + 1) // 2), base, scores.data_ptr() if scores is not None else None,
+            _lib.current_stream_ptr()))
+    return out
+
+
 class LiveDetectorHost:
     """The host restatement of the live detector: K x T SingleTargetRecognizeCommands (one per keyword head and threshold) fed push by
     push.  step() returns what one mkws_detect_live_step leaves behind, and is the specification it is held to bit for bit."""

@@ -471,7 +471,6 @@ def default_live_flags(thresholds):
 def _live_setup(self, thresholds, flags, model_settings, keywords, fired_only):
     """What LiveSession and LiveSessionGroup derive from their arguments once embedding, heads and hops are set: thresholds, flags,
     keywords, the stream's geometry, the detector's history and the frontend handle.  -> the model settings."""
-    from ..detector import live_history
     self.thresholds = [float(t) for t in thresholds]
     if not self.thresholds:
         raise ValueError("at least one threshold")
@@ -482,6 +481,13 @@ def _live_setup(self, thresholds, flags, model_settings, keywords, fired_only):
     self.keywords = list(keywords)
     if len(self.keywords) != N:
         raise ValueError(f"{len(self.keywords)} keywords for {N} heads")
+    return _live_geometry(self, model_settings, fired_only)
+
+
+def _live_geometry(self, model_settings, fired_only):
+    """The part of _live_setup that does not depend on who owns thresholds and keywords (LiveRoutedGroup: the routes do): from
+    self.flags, self.heads and self.hops the stream's geometry, the detector's history and the frontend handle.  -> the model settings."""
+    from ..detector import live_history
     if self.heads[0].classes != len(self.flags.labels()):
         raise ValueError("The results for recognition should contain {} elements, but there are {} produced".format(
             len(self.flags.labels()), self.heads[0].classes))
@@ -651,7 +657,8 @@ class LiveSessionGroup:
         frontend push of all slots (2 launches) -> mkws_embed_forward at batch streams * hops_per_push -> mkws_heads_forward
         -> detector step of all slots (1 launch),
     replayed as one hipGraph: per tick one pinned upload (the [S, push] audio and the active mask), one replay, one download of the packed
-    counts and events, one synchronise.  The slots share the heads, thresholds and flags; their states are the rows of two device
+    counts and events, one synchronise.  The slots share the heads, thresholds and flags (LiveRoutedGroup below: keywords and thresholds per
+    slot); their states are the rows of two device
     tensors (fstates, dstates: a row is a one-stream state block), and a slot that is not active in a tick is not touched by it.
 
     What is promised, piece by piece:
@@ -680,22 +687,34 @@ class LiveSessionGroup:
                              f"embedding handle's max_batch={embedding.max_batch}")
         ms = _live_setup(self, thresholds, flags, model_settings, keywords, fired_only)
         self.scheduler = LiveGroupScheduler(self.streams, self.push_samples)
-        dev = embedding.device
-        S, N, T, h, P = self.streams, len(self.heads), len(self.thresholds), self.hops, self.push_samples
-        with torch.cuda.device(dev):
-            # the static graph input, ONE buffer so that a tick is one upload: the NEW samples [S, push] (float32), then the active mask [S] (int32)
-            self.d_in = torch.zeros(S * P + S, dtype=torch.float32, device=dev)
-            self.audio, self.active = self.d_in[:S * P].view(S, P), self.d_in[S * P:].view(torch.int32)
-            self.fstates = self.fe.live_state_many(S, self.window_samples, self.hop_samples, h, device=dev)
-            self.dstates = live_detector_state_many(S, N, T, self.history, device=dev)
-            self.spec = torch.zeros((S * h, ms["spectrogram_length"], ms["fingerprint_width"]), dtype=torch.float32, device=dev)
-            self.meta = torch.zeros((S, 2 + h), dtype=torch.int64, device=dev)
-            self.d_thr = torch.tensor(self.thresholds, dtype=torch.float64, device=dev)
-            self.out = torch.zeros(live_out_words_many(S, N, T, h), dtype=torch.int64, device=dev)   # counts and events: the one D2H per tick
-            self.h_in = torch.zeros(S * P + S, dtype=torch.float32).pin_memory()
-            self.h_out = torch.zeros(self.out.numel(), dtype=torch.int64).pin_memory()
-        self.h_audio, self.h_active = self.h_in[:S * P].view(S, P).numpy(), self.h_in[S * P:].view(torch.int32).numpy()
+        S, N, T, h = self.streams, len(self.heads), len(self.thresholds), self.hops
+        with torch.cuda.device(embedding.device):
+            self._slot_buffers(ms)
+            self.dstates = live_detector_state_many(S, N, T, self.history, device=embedding.device)
+            self.d_thr = torch.tensor(self.thresholds, dtype=torch.float64, device=embedding.device)
+            self._out_buffers(live_out_words_many(S, N, T, h))
         self._Head = Head
+        self._start(use_graph)
+
+    def _slot_buffers(self, ms):
+        """The per-slot device buffers of a tick and the pinned mirror of its one upload."""
+        import torch
+        dev, S, h, P = self.embedding.device, self.streams, self.hops, self.push_samples
+        # the static graph input, ONE buffer so that a tick is one upload: the NEW samples [S, push] (float32), then the active mask [S] (int32)
+        self.d_in = torch.zeros(S * P + S, dtype=torch.float32, device=dev)
+        self.audio, self.active = self.d_in[:S * P].view(S, P), self.d_in[S * P:].view(torch.int32)
+        self.fstates = self.fe.live_state_many(S, self.window_samples, self.hop_samples, h, device=dev)
+        self.spec = torch.zeros((S * h, ms["spectrogram_length"], ms["fingerprint_width"]), dtype=torch.float32, device=dev)
+        self.meta = torch.zeros((S, 2 + h), dtype=torch.int64, device=dev)
+        self.h_in = torch.zeros(S * P + S, dtype=torch.float32).pin_memory()
+        self.h_audio, self.h_active = self.h_in[:S * P].view(S, P).numpy(), self.h_in[S * P:].view(torch.int32).numpy()
+
+    def _out_buffers(self, words):
+        import torch
+        self.out = torch.zeros(words, dtype=torch.int64, device=self.embedding.device)   # counts and events: the one D2H per tick
+        self.h_out = torch.zeros(words, dtype=torch.int64).pin_memory()
+
+    def _start(self, use_graph):
         self.graph = None
         self.recaptures = 0
         self.last_records = {}
@@ -758,16 +777,19 @@ class LiveSessionGroup:
         self.graph = None
         self.probs = self.d_in = self.audio = self.active = self.fstates = self.dstates = self.spec = self.meta = self.out = None
 
-    def _tick(self, active, audio, records):
-        """One tick (LiveGroupScheduler's): appends the records (window, head, threshold index, fired, score) of the events it completed to
-        records[slot]."""
+    def _before_replay(self):
+        """Hook between a tick's upload and its replay, on the tick's stream (LiveRoutedGroup uploads its edited tables here)."""
+
+    def _exchange(self, active, audio):
+        """The device part of one tick (LiveGroupScheduler's): one upload, one replay (or the eager chain), one download into h_out, one
+        synchronise; the host mirrors of the slots' positions advanced.  -> {active slot: index of its first new window}."""
         import torch
-        from ..detector import live_unpack_many
         dev = self.embedding.device
         self.h_audio[:] = audio
         self.h_active[:] = active
         with torch.cuda.device(dev):
             self.d_in.copy_(self.h_in, non_blocking=True)
+            self._before_replay()
             if self.graph is not None:
                 if self.embedding.get_option("exchange_error"):
                     # LiveSession's protocol: the PREVIOUS replay ran a failed exchange (all-NaN probabilities: the detectors scored NaN and
@@ -783,6 +805,12 @@ class LiveSessionGroup:
         first = {s: self.windows_seen(s) for s in on}
         for s in on:
             self.samples_pushed[s] += self.push_samples
+        return first
+
+    def _tick(self, active, audio, records):
+        """One tick: appends the records (window, head, threshold index, fired, score) of the events it completed to records[slot]."""
+        from ..detector import live_unpack_many
+        first = self._exchange(active, audio)
         counts, events = live_unpack_many(self.h_out.numpy(), self.streams, len(self.heads), len(self.thresholds), self.hops)
         if counts.any():
             fresh = {}
@@ -792,6 +820,9 @@ class LiveSessionGroup:
             for s, rec in fresh.items():
                 rec.sort(key=lambda r: r[:3])
                 records.setdefault(s, []).extend(rec)
+
+    def _rows(self, records):
+        return _live_rows(self, records)
 
     def feed(self, chunks):
         """chunks: {slot: samples} or a length-S sequence with None for silent slots; samples are float32 of any length (numpy, CPU or CUDA
@@ -804,7 +835,197 @@ class LiveSessionGroup:
         for active, audio in self.scheduler.feed(dict(fed)):
             self._tick(active, audio, records)
         self.last_records = records
-        return {k: _live_rows(self, rec) for k, rec in records.items()}
+        return {k: self._rows(rec) for k, rec in records.items()}
+
+
+class LiveRouteTable:
+    """The host mirror of a route table: `max_routes` routes over `streams` slots and `n_heads` entries of a head table, `n_thresholds`
+    thresholds each.  route_slot int32 [R] (-1: free), route_head int32 [R], thresholds float64 [R, T] are what the device copies hold
+    after the next upload; .dirty says that they differ from them.  No device work: attach and detach only edit the mirrors."""
+
+    def __init__(self, streams, n_heads, max_routes, n_thresholds, average_window_duration_ms=0):
+        self.streams, self.n_heads, self.max_routes, self.n_thresholds = int(streams), int(n_heads), int(max_routes), int(n_thresholds)
+        if self.streams < 1 or self.n_heads < 1 or self.max_routes < 1 or not 1 <= self.n_thresholds <= 1024:
+            raise ValueError(f"LiveRouteTable({streams}, {n_heads}, {max_routes}, {n_thresholds}): at least one slot, head and route, 1 .. 1024 thresholds")
+        self.avg = average_window_duration_ms
+        self.route_slot = np.full(self.max_routes, -1, np.int32)
+        self.route_head = np.zeros(self.max_routes, np.int32)
+        self.thresholds = np.zeros((self.max_routes, self.n_thresholds), np.float64)
+        self.keywords = [None] * self.max_routes
+        self.dirty = True                                # nothing has been uploaded yet
+
+    def route(self, route):
+        if not 0 <= int(route) < self.max_routes:
+            raise ValueError(f"route {route}: from 0 to {self.max_routes - 1}")
+        return int(route)
+
+    def attach(self, slot, head_index, keyword, thresholds):
+        """-> the route id: the lowest free one.  ValueError for a full table, a slot or head index out of range, and anything but
+        n_thresholds thresholds."""
+        from ..detector import _check_thresholds
+        thr = _check_thresholds(thresholds, self.avg)
+        if thr.size != self.n_thresholds:
+            raise ValueError(f"{thr.size} thresholds for a table of {self.n_thresholds} per route")
+        if not 0 <= int(slot) < self.streams:
+            raise ValueError(f"slot {slot}: from 0 to {self.streams - 1}")
+        if not 0 <= int(head_index) < self.n_heads:
+            raise ValueError(f"head index {head_index}: from 0 to {self.n_heads - 1}")
+        free = np.flatnonzero(self.route_slot < 0)
+        if free.size == 0:
+            raise ValueError(f"the route table is full ({self.max_routes} routes)")
+        r = int(free[0])
+        self.route_slot[r], self.route_head[r], self.thresholds[r], self.keywords[r] = int(slot), int(head_index), thr, str(keyword)
+        self.dirty = True
+        return r
+
+    def detach(self, route):
+        r = self.route(route)
+        if self.route_slot[r] >= 0:
+            self.route_slot[r], self.keywords[r] = -1, None
+            self.dirty = True
+
+    def routes_of(self, slot):
+        return np.flatnonzero(self.route_slot == int(slot)).tolist()
+
+    def words(self):
+        """The three tables as the int64 words of one upload (_lib.pack_words): route_slot | route_head | thresholds."""
+        from .._lib import pack_words
+        return pack_words([self.route_slot, self.route_head, self.thresholds])
+
+
+class LiveRoutedGroup(LiveSessionGroup):
+    """LiveSessionGroup whose slots each spot their own keywords: a ROUTE says "this slot listens for this entry of the head table at
+    these thresholds", and heads and detectors do work per route instead of per (slot, head).  A tick is ONE chain on one stream,
+        frontend push of all slots (2 launches) -> mkws_embed_forward at batch streams * hops_per_push
+        -> mkws_head_group_forward_routes -> mkws_detect_live_step_routes,
+    replayed as one hipGraph: per tick one pinned upload (audio and active mask), one replay, one download of max_routes * n_thresholds
+    counts and their events, one synchronise.  The route table (route_slot, route_head, thresholds) lives in device memory and is read by
+    the kernels: attach() and detach() edit host mirrors and set .table.dirty, the next tick uploads the three small tables before its
+    replay, ordered on the same stream.  Nothing is re-captured: .graph stays the same object and .recaptures stays 0.
+
+    heads: a list of Head objects of equal dimensions, held in one HeadGroup created once; entries no route names are spare.
+    Head.set_params on an entry is how a newly fine-tuned keyword enters the table (the group holds device pointers).
+
+    What is promised, piece by piece:
+      * the frontend and embedding legs are LiveSessionGroup's, unchanged;
+      * a tick's probabilities (.probs [max_routes, h, 3]) are, for every attached route, torch.equal to Head.forward of its head on its
+        slot's rows of embedding.forward(group.spec);
+      * a route's events are byte-equal to detect_on_device over the probability rows it received since attach(), at its slot's window
+        times, with its own thresholds: a route attached in mid-stream starts with a fresh detector;
+      * with every slot routed to every head at the same thresholds, feed() returns LiveSessionGroup's rows, scores bit-equal; within a
+        window the rows are ordered by route id, then threshold."""
+
+    def __init__(self, embedding, heads, streams, max_routes, n_thresholds=1, flags=None, model_settings=None, hops_per_push=1, fired_only=True,
+                 use_graph=True):
+        import torch
+        from ..detector import live_detector_state_routes, live_out_words_routes
+        from ..head import HeadGroup
+        self.embedding, self.heads, self.hops, self.streams = embedding, list(heads), int(hops_per_push), int(streams)
+        if self.streams < 1 or not 1 <= self.hops or self.streams * self.hops > embedding.max_batch:
+            raise ValueError(f"LiveRoutedGroup(streams={streams}, hops_per_push={hops_per_push}): streams * hops_per_push from 1 to the "
+                             f"embedding handle's max_batch={embedding.max_batch}")
+        if not self.heads:
+            raise ValueError("LiveRoutedGroup: at least one head in the table")
+        self.flags = flags if flags is not None else default_live_flags([])
+        self.table = LiveRouteTable(self.streams, len(self.heads), max_routes, n_thresholds, self.flags.average_window_duration_ms)
+        ms = _live_geometry(self, model_settings, fired_only)
+        self.scheduler = LiveGroupScheduler(self.streams, self.push_samples)
+        dev = embedding.device
+        R, T, h = self.table.max_routes, self.table.n_thresholds, self.hops
+        with torch.cuda.device(dev):
+            self.head_group = HeadGroup(self.heads)
+            self._slot_buffers(ms)
+            self.dstates = live_detector_state_routes(R, T, self.history, device=dev)
+            # the route table, ONE buffer so that an edit is one upload: route_slot [R] | route_head [R] (int32) | thresholds [R, T] (float64)
+            words, offsets = self.table.words()
+            self.d_table = torch.zeros(words.size, dtype=torch.int64, device=dev)
+            self.h_table = torch.zeros(words.size, dtype=torch.int64).pin_memory()
+            as_bytes = self.d_table.view(torch.uint8)
+            self.route_slot = as_bytes[offsets[0]:offsets[0] + 4 * R].view(torch.int32)
+            self.route_head = as_bytes[offsets[1]:offsets[1] + 4 * R].view(torch.int32)
+            self.d_thr = as_bytes[offsets[2]:offsets[2] + 8 * R * T].view(torch.float64).view(R, T)
+            self.probs_buf = torch.zeros((R, h, self.heads[0].classes), dtype=torch.float32, device=dev)
+            self.invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._out_buffers(live_out_words_routes(R, T, h))
+            self._before_replay()                        # the empty table: every route disabled
+        self._start(use_graph)
+        torch.cuda.current_stream(dev).synchronize()     # (the pinned mirror of the table is free to be edited)
+
+    def attach(self, slot, head_index, keyword, thresholds):
+        """Slot `slot` listens for entry `head_index` of the head table, reported as `keyword`, at these n_thresholds thresholds -> the
+        route id (the lowest free one).  The route starts with a fresh detector at the next tick.  Host work and one small memset; nothing
+        is re-captured."""
+        r = self.table.attach(slot, head_index, keyword, thresholds)
+        self.dstates[r].zero_()
+        return r
+
+    def detach(self, route):
+        """Disables the route: from the next tick on it is neither computed nor reported."""
+        self.table.detach(route)
+
+    def _before_replay(self):
+        if self.table.dirty:
+            self.h_table.numpy()[:] = self.table.words()[0]
+            self.d_table.copy_(self.h_table, non_blocking=True)
+            # what this tick's events are reported with (the host mirrors may be edited again before the next one)
+            self._live = (self.table.route_slot.copy(), list(self.table.keywords), self.table.thresholds.copy())
+            self.table.dirty = False
+
+    def _chain(self):
+        from ..detector import detect_live_step_routes
+        f = self.flags
+        self.fe.live_push_many(self.fstates, self.audio, self.window_samples, self.hop_samples, self.hops, active=self.active,
+                               spec=self.spec, meta=self.meta)
+        probs, _ = self.head_group.forward_routes(self.embedding.forward(self.spec), self.route_slot, self.route_head, self.hops, self.streams,
+                                                  out=self.probs_buf, invalid=self.invalid)
+        detect_live_step_routes(self.dstates, probs, self.meta, self.route_slot, self.d_thr, f.average_window_duration_ms, f.suppression_ms,
+                                f.minimum_count, self.history, target_id=2, fired_only=self.fired_only, out=self.out)
+        return probs
+
+    def reset(self, slot=None):
+        """LiveSessionGroup.reset; the detector slices zeroed are those of the routes attached to the slot (None: all of them)."""
+        if slot is None:
+            self.fstates.zero_()
+            self.dstates.zero_()
+            self.spec.zero_()
+            self.samples_pushed = [0] * self.streams
+        else:
+            slot = self.scheduler.slot(slot)
+            self.fstates[slot].zero_()
+            for r in self.table.routes_of(slot):
+                self.dstates[r].zero_()
+            self.samples_pushed[slot] = 0
+        self.scheduler.reset(slot)
+        self.last_records = {}
+
+    def close(self):
+        super().close()
+        self.d_table = self.route_slot = self.route_head = self.d_thr = self.probs_buf = self.invalid = None
+        if getattr(self, "head_group", None) is not None:
+            self.head_group.close()
+            self.head_group = None
+
+    def _tick(self, active, audio, records):
+        """One tick: appends the records (window, route, threshold index, fired, score, keyword, threshold) of the events it completed to
+        records[slot]."""
+        from ..detector import live_unpack_many
+        first = self._exchange(active, audio)
+        slots, keywords, thresholds = self._live
+        counts, events = live_unpack_many(self.h_out.numpy(), self.table.max_routes, 1, self.table.n_thresholds, self.hops)
+        if counts.any():
+            fresh = {}
+            for r, _, k in zip(*np.nonzero(counts)):
+                s = int(slots[r])
+                for w, fired, score in events[r, 0, k, :counts[r, 0, k]].tolist():
+                    fresh.setdefault(s, []).append((first[s] + w, int(r), int(k), fired, score, keywords[r], float(thresholds[r, k])))
+            for s, rec in fresh.items():
+                rec.sort(key=lambda x: x[:3])
+                records.setdefault(s, []).extend(rec)
+
+    def _rows(self, records):
+        from ..frontend import live_window_time_ms
+        return [[kw if fired else input_data.SILENCE_LABEL, live_window_time_ms(w, self.hop_samples, self.sample_rate), score, thr]
+                for w, _, _, fired, score, kw, thr in records]
 
 
 def detect(inferences, flags: StreamFlags, threshold, sample_rate=16000, data_samples=None):

@@ -152,6 +152,29 @@ class Head:
             _lib.check(self.L.mkws_head_adam_step(self.h, lr, beta1, beta2, eps, self.step_t, grad_scale, _lib.current_stream_ptr()))
 
 
+def check_forward_routes(in_dim, classes, device, emb, route_slot, route_head, rows_per_slot, n_slots, out=None, invalid=None):
+    """What HeadGroup.forward_routes refuses, decided before any device call: emb a contiguous float32 [B, in_dim], route_slot and
+    route_head contiguous int32 vectors of one length, `out` (if given) a contiguous float32 [n_routes, rows_per_slot, classes], `invalid`
+    (if given) an int32 [1], all on `device`; rows_per_slot and n_slots not negative.  -> (B, n_routes).  ValueError otherwise."""
+    import torch
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.shape[1] != in_dim or emb.dtype != torch.float32 or not emb.is_contiguous() or emb.device != device:
+        raise ValueError(f"HeadGroup.forward_routes takes a contiguous float32 emb [B, {in_dim}] on {device}")
+    for name, t in (("route_slot", route_slot), ("route_head", route_head)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"HeadGroup.forward_routes: {name} must be a contiguous int32 vector on {device}")
+    R = int(route_slot.shape[0])
+    if int(route_head.shape[0]) != R:
+        raise ValueError(f"HeadGroup.forward_routes: {int(route_head.shape[0])} head indices for {R} routes")
+    if int(rows_per_slot) < 0 or int(n_slots) < 0:
+        raise ValueError(f"HeadGroup.forward_routes: rows_per_slot={rows_per_slot}, n_slots={n_slots}")
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (R, int(rows_per_slot), classes) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.device != device):
+        raise ValueError(f"HeadGroup.forward_routes: out must be a contiguous float32 [{R}, {int(rows_per_slot)}, {classes}] on {device}")
+    if invalid is not None and (not torch.is_tensor(invalid) or invalid.numel() != 1 or invalid.dtype != torch.int32 or invalid.device != device):
+        raise ValueError(f"HeadGroup.forward_routes: invalid must be an int32 [1] on {device}")
+    return int(emb.shape[0]), R
+
+
 class HeadGroup:
     """Several Heads of equal dimensions stepped side by side (mkws_head_group_*, include/mkws.h): one launch per stage for all of
     them instead of four small dependent launches per head.  Every head computes what Head.loss_grad + Head.adam_step compute on it
@@ -218,6 +241,24 @@ class HeadGroup:
             _lib.check(self.L.mkws_head_group_forward_segments(self.h, ctypes.c_void_p(emb.data_ptr()), B, int(row_base), ctypes.c_void_p(seg_offsets.data_ptr()),
                                                                ctypes.c_void_p(seg_head.data_ptr()), S, ctypes.c_void_p(probs.data_ptr()),
                                                                ctypes.c_void_p(bad.data_ptr()), _lib.current_stream_ptr()))
+        return probs, bad
+
+    def forward_routes(self, emb, route_slot, route_head, rows_per_slot, n_slots, out=None, invalid=None):
+        """The group as a head table behind a ROUTE table (mkws_head_group_forward_routes): emb CUDA float32 [B, in] holds rows_per_slot
+        rows per slot; route r = member route_head[r] on the rows of slot route_slot[r] (CUDA int32 [R] each; the kernel reads them, so they
+        may be rewritten between calls or replays).  -> (probs CUDA [R, rows_per_slot, classes] -- `out` if given --, invalid CUDA int32
+        [1] -- `invalid` if given).  A row's probabilities are Head.forward's of its head on that embedding row, bit for bit; a route with
+        slot < 0 is disabled (its rows are not written); one with a slot >= n_slots, a head index outside the group or rows past B gets NaN
+        rows and is counted in `invalid`.  Asynchronous: nothing is copied and nothing synchronises."""
+        import torch
+        classes = self.heads[0].classes
+        B, R = check_forward_routes(self.in_dim, classes, self.device, emb, route_slot, route_head, rows_per_slot, n_slots, out, invalid)
+        probs = out if out is not None else torch.empty((R, int(rows_per_slot), classes), dtype=torch.float32, device=self.device)
+        bad = invalid if invalid is not None else torch.zeros(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mkws_head_group_forward_routes(self.h, ctypes.c_void_p(emb.data_ptr()), B, int(rows_per_slot), int(n_slots),
+                                                             ctypes.c_void_p(route_slot.data_ptr()), ctypes.c_void_p(route_head.data_ptr()), R,
+                                                             ctypes.c_void_p(probs.data_ptr()), ctypes.c_void_p(bad.data_ptr()), _lib.current_stream_ptr()))
         return probs, bad
 
     def loss_grad(self, emb, labels, rows=None, offset=0):
