@@ -694,7 +694,15 @@ int mkws_op_gemm(const float* d_A, const float* d_B, float* d_C, int M, int N, i
  *                  GEMM); 0 = the LDS-staged kernel for everything.
  *   "gemm_ring_tn" (default 0; MKWS_TRAIN_GEMM_TN2): the same for weight gradients (transA = 1): 0 none, 1 small outputs over >= 4096 rows, 2 all.
  *                  Faster per launch and in a single-stream step, slower inside the trainer's two-stream step (profiles/r05_notes.md).
- * mkws_op_get_option returns the value, or a negative mkws_status for an unknown name. */
+ * mkws_op_get_option returns the value, or a negative mkws_status for an unknown name.
+ * mkws_op_get_option also answers the launch constants the operators route by -- read-only: mkws_op_set_option on one of these names
+ * fails with MKWS_ERR_INVALID_ARG.  Tests take their shapes from them, so that a retune moves the tests along with the routes:
+ *   "bn_small_rows"      (1024) mkws_op_bn_act_bwd(_ex): up to this many rows both backward steps are one launch, above it two
+ *   "bn_chunk_cap"       (128)  row chunks of the BatchNorm statistics / backward-reduce launches: 128 rows each up to cap * 128 rows, even shares above
+ *   "bn_apply_chunk_cap" (256)  the same for the normalise / backward-apply launches
+ *   "bn_max_chunks"      (256)  mkws_op_dwconv_bn_fwd: up to this many chunks of 128 output rows the convolution leaves the chunk statistics itself
+ *   "bn_max_gemm_tiles"  (160)  mkws_op_conv_bn_fwd: the same for the GEMM's 64-row tiles
+ *   "grid_cap"           (8192) workgroups (256 elements each) of an elementwise launch; larger tensors are walked by grid-stride loops */
 int mkws_op_set_option(const char* name, int value);
 int mkws_op_get_option(const char* name);
 /* Stream ordering for a trainer that spreads its launches over two streams (weight gradients next to the input-gradient chain): everything queued

@@ -1635,7 +1635,8 @@ __global__ __launch_bounds__(256) void train_adam_dev_kernel(float* __restrict__
   }
 }
 
-inline int grid_for(size_t total, int cap = 8192) {
+constexpr int kGridCap = 8192;             // workgroups of an elementwise launch; above kGridCap * 256 elements the kernels' grid-stride loops take over
+inline int grid_for(size_t total, int cap = kGridCap) {
   size_t g = (total + 255) / 256;
   return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
@@ -1698,6 +1699,8 @@ inline void launch_gemm_reduce(const float* part, int ksplit, float* C, int M, i
   const int S = fold_subs((long)M * N, ksplit);
   hipLaunchKernelGGL(gemm_reduce_kernel, dim3(fold_grid((long)M * N, S)), dim3(256), 0, s, part, ksplit, C, M, N, ldc, accumulate, bias, act, Act, S);
 }
+constexpr int kBnChunkCap = 128;           // row chunks of the BatchNorm statistics / backward-reduce launches (128 rows each until the cap binds, even shares above)
+constexpr int kBnApplyChunkCap = 256;      // row chunks of the BatchNorm normalise / backward-apply launches
 constexpr int kBnMaxChunks = 256;          // chunk statistics one BatchNorm launch folds per channel (a producer with more chunks keeps the separate statistics launch)
 constexpr int kBnMaxGemmTiles = 160;       // the same for GEMM row tiles (64 rows each: more, smaller chunks than the statistics kernel would make)
 const bool g_bn_small = [] { const char* e = getenv("MKWS_TRAIN_BN_SMALL"); return !(e && e[0] == '0'); }();      // A/B switch of bn_small_bwd_kernel
@@ -1903,8 +1906,18 @@ static int gemm_impl(const float* A, const float* B, float* C, int M, int N, int
   return MKWS_OK;
 }
 
+// The launch constants mkws_op_get_option answers (read-only): the values the launchers below route by
+static const int* launch_constant(const char* name) {
+  static const struct { const char* name; int value; } k[] = {{"bn_small_rows", kBnSmallRows}, {"bn_chunk_cap", kBnChunkCap}, {"bn_apply_chunk_cap", kBnApplyChunkCap},
+                                                              {"bn_max_chunks", kBnMaxChunks}, {"bn_max_gemm_tiles", kBnMaxGemmTiles}, {"grid_cap", kGridCap}};
+  for (const auto& e : k)
+    if (strcmp(name, e.name) == 0) return &e.value;
+  return nullptr;
+}
+
 int mkws_op_set_option(const char* name, int value) {
   MKWS_REQ(name, "op_set_option: name is NULL");
+  MKWS_REQ(!launch_constant(name), "'%s' is a launch constant: read-only", name);
   if (strcmp(name, "gemm_ring") == 0) { g_gemm2 = value != 0; return MKWS_OK; }
   if (strcmp(name, "gemm_ring_tn") == 0) { MKWS_REQ(value >= 0 && value <= 2, "gemm_ring_tn: 0, 1 or 2"); g_tn2 = value; return MKWS_OK; }
   return fail(MKWS_ERR_INVALID_ARG, "unknown training-operator option '%s'", name);
@@ -1914,6 +1927,7 @@ int mkws_op_get_option(const char* name) {
   MKWS_REQ(name, "op_get_option: name is NULL");
   if (strcmp(name, "gemm_ring") == 0) return g_gemm2;
   if (strcmp(name, "gemm_ring_tn") == 0) return g_tn2;
+  if (const int* k = launch_constant(name)) return *k;
   return fail(MKWS_ERR_INVALID_ARG, "unknown training-operator option '%s'", name);
 }
 
@@ -1929,7 +1943,7 @@ int mkws_op_dense_fwd(const float* X, const float* W, const float* bias, int act
 
 static int bn_stats_impl(const float* Z, int M, int C, float* mean, float* var, float* mmean, float* mvar, float momentum, hipStream_t s) {
   MKWS_REQ(C % 4 == 0, "bn_stats: C must be a multiple of 4");
-  const int chunks = row_chunks(M, 128);
+  const int chunks = row_chunks(M, kBnChunkCap);
   float* part = scratch_at((size_t)chunks * 2 * C, s);
   MKWS_REQ(part, "bn_stats: needs %zu floats of scratch (mkws_op_set_scratch)", (size_t)chunks * 2 * C);
   hipLaunchKernelGGL(bn_stats_partial_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, s, Z, part, M, C);
@@ -1954,11 +1968,11 @@ int mkws_op_bn_train_fwd_res(const float* Z, int M, int C, const float* gamma, c
   MKWS_REQ(group > 0 && (res || !row_scale), "bn_train_fwd_res: row_scale needs a residual input and a positive group");
   MKWS_REQ(C % 4 == 0, "bn_train_fwd: C must be a multiple of 4");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int chunks = row_chunks(M, 128);
+  const int chunks = row_chunks(M, kBnChunkCap);
   float* part = scratch_at((size_t)chunks * 2 * C, s);
   MKWS_REQ(part, "bn_train_fwd: needs %zu floats of scratch (mkws_op_set_scratch)", (size_t)chunks * 2 * C);
   hipLaunchKernelGGL(bn_stats_partial_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, s, Z, part, M, C);
-  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3((C + 63) / 64, row_chunks(M, 256)), dim3(256), 0, s, Z, part, chunks, gamma, beta, eps, act, momentum, moving_mean,
+  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3((C + 63) / 64, row_chunks(M, kBnApplyChunkCap)), dim3(256), 0, s, Z, part, chunks, gamma, beta, eps, act, momentum, moving_mean,
                      moving_var, mean, var, A, M, C, res, row_scale, group, 0);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
@@ -1979,7 +1993,7 @@ int mkws_op_conv_bn_fwd(const float* X, const float* W, float* Z, int M, int N, 
   bool fused = false;
   if (int rc = gemm_impl(X, W, Z, M, N, K, K, N, N, 0, 0, 0, 0, nullptr, 0, nullptr, s, part, &fused)) return rc;
   if (!fused) return mkws_op_bn_train_fwd_res(Z, M, N, gamma, beta, eps, act, momentum, moving_mean, moving_var, mean, var, A, res, row_scale, group, stream);
-  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3((N + 63) / 64, row_chunks(M, 256)), dim3(256), 0, s, Z, part, tiles, gamma, beta, eps, act, momentum, moving_mean,
+  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3((N + 63) / 64, row_chunks(M, kBnApplyChunkCap)), dim3(256), 0, s, Z, part, tiles, gamma, beta, eps, act, momentum, moving_mean,
                      moving_var, mean, var, A, M, N, res, row_scale, group, 64);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
@@ -2013,12 +2027,12 @@ int mkws_op_bn_act_bwd_ex(const float* Z, const float* mean, const float* var, c
     MKWS_HIP(hipGetLastError());
     return MKWS_OK;
   }
-  const int chunks = row_chunks(M, 128);
+  const int chunks = row_chunks(M, kBnChunkCap);
   float* part = scratch_at((size_t)chunks * 2 * C, s);
   MKWS_REQ(part, "bn_act_bwd: needs %zu floats of scratch (mkws_op_set_scratch)", (size_t)chunks * 2 * C);
   hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, s, Z, mean, var, gamma, beta, eps, act, dA, part, M, C, src, row_scale, bcast,
                      bscale, group);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((C + 63) / 64, row_chunks(M, 256)), dim3(256), 0, s, Z, mean, var, gamma, eps, dA, part, chunks, dgamma, dbeta, M, C);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((C + 63) / 64, row_chunks(M, kBnApplyChunkCap)), dim3(256), 0, s, Z, mean, var, gamma, eps, dA, part, chunks, dgamma, dbeta, M, C);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }
@@ -2055,7 +2069,7 @@ int mkws_op_dwconv_bn_fwd(const float* X, const float* W, float* Z, int B, int H
   MKWS_REQ(part, "dwconv_bn_fwd: needs %zu floats of scratch (mkws_op_set_scratch)", (size_t)chunks * 2 * C);
   if (k == 3) hipLaunchKernelGGL((dw_fwd_stats_kernel<3>), dim3((C + 63) / 64, chunks), dim3(256), 0, st, X, W, Z, part, B, H, Wd, C, s, pt, pl, Ho, Wo);
   else hipLaunchKernelGGL((dw_fwd_stats_kernel<5>), dim3((C + 63) / 64, chunks), dim3(256), 0, st, X, W, Z, part, B, H, Wd, C, s, pt, pl, Ho, Wo);
-  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3((C + 63) / 64, row_chunks(M, 256)), dim3(256), 0, st, Z, part, chunks, gamma, beta, eps, act, momentum, moving_mean,
+  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3((C + 63) / 64, row_chunks(M, kBnApplyChunkCap)), dim3(256), 0, st, Z, part, chunks, gamma, beta, eps, act, momentum, moving_mean,
                      moving_var, mean, var, A, M, C, nullptr, nullptr, 1, 128);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;

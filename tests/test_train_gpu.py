@@ -2,12 +2,11 @@
 Training operators (mkws_op_*) against plain PyTorch-CPU fp32/fp64 references of the same op, the whole
 training-mode network's gradients against oracle/efficientnet_train_oracle.py (float64 autograd, itself checked
 against finite differences in tests/test_oracle_train.py), and the two-phase transfer_learn call."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from tests.util_data import make_fewshot_dataset
+from tests.util_train_ops import make_ops
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -21,20 +20,7 @@ def _rel(a, b):
 
 @pytest.fixture(scope="module")
 def ops():
-    from multilingual_kws_amd import _lib
-    L = _lib.lib()
-    dev = torch.device("cuda:0")
-
-    class Ops:
-        pass
-    o = Ops()
-    o.L, o.dev, o.check, o.s = L, dev, _lib.check, _lib.current_stream_ptr
-    o.p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    o.t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-    # scratch arena for the partial sums of the fixed-order reductions (include/mkws.h: mkws_op_set_scratch)
-    o.scratch = torch.empty(4 << 20, dtype=torch.float32, device=dev)
-    _lib.check(L.mkws_op_set_scratch(o.p(o.scratch), o.scratch.numel()))
-    return o
+    return make_ops()
 
 
 @pytest.fixture(params=[0, 2], ids=["tn-staged", "tn-ring"])
@@ -53,6 +39,12 @@ def test_training_operator_options(ops):
     for name, vals in ((b"gemm_ring", (0, 1)), (b"gemm_ring_tn", (1, 2, 0))):
         for v in vals:
             assert L.mkws_op_set_option(name, v) == 0 and L.mkws_op_get_option(name) == v
+    # the launch constants the operators route by: answered by get_option, refused (MKWS_ERR_INVALID_ARG = -1) and left alone by set_option
+    for name, v in ((b"bn_small_rows", 1024), (b"bn_chunk_cap", 128), (b"bn_apply_chunk_cap", 256), (b"bn_max_chunks", 256), (b"bn_max_gemm_tiles", 160),
+                    (b"grid_cap", 8192)):
+        assert L.mkws_op_get_option(name) == v
+        assert L.mkws_op_set_option(name, v) == -1 and b"read-only" in L.mkws_last_error() and L.mkws_op_set_option(name, v + 1) == -1
+        assert L.mkws_op_get_option(name) == v
 
 
 @pytest.mark.parametrize("M,N,K,ta,tb,ks", [(130, 96, 16, 0, 0, 1), (77, 24, 144, 0, 0, 1), (64, 40, 100, 0, 1, 1), (16, 96, 4000, 1, 0, 7),
