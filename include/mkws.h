@@ -158,6 +158,75 @@ int mkws_frontend_live_push_many_f32(mkws_frontend* fe, void* d_states, size_t s
                                      uint16_t* d_raw, int64_t* d_meta, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sample-rate conversion in front of the frontend: a rational-ratio polyphase FIR resampler.  The reference converts its 48 kHz
+ * sources outside Python (`sox ... convert(samplerate=16000)`, luganda/luganda.py:145, notebooks/clean_msc_gsc.py:71); here it is a
+ * device stage with a stated filter.  With g = gcd(rate_in, rate_out): L = rate_out / g, M = rate_in / g, big = max(L, M),
+ * half = zero_crossings * big, fc = rolloff / big.  The prototype, in double for i = -half .. half, is
+ *   h[i + half] = L * fc * sinc(fc * i) * kaiser(2 * half + 1, kaiser_beta)[i + half]      (sinc(x) = sin(pi x) / (pi x)),
+ * T = ceil((2 * half + 1) / L) taps per phase, and the table is tab[j * L + p] = (float) h[p + j * L], zero where p + j * L > 2 * half.
+ * Output sample n, with m = n * M + off, q = m div L, p = m mod L (64-bit):
+ *   y[n] = sum_{j = 0 .. T-1} tab[j * L + p] * x[q - j],     x outside [0, n_in) = 0,
+ * accumulated from +0.0f with one float32 multiply and one float32 add per tap, j ascending, never fused: a numpy loop over float32
+ * reproduces every bit.  off = half is the time-aligned (centred) output, off = 0 the causal one = the centred one delayed by
+ * half / (L * rate_in) seconds = zero_crossings / min(rate_in, rate_out) (2 ms at the defaults down to 16 kHz).  n_in samples give
+ * ceil(n_in * L / M) output samples.  int16 input is (float) s / 32768.0f.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_RESAMPLE_MAX_TABLE_FLOATS (1 << 22)
+
+typedef struct mkws_resample_cfg {
+  int32_t rate_in;
+  int32_t rate_out;        /* 16000 */
+  int32_t zero_crossings;  /* 32 */
+  float kaiser_beta;       /* 9.0 */
+  float rolloff;           /* 0.95 */
+} mkws_resample_cfg;
+
+typedef struct mkws_resample mkws_resample;
+
+/* The defaults above for the given pair of rates. */
+void mkws_resample_default_cfg(mkws_resample_cfg* cfg, int rate_in, int rate_out);
+
+/* Host only (no GPU needed).  geometry: out = {L, M, T, half}.  host_taps: the table tab[j * L + p] as specified above (the device
+ * keeps its own arrangement of the same values); returns T * L, and writes nothing when dst is NULL or cap_floats is too small.
+ * out_samples: ceil(n_in * L / M).  MKWS_ERR_INVALID_ARG for NULL pointers, rates < 1, zero_crossings < 1, a rolloff outside (0, 1], a
+ * negative or non-finite kaiser_beta and n_in < 0; MKWS_ERR_UNSUPPORTED when T * L exceeds MKWS_RESAMPLE_MAX_TABLE_FLOATS.  Equal rates
+ * are legal (L = M = 1: a low-pass at rolloff * Nyquist). */
+int mkws_resample_geometry(const mkws_resample_cfg* cfg, int32_t out[4]);
+int mkws_resample_host_taps(const mkws_resample_cfg* cfg, float* dst, size_t cap_floats);
+int64_t mkws_resample_out_samples(const mkws_resample_cfg* cfg, int64_t n_in);
+
+/* The device handle: the table, uploaded once.  Refusals as mkws_resample_geometry, and MKWS_ERR_UNSUPPORTED for a ratio M / L so large
+ * that one workgroup's input span does not fit its LDS. */
+int mkws_resample_create(const mkws_resample_cfg* cfg, mkws_resample** out);
+void mkws_resample_destroy(mkws_resample* rs);
+
+/* Stateless batch form: B rows of n_in samples (float32, or int16 with in_i16 != 0), row b at d_in + b * in_stride elements ->
+ * row b of d_out at d_out + b * out_stride, mkws_resample_out_samples(n_in) samples each; centred != 0 selects off = half, else off = 0.
+ * MKWS_ERR_INVALID_ARG for NULL pointers, negative sizes and strides shorter than the rows; B == 0 and n_in == 0 return MKWS_OK with
+ * nothing launched.  One launch, asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_resample_forward(mkws_resample* rs, const void* d_in, int in_i16, int B, int64_t n_in, int64_t in_stride, int centred,
+                          float* d_out, int64_t out_stride, void* stream);
+
+/* Live form: the causal output fed push by push, written where mkws_frontend_live_push_many_f32 reads its d_audio.  A push takes
+ * exactly mkws_resample_live_in_samples(out_samples) = out_samples * M / L NEW input samples per active stream (MKWS_ERR_UNSUPPORTED
+ * if that is not a whole number) and writes exactly out_samples output samples into that stream's row of d_out
+ * [n_streams, out_samples]; d_in is [n_streams, in_samples].  Because in_samples * L = out_samples * M every push starts on phase 0.
+ * Stream s's state block is d_states + s * state_stride_bytes (a multiple of 8, at least mkws_resample_live_state_bytes();
+ * MKWS_ERR_INVALID_ARG otherwise), caller-owned: the int64 count of input samples pushed, then the last T - 1 input samples as float32,
+ * oldest first.  A zero-filled block is a fresh stream (reset = memset, snapshot / restore = copies, a slice of the many-stream tensor
+ * is a one-stream block).  A stream with d_active[s] == 0 (int32 [n_streams]; NULL = all active) is not advanced: its state slice and
+ * its output row are untouched and its input row is not read.
+ * The pushes of a stream, concatenated, are the first pushes * out_samples samples of mkws_resample_forward(centred = 0) over that
+ * stream's whole input, bit for bit -- whatever the chunking, whatever the other streams do, and whether the input arrived as int16 or
+ * as the same values in float32.  n_streams == 0 and out_samples == 0 return MKWS_OK with nothing launched.  One launch for any
+ * n_streams (one workgroup per stream: it reads the old history before it writes the new one), asynchronous on `stream`, allocates
+ * nothing, never synchronises: capturable (a replayed graph advances the streams: the state is device memory). */
+int mkws_resample_live_in_samples(const mkws_resample* rs, int out_samples);
+size_t mkws_resample_live_state_bytes(const mkws_resample* rs);
+int mkws_resample_live_push_many(mkws_resample* rs, void* d_states, size_t state_stride_bytes, int n_streams, const int32_t* d_active,
+                                 const void* d_in, int in_i16, int out_samples, float* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Embedding model.  Replaces `embedding.predict(x)` on the Keras model
  *   EfficientNetB0(include_top=False, weights=None, input_shape=(49,40,1)) -> GAP ->
  *   Dense 2048 relu -> Dense 2048 relu -> Dense 1024 selu ("dense_2")

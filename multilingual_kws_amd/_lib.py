@@ -39,9 +39,16 @@ class DetectEvent(ctypes.Structure):
     _fields_ = [("window", ctypes.c_int32), ("fired", ctypes.c_int32), ("score", ctypes.c_double)]
 
 
+class ResampleCfg(ctypes.Structure):
+    """mkws_resample_cfg (include/mkws.h)."""
+    _fields_ = [("rate_in", ctypes.c_int32), ("rate_out", ctypes.c_int32), ("zero_crossings", ctypes.c_int32),
+                ("kaiser_beta", ctypes.c_float), ("rolloff", ctypes.c_float)]
+
+
 # every symbol include/mkws.h declares: (name, restype, argtypes)
 _P, _I, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _CFG = ctypes.POINTER(FrontendCfg)
+_RCFG, _I64 = ctypes.POINTER(ResampleCfg), ctypes.c_int64
 SYMBOLS = [
     ("mkws_abi_version", _I, []),
     ("mkws_last_error", ctypes.c_char_p, []),
@@ -57,6 +64,16 @@ SYMBOLS = [
     ("mkws_frontend_live_state_bytes", _SZ, [_P, _I, _I, _I]),
     ("mkws_frontend_live_push_f32", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     ("mkws_frontend_live_push_many_f32", _I, [_P, _P, _SZ, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    ("mkws_resample_default_cfg", None, [_RCFG, _I, _I]),
+    ("mkws_resample_geometry", _I, [_RCFG, _P]),
+    ("mkws_resample_host_taps", _I, [_RCFG, _P, _SZ]),
+    ("mkws_resample_out_samples", _I64, [_RCFG, _I64]),
+    ("mkws_resample_create", _I, [_RCFG, ctypes.POINTER(_P)]),
+    ("mkws_resample_destroy", None, [_P]),
+    ("mkws_resample_forward", _I, [_P, _P, _I, _I, _I64, _I64, _I, _P, _I64, _P]),
+    ("mkws_resample_live_in_samples", _I, [_P, _I]),
+    ("mkws_resample_live_state_bytes", _SZ, [_P]),
+    ("mkws_resample_live_push_many", _I, [_P, _P, _SZ, _I, _P, _P, _I, _I, _P, _P]),
     ("mkws_embed_weight_count", _SZ, []),
     ("mkws_embed_weight_manifest", _I, [ctypes.c_char_p, _SZ]),
     ("mkws_embed_create", _I, [_P, _SZ, _I, ctypes.POINTER(_P)]),

@@ -394,10 +394,12 @@ class StreamingSession:
 
 class LivePushCutter:
     """The host part of LiveSession.feed: chunks of any length -> whole pushes of `push_samples` samples; what does not fill a push
-    waits for the next chunk.  The pushes depend on the samples fed so far only, not on how they were cut into chunks."""
+    waits for the next chunk.  The pushes depend on the samples fed so far only, not on how they were cut into chunks.  pcm16 (the
+    sessions set it with input_rate): an int16 chunk is PCM and is taken as s / 32768, which is exact; without it every chunk is cast
+    to float32 as it is."""
 
-    def __init__(self, push_samples):
-        self.push_samples = int(push_samples)
+    def __init__(self, push_samples, pcm16=False):
+        self.push_samples, self.pcm16 = int(push_samples), bool(pcm16)
         self.reset()
 
     def reset(self):
@@ -405,7 +407,10 @@ class LivePushCutter:
 
     def cut(self, chunk):
         """float32 samples -> [full pushes, push_samples] (a view of a fresh array; may have zero rows)."""
-        a = np.asarray(chunk, dtype=np.float32).reshape(-1)
+        if self.pcm16 and np.asarray(chunk).dtype == np.int16:
+            a = (np.asarray(chunk).astype(np.float32) / np.float32(32768.0)).reshape(-1)
+        else:
+            a = np.asarray(chunk, dtype=np.float32).reshape(-1)
         if self.rest.size:
             a = np.concatenate([self.rest, a])
         full = a.size // self.push_samples
@@ -420,11 +425,11 @@ class LiveGroupScheduler:
     but the cutters' unfinished pushes waits between calls: tick t of a feed holds the t-th push each slot completed in it.  What a slot
     pushes depends only on the samples fed to THAT slot so far, never on how they were cut into chunks or on the other slots."""
 
-    def __init__(self, streams, push_samples):
+    def __init__(self, streams, push_samples, pcm16=False):
         self.streams, self.push_samples = int(streams), int(push_samples)
         if self.streams < 1 or self.push_samples < 1:
             raise ValueError(f"LiveGroupScheduler({streams}, {push_samples}): at least one slot and one sample per push")
-        self.cutters = [LivePushCutter(self.push_samples) for _ in range(self.streams)]
+        self.cutters = [LivePushCutter(self.push_samples, pcm16) for _ in range(self.streams)]
 
     def reset(self, slot=None):
         for c in (self.cutters if slot is None else [self.cutters[self.slot(slot)]]):
@@ -502,6 +507,37 @@ def _live_geometry(self, model_settings, fired_only):
     return ms
 
 
+def _live_input(self, input_rate):
+    """The input side of a live session, once _live_geometry has run: self.in_push_samples, the samples of one push as the caller feeds
+    them.  input_rate None or the model's own rate: the push itself, and nothing else changes (no .resampler attribute, the same chain).
+    Otherwise self.resampler converts on the device, first launch of the chain, and a push of push_samples model-rate samples takes
+    live_in_samples(push_samples) fed ones -- ValueError naming the smallest hops_per_push when that is not a whole number."""
+    self.input_rate = self.sample_rate if input_rate is None else int(input_rate)
+    self.in_push_samples = self.push_samples
+    if self.input_rate == self.sample_rate:
+        return
+    from ..resample import live_push_hops
+    if self.input_rate < 1:
+        raise ValueError(f"input_rate={input_rate}")
+    need = live_push_hops(self.input_rate, self.sample_rate, self.hop_samples)
+    if self.hops % need:
+        raise ValueError(f"input_rate={self.input_rate}: a push of {self.hops} hop(s) of {self.hop_samples} samples at {self.sample_rate} Hz is "
+                         f"{self.push_samples * self.input_rate / self.sample_rate:g} input samples, not a whole number; the smallest "
+                         f"hops_per_push that works is {need} (and its multiples)")
+    self.resampler = input_data._resampler_for(self.input_rate, self.sample_rate, self.embedding.device)    # shared, never closed here
+    self.in_push_samples = self.resampler.live_in_samples(self.push_samples)
+
+
+def _fed_samples(chunk):
+    """A chunk as feed() takes it -> numpy on the host; a tensor comes as float32, or as int16 if it is that (the cutters decide what an
+    int16 chunk means)."""
+    import torch
+    if torch.is_tensor(chunk):
+        chunk = chunk.detach().reshape(-1)
+        return chunk.to("cpu").numpy() if chunk.dtype == torch.int16 else chunk.to("cpu", torch.float32).numpy()
+    return chunk
+
+
 def _live_rows(self, records):
     """records (window, head, threshold index, fired, score) -> feed()'s rows [keyword, time_ms, score, threshold]."""
     from ..frontend import live_window_time_ms
@@ -522,10 +558,17 @@ class LiveSession:
 
     models: TransferLearnedModel(s) sharing one embedding (or embedding= and heads=); keywords: their target words (default
     flags.target_keyword, or "keyword_<i>"); flags: a StreamFlags, of which average_window_duration_ms, suppression_ms, minimum_count,
-    clip_duration_ms and clip_stride_ms are used; fired_only=False also reports the class's releases (label "_silence_")."""
+    clip_duration_ms and clip_stride_ms are used; fired_only=False also reports the class's releases (label "_silence_").
+
+    input_rate: the rate of the audio fed, when it is not the model's 16 kHz (None or 16000: the chain and the graph are exactly the
+    ones above).  feed() then takes chunks at that rate, float32 or int16 PCM (which the cutter brings to float32 on the host, s / 32768: the
+    upload is float32 either way); a push is live_in_samples(push_samples) of them, uploaded at their own rate, and the conversion (resample.Resampler.live_push_many, state in device memory like the other two) is the first launch of the
+    chain.  samples_seen counts input-rate samples; windows and time_ms are in the 16 kHz timeline.  The live conversion is causal: its
+    output lags the audio by Resampler.delay_ms (2 ms from 48 or 44.1 kHz, a tenth of a hop), which is not compensated.  A rate whose push
+    is not a whole number of input samples raises ValueError naming the smallest hops_per_push that works (11 025 Hz: 2)."""
 
     def __init__(self, models=None, thresholds=(0.9,), flags=None, model_settings=None, hops_per_push=1, embedding=None, heads=None,
-                 keywords=None, fired_only=True, use_graph=True):
+                 keywords=None, fired_only=True, use_graph=True, input_rate=None):
         import torch
         from ..detector import live_detector_state, live_out_words
         from ..head import Head
@@ -536,7 +579,8 @@ class LiveSession:
         if not 1 <= self.hops <= embedding.max_batch:
             raise ValueError(f"LiveSession(hops_per_push={hops_per_push}): from 1 to the embedding handle's max_batch={embedding.max_batch}")
         ms = _live_setup(self, thresholds, flags, model_settings, keywords, fired_only)
-        self.cutter = LivePushCutter(self.push_samples)
+        _live_input(self, input_rate)
+        self.cutter = LivePushCutter(self.in_push_samples, pcm16=hasattr(self, "resampler"))
         dev = embedding.device
         N, T, h = len(self.heads), len(self.thresholds), self.hops
         with torch.cuda.device(dev):
@@ -547,8 +591,13 @@ class LiveSession:
             self.meta = torch.zeros(2 + h, dtype=torch.int64, device=dev)
             self.d_thr = torch.tensor(self.thresholds, dtype=torch.float64, device=dev)
             self.out = torch.zeros(live_out_words(N, T, h), dtype=torch.int64, device=dev)      # counts and events: the one D2H per push
-            self.h_audio = torch.zeros(self.push_samples, dtype=torch.float32).pin_memory()
+            self.h_audio = torch.zeros(self.in_push_samples, dtype=torch.float32).pin_memory()
             self.h_out = torch.zeros(self.out.numel(), dtype=torch.int64).pin_memory()
+            self.d_upload = self.audio                  # where a push's samples land: the frontend's input, or the resampler's
+            if hasattr(self, "resampler"):
+                self.raw = torch.zeros((1, self.in_push_samples), dtype=torch.float32, device=dev)
+                self.rstate = self.resampler.live_state_many(1, device=dev)
+                self.d_upload = self.raw[0]
         self._Head = Head
         self.graph = None
         self.recaptures = 0
@@ -561,6 +610,8 @@ class LiveSession:
     def _chain(self):
         from ..detector import detect_live_step
         f = self.flags
+        if hasattr(self, "resampler"):
+            self.resampler.live_push_many(self.rstate, self.raw, self.push_samples, out=self.audio)
         self.fe.live_push(self.fstate, self.audio, self.window_samples, self.hop_samples, self.hops, spec=self.spec, meta=self.meta)
         probs = self._Head.forward_many(self.heads, self.embedding.forward(self.spec))
         detect_live_step(self.dstate, probs, self.meta, self.d_thr, f.average_window_duration_ms, f.suppression_ms, f.minimum_count,
@@ -572,7 +623,8 @@ class LiveSession:
         chain is stateful and the warm-up runs it: both state blocks are put back afterwards, so capturing does not advance the stream."""
         import torch
         dev = self.embedding.device
-        kept = (self.fstate.clone(), self.dstate.clone())
+        states = [self.fstate, self.dstate] + ([self.rstate] if hasattr(self, "resampler") else [])
+        kept = [t.clone() for t in states]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -582,20 +634,22 @@ class LiveSession:
         with torch.cuda.graph(g):
             self.probs = self._chain()
         self.graph = g
-        self.fstate.copy_(kept[0])
-        self.dstate.copy_(kept[1])
+        for t, k in zip(states, kept):
+            t.copy_(k)
 
     def reset(self):
         """Starts a new stream: both state blocks zeroed, the unfinished push dropped."""
         self.fstate.zero_()
         self.dstate.zero_()
+        if hasattr(self, "resampler"):
+            self.rstate.zero_()
         self.cutter.reset()
         self.samples_pushed = 0                         # the host's mirror of the state block's first int64
         self.last_records = []
 
     @property
     def samples_seen(self):
-        return self.samples_pushed + int(self.cutter.rest.size)
+        return self.samples_pushed // self.push_samples * self.in_push_samples + int(self.cutter.rest.size)
 
     @property
     def windows_seen(self):
@@ -604,7 +658,9 @@ class LiveSession:
 
     def close(self):
         self.graph = None
-        self.probs = self.audio = self.fstate = self.dstate = self.spec = self.meta = self.out = None
+        self.probs = self.audio = self.fstate = self.dstate = self.spec = self.meta = self.out = self.d_upload = None
+        if hasattr(self, "resampler"):
+            self.raw = self.rstate = None
 
     def _push(self, samples):
         """One push of push_samples new samples (numpy) -> records (window, head, threshold index, fired, score) of the events it completed."""
@@ -613,7 +669,7 @@ class LiveSession:
         dev = self.embedding.device
         self.h_audio.numpy()[:] = samples
         with torch.cuda.device(dev):
-            self.audio.copy_(self.h_audio, non_blocking=True)
+            self.d_upload.copy_(self.h_audio, non_blocking=True)
             if self.graph is not None:
                 if self.embedding.get_option("exchange_error"):
                     # StreamingSession's protocol: the PREVIOUS replay ran a failed exchange (all-NaN probabilities: the detector scored
@@ -641,11 +697,8 @@ class LiveSession:
         there) -> [[keyword, time_ms, score, threshold], ...] for the events the chunk completed, ordered by window, keyword and
         threshold.  time_ms is the start of the window, as detect() reports it.  The same events as records (window, head index,
         threshold index, fired, score) are kept in .last_records."""
-        import torch
-        if torch.is_tensor(chunk):
-            chunk = chunk.detach().reshape(-1).to("cpu", torch.float32).numpy()
         records = []
-        for samples in self.cutter.cut(chunk):
+        for samples in self.cutter.cut(_fed_samples(chunk)):
             records.extend(self._push(samples))
         self.last_records = records
         return _live_rows(self, records)
@@ -671,10 +724,13 @@ class LiveSessionGroup:
     NOT promised: equality of a slot's probabilities with those of its own batch-1 LiveSession -- the embedding handle picks another plan
     at another batch size (equal up to its rounding; tools/bench_live_group.py measures the difference).
 
-    Arguments as LiveSession's; streams * hops_per_push must not exceed the embedding handle's max_batch."""
+    Arguments as LiveSession's; streams * hops_per_push must not exceed the embedding handle's max_batch.  input_rate as LiveSession's:
+    every slot is fed at that rate, the tick's one upload carries the unconverted samples [S, in_push] (float32) and the active mask, and the conversion of
+    all slots is one more launch at the head of the chain (an inactive slot's resampler state is not touched either); samples_seen counts
+    input-rate samples, and the causal delay of Resampler.delay_ms is not compensated."""
 
     def __init__(self, models=None, streams=1, thresholds=(0.9,), flags=None, model_settings=None, hops_per_push=1, embedding=None, heads=None,
-                 keywords=None, fired_only=True, use_graph=True):
+                 keywords=None, fired_only=True, use_graph=True, input_rate=None):
         import torch
         from ..detector import live_detector_state_many, live_out_words_many
         from ..head import Head
@@ -686,7 +742,8 @@ class LiveSessionGroup:
             raise ValueError(f"LiveSessionGroup(streams={streams}, hops_per_push={hops_per_push}): streams * hops_per_push from 1 to the "
                              f"embedding handle's max_batch={embedding.max_batch}")
         ms = _live_setup(self, thresholds, flags, model_settings, keywords, fired_only)
-        self.scheduler = LiveGroupScheduler(self.streams, self.push_samples)
+        _live_input(self, input_rate)
+        self.scheduler = LiveGroupScheduler(self.streams, self.in_push_samples, pcm16=hasattr(self, "resampler"))
         S, N, T, h = self.streams, len(self.heads), len(self.thresholds), self.hops
         with torch.cuda.device(embedding.device):
             self._slot_buffers(ms)
@@ -699,10 +756,14 @@ class LiveSessionGroup:
     def _slot_buffers(self, ms):
         """The per-slot device buffers of a tick and the pinned mirror of its one upload."""
         import torch
-        dev, S, h, P = self.embedding.device, self.streams, self.hops, self.push_samples
+        dev, S, h, P = self.embedding.device, self.streams, self.hops, self.in_push_samples
         # the static graph input, ONE buffer so that a tick is one upload: the NEW samples [S, push] (float32), then the active mask [S] (int32)
         self.d_in = torch.zeros(S * P + S, dtype=torch.float32, device=dev)
         self.audio, self.active = self.d_in[:S * P].view(S, P), self.d_in[S * P:].view(torch.int32)
+        if hasattr(self, "resampler"):
+            # the samples uploaded are the fed ones; the frontend's input is what the resampler writes
+            self.raw, self.audio = self.audio, torch.zeros((S, self.push_samples), dtype=torch.float32, device=dev)
+            self.rstates = self.resampler.live_state_many(S, device=dev)
         self.fstates = self.fe.live_state_many(S, self.window_samples, self.hop_samples, h, device=dev)
         self.spec = torch.zeros((S * h, ms["spectrogram_length"], ms["fingerprint_width"]), dtype=torch.float32, device=dev)
         self.meta = torch.zeros((S, 2 + h), dtype=torch.int64, device=dev)
@@ -726,6 +787,7 @@ class LiveSessionGroup:
     def _chain(self):
         from ..detector import detect_live_step_many
         f = self.flags
+        self._resample_push()
         self.fe.live_push_many(self.fstates, self.audio, self.window_samples, self.hop_samples, self.hops, active=self.active,
                                spec=self.spec, meta=self.meta)
         probs = self._Head.forward_many(self.heads, self.embedding.forward(self.spec))
@@ -733,12 +795,18 @@ class LiveSessionGroup:
                               self.history, target_id=2, fired_only=self.fired_only, out=self.out)
         return probs
 
+    def _resample_push(self):
+        """With input_rate: the first launch of the chain, the fed samples of every active slot -> self.audio."""
+        if hasattr(self, "resampler"):
+            self.resampler.live_push_many(self.rstates, self.raw, self.push_samples, active=self.active, out=self.audio)
+
     def _capture(self):
         """LiveSession._capture for the group: warm-up and capture on a single stream (the chain is one branch), BOTH state tensors put back
         afterwards, so capturing advances no slot."""
         import torch
         dev = self.embedding.device
-        kept = (self.fstates.clone(), self.dstates.clone())
+        states = [self.fstates, self.dstates] + ([self.rstates] if hasattr(self, "resampler") else [])
+        kept = [t.clone() for t in states]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -748,8 +816,8 @@ class LiveSessionGroup:
         with torch.cuda.graph(g):
             self.probs = self._chain()
         self.graph = g
-        self.fstates.copy_(kept[0])
-        self.dstates.copy_(kept[1])
+        for t, k in zip(states, kept):
+            t.copy_(k)
 
     def reset(self, slot=None):
         """Starts a new stream in `slot` (None: in every slot): its two state slices zeroed, its unfinished push dropped."""
@@ -763,11 +831,13 @@ class LiveSessionGroup:
             self.fstates[slot].zero_()
             self.dstates[slot].zero_()
             self.samples_pushed[slot] = 0
+        if hasattr(self, "resampler"):
+            (self.rstates if slot is None else self.rstates[slot]).zero_()
         self.scheduler.reset(slot)
         self.last_records = {}
 
     def samples_seen(self, slot):
-        return self.samples_pushed[self.scheduler.slot(slot)] + self.scheduler.pending(slot)
+        return self.samples_pushed[self.scheduler.slot(slot)] // self.push_samples * self.in_push_samples + self.scheduler.pending(slot)
 
     def windows_seen(self, slot):
         from ..frontend import live_windows
@@ -776,6 +846,8 @@ class LiveSessionGroup:
     def close(self):
         self.graph = None
         self.probs = self.d_in = self.audio = self.active = self.fstates = self.dstates = self.spec = self.meta = self.out = None
+        if hasattr(self, "resampler"):
+            self.raw = self.rstates = None
 
     def _before_replay(self):
         """Hook between a tick's upload and its replay, on the tick's stream (LiveRoutedGroup uploads its edited tables here)."""
@@ -829,8 +901,7 @@ class LiveSessionGroup:
         tensor, which is brought to the host: the pushes are cut there).  Runs the ticks the chunks complete -> {slot: [[keyword, time_ms,
         score, threshold], ...]} with one entry per slot fed, each slot's rows ordered as LiveSession.feed orders them.  The same events
         as records (window, head index, threshold index, fired, score) are kept per slot in .last_records."""
-        import torch
-        fed = [(k, v.detach().reshape(-1).to("cpu", torch.float32).numpy() if torch.is_tensor(v) else v) for k, v in self.scheduler.chunks(chunks)]
+        fed = [(k, _fed_samples(v)) for k, v in self.scheduler.chunks(chunks)]
         records = {k: [] for k, _ in fed}
         for active, audio in self.scheduler.feed(dict(fed)):
             self._tick(active, audio, records)
@@ -916,7 +987,7 @@ class LiveRoutedGroup(LiveSessionGroup):
         window the rows are ordered by route id, then threshold."""
 
     def __init__(self, embedding, heads, streams, max_routes, n_thresholds=1, flags=None, model_settings=None, hops_per_push=1, fired_only=True,
-                 use_graph=True):
+                 use_graph=True, input_rate=None):
         import torch
         from ..detector import live_detector_state_routes, live_out_words_routes
         from ..head import HeadGroup
@@ -929,7 +1000,8 @@ class LiveRoutedGroup(LiveSessionGroup):
         self.flags = flags if flags is not None else default_live_flags([])
         self.table = LiveRouteTable(self.streams, len(self.heads), max_routes, n_thresholds, self.flags.average_window_duration_ms)
         ms = _live_geometry(self, model_settings, fired_only)
-        self.scheduler = LiveGroupScheduler(self.streams, self.push_samples)
+        _live_input(self, input_rate)
+        self.scheduler = LiveGroupScheduler(self.streams, self.in_push_samples, pcm16=hasattr(self, "resampler"))
         dev = embedding.device
         R, T, h = self.table.max_routes, self.table.n_thresholds, self.hops
         with torch.cuda.device(dev):
@@ -974,6 +1046,7 @@ class LiveRoutedGroup(LiveSessionGroup):
     def _chain(self):
         from ..detector import detect_live_step_routes
         f = self.flags
+        self._resample_push()
         self.fe.live_push_many(self.fstates, self.audio, self.window_samples, self.hop_samples, self.hops, active=self.active,
                                spec=self.spec, meta=self.meta)
         probs, _ = self.head_group.forward_routes(self.embedding.forward(self.spec), self.route_slot, self.route_head, self.hops, self.streams,
@@ -995,6 +1068,8 @@ class LiveRoutedGroup(LiveSessionGroup):
             for r in self.table.routes_of(slot):
                 self.dstates[r].zero_()
             self.samples_pushed[slot] = 0
+        if hasattr(self, "resampler"):
+            (self.rstates if slot is None else self.rstates[slot]).zero_()
         self.scheduler.reset(slot)
         self.last_records = {}
 
@@ -1238,11 +1313,12 @@ def operating_curves(inferences, flags: StreamFlags, thresholds, groundtruth, ke
 
 
 def _shared_embedding_passes(keywords, models, wav, groundtruth, thresholds, inference_chunk_len_seconds, average_window_duration_ms,
-                             suppression_ms, time_tolerance_ms):
+                             suppression_ms, time_tolerance_ms, resample=False):
     """What multi_keyword_detections and multi_keyword_operating_curves do with a recording before their detector runs: the argument
     checks and the wav are done when this returns -> (keywords as a list, the StreamFlags of the run, sample rate, samples of the
     recording, an iterator over the distinct embeddings of `models` that yields (indices of the models on it, their softmax outputs
-    [len(indices), windows, 3] on the device): one streaming_inferences pass each)."""
+    [len(indices), windows, 3] on the device): one streaming_inferences pass each).  resample=True: a recording at another rate than the
+    model's is converted on the device first (input_data.to_sample_rate, centred); rate and samples are then the converted audio's."""
     keywords, models = list(keywords), list(models)
     if len(models) != len(keywords) or len(set(keywords)) != len(keywords):
         raise ValueError(f"discrepancy: {len(models)} models provided for {len(set(keywords))} keywords")
@@ -1251,6 +1327,10 @@ def _shared_embedding_passes(keywords, models, wav, groundtruth, thresholds, inf
     with open(wav, "rb") as f:
         audio, sample_rate = input_data.decode_wav(f.read())
     model_settings = input_data.standard_microspeech_model_settings(label_count=3)
+    if resample and sample_rate != model_settings["sample_rate"]:
+        import torch
+        audio = input_data.to_sample_rate(torch.from_numpy(audio).cuda(), sample_rate, model_settings["sample_rate"])   # stays on the device
+        sample_rate = model_settings["sample_rate"]
     flags = StreamFlags(wav=wav, ground_truth=groundtruth, target_keyword=keywords[0] if keywords else "", detection_thresholds=thresholds,
                         average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms,
                         time_tolerance_ms=time_tolerance_ms, max_chunk_length_sec=inference_chunk_len_seconds)
@@ -1266,14 +1346,16 @@ def _shared_embedding_passes(keywords, models, wav, groundtruth, thresholds, inf
 
 
 def multi_keyword_operating_curves(keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds=1200,
-                                   average_window_duration_ms=100, suppression_ms=500, time_tolerance_ms=750, num_nontarget_words=None):
+                                   average_window_duration_ms=100, suppression_ms=500, time_tolerance_ms=750, num_nontarget_words=None,
+                                   resample=False):
     """From a recording to {keyword: [tpr_fpr's dict per threshold]} for N keywords: one pass over the wav on the shared embedding
     (streaming_inferences(as_device=True), as multi_keyword_detections), then operating_curves on the device tensor -- the probabilities,
     the detections and the matching never visit the host.  groundtruth_csv: rows `keyword,time_ms` (run.py's ground-truth file).  The
-    other arguments are multi_keyword_detections' flags; the recording's duration is its sample count over its sample rate."""
+    other arguments are multi_keyword_detections' flags (resample too); the recording's duration is its sample count over its sample rate."""
     thresholds = list(thresholds)
     keywords, flags, sample_rate, data_samples, passes = _shared_embedding_passes(
-        keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, time_tolerance_ms)
+        keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, time_tolerance_ms,
+        resample=resample)
     groundtruth_data = _read_groundtruth(groundtruth_csv)
     curves = {}
     for idxs, got in passes:
@@ -1362,7 +1444,7 @@ def eval_stream_test(st: StreamTarget, live_model=None):
 
 
 def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inference_chunk_len_seconds=1200, groundtruth=None,
-                             average_window_duration_ms=100, suppression_ms=500, write_detections=None):
+                             average_window_duration_ms=100, suppression_ms=500, write_detections=None, resample=False):
     """The detections dict of run.py:89-152 for N keywords from ONE pass over the recording.
 
     The reference loads one full Keras model per keyword and repeats the window loop, the micro-frontend and the EfficientNet forward
@@ -1372,10 +1454,13 @@ def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inf
     [detection_threshold], average_window_duration_ms=100, suppression_ms=500, max_chunk_length_sec=inference_chunk_len_seconds);
     they are merged and sorted by time (stable, like the reference's sorted()).  -> dict(keywords=..., detections=[dict(keyword, time_ms,
     confidence, groundtruth)], min_threshold=...): groundtruth "ng" without a ground-truth file, otherwise tpr_fpr.get_groundtruth's
-    classification against its rows `keyword,time_ms` (as shipped: first keyword only).  Also written as JSON to write_detections."""
+    classification against its rows `keyword,time_ms` (as shipped: first keyword only).  Also written as JSON to write_detections.
+    resample=True: a recording whose rate differs from the model's 16 kHz is converted on the device (resample.Resampler, centred) before
+    windowing, and the times are those of the converted audio; with the default the recording is taken as it is."""
     import json
     keywords, flags, sample_rate, data_samples, passes = _shared_embedding_passes(
-        keywords, models, wav, groundtruth, [detection_threshold], inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, 750)
+        keywords, models, wav, groundtruth, [detection_threshold], inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, 750,
+        resample=resample)
     per_keyword = [None] * len(keywords)                            # keyword -> its found_words_w_confidences
     for idxs, got in passes:
         found = detect_many(got, flags, [detection_threshold], sample_rate, data_samples=data_samples, keywords=[keywords[i] for i in idxs])

@@ -106,6 +106,54 @@ def _read_wav(path, desired_samples=-1):
         return decode_wav(f.read(), desired_samples)[0]
 
 
+_resamplers = {}
+
+
+def _resampler_for(rate_in, rate_out, device=None):
+    """The process-wide Resampler of a pair of rates on `device` (default: the current one), created there.  The handle is SHARED by
+    every caller at that rate and lives as long as the process, like the frontends above: it holds only the read-only tap table
+    (a stream's state is the caller's), and nobody who got it from here may close it."""
+    import torch
+    from ..resample import Resampler
+    index = torch.cuda.current_device() if device is None else torch.device(device).index
+    if index is None:                                   # "cuda" without an index
+        index = torch.cuda.current_device()
+    key = (int(rate_in), int(rate_out), index)
+    rs = _resamplers.get(key)
+    if rs is None:
+        with torch.cuda.device(index):
+            rs = _resamplers[key] = Resampler(rate_in, rate_out)
+    return rs
+
+
+def to_sample_rate(audio, rate_in, rate_out=16000):
+    """What the reference leaves to `sox ... convert(samplerate=16000)` (luganda/luganda.py:145): audio [n] or [B, n], float32 or int16,
+    numpy or tensor, at rate_in -> float32 of the same kind at rate_out with ceil(n * rate_out / rate_in) samples per row, time-aligned
+    (resample.Resampler.forward, centred; the filter: DESIGN.md section 22).  Equal rates: the audio itself as float32 (int16 / 32768)."""
+    import torch
+    if int(rate_in) == int(rate_out):
+        if torch.is_tensor(audio):
+            return audio.to(torch.float32) / 32768.0 if audio.dtype == torch.int16 else audio.to(torch.float32)
+        a = np.asarray(audio)
+        return a.astype(np.float32) / np.float32(32768.0) if a.dtype == np.int16 else a.astype(np.float32)
+    device = audio.device if torch.is_tensor(audio) and audio.is_cuda else None
+    return _resampler_for(rate_in, rate_out, device).forward(audio, centred=True)
+
+
+def read_wav_at(path, sample_rate=16000, desired_samples=-1):
+    """A PCM16 WAV at any rate -> float32 [samples] at sample_rate: decoded, converted on the device when the file's rate differs
+    (to_sample_rate), then zero-padded or truncated to desired_samples as decode_wav does."""
+    with open(path, "rb") as f:
+        x, rate = decode_wav(f.read(), -1)
+    x = to_sample_rate(x, rate, sample_rate)
+    if desired_samples is not None and desired_samples > 0:
+        if x.shape[0] >= desired_samples:
+            x = x[:desired_samples]
+        else:
+            x = np.concatenate([x, np.zeros(desired_samples - x.shape[0], np.float32)])
+    return x
+
+
 def load_unknown_files(unknown_words_dir, listing="unknown_files.txt"):
     """The unknown-words bank layout the reference's few-shot CLI consumes (run.py:272-278): a directory holding
     `unknown_files.txt`, one WAV path per line relative to that directory.  Returns absolute-ish path strings."""

@@ -1,0 +1,176 @@
+"""The resampler's filter, on the host: taps against scipy's firwin, the frequency response the design states, geometry, lengths, refusals,
+and the float32 restatement (tests/util_resample.py, what the device is held to bit for bit) against the analytic resampling of tones."""
+import ctypes
+from math import gcd
+
+import numpy as np
+import pytest
+
+from multilingual_kws_amd import _lib, resample
+from tests.util_resample import RATES, polyphase
+
+OUT = 16000
+
+
+def _cfg(rate, **over):
+    return resample.make_cfg(rate, OUT, **over)
+
+
+def _formulas(rate_in, rate_out=OUT, zc=32):
+    g = gcd(rate_in, rate_out)
+    L, M = rate_out // g, rate_in // g
+    half = zc * max(L, M)
+    return dict(L=L, M=M, T=-(-(2 * half + 1) // L), half=half)
+
+
+@pytest.fixture(scope="module")
+def taps():
+    return {r: resample.host_taps(_cfg(r)) for r in RATES}
+
+
+def test_defaults():
+    cfg = _cfg(48000)
+    assert (cfg.rate_in, cfg.rate_out, cfg.zero_crossings, cfg.kaiser_beta, cfg.rolloff) == (48000, 16000, 32, 9.0, np.float32(0.95))
+
+
+@pytest.mark.parametrize("rate", RATES)
+def test_geometry_and_taps_against_firwin(rate, taps):
+    from scipy.signal import firwin
+    g = resample.geometry(_cfg(rate))
+    assert g == _formulas(rate)
+    L, T, half = g["L"], g["T"], g["half"]
+    tab = taps[rate]
+    assert tab.shape == (T, L) and tab.dtype == np.float32
+    want = np.zeros(T * L, np.float32)
+    want[:2 * half + 1] = (L * firwin(2 * half + 1, float(np.float32(0.95)) / max(L, g["M"]), window=("kaiser", 9.0), scale=False)).astype(np.float32)
+    ulp = np.spacing(np.abs(want).max())
+    assert np.abs(tab.reshape(-1) - want).max() <= ulp
+    assert not tab.reshape(-1)[2 * half + 1:].any()
+    phase_sum = tab.astype(np.float64).sum(0)
+    assert np.abs(phase_sum - 1).max() <= 1e-5, np.abs(phase_sum - 1).max()
+    assert np.abs(tab.astype(np.float64)).sum(0).max() <= 2.5
+
+
+@pytest.mark.parametrize("rate", RATES)
+def test_frequency_response(rate, taps):
+    """Flat within +-0.001 dB up to 0.86 Nyq and at most -89 dB from 1.04 Nyq on, Nyq = min(rates) / 2: for 48 -> 16 kHz flat to 6880 Hz and
+    every alias above -89 dB lands above 7680 Hz, outside the frontend's 7500 Hz band."""
+    g = _formulas(rate)
+    L, big = g["L"], max(g["L"], g["M"])
+    h = taps[rate].astype(np.float64).reshape(-1)[:2 * g["half"] + 1]
+    nfft = 1 << 21
+    H = np.abs(np.fft.rfft(h, nfft)) / L
+    f = np.arange(H.size) / (nfft / 2) * big                     # in units of Nyq
+    db = 20 * np.log10(np.maximum(H, 1e-300))
+    passband, stopband = db[f <= 0.86], db[f >= 1.04]
+    print(rate, "passband", passband.min(), passband.max(), "stopband", stopband.max())
+    assert np.abs(passband).max() <= 0.001
+    assert stopband.max() <= -89.0
+
+
+@pytest.mark.parametrize("rate", RATES)
+def test_out_samples(rate):
+    g, cfg = _formulas(rate), _cfg(rate)
+    L, M = g["L"], g["M"]
+    for n in [0, 1, 2, M - 1, M, M + 1, 3 * M - 1, 3 * M, 3 * M + 1, 16000, rate, 13_500_000, 1 << 40]:
+        assert resample.out_samples(cfg, n) == -(-n * L // M)
+    with pytest.raises(_lib.MkwsError) as e:
+        resample.out_samples(cfg, -1)
+    assert e.value.code == -1
+
+
+def test_equal_rates_are_legal():
+    assert resample.geometry(_cfg(16000)) == dict(L=1, M=1, T=65, half=32)
+    assert resample.geometry(resample.make_cfg(8000, 8000, zero_crossings=30)) == dict(L=1, M=1, T=61, half=30)
+    assert resample.out_samples(_cfg(16000), 12345) == 12345
+
+
+def test_refusals():
+    L = _lib.lib()
+    out4, INVALID, UNSUPPORTED = (ctypes.c_int32 * 4)(), -1, -2
+    assert L.mkws_resample_geometry(None, out4) == INVALID
+    assert L.mkws_resample_geometry(ctypes.byref(_cfg(48000)), None) == INVALID
+    assert L.mkws_resample_host_taps(None, None, 0) == INVALID
+    assert L.mkws_resample_out_samples(None, 5) == INVALID
+    for bad in (dict(rate=0), dict(rate=-48000), dict(rate_out=0), dict(zero_crossings=0), dict(rolloff=0.0), dict(rolloff=1.5),
+                dict(rolloff=float("nan")), dict(kaiser_beta=-1.0)):
+        cfg = resample.make_cfg(bad.get("rate", 48000), bad.get("rate_out", OUT), **{k: v for k, v in bad.items() if not k.startswith("rate")})
+        assert L.mkws_resample_geometry(ctypes.byref(cfg), out4) == INVALID, bad
+        assert L.mkws_resample_host_taps(ctypes.byref(cfg), None, 0) == INVALID, bad
+        assert L.mkws_resample_out_samples(ctypes.byref(cfg), 10) == INVALID, bad
+        h = ctypes.c_void_p()
+        assert L.mkws_resample_create(ctypes.byref(cfg), ctypes.byref(h)) == INVALID and not h.value, bad
+    assert L.mkws_resample_geometry(ctypes.byref(resample.make_cfg(48000, OUT, rolloff=1.0)), out4) == 0
+    # the table cap: 1 << 22 floats
+    big = resample.make_cfg(15999, 16000, zero_crossings=200)            # 2 * 200 * 16000 + 1 > 1 << 22
+    assert L.mkws_resample_geometry(ctypes.byref(big), out4) == UNSUPPORTED
+    assert b"table" in L.mkws_last_error()
+    assert L.mkws_resample_geometry(ctypes.byref(resample.make_cfg(15999, 16000, zero_crossings=100)), out4) == 0
+    # absurd settings are refused on their factors, before any product of them is formed
+    for huge in (resample.make_cfg(2 ** 31 - 1, 1, zero_crossings=2 ** 31 - 1), resample.make_cfg(1, 2 ** 31 - 1, zero_crossings=2 ** 31 - 1),
+                 resample.make_cfg(3, 2, zero_crossings=2 ** 31 - 1), resample.make_cfg(2 ** 31 - 1, 2 ** 31 - 2)):
+        assert L.mkws_resample_geometry(ctypes.byref(huge), out4) == UNSUPPORTED
+        assert L.mkws_resample_out_samples(ctypes.byref(huge), 10) == UNSUPPORTED
+    # a host_taps buffer that is too small is not written
+    buf = np.full(4, 7.0, np.float32)
+    assert L.mkws_resample_host_taps(ctypes.byref(_cfg(48000)), buf.ctypes.data, 4) == 193 and (buf == 7.0).all()
+    # handle-taking calls refuse a NULL handle before anything else
+    assert L.mkws_resample_create(ctypes.byref(_cfg(48000)), None) == INVALID
+    assert L.mkws_resample_forward(None, None, 0, 1, 1, 1, 1, None, 1, None) == INVALID
+    assert L.mkws_resample_live_in_samples(None, 320) == INVALID
+    assert L.mkws_resample_live_state_bytes(None) == 0
+    assert L.mkws_resample_live_push_many(None, None, 8, 1, None, None, 0, 320, None, None) == INVALID
+    L.mkws_resample_destroy(None)
+
+
+def test_live_geometry():
+    want = {48000: 960, 44100: 882, 32000: 640, 22050: 441, 11025: None, 8000: 160}
+    for rate, n in want.items():
+        if n is None:
+            with pytest.raises(ValueError, match="not a whole number"):
+                resample.live_in_samples(_cfg(rate), 320)
+        else:
+            assert resample.live_in_samples(_cfg(rate), 320) == n
+    assert resample.live_in_samples(_cfg(11025), 640) == 441
+    assert [resample.live_push_hops(r, OUT, 320) for r in RATES] == [1, 1, 1, 1, 2, 1]
+
+
+@pytest.mark.parametrize("rate", RATES)
+def test_emulator_against_analytic_tones(rate, taps):
+    """Six tones below 0.85 Nyq, amplitudes summing to A = 0.8, resampled by the float32 restatement (centred) against the same tones
+    evaluated at the output instants.  Interior samples lie within A * 3.5e-5 + (T + 1) * 2^-24 * 2.5 * A: the passband ripple of
+    test_frequency_response as a ratio (0.0003 dB), and the float32 rounding of T multiply-adds whose |tap| sum is at most 2.5."""
+    g = _formulas(rate)
+    L, M, T, half = g["L"], g["M"], g["T"], g["half"]
+    nyq, A = min(rate, OUT) / 2, 0.8
+    freqs = nyq * np.array([0.03, 0.17, 0.31, 0.52, 0.71, 0.85 - 1e-3])
+    amps = A * np.array([0.3, 0.2, 0.2, 0.1, 0.1, 0.1])
+    phases = np.array([0.1, 1.3, 2.9, 4.1, 5.3, 0.7])
+    n_in = int(0.25 * rate)
+    t_in = np.arange(n_in) / rate
+    x = (amps[:, None] * np.sin(2 * np.pi * freqs[:, None] * t_in + phases[:, None])).sum(0).astype(np.float32)
+    n_out = -(-n_in * L // M)
+    ns = np.arange(n_out)
+    q = (ns * M + half) // L
+    interior = ns[(q - (T - 1) >= 0) & (q < n_in)]
+    assert interior.size > n_out // 2
+    got = polyphase(x, taps[rate], M, half, np.float32, ns=interior)
+    assert got.dtype == np.float32
+    want = (amps[:, None] * np.sin(2 * np.pi * freqs[:, None] * (interior / OUT) + phases[:, None])).sum(0)
+    err = np.abs(got.astype(np.float64) - want).max()
+    bound = A * 3.5e-5 + (T + 1) * 2.0 ** -24 * 2.5 * A
+    print(rate, "worst interior error", err, "bound", bound)
+    assert err <= bound
+
+
+def test_cutter_takes_pcm16_only_when_told():
+    """The live sessions' cutter: with pcm16 (set with input_rate) an int16 chunk is s / 32768; without it nothing changes."""
+    from multilingual_kws_amd.embedding.batch_streaming_analysis import LiveGroupScheduler, LivePushCutter
+    pcm = np.array([-32768, -1, 0, 1, 16384, 32767], np.int16)
+    assert np.array_equal(LivePushCutter(3, pcm16=True).cut(pcm), (pcm.astype(np.float32) / np.float32(32768)).reshape(2, 3))
+    assert np.array_equal(LivePushCutter(3).cut(pcm), pcm.astype(np.float32).reshape(2, 3))
+    mixed = LivePushCutter(4, pcm16=True)
+    assert mixed.cut(pcm[:3]).shape == (0, 4)
+    assert np.array_equal(mixed.cut(np.array([0.25, 0.5], np.float32)), np.array([[-1.0, -1 / 32768, 0.0, 0.25]], np.float32)) and mixed.rest.tolist() == [0.5]
+    active, audio = LiveGroupScheduler(2, 3, pcm16=True).feed({1: pcm[:3]})[0]
+    assert active.tolist() == [0, 1] and np.array_equal(audio[1], pcm[:3].astype(np.float32) / np.float32(32768))
