@@ -227,6 +227,68 @@ int mkws_resample_live_push_many(mkws_resample* rs, void* d_states, size_t state
                                  const void* d_in, int in_i16, int out_samples, float* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * WAV sample data decoded on the device: the bytes of a file's `data` chunk, in any common format and channel layout, become float32
+ * audio in one launch for a whole batch of files.  The reference leaves formats and channels to `sox` / `soxi` (run.py:259-268,
+ * luganda/luganda.py:145, word_extraction.py:223-231).  A FRAME is `channels` consecutive little-endian samples; a sample of b bytes
+ * becomes a float32 by exactly this rule (s = the sign-extended little-endian integer, b0 = the single byte):
+ *   MKWS_PCM_U8     1 byte    (float)((int)b0 - 128) / 128.0f
+ *   MKWS_PCM_S16    2 bytes   (float)s / 32768.0f                    (what decode_wav and the resampler's int16 input do)
+ *   MKWS_PCM_S24    3 bytes   (float)s / 8388608.0f                  (exact)
+ *   MKWS_PCM_S32    4 bytes   (float)s, round to nearest even, times 2^-31   (so 2^31 - 1 gives 1.0f)
+ *   MKWS_PCM_F32    4 bytes   the stored bits
+ *   MKWS_PCM_F64    8 bytes   (float)d, round to nearest even (a result below the smallest normal float is not pinned)
+ *   MKWS_PCM_MULAW  1 byte    u = ~b0 & 0xFF; t = (((u & 0x0F) << 3) + 0x84) << ((u >> 4) & 7); s = (u & 0x80) ? 0x84 - t : t - 0x84;
+ *                             (float)s / 32768.0f                    (G.711 mu-law: +-32124)
+ *   MKWS_PCM_ALAW   1 byte    a = b0 ^ 0x55; t = (a & 0x0F) << 4; seg = (a & 0x70) >> 4; seg 0: t += 8; seg 1: t += 0x108;
+ *                             else t = (t + 0x108) << (seg - 1); s = (a & 0x80) ? t : -t; (float)s / 32768.0f   (G.711 A-law: +-32256)
+ * Channel c >= 0 of a frame is that sample's value.  Channel -1 (MKWS_PCM_MIX) starts from +0.0f, adds the channels' values in channel
+ * order with one float32 add each and divides once by (float)channels: a sequential numpy float32 loop reproduces every bit.
+ * ---------------------------------------------------------------------------------------------- */
+enum {
+  MKWS_PCM_U8 = 0,
+  MKWS_PCM_S16 = 1,
+  MKWS_PCM_S24 = 2,
+  MKWS_PCM_S32 = 3,
+  MKWS_PCM_F32 = 4,
+  MKWS_PCM_F64 = 5,
+  MKWS_PCM_MULAW = 6,
+  MKWS_PCM_ALAW = 7,
+  MKWS_PCM_NUM_FORMATS = 8
+};
+#define MKWS_PCM_MIX (-1)
+
+/* One work item: n_frames frames that start at byte byte_offset of the byte buffer (any byte: no alignment is assumed) become out_len
+ * floats at d_out + out_offset.  48 bytes; a table of them is 8-byte aligned. */
+typedef struct mkws_pcm_item {
+  int64_t byte_offset;
+  int64_t n_frames;
+  int64_t out_offset;   /* in floats */
+  int64_t out_len;
+  int32_t format;       /* MKWS_PCM_* */
+  int32_t channels;
+  int32_t channel;      /* 0 .. channels - 1, or MKWS_PCM_MIX */
+  int32_t reserved;     /* 0 */
+} mkws_pcm_item;
+
+/* Host only (no GPU needed): bytes of one frame = bytes of a sample * channels.  MKWS_ERR_INVALID_ARG for an unknown format, channels < 1
+ * and a product above INT32_MAX. */
+int mkws_pcm_frame_bytes(int format, int channels);
+
+/* d_bytes uint8 [n_bytes], d_items [n_items] (device memory, like the route tables), d_out float32 [out_floats], d_invalid int32 [1].
+ * For item k and i in [0, out_len): d_out[out_offset + i] = the value of frame i if i < n_frames, else +0.0f -- the launch writes the
+ * zero padding itself, and out_len < n_frames truncates.  The kernel checks every item before it reads or writes for it, in 64-bit:
+ * format in [0, MKWS_PCM_NUM_FORMATS), channels >= 1, -1 <= channel < channels, n_frames >= 0, 0 <= out_len <= max_out_len,
+ * 0 <= byte_offset <= n_bytes with all n_frames frames inside [byte_offset, n_bytes), and [out_offset, out_offset + out_len) inside
+ * [0, out_floats).  An item that fails writes nothing and adds 1 to *d_invalid (set to 0 by every call that launches); the other items
+ * are unaffected.  No byte outside [0, n_bytes) is read and no float outside an item's own range is written; the ranges of two items
+ * should not overlap (the order of their stores is then undefined).  MKWS_ERR_INVALID_ARG for negative sizes and NULL buffers,
+ * MKWS_ERR_UNSUPPORTED for a grid of n_items * ceil(max_out_len / 1024) workgroups beyond one launch; n_items == 0 or max_out_len == 0
+ * returns MKWS_OK with nothing launched (and *d_invalid untouched).  One launch for any n_items, asynchronous on `stream`, allocates
+ * nothing, never synchronises: capturable. */
+int mkws_pcm_decode(const uint8_t* d_bytes, int64_t n_bytes, const mkws_pcm_item* d_items, int n_items, int64_t max_out_len, float* d_out,
+                    int64_t out_floats, int32_t* d_invalid, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Embedding model.  Replaces `embedding.predict(x)` on the Keras model
  *   EfficientNetB0(include_top=False, weights=None, input_shape=(49,40,1)) -> GAP ->
  *   Dense 2048 relu -> Dense 2048 relu -> Dense 1024 selu ("dense_2")

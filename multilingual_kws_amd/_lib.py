@@ -45,6 +45,12 @@ class ResampleCfg(ctypes.Structure):
                 ("kaiser_beta", ctypes.c_float), ("rolloff", ctypes.c_float)]
 
 
+class PcmItem(ctypes.Structure):
+    """mkws_pcm_item (include/mkws.h)."""
+    _fields_ = [("byte_offset", ctypes.c_int64), ("n_frames", ctypes.c_int64), ("out_offset", ctypes.c_int64), ("out_len", ctypes.c_int64),
+                ("format", ctypes.c_int32), ("channels", ctypes.c_int32), ("channel", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 # every symbol include/mkws.h declares: (name, restype, argtypes)
 _P, _I, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _CFG = ctypes.POINTER(FrontendCfg)
@@ -74,6 +80,8 @@ SYMBOLS = [
     ("mkws_resample_live_in_samples", _I, [_P, _I]),
     ("mkws_resample_live_state_bytes", _SZ, [_P]),
     ("mkws_resample_live_push_many", _I, [_P, _P, _SZ, _I, _P, _P, _I, _I, _P, _P]),
+    ("mkws_pcm_frame_bytes", _I, [_I, _I]),
+    ("mkws_pcm_decode", _I, [_P, _I64, _P, _I, _I64, _P, _I64, _P, _P]),
     ("mkws_embed_weight_count", _SZ, []),
     ("mkws_embed_weight_manifest", _I, [ctypes.c_char_p, _SZ]),
     ("mkws_embed_create", _I, [_P, _SZ, _I, ctypes.POINTER(_P)]),

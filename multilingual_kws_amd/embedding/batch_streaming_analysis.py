@@ -1313,24 +1313,33 @@ def operating_curves(inferences, flags: StreamFlags, thresholds, groundtruth, ke
 
 
 def _shared_embedding_passes(keywords, models, wav, groundtruth, thresholds, inference_chunk_len_seconds, average_window_duration_ms,
-                             suppression_ms, time_tolerance_ms, resample=False):
+                             suppression_ms, time_tolerance_ms, resample=False, channel=0):
     """What multi_keyword_detections and multi_keyword_operating_curves do with a recording before their detector runs: the argument
     checks and the wav are done when this returns -> (keywords as a list, the StreamFlags of the run, sample rate, samples of the
     recording, an iterator over the distinct embeddings of `models` that yields (indices of the models on it, their softmax outputs
     [len(indices), windows, 3] on the device): one streaming_inferences pass each).  resample=True: a recording at another rate than the
-    model's is converted on the device first (input_data.to_sample_rate, centred); rate and samples are then the converted audio's."""
+    model's is converted on the device first (input_data.to_sample_rate, centred); rate and samples are then the converted audio's.
+    With resample=True the recording may have any supported WAV format and `channel` (an int, or "mix") selects what is heard: it is
+    read by input_data.read_recording, unless it is the first channel of a 16-bit PCM file at the model's rate, which is decoded on the
+    host as before.  The default path reads the first channel of a 16-bit PCM file and takes no other channel."""
     keywords, models = list(keywords), list(models)
     if len(models) != len(keywords) or len(set(keywords)) != len(keywords):
         raise ValueError(f"discrepancy: {len(models)} models provided for {len(set(keywords))} keywords")
     if inference_chunk_len_seconds <= 0:
         raise ValueError("inference_chunk_len_seconds must be positive")
-    with open(wav, "rb") as f:
-        audio, sample_rate = input_data.decode_wav(f.read())
     model_settings = input_data.standard_microspeech_model_settings(label_count=3)
-    if resample and sample_rate != model_settings["sample_rate"]:
-        import torch
-        audio = input_data.to_sample_rate(torch.from_numpy(audio).cuda(), sample_rate, model_settings["sample_rate"])   # stays on the device
+    if not resample and channel != 0:
+        raise ValueError(f"channel={channel!r} needs resample=True: the default path reads the first channel of a 16-bit PCM file")
+    with open(wav, "rb") as f:
+        image = f.read()
+    if resample:
+        from .. import pcm
+        info = pcm.wav_info(image)
+    if resample and (info.rate != model_settings["sample_rate"] or info.format != "s16" or channel != 0):
         sample_rate = model_settings["sample_rate"]
+        audio = input_data.read_recording(image, sample_rate, channel)                # decoded and converted on the device, stays there
+    else:                                                                             # nothing to convert: taken as it is, as before
+        audio, sample_rate = input_data.decode_wav(image)
     flags = StreamFlags(wav=wav, ground_truth=groundtruth, target_keyword=keywords[0] if keywords else "", detection_thresholds=thresholds,
                         average_window_duration_ms=average_window_duration_ms, suppression_ms=suppression_ms,
                         time_tolerance_ms=time_tolerance_ms, max_chunk_length_sec=inference_chunk_len_seconds)
@@ -1347,15 +1356,16 @@ def _shared_embedding_passes(keywords, models, wav, groundtruth, thresholds, inf
 
 def multi_keyword_operating_curves(keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds=1200,
                                    average_window_duration_ms=100, suppression_ms=500, time_tolerance_ms=750, num_nontarget_words=None,
-                                   resample=False):
+                                   resample=False, channel=0):
     """From a recording to {keyword: [tpr_fpr's dict per threshold]} for N keywords: one pass over the wav on the shared embedding
     (streaming_inferences(as_device=True), as multi_keyword_detections), then operating_curves on the device tensor -- the probabilities,
     the detections and the matching never visit the host.  groundtruth_csv: rows `keyword,time_ms` (run.py's ground-truth file).  The
-    other arguments are multi_keyword_detections' flags (resample too); the recording's duration is its sample count over its sample rate."""
+    other arguments are multi_keyword_detections' flags (resample and channel too); the recording's duration is its sample count over its
+    sample rate."""
     thresholds = list(thresholds)
     keywords, flags, sample_rate, data_samples, passes = _shared_embedding_passes(
         keywords, models, wav, groundtruth_csv, thresholds, inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, time_tolerance_ms,
-        resample=resample)
+        resample=resample, channel=channel)
     groundtruth_data = _read_groundtruth(groundtruth_csv)
     curves = {}
     for idxs, got in passes:
@@ -1444,7 +1454,7 @@ def eval_stream_test(st: StreamTarget, live_model=None):
 
 
 def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inference_chunk_len_seconds=1200, groundtruth=None,
-                             average_window_duration_ms=100, suppression_ms=500, write_detections=None, resample=False):
+                             average_window_duration_ms=100, suppression_ms=500, write_detections=None, resample=False, channel=0):
     """The detections dict of run.py:89-152 for N keywords from ONE pass over the recording.
 
     The reference loads one full Keras model per keyword and repeats the window loop, the micro-frontend and the EfficientNet forward
@@ -1456,11 +1466,12 @@ def multi_keyword_detections(keywords, models, wav, detection_threshold=0.9, inf
     confidence, groundtruth)], min_threshold=...): groundtruth "ng" without a ground-truth file, otherwise tpr_fpr.get_groundtruth's
     classification against its rows `keyword,time_ms` (as shipped: first keyword only).  Also written as JSON to write_detections.
     resample=True: a recording whose rate differs from the model's 16 kHz is converted on the device (resample.Resampler, centred) before
-    windowing, and the times are those of the converted audio; with the default the recording is taken as it is."""
+    windowing, and the times are those of the converted audio; with the default the recording is taken as it is.  With resample=True the
+    file may have any supported WAV format and `channel` (an int, or "mix") selects which channel is heard."""
     import json
     keywords, flags, sample_rate, data_samples, passes = _shared_embedding_passes(
         keywords, models, wav, groundtruth, [detection_threshold], inference_chunk_len_seconds, average_window_duration_ms, suppression_ms, 750,
-        resample=resample)
+        resample=resample, channel=channel)
     per_keyword = [None] * len(keywords)                            # keyword -> its found_words_w_confidences
     for idxs, got in passes:
         found = detect_many(got, flags, [detection_threshold], sample_rate, data_samples=data_samples, keywords=[keywords[i] for i in idxs])

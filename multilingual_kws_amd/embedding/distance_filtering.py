@@ -27,15 +27,16 @@ def embedding_model(base_model_path="synthetic", base_model_output="dense_2", ma
     return model
 
 
-def embed_files(files, embedding, model_settings=None, batch_size=1024):
-    """dataperf_experiments.py:320-338: list of WAV paths -> float32 [N, 1024], in batches of `batch_size`."""
+def embed_files(files, embedding, model_settings=None, batch_size=1024, convert=False):
+    """dataperf_experiments.py:320-338: list of WAV paths -> float32 [N, 1024], in batches of `batch_size`.  convert=True: the files may
+    have any supported format, rate and channel count (input_data.read_clips: channel 0, decoded and converted on the device)."""
     if model_settings is None:
         model_settings = input_data.standard_microspeech_model_settings(label_count=3)
     files = [str(f) for f in files]
     out = np.zeros((len(files), 1024), dtype=np.float32)
     for s in range(0, len(files), batch_size):
         chunk = files[s:s + batch_size]
-        out[s:s + len(chunk)] = embedding.predict(_specs_for_files(chunk, model_settings))
+        out[s:s + len(chunk)] = embedding.predict(_specs_for_files(chunk, model_settings, convert=True) if convert else _specs_for_files(chunk, model_settings))
     return out
 
 
@@ -86,16 +87,20 @@ def _sklearn_fit(vectors, n_clusters, seed):
     return km.cluster_centers_.astype(np.float32), km.labels_.astype(np.int32), int(km.n_iter_)
 
 
-def _spec_batches(files, embedding, model_settings):
+def _spec_batches(files, embedding, model_settings, convert=False):
     """Decode and featurise `files` in batches of the handle's max_batch: yields (first row, CUDA spectrograms)."""
     import torch
     n_samples, mb = model_settings["desired_samples"], embedding.max_batch
     for s in range(0, len(files), mb):
+        if convert:
+            audio = input_data.read_clips(files[s:s + mb], model_settings["sample_rate"], n_samples, device=embedding.device)
+            yield s, input_data.to_micro_spectrogram(model_settings, audio)
+            continue
         audio = np.stack([input_data._read_wav(f, n_samples) for f in files[s:s + mb]])
         yield s, input_data.to_micro_spectrogram(model_settings, torch.from_numpy(audio).to(embedding.device))
 
 
-def cluster_and_sort_many(keyword_samples, embedding_model, seed=123, n_train=50, n_clusters=5, model_settings=None):
+def cluster_and_sort_many(keyword_samples, embedding_model, seed=123, n_train=50, n_clusters=5, model_settings=None, convert=False):
     """cluster_and_sort for K keywords on one embedding handle.  keyword_samples: K lists of paths; seed: an int or K ints.
     -> K dicts: the four keys of cluster_and_sort with the same types (sorted_clips, cluster_centers float32 [n_clusters, 1024],
     distances float32, train_clips) and labels (of the train clips), n_iter, nearest (the centre each eval clip is nearest to, in sorted
@@ -106,7 +111,8 @@ def cluster_and_sort_many(keyword_samples, embedding_model, seed=123, n_train=50
     mkws_kmeans_fit clusters the chunk (multilingual_kws_amd/kmeans.py: kmeans_host is the specification, held to sklearn), and
     mkws_kmeans_nearest runs on every batch of eval embeddings while it is on the device: no eval embedding is retained or copied, 8
     bytes per eval clip come back.  The distance is (float32) sqrt(sum((float64)centre - (float64)x)^2) against the float32 centres.
-    An embedding_model without a device `forward`, or a host without a GPU, takes the same flow through `predict` and kmeans_host."""
+    An embedding_model without a device `forward`, or a host without a GPU, takes the same flow through `predict` and kmeans_host.
+    convert=True: the clips may have any supported format, rate and channel count (input_data.read_clips, channel 0)."""
     import torch
     from .. import kmeans
     if model_settings is None:
@@ -128,13 +134,13 @@ def cluster_and_sort_many(keyword_samples, embedding_model, seed=123, n_train=50
     if not (hasattr(embedding_model, "forward") and torch.cuda.is_available()):
         results = []
         for k in range(K):
-            vectors = embed_files(train[k], embedding_model, model_settings)
+            vectors = embed_files(train[k], embedding_model, model_settings, convert=convert)
             fit = kmeans.kmeans_host(vectors, n_clusters, seeds[k])
             if fit.empty:
                 centers, labels, n_iter = _sklearn_fit(vectors, n_clusters, seeds[k])
             else:
                 centers, labels, n_iter = fit.centers.astype(np.float32), fit.labels, fit.n_iter
-            dist, which = kmeans.nearest_host(embed_files(evals[k], embedding_model, model_settings), centers)
+            dist, which = kmeans.nearest_host(embed_files(evals[k], embedding_model, model_settings, convert=convert), centers)
             results.append(_result(evals[k], train[k], centers, dist, which, labels, n_iter, fit.empty))
         return results
 
@@ -153,7 +159,7 @@ def cluster_and_sort_many(keyword_samples, embedding_model, seed=123, n_train=50
             d_train = torch.empty((len(train_files), dim), dtype=torch.float32, device=dev)
 
             def fit_pass():
-                for s, spec in _spec_batches(train_files, embedding_model, model_settings):
+                for s, spec in _spec_batches(train_files, embedding_model, model_settings, convert):
                     embedding_model.forward(spec, out=d_train[s:s + spec.shape[0]])
                 return kmeans.kmeans_fit_on_device(d_train, offsets, n_clusters, [seeds[k] for k in ks])     # ends in the copy back
 
@@ -173,7 +179,7 @@ def cluster_and_sort_many(keyword_samples, embedding_model, seed=123, n_train=50
                 d_emb = torch.empty((min(mb, n_eval), dim), dtype=torch.float32, device=dev)
                 d_out = torch.empty(2 * n_eval + n_batches, dtype=torch.int32, device=dev)     # distances, indices, a counter per batch
                 d_dist, d_which = d_out[:n_eval].view(torch.float32), d_out[n_eval:2 * n_eval]
-                for b, (s, spec) in enumerate(_spec_batches(eval_files, embedding_model, model_settings)):
+                for b, (s, spec) in enumerate(_spec_batches(eval_files, embedding_model, model_settings, convert)):
                     r = spec.shape[0]
                     embedding_model.forward(spec, out=d_emb[:r])
                     kmeans.nearest_on_device(d_emb[:r], d_group[s:s + r], fit.d_centers,
@@ -192,11 +198,11 @@ def cluster_and_sort_many(keyword_samples, embedding_model, seed=123, n_train=50
     return results
 
 
-def export_keyword_embeddings(clips_dir, dest_dir, embedding, model_settings=None, batch_size=1024, keywords=None):
+def export_keyword_embeddings(clips_dir, dest_dir, embedding, model_settings=None, batch_size=1024, keywords=None, convert=False):
     """dataperf_experiments.py:385-415: for every keyword directory under clips_dir write
     dest_dir/<keyword>.parquet with columns clip_id (path relative to clips_dir) and mswc_embedding_vector.
     Existing parquets are skipped (resume) and so are empty keyword directories, as in the reference loop.
-    Returns the list of files written."""
+    Returns the list of files written.  convert: embed_files' switch."""
     import pandas as pd
     clips_dir, dest_dir = Path(clips_dir), Path(dest_dir)
     dest_dir.mkdir(parents=True, exist_ok=True)
@@ -208,7 +214,7 @@ def export_keyword_embeddings(clips_dir, dest_dir, embedding, model_settings=Non
         dest = dest_dir / f"{keyword}.parquet"
         if dest.exists() or len(keyword_samples) == 0:
             continue
-        feature_vecs = embed_files(keyword_samples, embedding, model_settings, batch_size)
+        feature_vecs = embed_files(keyword_samples, embedding, model_settings, batch_size, convert=convert)
         id_paths = [str(fp.relative_to(clips_dir)) for fp in keyword_samples]
         df = pd.DataFrame(data=dict(clip_id=id_paths, mswc_embedding_vector=pd.Series(list(feature_vecs))))
         df.to_parquet(dest)

@@ -154,6 +154,146 @@ def read_wav_at(path, sample_rate=16000, desired_samples=-1):
     return x
 
 
+# ---------------------------------------------------------------------------------------------------
+# WAV files of any format, rate and channel layout, decoded on the device (pcm.py)
+# ---------------------------------------------------------------------------------------------------
+class _PinnedBytes:
+    """One pinned staging buffer per process for the sample bytes of a batch of files: it grows, and it is handed out again only after
+    the upload that read it has run (its event)."""
+
+    def __init__(self):
+        self.host, self.event = None, None
+
+    def take(self, total):
+        import torch
+        if self.event is not None:
+            self.event.synchronize()
+        if self.host is None or self.host.numel() < total:
+            self.host = torch.empty(max(total, 1 << 20), dtype=torch.uint8).pin_memory()
+        return self.host
+
+    def upload(self, total, device):
+        import torch
+        dev = torch.empty(total, dtype=torch.uint8, device=device)
+        dev.copy_(self.host[:total], non_blocking=True)
+        self.event = self.event or torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(device))
+        return dev
+
+
+_pinned_bytes = _PinnedBytes()
+
+
+def _wav_image(f):
+    """A path -> the file's bytes; bytes, bytearray and memoryview are taken as the file's contents."""
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return f
+    with open(f, "rb") as fh:
+        return fh.read()
+
+
+def _cuda_device(device):
+    import torch
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _upload_sample_bytes(images, infos, takes, device):
+    """The first takes[i] frames of every file's data chunk, each at a multiple of 16 bytes of ONE pinned buffer, and its single
+    asynchronous upload -> (uint8 device tensor, the byte offset of every file's frames in it)."""
+    offsets, total = [], 0
+    for info, take in zip(infos, takes):
+        offsets.append(total)
+        total += (take * info.frame_bytes + 15) & ~15
+    total = max(total, 16)
+    hv = _pinned_bytes.take(total).numpy()
+    for image, info, take, o in zip(images, infos, takes, offsets):
+        nb = take * info.frame_bytes
+        hv[o:o + nb] = np.frombuffer(image, dtype=np.uint8, count=nb, offset=info.data_offset)
+    return _pinned_bytes.upload(total, device), offsets
+
+
+def read_clips(files, sample_rate=16000, desired_samples=16000, channel=0, device=None):
+    """WAV files of any supported format (pcm.wav_info), rate and channel count -> float32 CUDA tensor [len(files), desired_samples] at
+    sample_rate: row i is file i's channel `channel` (an int, or "mix" for the mean of the channels), converted on the device when the
+    file's rate differs (to_sample_rate's filter, centred), zero-padded or truncated to desired_samples.  The sample bytes of all files
+    travel in one upload and are decoded by one mkws_pcm_decode launch; the resampler runs once per distinct rate.  For a 16-bit PCM
+    file at sample_rate a row is _read_wav(f, desired_samples) bit for bit, at another rate read_wav_at(f, sample_rate,
+    desired_samples).  An entry of `files` may also be the file's bytes."""
+    import torch
+    from .. import pcm
+    files, n = list(files), int(desired_samples)
+    if n < 1:
+        raise ValueError(f"read_clips: desired_samples = {desired_samples} (at least 1)")
+    dev, ch = _cuda_device(device), pcm.channel_index(channel)
+    B = len(files)
+    if B == 0:
+        return torch.zeros((0, n), dtype=torch.float32, device=dev)
+    images = [_wav_image(f) for f in files]
+    infos = [pcm.wav_info(b) for b in images]
+    takes, groups = [0] * B, {}
+    for i, info in enumerate(infos):
+        if not -1 <= ch < info.channels:
+            raise ValueError(f"read_clips: channel {channel!r} of file {i}, which has {info.channels} channels")
+        if info.rate == int(sample_rate):
+            takes[i] = min(info.frames, n)
+        else:
+            # output j reads inputs up to (j * M + half) div L (include/mkws.h): the first n outputs depend on no frame beyond this one
+            g = _resampler_for(info.rate, sample_rate, dev).geometry
+            takes[i] = min(info.frames, ((n - 1) * g["M"] + g["half"]) // g["L"] + 1)
+            groups.setdefault(info.rate, []).append(i)
+    with torch.cuda.device(dev):
+        d_bytes, offsets = _upload_sample_bytes(images, infos, takes, dev)
+        # the output: the result's B rows, then one scratch block [rows, widest row] per foreign rate
+        rows, floats, blocks = [None] * B, B * n, {}
+        for rate, idx in groups.items():
+            width = max(1, max(takes[i] for i in idx))
+            blocks[rate] = (floats, width)
+            for j, i in enumerate(idx):
+                rows[i] = (floats + j * width, width)
+            floats += len(idx) * width
+        for i, info in enumerate(infos):
+            if rows[i] is None:
+                rows[i] = (i * n, n)
+        items = pcm.make_items([(offsets[i], takes[i], rows[i][0], rows[i][1], infos[i].format, infos[i].channels, ch) for i in range(B)])
+        flat = pcm.decode_on_device(d_bytes, items, out_floats=floats)
+        result = flat[:B * n].view(B, n)
+        for rate, idx in groups.items():
+            rs = _resampler_for(rate, sample_rate, dev)
+            base, width = blocks[rate]
+            y = rs.forward(flat[base:base + len(idx) * width].view(len(idx), width), centred=True)
+            m = min(n, y.shape[1])
+            # a shorter row inside the zero-padded block keeps the filter's tail past its own end: zero what read_wav_at never computes
+            meta = torch.tensor([idx, [min(n, rs.out_samples(infos[i].frames)) for i in idx]], dtype=torch.int64).to(dev, non_blocking=True)
+            keep = torch.arange(m, device=dev)[None, :] < meta[1][:, None]
+            block = torch.zeros((len(idx), n), dtype=torch.float32, device=dev)
+            block[:, :m] = torch.where(keep, y[:, :m], torch.zeros((), dtype=torch.float32, device=dev))
+            result.index_copy_(0, meta[0], block)
+    return result.clone() if groups else result      # without the scratch blocks behind it
+
+
+def read_recording(path, sample_rate=16000, channel=0, device=None):
+    """One WAV file of any supported format, rate and channel count, whole -> float32 CUDA tensor [samples] at sample_rate: the chain of
+    read_clips for one long file (decoded by mkws_pcm_decode, converted by to_sample_rate's resampler when the rate differs).  For a
+    16-bit PCM file it is to_sample_rate(decode_wav(...)) bit for bit."""
+    import torch
+    from .. import pcm
+    dev, ch = _cuda_device(device), pcm.channel_index(channel)
+    image = _wav_image(path)
+    info = pcm.wav_info(image)
+    if not -1 <= ch < info.channels:
+        raise ValueError(f"read_recording: channel {channel!r} of a file with {info.channels} channels")
+    if info.frames == 0:
+        return torch.zeros(0, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        d_bytes, offsets = _upload_sample_bytes([image], [info], [info.frames], dev)
+        x = pcm.decode_on_device(d_bytes, pcm.make_items([(offsets[0], info.frames, 0, info.frames, info.format, info.channels, ch)]),
+                                 out_floats=info.frames)
+        if info.rate != int(sample_rate):
+            x = _resampler_for(info.rate, sample_rate, dev).forward(x, centred=True)
+    return x
+
+
 def load_unknown_files(unknown_words_dir, listing="unknown_files.txt"):
     """The unknown-words bank layout the reference's few-shot CLI consumes (run.py:272-278): a directory holding
     `unknown_files.txt`, one WAV path per line relative to that directory.  Returns absolute-ish path strings."""
@@ -383,8 +523,12 @@ class BatchGroups:
 class AudioDataset:
     def __init__(self, model_settings, commands, background_data_dir, unknown_files, time_shift_ms=100,
                  background_frequency=0.8, background_volume_range=0.1, silence_percentage=10.0,
-                 unknown_percentage=10.0, spec_aug_params=SpecAugParams(), seed=None) -> None:
+                 unknown_percentage=10.0, spec_aug_params=SpecAugParams(), seed=None, convert=False) -> None:
+        """convert=True: the clip files (training shots, validation set, unknown bank) and the background tracks may have any supported
+        format, rate and channel count; they are decoded and brought to the model's rate on the device (read_clips / read_recording,
+        channel 0).  With the default every file is taken as 16-bit PCM at the model's rate."""
         self.model_settings = model_settings
+        self.convert = bool(convert)
         self._device = None
         self.rng = np.random.default_rng(seed)
         self.get_background_data(background_data_dir)
@@ -425,6 +569,9 @@ class AudioDataset:
         tracks = []
         if background_dir is not None:
             for p in sorted(glob.glob(os.path.join(background_dir, "*.wav"))):
+                if self.convert:           # whole files at the model's rate; the host copy feeds the single-clip helpers below
+                    tracks.append(read_recording(p, self.model_settings["sample_rate"]).cpu().numpy())
+                    continue
                 tracks.append(_read_wav(p))
         self.background_sizes = np.asarray([t.shape[0] for t in tracks], dtype=np.int64)
         if tracks:
@@ -461,6 +608,8 @@ class AudioDataset:
     def _upload_bank(self, files):
         import torch
         n = self.model_settings["desired_samples"]
+        if self.convert and len(files):
+            return read_clips(files, self.model_settings["sample_rate"], n, device=self.device)
         arr = np.zeros((max(1, len(files)), n), dtype=np.float32)
         for i, f in enumerate(files):
             arr[i] = _read_wav(f, n)

@@ -359,6 +359,7 @@ def transfer_learn_many(
     verbose=1,
     seed=None,
     side_by_side=None,
+    convert=False,
 ):
     """transfer_learn for several target keywords on ONE frozen embedding, their heads trained side by side.
 
@@ -373,7 +374,8 @@ def transfer_learn_many(
 
     There is no backprop_into_embedding here: that phase trains one embedding per keyword and has nothing to share -- call
     transfer_learn.  Under torch.distributed with more than one rank the targets run one after the other through transfer_learn (same
-    results; one collective per optimizer step, as there), and each model has its own embedding handle."""
+    results; one collective per optimizer step, as there), and each model has its own embedding handle.
+    convert: AudioDataset's switch (clip files and background tracks of any supported format, rate and channel count)."""
     from ..embedding_model import OUTPUT_LAYERS
     targets = list(targets)
     if len(targets) == 0:
@@ -395,7 +397,7 @@ def transfer_learn_many(
         raise ValueError("side_by_side must be at least 1")
     common = dict(unknown_files=unknown_files, num_epochs=num_epochs, num_batches=num_batches, batch_size=batch_size, primary_lr=primary_lr,
                   model_settings=model_settings, base_model_path=base_model_path, base_model_output=base_model_output,
-                  UNKNOWN_PERCENTAGE=UNKNOWN_PERCENTAGE, bg_datadir=bg_datadir, verbose=verbose)
+                  UNKNOWN_PERCENTAGE=UNKNOWN_PERCENTAGE, bg_datadir=bg_datadir, verbose=verbose, convert=convert)
     if parallel.world_size() > 1:
         return [transfer_learn(t, train_files[i], val_files[i], backprop_into_embedding=False, embedding_lr=0, csvlog_dest=csvs[i],
                                seed=seeds[i], **common) for i, t in enumerate(targets)]
@@ -415,7 +417,7 @@ def transfer_learn_many(
             xfers.append(TransferLearnedModel(embedding, head, blob, str(base_model_path)))
             ds = input_data.AudioDataset(model_settings=model_settings, commands=[targets[i]], background_data_dir=bg_datadir,
                                          unknown_files=unknown_files, unknown_percentage=UNKNOWN_PERCENTAGE,
-                                         spec_aug_params=input_data.SpecAugParams(percentage=80), seed=seeds[i])
+                                         spec_aug_params=input_data.SpecAugParams(percentage=80), seed=seeds[i], convert=convert)
             if donor is None:
                 donor = ds
             else:
@@ -506,10 +508,11 @@ def transfer_learn(
     csvlog_dest: Optional[os.PathLike] = None,
     verbose=1,
     seed=None,
+    convert=False,
 ):
     """Single-target few-shot fine-tune; see the reference's docstring ("this only works for
     single-target models").  Extra keyword: `seed` (augmentation + head init; rank is added under DP).
-    batch_size is the PER-RANK batch under torch.distributed (weak scaling)."""
+    batch_size is the PER-RANK batch under torch.distributed (weak scaling).  convert: AudioDataset's switch."""
     from ..embedding_model import OUTPUT_LAYERS
     if base_model_output not in OUTPUT_LAYERS:       # reference :38-42 cuts at get_layer(name=base_model_output)
         raise ValueError(f"base_model_output {base_model_output!r}: this build cuts the embedding at one of {sorted(OUTPUT_LAYERS)}")
@@ -537,6 +540,7 @@ def transfer_learn(
         unknown_percentage=UNKNOWN_PERCENTAGE,
         spec_aug_params=input_data.SpecAugParams(percentage=80),
         seed=None if seed is None else int(seed) + 1000003 * rank,   # decorrelated per-rank streams
+        convert=convert,
     )
     train_ds, val_ds = _few_shot_datasets(audio_dataset, train_files, val_files, batch_size)
 
@@ -601,10 +605,14 @@ def transfer_learn(
     return _finish(xfer, history, target, num_epochs, batch_size, num_batches, csvlog_dest if rank == 0 else None)
 
 
-def _specs_for_files(files, model_settings):
-    """file2spec over a list, batched: decode on the host, one frontend launch for all clips."""
+def _specs_for_files(files, model_settings, convert=False):
+    """file2spec over a list, batched: decode on the host, one frontend launch for all clips.  convert=True: decoded and brought to the
+    model's rate on the device instead (input_data.read_clips, channel 0)."""
     import torch
     n = model_settings["desired_samples"]
+    if convert and len(files):
+        audio = input_data.read_clips(files, model_settings["sample_rate"], n)
+        return input_data.to_micro_spectrogram(model_settings, audio).cpu().numpy()
     audio = np.stack([input_data._read_wav(f, n) for f in files]) if len(files) else np.zeros((0, n), np.float32)
     if len(files) == 0:
         return np.zeros((0, model_settings["spectrogram_length"], model_settings["fingerprint_width"]), np.float32)
@@ -671,10 +679,12 @@ def _shared_embedding(models):
     return embedding, heads
 
 
-def evaluate_files_many(files_to_evaluate: List[os.PathLike], models, model_settings: Dict, as_device=False):
+def evaluate_files_many(files_to_evaluate: List[os.PathLike], models, model_settings: Dict, as_device=False, convert=False):
     """evaluate_files_single_target for K models on one embedding handle: every clip is decoded, featurised and embedded ONCE (in
     batches of the handle's max_batch) and all K heads run in one launch per batch.  -> preds [K, N, classes], numpy or (as_device=True)
-    a CUDA tensor; preds[k] has the bits of evaluate_files_single_target(files_to_evaluate, 2, models[k], model_settings)[1]."""
+    a CUDA tensor; preds[k] has the bits of evaluate_files_single_target(files_to_evaluate, 2, models[k], model_settings)[1].
+    convert=True: the files may have any supported format, rate and channel count; each batch is decoded and brought to the model's rate
+    on the device (input_data.read_clips, channel 0).  With the default a file is taken as 16-bit PCM at the model's rate."""
     import torch
     embedding, heads = _shared_embedding(models)
     files = [os.fspath(f) for f in files_to_evaluate]
@@ -682,6 +692,10 @@ def evaluate_files_many(files_to_evaluate: List[os.PathLike], models, model_sett
     specs = []                                           # featurised once, whatever happens to the embedding passes below
     with torch.cuda.device(embedding.device):
         for s in range(0, len(files), mb):
+            if convert:
+                audio = input_data.read_clips(files[s:s + mb], model_settings["sample_rate"], n_samples, device=embedding.device)
+                specs.append(input_data.to_micro_spectrogram(model_settings, audio))
+                continue
             audio = np.stack([input_data._read_wav(f, n_samples) for f in files[s:s + mb]])
             specs.append(input_data.to_micro_spectrogram(model_settings, torch.from_numpy(audio).to(embedding.device)))
 
@@ -698,14 +712,15 @@ def evaluate_files_many(files_to_evaluate: List[os.PathLike], models, model_sett
     return embedding.checked(run)
 
 
-def classification_curves(models, target_files, unknown_files, model_settings: Optional[Dict] = None, thresholds=None, multiclass=False):
+def classification_curves(models, target_files, unknown_files, model_settings: Optional[Dict] = None, thresholds=None, multiclass=False,
+                          convert=False):
     """The classification ROC of K keyword models on one embedding handle (the reference's batch_transfer_learning_analysis.py:114-171
     followed by roc_single_target, one keyword at a time there).  target_files / unknown_files: K lists of WAV paths, model k's target
     clips and its non-target clips; the lists may overlap (one non-target pool for all keywords is the usual case) and a path listed
     twice counts twice.  Every distinct path is embedded once, all heads run in one launch per batch (evaluate_files_many) and the counts
     are taken on the device (transfer_learning_analysis.roc_many): no probability leaves the device.
     -> one dict per keyword: tprs, fprs, threshs (what roc_single_target -- multiclass=True: roc_sc -- returns for that keyword's
-    confidences, at `thresholds`, default the reference's 101), n_target, n_unknown."""
+    confidences, at `thresholds`, default the reference's 101), n_target, n_unknown.  convert: evaluate_files_many's switch."""
     from .transfer_learning_analysis import roc_many
     models = list(models)
     _shared_embedding(models)
@@ -717,7 +732,7 @@ def classification_curves(models, target_files, unknown_files, model_settings: O
     row = {}                                             # distinct paths in first-seen order
     positives = [[row.setdefault(os.fspath(f), len(row)) for f in fs] for fs in target_files]
     negatives = [[row.setdefault(os.fspath(f), len(row)) for f in fs] for fs in unknown_files]
-    preds = evaluate_files_many(list(row), models, model_settings, as_device=True)
+    preds = evaluate_files_many(list(row), models, model_settings, as_device=True, convert=convert)
     curves = roc_many(preds, positives, negatives, thresholds=thresholds, multiclass=multiclass, target_id=2, negative_class=1)
     return [dict(tprs=tprs, fprs=fprs, threshs=threshs, n_target=len(positives[k]), n_unknown=len(negatives[k]))
             for k, (tprs, fprs, threshs) in enumerate(curves)]

@@ -32,12 +32,13 @@ def inference(
     write_detections: Optional[os.PathLike] = None,
     overwrite: bool = False,
     resample: bool = False,
+    channel=0,
 ):
     """Runs inference on a streaming audio file; arguments as the reference's (keywords: list of target words, or one word; modelpaths:
     comma-delimited string of saved few-shot model directories -- a list of paths or of live TransferLearnedModels is accepted too;
     detection_threshold: detector threshold; inference_chunk_len_seconds: chunk length of the recording; write_detections: where to
     write detections.json; resample: convert a recording that is not at 16 kHz on the device first -- the reference expects sox to have
-    done that -- see multi_keyword_detections).  Returns the detections dict (the reference returns None and only writes the file)."""
+    done that -- see multi_keyword_detections; channel: with resample, which channel of the recording is heard, an int or "mix").  Returns the detections dict (the reference returns None and only writes the file)."""
     if isinstance(keywords, str) or len(keywords[0]) == 1:
         print(f"NOTE - assuming a single keyword was passed in: {keywords}")
         keywords = ["".join(keywords)]
@@ -58,7 +59,7 @@ def inference(
     models = live if len(live) == len(modelpaths) else transfer_learning.load_models_shared(modelpaths)
     detections = sa.multi_keyword_detections(keywords, models, wav, detection_threshold=detection_threshold,
                                              inference_chunk_len_seconds=inference_chunk_len_seconds, groundtruth=groundtruth,
-                                             write_detections=write_detections, resample=resample)
+                                             write_detections=write_detections, resample=resample, channel=channel)
     for d in detections["detections"]:
         print(d)
     return detections
