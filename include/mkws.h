@@ -289,6 +289,61 @@ int mkws_pcm_decode(const uint8_t* d_bytes, int64_t n_bytes, const mkws_pcm_item
                     int64_t out_floats, int32_t* d_invalid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Device audio encoded into WAV sample data: the inverse of the decode above.  Windows of float32 recordings in device memory become
+ * the bytes of MONO sample data in any of the MKWS_PCM_* formats, cut, faded and scaled on the way, in one launch for a whole batch of
+ * files.  The reference leaves all of it to `sox` (`trim`, `fade`, `pad`, `convert`: embedding/word_extraction.py:223-231,
+ * luganda/luganda.ipynb cell 21, notebooks/sox_batch.py).
+ *
+ * One work item: its recording is d_src[src_offset .. src_offset + src_len) of a flat float32 buffer.  For i in [0, n_frames)
+ *   x = d_src[src_offset + start + i]  if 0 <= start + i < src_len,  else +0.0f      (zero padding on either side needs no buffer)
+ *   f = f_in * f_out,  f_in  = (float)i / (float)fade_in                    if i < fade_in,              else 1.0f
+ *                      f_out = (float)(n_frames - 1 - i) / (float)fade_out  if i >= n_frames - fade_out, else 1.0f
+ *   v = (x * gain) * f                                  (every product and quotient one float32 operation, round to nearest even)
+ * and the sample of v goes to bytes [byte_offset + i * b, byte_offset + (i + 1) * b) of the byte buffer, little-endian, b = the
+ * sample's size.  With gain == 1.0f and no fade a finite x passes through bit for bit.  rint rounds half-way cases to even:
+ *   MKWS_PCM_U8     rint(v * 128.0f) + 128 clamped to [0, 255]
+ *   MKWS_PCM_S16    q = rint(v * 32768.0f) clamped to [-32768, 32767]
+ *   MKWS_PCM_S24    rint(v * 8388608.0f) clamped to [-8388608, 8388607]
+ *   MKWS_PCM_S32    t = v * 2147483648.0f;  t >= 2^31: 2^31 - 1;  t <= -2^31: -2^31;  else rint(t)
+ *   MKWS_PCM_F32    the bits of v
+ *   MKWS_PCM_F64    (double)v
+ *   MKWS_PCM_MULAW  m = q >> 2; mask = 0xFF; m < 0: m = -m, mask = 0x7F; m = min(m, 8159) + 33; seg = the first of the segment ends
+ *                   0x3F, 0x7F, ..., 0x1FFF that m does not exceed; code = (seg << 4) | ((m >> (seg + 1)) & 15), or 0x7F when m exceeds
+ *                   them all (the clipped magnitude 8192 does); the byte is code ^ mask
+ *   MKWS_PCM_ALAW   m = q >> 3; mask = 0xD5; m < 0: m = -m - 1, mask = 0x55; seg = the first of the ends 0x1F, 0x3F, ..., 0xFFF that m
+ *                   does not exceed; code = (seg << 4) | ((seg < 2 ? m >> 1 : m >> seg) & 15); the byte is code ^ mask
+ * A NaN v gives the code of zero in the integer and G.711 formats (u8: 128, mu-law: 0xFF, A-law: 0xD5).  The G.711 rules are the usual
+ * closed-form compressors (CPython's audioop.lin2ulaw / lin2alaw give the same byte for all 65 536 inputs), NOT the nearest decoded
+ * value; they invert the decode rule above on every code but mu-law 0x7F (negative zero, re-encoded as 0xFF).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* 64 bytes; a table of them is 8-byte aligned. */
+typedef struct mkws_pcm_encode_item {
+  int64_t src_offset;   /* in floats */
+  int64_t src_len;
+  int64_t start;        /* frame 0 of the item is sample `start` of its recording; may be negative or past the end */
+  int64_t n_frames;
+  int64_t byte_offset;  /* any byte: no alignment is assumed */
+  int64_t fade_in;      /* frames, >= 0 */
+  int64_t fade_out;
+  float gain;
+  int32_t format;       /* MKWS_PCM_* */
+} mkws_pcm_encode_item;
+
+/* d_src float32 [src_floats], d_items [n_items] (device memory), d_out uint8 [out_bytes], d_invalid int32 [1].  The kernel checks every
+ * item before it reads or writes for it, in 64-bit: format in [0, MKWS_PCM_NUM_FORMATS), 0 <= n_frames <= max_frames, fade_in >= 0,
+ * fade_out >= 0, src_len >= 0, -2^61 <= start <= 2^61, [src_offset, src_offset + src_len) inside [0, src_floats) and
+ * [byte_offset, byte_offset + n_frames * b) inside [0, out_bytes).  An item that fails writes nothing and adds 1 to *d_invalid (set to
+ * 0 by every call that launches); the other items are unaffected.  No float outside an item's [src_offset, src_offset + src_len) is
+ * read and NO BYTE OUTSIDE AN ITEM'S OWN BYTE RANGE IS WRITTEN: items of 1-byte and 3-byte samples may start and end at any address and
+ * may abut (the ranges of two items should not overlap: the order of their stores is then undefined).  MKWS_ERR_INVALID_ARG for
+ * negative sizes and NULL buffers, MKWS_ERR_UNSUPPORTED for a grid of n_items * ceil(max_frames / 1024) workgroups beyond one launch;
+ * n_items == 0 or max_frames == 0 returns MKWS_OK with nothing launched (and *d_invalid untouched).  One launch for any n_items,
+ * asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_pcm_encode(const float* d_src, int64_t src_floats, const mkws_pcm_encode_item* d_items, int n_items, int64_t max_frames,
+                    uint8_t* d_out, int64_t out_bytes, int32_t* d_invalid, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Embedding model.  Replaces `embedding.predict(x)` on the Keras model
  *   EfficientNetB0(include_top=False, weights=None, input_shape=(49,40,1)) -> GAP ->
  *   Dense 2048 relu -> Dense 2048 relu -> Dense 1024 selu ("dense_2")

@@ -51,6 +51,13 @@ class PcmItem(ctypes.Structure):
                 ("format", ctypes.c_int32), ("channels", ctypes.c_int32), ("channel", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class PcmEncodeItem(ctypes.Structure):
+    """mkws_pcm_encode_item (include/mkws.h)."""
+    _fields_ = [("src_offset", ctypes.c_int64), ("src_len", ctypes.c_int64), ("start", ctypes.c_int64), ("n_frames", ctypes.c_int64),
+                ("byte_offset", ctypes.c_int64), ("fade_in", ctypes.c_int64), ("fade_out", ctypes.c_int64), ("gain", ctypes.c_float),
+                ("format", ctypes.c_int32)]
+
+
 # every symbol include/mkws.h declares: (name, restype, argtypes)
 _P, _I, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _CFG = ctypes.POINTER(FrontendCfg)
@@ -82,6 +89,7 @@ SYMBOLS = [
     ("mkws_resample_live_push_many", _I, [_P, _P, _SZ, _I, _P, _P, _I, _I, _P, _P]),
     ("mkws_pcm_frame_bytes", _I, [_I, _I]),
     ("mkws_pcm_decode", _I, [_P, _I64, _P, _I, _I64, _P, _I64, _P, _P]),
+    ("mkws_pcm_encode", _I, [_P, _I64, _P, _I, _I64, _P, _I64, _P, _P]),
     ("mkws_embed_weight_count", _SZ, []),
     ("mkws_embed_weight_manifest", _I, [ctypes.c_char_p, _SZ]),
     ("mkws_embed_create", _I, [_P, _SZ, _I, ctypes.POINTER(_P)]),

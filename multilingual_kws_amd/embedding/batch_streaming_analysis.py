@@ -11,6 +11,7 @@ for bit, and the path for hosts without a GPU.  StreamTarget / eval_stream_test 
 their multi-keyword form on ONE shared embedding pass (run.py:89-152 runs one full model per keyword).  operating_curves /
 multi_keyword_operating_curves go on from the detector to tpr_fpr's summary per keyword and threshold without leaving the device
 (mkws_detect_score); tpr_fpr.tpr_fpr is their yardstick and their path on a host without a GPU."""
+import math
 import os
 import pickle
 from dataclasses import dataclass
@@ -1121,6 +1122,54 @@ def detect(inferences, flags: StreamFlags, threshold, sample_rate=16000, data_sa
             found.append([element.found_command, t_ms])
             found_conf.append([element.found_command, t_ms, element.score])
     return found, found_conf
+
+
+def detection_windows(times_ms, n_samples, sample_rate, before_ms=1000, after_ms=1000, pad=False):
+    """[(start, n_frames)] in frames of a recording of n_samples samples: the window [t - before_ms, t + after_ms] of every t of
+    times_ms, its ends at floor(ms * sample_rate / 1000).  pad=False: clamped to the recording, as sox `trim` clamps at its end (and
+    cannot start in front of it); pad=True: the full window, to be zero-filled where it leaves the recording."""
+    windows = []
+    for t in times_ms:
+        a = math.floor((t - before_ms) * sample_rate / 1000)
+        b = max(a, math.floor((t + after_ms) * sample_rate / 1000))
+        if not pad:
+            a, b = min(max(a, 0), n_samples), min(max(b, 0), n_samples)
+        windows.append((a, b - a))
+    return windows
+
+
+def extract_detections(detections, wav, dest_dir=None, target_word=None, before_ms=1000, after_ms=1000, sample_rate=None, format="s16",
+                       pad=False):
+    """The harvest of luganda/luganda.ipynb cell 21 (one sox `trim` process per detection there): every detection's
+    [t - before_ms, t + after_ms] of the recording as a mono WAV file in `format`, all of them cut and encoded in ONE mkws_pcm_encode
+    launch and one download (input_data._encode_images).  detections: the [(keyword, time_ms), ...] list detect / eval_stream_test
+    return per threshold.  wav: the path of a WAV file of any supported format, read by input_data.read_recording at its own rate
+    unless sample_rate is given; or the recording itself with sample_rate, a float32 CUDA tensor [samples] (a numpy array is encoded on
+    the host, byte for byte the same).  Windows: detection_windows.  -> with dest_dir (made if absent) the paths written,
+    f"{ix:03d}_{target_word}_detection_{time_ms}ms.wav" as in the notebook (target_word defaults to each detection's own keyword);
+    without it the file images (bytes)."""
+    from .. import pcm
+    detections = list(detections)
+    if isinstance(wav, (str, os.PathLike, bytes, bytearray, memoryview)):
+        image = input_data._wav_image(wav)
+        if sample_rate is None:
+            sample_rate = pcm.wav_info(image).rate
+        wav = input_data.read_recording(image, sample_rate)
+    elif sample_rate is None:
+        raise ValueError("extract_detections: a recording that is not a file needs its sample_rate")
+    host = input_data._host_audio(wav)
+    audio = wav.reshape(-1) if host is None else host.reshape(-1)
+    if host is None and not audio.is_contiguous():
+        audio = audio.contiguous()
+    n, rate = int(audio.shape[0]), int(sample_rate)
+    windows = detection_windows([t for _, t in detections], n, rate, before_ms, after_ms, pad)
+    images = input_data._encode_images(audio, [[(0, n, a, nf, 0, 0, 1.0)] for a, nf in windows], rate, format)
+    if dest_dir is None:
+        return images
+    paths = [os.path.join(os.fspath(dest_dir), f"{ix:03d}_{kw if target_word is None else target_word}_detection_{t}ms.wav")
+             for ix, (kw, t) in enumerate(detections)]
+    os.makedirs(os.fspath(dest_dir), exist_ok=True)
+    return input_data._write_images(images, paths)
 
 
 def _keyword_planes(inferences, flags, keywords):

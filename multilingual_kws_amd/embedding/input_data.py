@@ -180,8 +180,21 @@ class _PinnedBytes:
         self.event.record(torch.cuda.current_stream(device))
         return dev
 
+    def download(self, dev):
+        """The other way: the bytes of a uint8 device tensor through ONE asynchronous copy into the pinned buffer -> the numpy view of
+        them once the copy has run (valid until the buffer is taken again)."""
+        import torch
+        total = int(dev.numel())
+        host = self.take(total)
+        host[:total].copy_(dev, non_blocking=True)
+        self.event = self.event or torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(dev.device))
+        self.event.synchronize()
+        return host.numpy()[:total]
+
 
 _pinned_bytes = _PinnedBytes()
+_pinned_out = _PinnedBytes()      # the encoders' download buffer: an upload in flight never waits for a download
 
 
 def _wav_image(f):
@@ -292,6 +305,122 @@ def read_recording(path, sample_rate=16000, channel=0, device=None):
         if info.rate != int(sample_rate):
             x = _resampler_for(info.rate, sample_rate, dev).forward(x, centred=True)
     return x
+
+
+# ---------------------------------------------------------------------------------------------------
+# the way out: device audio cut, faded and encoded into WAV files of any format (pcm.py)
+# ---------------------------------------------------------------------------------------------------
+def _host_audio(audio):
+    """None for a CUDA tensor; the float32 numpy array of anything else (a CPU tensor, an array, a list)."""
+    import torch
+    if torch.is_tensor(audio):
+        return None if audio.is_cuda else audio.to(torch.float32).numpy()
+    return np.asarray(audio, dtype=np.float32)
+
+
+def _encode_images(src, images, sample_rate, format):
+    """The common core of the writers.  src: the audio, a CUDA float32 tensor or a numpy float32 array, indexed flat; images: for every
+    file the list of its pieces (src_offset, src_len, start, n_frames, fade_in, fade_out, gain), which follow one another in the file's
+    sample data -> the whole file images, header included.  A CUDA source: ONE mkws_pcm_encode launch for every piece of every file
+    into one byte buffer, each file's sample data on a 16-byte boundary with room for its header in front, ONE asynchronous download
+    into the pinned buffer, the headers filled in on the host.  A numpy source: the same layout through pcm.encode_items_host."""
+    import torch
+    from .. import pcm
+    name = pcm._format_name(format)
+    sb, head = pcm.SAMPLE_BYTES[name], len(pcm.wav_header(name, sample_rate, 0))
+    rows, spans, total = [], [], 0
+    for pieces in images:
+        at = (total + head + 15) & ~15
+        frames = 0
+        for so, sl, st, nf, fi, fo, gain in pieces:
+            rows.append((so, sl, st, nf, at + frames * sb, fi, fo, gain, name))
+            frames += int(nf)
+        spans.append((at, frames))
+        total = at + frames * sb + (frames * sb & 1)
+    items = pcm.make_encode_items(rows)
+    if torch.is_tensor(src) and src.is_cuda:
+        with torch.cuda.device(src.device):
+            out = torch.empty(max(total, 16), dtype=torch.uint8, device=src.device)
+            out, invalid = pcm.encode_on_device(src.to(torch.float32).contiguous().view(-1), items, out=out, check=False)
+            hv = _pinned_out.download(out)
+            bad = int(invalid.cpu()[0])
+        if bad:
+            raise ValueError(f"mkws_pcm_encode refused {bad} of {len(items)} items")
+    else:
+        hv = pcm.encode_items_host(src, items, out_bytes=max(total, 16))
+    result = []
+    for at, frames in spans:
+        nb = frames * sb
+        hv[at - head:at] = np.frombuffer(pcm.wav_header(name, sample_rate, frames), dtype=np.uint8)
+        if nb & 1:
+            hv[at + nb] = 0                                 # the pad byte of an odd data chunk
+        result.append(hv[at - head:at + nb + (nb & 1)].tobytes())
+    return result
+
+
+def _write_images(images, paths):
+    paths = [os.fspath(p) for p in paths]
+    if len(paths) != len(images):
+        raise ValueError(f"{len(images)} files but {len(paths)} paths")
+    for image, path in zip(images, paths):
+        parent = os.path.dirname(path)
+        if parent:
+            os.makedirs(parent, exist_ok=True)
+        with open(path, "wb") as fh:
+            fh.write(image)
+    return paths
+
+
+def encode_wav(audio, sample_rate=16000, format="s16", lengths=None, fade_ms=0, gain=1.0):
+    """The inverse of decode_wav: audio [B, n] or [n], float32 in [-1, 1] -> a list of B whole mono WAV file images (bytes) in `format`
+    (pcm.FORMATS: u8, s16, s24, s32, f32, f64, mulaw, alaw), each by the sample rule of include/mkws.h ("Device audio encoded into WAV
+    sample data": round half to even, clamped at the rails).  lengths: the frames of every row's file (default n; a longer file is
+    zero-padded); fade_ms: a linear fade-in and fade-out of that many milliseconds; gain: a factor on every sample.  A CUDA tensor is
+    encoded on the device, all rows in one mkws_pcm_encode launch and one download; a CPU tensor or an array goes through
+    pcm.encode_host, byte for byte the same."""
+    import torch
+    host = _host_audio(audio)
+    a = audio if host is None else host
+    if a.ndim == 1:
+        a = a[None]
+    if a.ndim != 2:
+        raise ValueError(f"encode_wav: audio of shape {tuple(a.shape)} ([B, n] or [n])")
+    B, n = int(a.shape[0]), int(a.shape[1])
+    lengths = [n] * B if lengths is None else [int(v) for v in lengths]
+    if len(lengths) != B or min(lengths, default=0) < 0:
+        raise ValueError(f"encode_wav: {len(lengths)} lengths for {B} rows (each at least 0)")
+    fade = int(fade_ms * int(sample_rate) / 1000)
+    if fade < 0:
+        raise ValueError(f"encode_wav: fade_ms = {fade_ms}")
+    if host is None and not a.is_contiguous():
+        a = a.contiguous()
+    return _encode_images(a, [[(r * n, n, 0, lengths[r], fade, fade, float(gain))] for r in range(B)], sample_rate, format)
+
+
+def write_clips(audio, paths, sample_rate=16000, format="s16", lengths=None, fade_ms=0, gain=1.0):
+    """encode_wav, and row i written to paths[i] (parent directories are made) -> the paths."""
+    return _write_images(encode_wav(audio, sample_rate, format, lengths, fade_ms, gain), paths)
+
+
+def convert_clips(files, dests, sample_rate=16000, format="s16", channel=0, desired_samples=None, batch=1024):
+    """The device form of notebooks/sox_batch.py's convert_16k_wav (one sox process per file there): WAV files of any supported format,
+    rate and channel count -> mono WAV files at sample_rate in `format`, `batch` files at a time through read_clips and write_clips
+    (per batch: one upload, one decode launch, the resampler once per distinct rate, one encode launch, one download).  Every file
+    keeps its own converted length, ceil(frames * sample_rate / rate), unless desired_samples pads or truncates them all -> dests."""
+    from .. import pcm
+    files, dests = list(files), [os.fspath(d) for d in dests]
+    if len(files) != len(dests):
+        raise ValueError(f"convert_clips: {len(files)} files but {len(dests)} destinations")
+    dev = _cuda_device(None)
+    for b0 in range(0, len(files), max(1, int(batch))):
+        images = [_wav_image(f) for f in files[b0:b0 + max(1, int(batch))]]
+        lengths, width = None, desired_samples
+        if desired_samples is None:
+            infos = [pcm.wav_info(b) for b in images]
+            lengths = [i.frames if i.rate == int(sample_rate) else _resampler_for(i.rate, sample_rate, dev).out_samples(i.frames) for i in infos]
+            width = max(1, max(lengths))
+        write_clips(read_clips(images, sample_rate, width, channel, dev), dests[b0:b0 + len(images)], sample_rate, format, lengths)
+    return dests
 
 
 def load_unknown_files(unknown_words_dir, listing="unknown_files.txt"):
