@@ -41,6 +41,7 @@ def test_live_session_equals_its_offline_pieces():
     import torch
     from multilingual_kws_amd.detector import detect_on_device
     from multilingual_kws_amd.embedding import input_data
+    from multilingual_kws_amd.frontend import Frontend
     ms = input_data.standard_microspeech_model_settings(3)
     audio = _recording()
     emb, models = _models()
@@ -49,16 +50,22 @@ def test_live_session_equals_its_offline_pieces():
     assert sess.graph is not None and sess.samples_seen == 0 and sess.windows_seen == 0
     window_loop = bsa.StreamingSession(models, ms, batch=1)
     # (a) hop by hop: every push's probabilities are StreamingSession.infer's on that window, bit for bit
-    got, records, probs = [], [], []
+    got, records, probs, spec = [], [], [], []
     for i in range(SAMPLES // HOP):
+        before = sess.windows_seen
         got += sess.feed(torch.from_numpy(audio[i * HOP:(i + 1) * HOP]).cuda() if i % 2 else audio[i * HOP:(i + 1) * HOP])
         records += sess.last_records
+        spec.append(sess.spec[:sess.windows_seen - before].clone())
         if sess.windows_seen:
             w = sess.windows_seen - 1
             mine = sess.probs.clone()
             assert torch.equal(mine, window_loop.infer(audio[w * HOP:w * HOP + CLIP])), w
             probs.append(mine[:, 0])
     assert sess.windows_seen == WINDOWS == len(probs) and sess.samples_seen == SAMPLES and sess.recaptures == 0
+    # every push's spectrogram rows are Frontend.stream's over the whole recording, bit for bit
+    fe = Frontend(max_samples=SAMPLES)
+    assert torch.equal(torch.cat(spec), fe.stream(torch.from_numpy(audio).cuda(), CLIP, HOP)[:WINDOWS])
+    fe.close()
     probs = torch.stack(probs, dim=1)                                       # [3, 51, 3]
     assert torch.isfinite(probs).all()
     # (b) the detections are detect_on_device's over those probabilities
