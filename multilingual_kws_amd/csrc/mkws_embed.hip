@@ -105,7 +105,16 @@ __device__ __forceinline__ void wg_trace_end() {
     for (int k_ = 0; k_ < 8; ++k_) p_[k_] = (unsigned long long)ph_acc_[k_]; } } while (0)
 #define MKWS_WG_BEGIN() wg_trace_begin()
 #define MKWS_WG_END() wg_trace_end()
+// mbconv_mid_kernel: thread 0 adds the wall-clock time since its last stamp to slot k of an LDS table that it copies out at the end
+// (timing_report_mid prints the means).  Slots: 0 start, 1 prologue, 2 + 4 * chunk + {0 P1 tasks of wave 0 done, 1 P1 constants stored +
+// barrier passed, 2 P2 items done, 3 P2 constants stored + barrier passed}, 26.. SE tail per barrier, 32 projection: wait for the
+// weight ring, 33 projection MFMA loop + epilogue of wave 0, 34 last wave done, 35 end.
+constexpr int kMidStamps = 40, kMidStampSE = 26, kMidStampProj = 32;
+constexpr int kMidStampFloats = 2 * kMidStamps + 2;     // the table follows the kernel's LDS carve
+#define MID_STAMP(k) do { if (threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); s_stamp[k] += t_ - t_mark; t_mark = t_; } } while (0)
 #else
+#define MID_STAMP(k)
+constexpr int kMidStampFloats = 0;
 #define MKWS_WG_BEGIN()
 #define MKWS_WG_END()
 #define MKWS_ABLATE(bit) false
@@ -1198,6 +1207,19 @@ __device__ __forceinline__ void stream_mfma(f32x4 (&acc)[NTW][MT], f32x4 (&wq)[D
   if (SPLIT) acc[0][0] += acc_odd;
 }
 
+// Sum of v over the 64 lanes of a wave (all active), the same bits in every lane and one fixed tree: within each row of 16 lanes by DPP
+// (lane pairs, quads, halves, the row), then the four row sums as (r0 + r1) + (r2 + r3).  No LDS round trip.
+__device__ __forceinline__ float wave_sum64_(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, false));   // row_half_mirror
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, false));   // row_mirror
+  const int b = __builtin_bit_cast(int, v);
+  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
+  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
+  return (r0 + r1) + (r2 + r3);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Whole-MBConv kernel for big-image blocks (used for 3a and 4a): expand -> depthwise -> squeeze-excite -> gated
 // projection (+ residual) in ONE launch, G clips per workgroup, two workgroups per CU.  Only the block input and
@@ -1213,8 +1235,10 @@ __device__ __forceinline__ void stream_mfma(f32x4 (&acc)[NTW][MT], f32x4 (&wq)[D
 //              requests the depthwise taps / BN constants that P2 of the same chunk needs and stores them just
 //              before the barrier; P2 does the same for the expand weights / BN constants of the next chunk.
 //              Two barriers per chunk.
-//   SE         channel means = fixed-order two-step column sums of D;  r = swish(mean . Wr + br) (thread =
-//              (unit, channel slice), slices folded in fixed order);  gate = sigmoid(r . We + be)
+//   SE         three barriers.  Channel means: a strip item of P2 leaves the sum of its SEG outputs in a slot, and a thread per
+//              (clip, channel) adds the slots of its channel in ascending order during the next chunk's P1 (quad-item
+//              instantiations: fixed-order two-step column sums of D after the loop);  r = swish(mean . Wr + br): a wave per
+//              unit, lanes stride the channels, one fixed DPP / readlane tree;  gate = sigmoid(r . We + be), thread per channel
 //   project    wave = (n-tile, row-tile lane): the K fragments of its n-tile stream through a register ring
 //              (requested before the SE phase), each feeding the wave's row tiles; gated D rows are the MFMA B
 //              operands, read from LDS; BN, residual
@@ -1245,7 +1269,11 @@ struct MidGeom {
   static constexpr int oMean = oD + G * HoWo * LDD;
   static constexpr int oGate = oMean + G * CEXP;
   static constexpr int oR = oGate + G * CEXP;
-  static constexpr int lds_floats = oR + G * 16;
+  // strip items (SEG > 1) leave the sum of their SEG outputs here, one slot per (clip, output row, row segment) and channel of the chunk
+  static constexpr bool SQ = SEG > 1;
+  static constexpr int NSLOT = HoT * NSEG;
+  static constexpr int oSq = oR + G * 16;                        // [G][NSLOT][CC]
+  static constexpr int lds_floats = oSq + (SQ ? G * NSLOT * CC : 0);
   static_assert(NSEG * SEG == WoT, "segments tile the output row");
   static_assert(CEXP % CC == 0 && CC % 16 == 0, "chunks are whole MFMA tiles");
 };
@@ -1259,17 +1287,19 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
   constexpr int NW = NTHR / 64;
   constexpr int SE_MAX = 10;                                     // SE units of blocks 2a..4a: 4, 6, 6, 10, 10
   constexpr int TAP_ROW_UNROLL = (KS == 5) ? 1 : KS;             // 5x5: one tap row at a time (register budget at 4 waves per SIMD)
-  constexpr int NSL = NTHR / 16;                                 // channel slices of the SE reduce FC
-  constexpr int CPS = (CEXP + NSL - 1) / NSL;                    // channels per slice
+  constexpr int UPW = (SE_MAX + NW - 1) / NW;                    // SE reduce FC: units per wave (wave w owns units w, w + NW, ..)
+  constexpr int CPL = (CEXP + 63) / 64;                          // ... and channels per lane (lane l takes channels l, l + 64, ..)
+  constexpr bool SQ = GM::SQ;                                    // channel sums come from the depthwise phase's strip items
+  constexpr int NSLOT = GM::NSLOT;
   constexpr int CQ = CEXP / 4;                                   // channel quads of D
   constexpr int RS = NTHR / (G * CQ);                            // row slices of the column-sum pass
   constexpr int R1 = (NS1 + NTHR - 1) / NTHR, R2 = (NS2 + NTHR - 1) / NTHR;
   static_assert(NTHR % 64 == 0 && NTHR >= CEXP && NTHR >= 16 * G && RS >= 1, "thread roles");
-  static_assert(NTHR * G <= KCT * MTI * 256 && G * RS * CEXP <= GM::oD - GM::oS1, "aliased scratch fits");
+  static_assert(G * RS * CEXP <= GM::oD - GM::oS1, "aliased scratch fits");
+  static_assert(SQ == PAIR && NTHR >= G * CC, "strip items are channel-pair items; a thread per (clip, channel of the chunk) folds their sums");
   extern __shared__ __attribute__((aligned(16))) float s_mid[];
   MKWS_WG_BEGIN();
   float* s_X = s_mid + GM::oX;
-  float* s_part = s_X;                                           // [NSL][16][G] SE reduce partials (X fragments are dead by then)
   float* s_W = s_mid + GM::oS1;                                  // [KCT][NTC][256] expand weight fragments
   float* s_scE = s_W + NW4 * 4;                                  // [CC], then shE [CC]
   float* s_wd = s_mid + GM::oS2;                                 // [KS*KS][CC] depthwise taps
@@ -1280,6 +1310,7 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
   float* s_mean = s_mid + GM::oMean;                             // [G][CEXP]
   float* s_gate = s_mid + GM::oGate;                             // [G][CEXP]
   float* s_r = s_mid + GM::oR;                                   // [G][16]
+  float* s_sq = s_mid + GM::oSq;                                 // [G][NSLOT][CC] strip sums of the chunk whose depthwise phase ran last
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // uniform by construction: keeps wave-dependent offsets / branches on the scalar unit
   const int g = lane >> 4, c = lane & 15;
@@ -1288,9 +1319,12 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
   const int rows = gvalid * HW, rows_out = gvalid * HoWo;
   const size_t row0_in = (size_t)b0 * HW, row0_out = (size_t)b0 * HoWo;
 #ifdef MKWS_FRONT_TIMING
-  unsigned long long* dbgp = a.dbg_t + (size_t)blockIdx.x * 8;
-  unsigned long long t_p1 = 0, t_p2 = 0, t_red = 0, t_mark = 0;
-  if (tid == 0) { t_mark = wall_clock64(); dbgp[0] = t_mark; }
+  unsigned long long* s_stamp = reinterpret_cast<unsigned long long*>(s_mid + ((GM::lds_floats + 1) & ~1));
+  unsigned long long t_mark = 0;
+  if (tid == 0) {
+    for (int k = 0; k < kMidStamps; ++k) s_stamp[k] = 0;
+    t_mark = wall_clock64(); s_stamp[0] = t_mark;
+  }
 #endif
   // staged constants: element e (float4) of a phase's list comes from base + chunk * stride
   auto src1 = [&](int e, int chn) -> const float* {
@@ -1338,22 +1372,38 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
   if (tid < LDE / 4) *reinterpret_cast<f32x4*>(s_E + (size_t)G * HW * LDE + 4 * tid) = (f32x4){0.f, 0.f, 0.f, 0.f};
   store1();
   __syncthreads();
+  MID_STAMP(1);
 
   // The SE weights of this thread's role are requested HERE, a whole chunk loop ahead of their use (round 4: requested at the top of the SE
   // phase, two barriers in front of the reduce FC, their L2 round trip was part of every clip's 3 us of SE; the kernel holds 80-92 of the
   // 128 registers a wave may use, the ~16 these occupy during the loop are free).
-  float wr_pre[CPS], we_pre[SE_MAX], br_pre = 0.0f, be_pre = 0.0f;
+  float wr_pre[UPW][CPL], we_pre[SE_MAX], br_pre[UPW], be_pre = 0.0f;
   auto request_se = [&]() {
-    const int n = tid & 15, sl = tid >> 4;
 #pragma unroll
-    for (int i = 0; i < CPS; ++i) {
-      const int ch = sl * CPS + i;
-      wr_pre[i] = (ch < CEXP && n < a.se) ? a.Wr[(size_t)ch * a.se + n] : 0.0f;
+    for (int u = 0; u < UPW; ++u) {
+      const int n = wave + NW * u;
+#pragma unroll
+      for (int i = 0; i < CPL; ++i) {
+        const int ch = lane + 64 * i;
+        wr_pre[u][i] = (ch < CEXP && n < a.se) ? a.Wr[(size_t)ch * a.se + n] : 0.0f;
+      }
+      br_pre[u] = (n < a.se) ? a.br[n] : 0.0f;
     }
 #pragma unroll
     for (int n2 = 0; n2 < SE_MAX; ++n2) we_pre[n2] = (tid < CEXP && n2 < a.se) ? a.We[(size_t)n2 * CEXP + tid] : 0.0f;
-    br_pre = (tid < 16 * G && tid / G < a.se) ? a.br[tid / G] : 0.0f;
     be_pre = (tid < CEXP) ? a.be[tid] : 0.0f;
+  };
+  // SE squeeze, strip instantiations: the last G * CC threads (waves with the fewest P1 tasks) add the NSLOT strip sums of their
+  // (clip, channel) in ascending slot order, whatever gvalid is, while the other waves already expand the next chunk
+  auto fold_sq = [&](int chn) {
+    const int f = tid - (NTHR - G * CC);
+    if (f >= 0) {
+      const int gi = f / CC, cc = f - gi * CC;
+      float t = s_sq[(size_t)gi * NSLOT * CC + cc];
+#pragma unroll
+      for (int sl = 1; sl < NSLOT; ++sl) t += s_sq[((size_t)gi * NSLOT + sl) * CC + cc];
+      s_mean[gi * CEXP + chn * CC + cc] = t * (1.0f / (float)HoWo);
+    }
   };
   if (!MKWS_ABLATE(16)) request_se();                            // (timing build, MKWS_ABLATE=16: the round-3 position, for the A/B)
 
@@ -1361,6 +1411,9 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
     const int ch0 = chn * CC;
     // ---- P1: expand this chunk into LDS ----
     load2(chn);
+    if constexpr (SQ) {
+      if (chn > 0) fold_sq(chn - 1);
+    }
     {
       const int ntasks = MKWS_ABLATE(1) ? 0 : ((rows + 15) / 16) * NTC;
       for (int t = wave; t < ntasks; t += NW) {
@@ -1381,11 +1434,10 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
         }
       }
     }
+    MID_STAMP(2 + 4 * chn);
     store2();
     __syncthreads();
-#ifdef MKWS_FRONT_TIMING
-    if (tid == 0) { const unsigned long long t = wall_clock64(); t_p1 += t - t_mark; t_mark = t; }
-#endif
+    MID_STAMP(3 + 4 * chn);
     // ---- P2: depthwise from LDS -> D[:, chunk] ----
     if (chn + 1 < NCH) load1(chn + 1);
     if constexpr (PAIR) {
@@ -1429,12 +1481,15 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
         }
         const f32x2 scd = *reinterpret_cast<const f32x2*>(s_scD + 2 * tp), shd = *reinterpret_cast<const f32x2*>(s_scD + CC + 2 * tp);
         float* dout = s_D + (size_t)(gi * HoWo + oh * WoT + sg * SEG) * LDD + ch0 + 2 * tp;
+        f32x2 ysum = {0.f, 0.f};
 #pragma unroll
         for (int o = 0; o < SEG; ++o) {
           f32x2 y = acc[o] * scd + shd;
           y = swish2_(y);
           *reinterpret_cast<f32x2*>(dout + (size_t)o * LDD) = y;
+          ysum += y;
         }
+        *reinterpret_cast<f32x2*>(s_sq + (size_t)((gi * HoT + oh) * NSEG + sg) * CC + 2 * tp) = ysum;
       }
     } else {
       const int zrow = G * HW;
@@ -1480,18 +1535,20 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
         }
       }
     }
+    MID_STAMP(4 + 4 * chn);
     if (chn + 1 < NCH) store1();
     __syncthreads();
-#ifdef MKWS_FRONT_TIMING
-    if (tid == 0) { const unsigned long long t = wall_clock64(); t_p2 += t - t_mark; t_mark = t; }
-#endif
+    MID_STAMP(5 + 4 * chn);
   }
   // The first fragments of the projection weight stream of this wave's n-tile are requested here (L2 hits: every workgroup uses the
   // same ones); the SE weights of this thread's role were requested in front of the chunk loop.
   if (MKWS_ABLATE(16)) request_se();
   constexpr int NWP = NW / NTP;                                  // row-tile lanes per n-tile (waves beyond NWP*NTP idle in the projection)
   constexpr int MTW = (MTO + NWP - 1) / NWP;                     // row tiles per wave
-  constexpr int PD = (KC >= 8) ? 8 : 4;                          // depth of the projection weight ring
+  // Depth of the projection weight ring.  Every wave requests its ring at once and the CU's vector-memory path takes 16 cycles per
+  // buffer_load_dwordx4: eight deep, the 16 waves of 2b queued 128 KB = 2048 cycles (1 us, all of it in front of the next barrier:
+  // profiles/mid_phases.txt).  Four fragments are 1000 cycles of a SIMD's MFMA time ahead, more than an L2 round trip.
+  constexpr int PD = 4;
   const int ntp = wave % NTP, rlp = wave / NTP;
   const WBuf p_w(a.WpP, (unsigned)(g * 64 + c * 4));
   f32x4 wqp[PD][1];
@@ -1503,45 +1560,55 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
     }
   }
   if (!MKWS_ABLATE(4)) {
-  // ---- SE squeeze: column sums of D in two fixed-order steps (row slices, then slices) ----
-  if (tid < G * RS * CQ) {
-    const int q = tid % CQ, rs = (tid / CQ) % RS, gi = tid / (CQ * RS);
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
-    for (int r = rs; r < HoWo; r += RS) t += *reinterpret_cast<const f32x4*>(s_D + (size_t)(gi * HoWo + r) * LDD + 4 * q);
-    s_csum[tid] = t;
-  }
-  __syncthreads();
-  if (tid < G * CQ) {
-    const int q = tid % CQ, gi = tid / CQ;
-    f32x4 t = s_csum[(size_t)gi * RS * CQ + q];
+  if constexpr (SQ) {
+    // ---- SE squeeze: the strip sums of the last chunk (those of the earlier chunks were folded during the following P1) ----
+    fold_sq(NCH - 1);
+  } else {
+    // ---- SE squeeze: column sums of D in two fixed-order steps (row slices, then slices) ----
+    if (tid < G * RS * CQ) {
+      const int q = tid % CQ, rs = (tid / CQ) % RS, gi = tid / (CQ * RS);
+      f32x4 t = {0.f, 0.f, 0.f, 0.f};
+      for (int r = rs; r < HoWo; r += RS) t += *reinterpret_cast<const f32x4*>(s_D + (size_t)(gi * HoWo + r) * LDD + 4 * q);
+      s_csum[tid] = t;
+    }
+    __syncthreads();
+    MID_STAMP(kMidStampSE + 0);
+    if (tid < G * CQ) {
+      const int q = tid % CQ, gi = tid / CQ;
+      f32x4 t = s_csum[(size_t)gi * RS * CQ + q];
 #pragma unroll 4
-    for (int rs = 1; rs < RS; ++rs) t += s_csum[((size_t)gi * RS + rs) * CQ + q];
-    *reinterpret_cast<f32x4*>(s_mean + (size_t)gi * CEXP + 4 * q) = t * (1.0f / (float)HoWo);
-  }
-  __syncthreads();
-  // ---- SE reduce: thread (unit n, channel slice sl) folds its CPS channels; slices are then added in fixed order ----
-  {
-    const int n = tid & 15, sl = tid >> 4;
-#pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-      float v = 0.0f;
-#pragma unroll
-      for (int i = 0; i < CPS; ++i) {
-        const int ch = sl * CPS + i;
-        v += s_mean[gi * CEXP + (ch < CEXP ? ch : 0)] * wr_pre[i];
-      }
-      s_part[(sl * 16 + n) * G + gi] = v;
+      for (int rs = 1; rs < RS; ++rs) t += s_csum[((size_t)gi * RS + rs) * CQ + q];
+      *reinterpret_cast<f32x4*>(s_mean + (size_t)gi * CEXP + 4 * q) = t * (1.0f / (float)HoWo);
     }
   }
   __syncthreads();
-  if (tid < 16 * G) {
-    const int n = tid / G, gi = tid - n * G;
-    float v = 0.0f;
-#pragma unroll 8
-    for (int sl = 0; sl < NSL; ++sl) v += s_part[(sl * 16 + n) * G + gi];
-    s_r[gi * 16 + n] = (n < a.se) ? swishf_(v + br_pre) : 0.0f;
+  MID_STAMP(kMidStampSE + 1);
+  // ---- SE reduce: wave w owns units w, w + NW, ..; a lane multiplies its CPL channels in ascending order, the 64 lane sums meet in the
+  // fixed tree of wave_sum64_ (every clip of the workgroup the same way: nothing depends on gvalid) and lane 0 finishes the unit ----
+  if (tid < 16 * G && (tid & 15) >= a.se) s_r[tid] = 0.0f;
+#pragma unroll
+  for (int u = 0; u < UPW; ++u) {
+    if (wave + NW * u < a.se) {
+      float v[G];
+#pragma unroll
+      for (int gi = 0; gi < G; ++gi) {
+        v[gi] = 0.0f;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+          const int ch = lane + 64 * i;
+          v[gi] += s_mean[gi * CEXP + (ch < CEXP ? ch : 0)] * wr_pre[u][i];
+        }
+      }
+#pragma unroll
+      for (int gi = 0; gi < G; ++gi) v[gi] = wave_sum64_(v[gi]);
+      if (lane == 0) {
+#pragma unroll
+        for (int gi = 0; gi < G; ++gi) s_r[gi * 16 + wave + NW * u] = swishf_(v[gi] + br_pre[u]);
+      }
+    }
   }
   __syncthreads();
+  MID_STAMP(kMidStampSE + 3);
   if (tid < CEXP) {
 #pragma unroll
     for (int gi = 0; gi < G; ++gi) {
@@ -1555,8 +1622,10 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
   }
   __syncthreads();
   }
+  MID_STAMP(kMidStampSE + 4);
 #ifdef MKWS_FRONT_TIMING
-  if (tid == 0) { const unsigned long long t = wall_clock64(); t_red += t - t_mark; t_mark = t; }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // the projection's weight ring, requested in front of the SE tail, has arrived
+  MID_STAMP(kMidStampProj + 0);
 #endif
   // ---- gated projection (+ BN, residual): every weight fragment of the stream feeds this wave's MTW row tiles ----
   if (rlp < NWP && !MKWS_ABLATE(8)) {
@@ -1604,8 +1673,14 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
     }
   }
 #ifdef MKWS_FRONT_TIMING
+  MID_STAMP(kMidStampProj + 1);
   __syncthreads();
-  if (tid == 0) { const unsigned long long t = wall_clock64(); dbgp[1] = t_p1; dbgp[2] = t_p2; dbgp[3] = t_red; dbgp[4] = t - t_mark; dbgp[5] = t; }
+  MID_STAMP(kMidStampProj + 2);
+  if (tid == 0 && a.dbg_t) {
+    s_stamp[kMidStampProj + 3] = t_mark;
+    unsigned long long* dbgp = a.dbg_t + (size_t)blockIdx.x * kMidStamps;
+    for (int k = 0; k < kMidStamps; ++k) dbgp[k] = s_stamp[k];
+  }
 #endif
   MKWS_WG_END();
 }
@@ -1617,7 +1692,7 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
 // FCs run in the workgroup (weights requested at kernel start, consumed after the staging), and the projection reads its
 // gated operand rows from LDS while its weight fragments stream through a register ring that was requested at kernel
 // start.  Replaces se_reduce_kernel + se_expand_kernel + the gated pw_gemm_kernel (three launches, a [B, C] gate round
-// trip and a second pass over D per N split).  Same arithmetic order per output as mbconv_mid_kernel's tail.
+// trip and a second pass over D per N split).
 struct BackArgs {
   const float* D; const float* X; int Cin;
   const float* Wr; const float* br; const float* We; const float* be; int se;
@@ -5129,15 +5204,15 @@ bool mid_supported(const BlockPlan& b) {
 template <int KS, int S, int KCT, int HT, int WT, int CEXP, int CC, int NTP, int G, int SEG, int NTHR, int WPE, bool PAIR = false>
 int launch_mid_inst(hipStream_t s, const char* stage, MidArgs a) {
   using GM = MidGeom<KS, S, KCT, HT, WT, CEXP, CC, G, SEG>;
-  constexpr size_t lds = (size_t)GM::lds_floats * sizeof(float);
+  constexpr size_t lds = (size_t)(GM::lds_floats + kMidStampFloats) * sizeof(float);
   static_assert(lds <= 160 * 1024, "LDS carve exceeds one CU");
   ProfScope ps(stage, std::string("mbconv_mid_kernel<") + std::to_string(KS) + "," + std::to_string(S) + "," + std::to_string(HT) + "," + std::to_string(WT) +
                           "," + std::to_string(CEXP) + "," + std::to_string(CC) + "," + std::to_string(G) + "," + std::to_string(NTHR) + ">");
   const dim3 grid((a.B + G - 1) / G);
-  timing_arm(a);
+  timing_arm(a, grid.x);
   wg_trace_arm();
   if (int rc = launch_big_lds(&mbconv_mid_kernel<KS, S, KCT, HT, WT, CEXP, CC, NTP, G, SEG, NTHR, WPE, PAIR>, 160 * 1024, grid, dim3(NTHR), lds, s, a)) return rc;
-  timing_report_mid(s, stage, CC, G, grid.x, NTHR, lds);
+  timing_report_mid(s, stage, CC, G, GM::NCH, grid.x, NTHR, lds);
   wg_trace_report(s, stage, "mid", (size_t)grid.x);
   return MKWS_OK;
 }

@@ -30,7 +30,8 @@ inline unsigned long long* timing_buffer(unsigned long long** slot, size_t words
 }
 inline unsigned long long* gemm_timing_buffer() { static unsigned long long* d = nullptr; return timing_buffer(&d, 2 * 65536); }
 inline unsigned long long* front_timing_buffer() { static unsigned long long* d = nullptr; return timing_buffer(&d, 4 * 65536); }
-inline unsigned long long* mid_timing_buffer() { static unsigned long long* d = nullptr; return timing_buffer(&d, 8 * 65536); }
+constexpr size_t kMidStampWords = 8 * 65536;
+inline unsigned long long* mid_timing_buffer() { static unsigned long long* d = nullptr; return timing_buffer(&d, kMidStampWords); }
 // the whole-block kernels (block, pair, cluster, cluster chain): 8 stamps per workgroup
 inline unsigned long long* block_timing_buffer() { static unsigned long long* d = nullptr; return timing_buffer(&d, 8 * 4096); }
 inline unsigned long long* chain_timing_buffer() { static unsigned long long* d = nullptr; return timing_buffer(&d, 4096 * kChainMax * 8 + 4096); }
@@ -44,7 +45,7 @@ inline std::vector<unsigned long long> timing_fetch(hipStream_t s, const unsigne
 // ---- arming: point the launch's argument struct at its stamp buffer -------------------------------------------------------------
 inline void timing_arm(GemmArgs& a, const dim3& grid) { a.dbg_clk = (grid.x * grid.y <= 65536 && a.splitk == 1) ? gemm_timing_buffer() : nullptr; }
 inline void timing_arm(FrontArgs& a) { a.dbg_t = front_timing_buffer(); }
-inline void timing_arm(MidArgs& a) { a.dbg_t = mid_timing_buffer(); }
+inline void timing_arm(MidArgs& a, unsigned nwg) { a.dbg_t = ((size_t)nwg * kMidStamps <= kMidStampWords) ? mid_timing_buffer() : nullptr; }
 inline void timing_arm(BlockArgs& a) { a.dbg_t = block_timing_buffer(); }
 // (cluster kernels: padding workgroups leave before the first stamp, so the report tells live members by a nonzero stamp)
 inline void timing_arm(BlockArgs& a, hipStream_t s) { a.dbg_t = block_timing_buffer(); (void)hipMemsetAsync(a.dbg_t, 0, sizeof(unsigned long long) * 8 * 4096, s); }
@@ -221,16 +222,27 @@ inline void timing_report_cluster_chain(hipStream_t s, const BlockPlan* blocks, 
   }
 }
 
-inline void timing_report_mid(hipStream_t s, const char* stage, int CC, int G, unsigned nwg, int nthr, size_t lds) {
-  const std::vector<unsigned long long> h = timing_fetch(s, mid_timing_buffer(), (size_t)nwg * 8);
-  double p1 = 0, p2 = 0, se = 0, pj = 0, tot = 0; unsigned long long t0 = ~0ull, t1 = 0;
+// mbconv_mid_kernel: means over the workgroups of the durations thread 0 stamped (the slot table stands at MID_STAMP)
+inline void timing_report_mid(hipStream_t s, const char* stage, int CC, int G, int nch, unsigned nwg, int nthr, size_t lds) {
+  if ((size_t)nwg * kMidStamps > kMidStampWords) return;           // not armed
+  const std::vector<unsigned long long> h = timing_fetch(s, mid_timing_buffer(), (size_t)nwg * kMidStamps);
+  double m[kMidStamps] = {}; unsigned long long t0 = ~0ull, t1 = 0;
   for (size_t i = 0; i < nwg; ++i) {
-    p1 += (double)h[8 * i + 1]; p2 += (double)h[8 * i + 2]; se += (double)h[8 * i + 3]; pj += (double)h[8 * i + 4]; tot += (double)(h[8 * i + 5] - h[8 * i]);
-    if (h[8 * i] < t0) t0 = h[8 * i];
-    if (h[8 * i + 5] > t1) t1 = h[8 * i + 5];
+    const unsigned long long* q = &h[i * kMidStamps];
+    for (int k = 1; k < kMidStampProj + 3; ++k) m[k] += (double)q[k] / nwg / 100.0;
+    m[0] += (double)(q[kMidStampProj + 3] - q[0]) / nwg / 100.0;
+    t0 = std::min(t0, q[0]); t1 = std::max(t1, q[kMidStampProj + 3]);
   }
-  fprintf(stderr, "[mid-timing] %s CC %d G %d: %u workgroups x %d thr, lds %zu: expand %.2f  depthwise %.2f  SE %.2f  project %.2f  total %.2f us per workgroup; span %.2f us\n",
-          stage, CC, G, nwg, nthr, lds, p1 / nwg / 100.0, p2 / nwg / 100.0, se / nwg / 100.0, pj / nwg / 100.0, tot / nwg / 100.0, (double)(t1 - t0) / 100.0);
+  double p1 = 0, p2 = 0, se = 0;
+  for (int c = 0; c < nch; ++c) { p1 += m[2 + 4 * c] + m[3 + 4 * c]; p2 += m[4 + 4 * c] + m[5 + 4 * c]; }
+  for (int k = kMidStampSE; k < kMidStampProj; ++k) se += m[k];
+  fprintf(stderr, "[mid-timing] %s CC %d G %d: %u workgroups x %d thr, lds %zu: prologue %.2f  expand %.2f  depthwise %.2f  SE %.2f  project %.2f  total %.2f us per workgroup; span %.2f us\n",
+          stage, CC, G, nwg, nthr, lds, m[1], p1, p2, se, m[kMidStampProj] + m[kMidStampProj + 1] + m[kMidStampProj + 2], m[0], (double)(t1 - t0) / 100.0);
+  fprintf(stderr, "[mid-phases] %s: chunks (P1 tasks of wave 0, +constants stored +barrier, P2 items, +constants stored +barrier):", stage);
+  for (int c = 0; c < nch; ++c) fprintf(stderr, " [%.2f %.2f %.2f %.2f]", m[2 + 4 * c], m[3 + 4 * c], m[4 + 4 * c], m[5 + 4 * c]);
+  fprintf(stderr, "; SE per barrier:");
+  for (int k = kMidStampSE; k < kMidStampProj; ++k) fprintf(stderr, " %.2f", m[k]);
+  fprintf(stderr, "; projection: ring wait %.2f  MFMA loop of wave 0 %.2f  last wave %.2f us\n", m[kMidStampProj], m[kMidStampProj + 1], m[kMidStampProj + 2]);
 }
 
 #endif  // MKWS_FRONT_TIMING

@@ -1,4 +1,4 @@
-"""Four identical passes of the hot path (frontend + embedding forward, B = 1024) -- the workload the PMC and
+"""Four (ONE_FWD_PASSES) identical passes of the hot path (frontend + embedding forward, B = 1024) -- the workload the PMC and
 phase-timing runs wrap (tools/pmc_traffic.sh, tools/gpu_round.sh, MKWS_LIB=...timing.so)."""
 import os
 import sys
@@ -13,6 +13,6 @@ B = int(os.environ.get("ONE_FWD_B", "1024"))      # 512 / 256: the handles of th
 em = EmbeddingModel(weights.synthetic_blob(), max_batch=B)
 fe = Frontend(max_samples=16000)
 audio = torch.from_numpy(synth.clips_float32(B)).to(dev)
-for _ in range(4):
+for _ in range(int(os.environ.get("ONE_FWD_PASSES", "4"))):
     em.forward(fe.forward(audio))
 torch.cuda.synchronize()
