@@ -344,6 +344,86 @@ int mkws_pcm_encode(const float* d_src, int64_t src_floats, const mkws_pcm_encod
                     uint8_t* d_out, int64_t out_bytes, int32_t* d_invalid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Test streams assembled on the device: pieces of float32 recordings in device memory are laid out on the time lines of R streams,
+ * faded, scaled, summed where they overlap, put over a looped background bed and clipped, in one launch for all R streams.  The
+ * reference strings its streaming tests together with one sox process per piece and one for the join
+ * (embedding/generate_stream_sentences.py:144-245, luganda/luganda.py:164-217); it has no background and no overlap.
+ *
+ * A stream r is d_out[out_offset .. out_offset + n_out).  Its items are d_items[first_item .. first_item + n_items), in ascending
+ * out_start.  The value at position t of stream r, for t in [0, n_out):
+ *   item k COVERS t iff 0 <= i < n_frames with i = t - out_start; its value there is
+ *     v_k = (x * gain) * (f_in * f_out)      x, f_in and f_out exactly as in mkws_pcm_encode above (x = +0.0f outside the recording;
+ *                                            every product and quotient one float32 operation, round to nearest even)
+ *   foreground s: the first covering item in table order sets s = v_k (no add to a zero: a lone item at gain 1.0f passes every bit
+ *     through, -0.0f and a quiet NaN included); every further covering item does s = s + v_k, one float32 add each, in ascending item
+ *     index; a position that no item covers has s = +0.0f
+ *   bed (bed_len > 0 and d_bed_gain given): b = d_src[bed_offset + ((bed_start + t) mod bed_len)], y = s + b * d_bed_gain[r] (a
+ *     multiply, then an add); without a bed y = s
+ *   with MKWS_STREAM_CLIP in `flags`: y > 1.0f gives 1.0f, y < -1.0f gives -1.0f, anything else (a NaN too) stays
+ * and d_out[out_offset + t] = y.  A sequential numpy float32 loop reproduces every bit (compose.mix_host).
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_STREAM_CLIP 1
+
+/* 64 bytes; a table of them is 8-byte aligned. */
+typedef struct mkws_stream_item {
+  int64_t src_offset;   /* the piece's recording: d_src[src_offset .. src_offset + src_len) of one flat float32 buffer */
+  int64_t src_len;
+  int64_t start;        /* frame 0 of the item is sample `start` of its recording; may leave it on either side (+0.0f there) */
+  int64_t n_frames;
+  int64_t out_start;    /* stream position of frame 0; may be negative or past the stream's end (the item is clipped to the stream) */
+  int64_t fade_in;      /* frames, >= 0, linear: mkws_pcm_encode's f_in / f_out */
+  int64_t fade_out;
+  float gain;
+  int32_t stream;       /* index of the stream descriptor it belongs to */
+} mkws_stream_item;
+
+/* 56 bytes; a table of them is 8-byte aligned. */
+typedef struct mkws_stream_desc {
+  int64_t out_offset;   /* in floats */
+  int64_t n_out;
+  int64_t bed_offset;   /* the background bed: d_src[bed_offset .. bed_offset + bed_len); bed_len == 0: no bed */
+  int64_t bed_len;
+  int64_t bed_start;    /* in [0, bed_len) when bed_len > 0 */
+  int64_t max_frames;   /* >= n_frames of every item of the stream: bounds the search for the items that reach a tile */
+  int32_t first_item;
+  int32_t n_items;
+} mkws_stream_desc;
+
+/* d_src float32 [src_floats], d_items [n_items], d_streams [n_streams] (device memory), d_bed_gain float32 [n_streams] or NULL (every
+ * stream then goes without its bed), d_out float32 [out_floats], d_invalid int32 [1]; max_out >= every n_out sizes the grid of
+ * n_streams * ceil(max_out / 1024) workgroups.  The kernel checks, in 64-bit, before anything is read or written for the thing
+ * checked.  An item: `stream` in [0, n_streams) and its own index inside that stream's [first_item, first_item + n_items);
+ * 0 <= n_frames <= the stream's max_frames; fade_in, fade_out, src_len >= 0; |start| <= 2^61 and |out_start| <= 2^61;
+ * [src_offset, src_offset + src_len) inside [0, src_floats).  A stream: 0 <= n_out <= max_out; [out_offset, out_offset + n_out) inside
+ * [0, out_floats); first_item, n_items >= 0 with first_item + n_items <= the table's n_items; bed_len >= 0, and when bed_len > 0 the bed
+ * inside [0, src_floats) and 0 <= bed_start < bed_len.  An invalid item contributes nothing; an invalid stream is not written at all;
+ * *d_invalid (set to 0 by every call that launches) ends as the number of invalid items plus invalid streams.  No float outside a
+ * valid item's recording or a valid stream's bed is read and NO FLOAT OUTSIDE A VALID STREAM'S OWN RANGE IS WRITTEN; every float of
+ * that range is written once (streams may abut; their ranges should not overlap).  Ascending out_start inside a stream is a
+ * PRECONDITION that the kernel does not check: the values of an unordered stream are unspecified, the guarantees on what is read and
+ * written hold all the same.  MKWS_ERR_INVALID_ARG for negative sizes and NULL buffers, MKWS_ERR_UNSUPPORTED for a grid beyond one
+ * launch; n_streams == 0 or max_out == 0 returns MKWS_OK with nothing launched (and *d_invalid untouched).  Asynchronous on `stream`,
+ * allocates nothing, never synchronises: capturable. */
+int mkws_stream_mix(const float* d_src, int64_t src_floats, const mkws_stream_item* d_items, int n_items, const mkws_stream_desc* d_streams,
+                    int n_streams, const float* d_bed_gain, int flags, int64_t max_out, float* d_out, int64_t out_floats, int32_t* d_invalid,
+                    void* stream);
+
+/* The powers a signal-to-noise ratio needs, from the same tables with the same checks (out_offset only has to be >= 0: nothing is
+ * written there).  d_partials float64 [n_streams * ceil(max_out / 1024) * 2]: slot (r * tiles + tile) holds the sum of (double)s *
+ * (double)s and the sum of (double)b * (double)b -- the foreground as defined above and the RAW bed -- over the tile's positions
+ * below n_out; a tile past n_out, an invalid stream and a stream without a bed (second sum) get +0.0.  One workgroup owns one slot:
+ * no atomics, and the order of the adds inside a tile depends on nothing but the tile, so a replay gives the same bits. */
+int mkws_stream_power(const float* d_src, int64_t src_floats, const mkws_stream_item* d_items, int n_items, const mkws_stream_desc* d_streams,
+                      int n_streams, int64_t max_out, double* d_partials, int32_t* d_invalid, void* stream);
+
+/* One workgroup per stream folds its slots in ascending tile order into P_fg and P_bed and writes
+ * d_bed_gain[r] = (float)(sqrt(P_fg / P_bed) * d_snr_scale[r]), or 0.0f where either power is not above zero or bed_len <= 0: with
+ * d_snr_scale[r] = 10^(-snr_db / 20) (computed by the host) the mixed stream has 10 log10(sum s^2 / sum (g b)^2) = snr_db over its n_out
+ * positions.  Reads nothing but the partials, the descriptors' bed_len and the scales.  Same errors and no-ops as above. */
+int mkws_stream_bed_gain(const double* d_partials, const mkws_stream_desc* d_streams, int n_streams, int64_t max_out, const double* d_snr_scale,
+                         float* d_bed_gain, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Embedding model.  Replaces `embedding.predict(x)` on the Keras model
  *   EfficientNetB0(include_top=False, weights=None, input_shape=(49,40,1)) -> GAP ->
  *   Dense 2048 relu -> Dense 2048 relu -> Dense 1024 selu ("dense_2")

@@ -58,6 +58,19 @@ class PcmEncodeItem(ctypes.Structure):
                 ("format", ctypes.c_int32)]
 
 
+class StreamItem(ctypes.Structure):
+    """mkws_stream_item (include/mkws.h)."""
+    _fields_ = [("src_offset", ctypes.c_int64), ("src_len", ctypes.c_int64), ("start", ctypes.c_int64), ("n_frames", ctypes.c_int64),
+                ("out_start", ctypes.c_int64), ("fade_in", ctypes.c_int64), ("fade_out", ctypes.c_int64), ("gain", ctypes.c_float),
+                ("stream", ctypes.c_int32)]
+
+
+class StreamDesc(ctypes.Structure):
+    """mkws_stream_desc (include/mkws.h)."""
+    _fields_ = [("out_offset", ctypes.c_int64), ("n_out", ctypes.c_int64), ("bed_offset", ctypes.c_int64), ("bed_len", ctypes.c_int64),
+                ("bed_start", ctypes.c_int64), ("max_frames", ctypes.c_int64), ("first_item", ctypes.c_int32), ("n_items", ctypes.c_int32)]
+
+
 # every symbol include/mkws.h declares: (name, restype, argtypes)
 _P, _I, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _CFG = ctypes.POINTER(FrontendCfg)
@@ -90,6 +103,9 @@ SYMBOLS = [
     ("mkws_pcm_frame_bytes", _I, [_I, _I]),
     ("mkws_pcm_decode", _I, [_P, _I64, _P, _I, _I64, _P, _I64, _P, _P]),
     ("mkws_pcm_encode", _I, [_P, _I64, _P, _I, _I64, _P, _I64, _P, _P]),
+    ("mkws_stream_mix", _I, [_P, _I64, _P, _I, _P, _I, _P, _I, _I64, _P, _I64, _P, _P]),
+    ("mkws_stream_power", _I, [_P, _I64, _P, _I, _P, _I, _I64, _P, _P, _P]),
+    ("mkws_stream_bed_gain", _I, [_P, _P, _I, _I64, _P, _P, _P]),
     ("mkws_embed_weight_count", _SZ, []),
     ("mkws_embed_weight_manifest", _I, [ctypes.c_char_p, _SZ]),
     ("mkws_embed_create", _I, [_P, _SZ, _I, ctypes.POINTER(_P)]),
