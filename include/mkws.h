@@ -882,6 +882,57 @@ int mkws_kmeans_nearest(const float* d_x, int dim, int n_rows, const int32_t* d_
                         int n_clusters, float* d_dist, int32_t* d_which, int32_t* d_invalid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K logistic regressions on embedding vectors: what the DataPerf selection harness of the reference
+ * (notebooks/dataperf_test_harness.py:242-256,318-408, notebooks/dataperf_experiments.py:121-192) does per split with
+ * sklearn.linear_model.LogisticRegression, for n_problems problems in one launch.  multilingual_kws_amd/logreg.py (objective,
+ * logreg_host) is the specification: problem p minimises
+ *     f(W, b) = C[p] * sum_i [ logsumexp_k(z_ik) - z_{i,y_i} ] + (kappa / 2) * sum W^2,   z_i = W x~_i + b,
+ * W [n_classes, dim], b [n_classes] unpenalised, kappa = 2 for two classes (sklearn's binary objective in two-row form) and 1 above.
+ * standardize = 1: x~ = (x - mu) / sigma over the problem's own rows (ddof 0, sigma = 0 -> 1); solved and penalised in that space,
+ * returned in raw space (W = W~ / sigma, b = b~ - W~ . mu / sigma).  The intercepts come back with sum_k b~_k = 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_LOGREG_MAX_ROWS 1024          /* rows of one problem */
+#define MKWS_LOGREG_MAX_CLASSES 8
+#define MKWS_LOGREG_MAX_DIM 1024
+
+/* Floats of workspace mkws_logreg_fit needs (the coefficients, the direction and the previous gradient of every problem). */
+size_t mkws_logreg_work_floats(int dim, int n_problems, int n_classes);
+
+/* d_x float32 [n_rows, dim]: the bank.  Problem p trains on bank rows d_rows[d_offsets[p] .. d_offsets[p+1]) with labels
+ * d_labels[...] in [0, n_classes), gathered through the list: no row is copied, rows may repeat inside a problem and across problems
+ * (d_offsets int32 [n_problems+1], non-decreasing and inside the lists: the caller checks).  d_C double [n_problems].
+ * d_coef float32 [n_problems, n_classes, dim], d_intercept float32 [n_problems, n_classes], d_stats double [n_problems, 2] =
+ * {objective, |gradient|_inf} as the device last saw them (at the returned point, in the space the problem was solved in),
+ * d_info int32 [n_problems, 4] = {status, n_iter, stop reason, rows}; stop reason 0 = |gradient|_inf <= gtol, 1 = max_iter steps were
+ * taken (sklearn's ConvergenceWarning, not an error).
+ *   status 0 fitted;
+ *   status 2 = an empty problem, more than MKWS_LOGREG_MAX_ROWS rows, a label outside [0, n_classes) or a row index outside
+ *              [0, n_rows): d_info = {2, 0, 0, rows}, nothing else is written for it and no bank row is read.  Neighbouring problems are
+ *              not affected.
+ * The solver is non-linear conjugate gradients with an exact line search on cached logits; every class row is fitted, also one with
+ * no sample.  One workgroup per problem, no floating-point atomics: two calls on the same input write the same bytes.
+ * d_work: mkws_logreg_work_floats(...) floats, contents unspecified before and after.
+ * MKWS_ERR_INVALID_ARG for NULL pointers, negative sizes, dim < 1, n_classes < 2, max_iter < 1, a NaN or negative gtol, standardize
+ * other than 0 / 1 and a workspace that is too small; MKWS_ERR_UNSUPPORTED above MKWS_LOGREG_MAX_CLASSES or MKWS_LOGREG_MAX_DIM.
+ * n_problems == 0 returns MKWS_OK with nothing launched.  Asynchronous on `stream`, allocates nothing, never synchronises: capturable
+ * like every other call. */
+int mkws_logreg_fit(const float* d_x, int n_rows, int dim, const int32_t* d_rows, const int32_t* d_labels, const int32_t* d_offsets,
+                    int n_problems, int n_classes, const double* d_C, int standardize, int max_iter, double gtol, float* d_coef,
+                    float* d_intercept, int32_t* d_info, double* d_stats, float* d_work, size_t work_floats, void* stream);
+
+/* Every problem scored on its OWN row list: entry e of d_rows / d_true (int32 [total]) belongs to the problem p with
+ * d_offsets[p] <= e < d_offsets[p+1].  logit_k = sum_d coef[p,k,d] * x[row,d] + intercept[p,k] in float32 (fused multiply-adds, lanes
+ * across dim, a butterfly sum); d_pred int32 [total] = the first argmax of the logits; d_probs (optional, may be NULL) float32
+ * [total, n_classes] their softmax; d_logits (optional, may be NULL) float32 [total, n_classes]; d_correct int32 [n_problems] = entries
+ * with d_pred == d_true, zeroed by the call itself (integer adds).  An entry outside every list, or whose row is outside [0, n_rows),
+ * is never dereferenced: d_pred = -1, NaN probabilities and logits, not counted.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers, negative sizes, dim < 1, n_classes < 2; MKWS_ERR_UNSUPPORTED above the caps.
+ * Asynchronous on `stream`, allocates nothing, never synchronises: capturable like every other call. */
+int mkws_logreg_score(const float* d_x, int n_rows, int dim, const int32_t* d_rows, const int32_t* d_true, const int32_t* d_offsets,
+                      int n_problems, int n_classes, const float* d_coef, const float* d_intercept, int total, int32_t* d_pred,
+                      float* d_probs, float* d_logits, int32_t* d_correct, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-batch assembly.  Replaces the per-clip tf.data map of AudioDataset.augment /
  * random_timeshift / random_background_sample / add_background
  * (multilingual_kws/embedding/input_data.py:141-157,227-304) and spec_augment (:306-369).

@@ -4,7 +4,7 @@ import importlib
 import sys
 
 _MODULES = ("input_data", "transfer_learning", "batch_streaming_analysis", "single_target_recognize_commands", "distance_filtering", "tpr_fpr",
-            "transfer_learning_analysis", "word_extraction", "generate_stream_sentences")
+            "transfer_learning_analysis", "word_extraction", "generate_stream_sentences", "selection_eval")
 
 for _m in _MODULES:
     _mod = importlib.import_module("multilingual_kws_amd.embedding." + _m)

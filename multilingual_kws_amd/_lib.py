@@ -126,6 +126,9 @@ SYMBOLS = [
     ("mkws_roc_count", _I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     ("mkws_kmeans_fit", _I, [_P, _I, _P, _I, _I, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
     ("mkws_kmeans_nearest", _I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
+    ("mkws_logreg_work_floats", _SZ, [_I, _I, _I]),
+    ("mkws_logreg_fit", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _SZ, _P]),
+    ("mkws_logreg_score", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     ("mkws_augment_batch", _I, [_P, _P, _P, ctypes.c_int64, _P, _I, _I, _P, _P]),
     ("mkws_specaug_apply", _I, [_P, _P, _I, _I, _I, _P]),
     ("mkws_specaug_apply_n", _I, [_P, _P, _I, _I, _I, _I, _I, _P]),

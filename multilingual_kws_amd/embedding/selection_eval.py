@@ -1,0 +1,163 @@
+"""The DataPerf selection harness on exported embeddings: what notebooks/dataperf_test_harness.py:318-408 does per
+experiment -- a classifier per cross-validation split on the target words' embedding vectors plus "unknown" vectors, the best split by
+validation score scored on the dev vectors -- for all splits of all experiments at once: one mkws_logreg_fit and two mkws_logreg_score
+launches (multilingual_kws_amd/logreg.py) instead of a multiprocessing.Pool of sklearn fits.
+
+The classifier is the LogisticRegression half of the reference (dataperf_test_harness.py:242-256: `logistic_regression` = "lr",
+`logistic_regression_with_scaling` = "lr_scaled").  The SVC(probability=True) half of the voting ensemble at :386-393 is NOT built: Platt
+scaling runs an internal 5-fold split with libsvm's own random generator, so there is no specification a device version could be held
+to.  The random forest, gradient boosting and L1 variants of :259-286 are not built either.
+
+Every problem is solved to the optimum of sklearn's objective rather than to where sklearn's lbfgs happens to stop (tol 1e-4, 100
+iterations: see logreg.py), so a score can differ from the reference's on rows that sit within that slack of a decision boundary."""
+import os
+from collections import namedtuple
+
+import numpy as np
+
+KeywordEmbeddings = namedtuple("KeywordEmbeddings", "bank clip_ids offsets")
+
+CLASSIFIERS = {"lr": False, "lr_scaled": True}       # name -> standardize
+
+
+def load_keyword_embeddings(parquet_dir, words):
+    """Reads what distance_filtering.export_keyword_embeddings writes: <parquet_dir>/<word>.parquet with columns clip_id and
+    mswc_embedding_vector.  -> KeywordEmbeddings(bank float32 [rows, dim] = the words' vectors one word after the other in file order,
+    clip_ids (list of str, one per bank row), offsets int64 [len(words) + 1]: word w owns bank rows offsets[w] .. offsets[w + 1])."""
+    import pandas as pd
+    banks, clip_ids, offsets = [], [], [0]
+    for word in words:
+        df = pd.read_parquet(os.path.join(str(parquet_dir), f"{word}.parquet"))
+        vectors = np.stack([np.asarray(v, dtype=np.float32) for v in df["mswc_embedding_vector"]]) if len(df) else None
+        if vectors is not None:
+            banks.append(vectors)
+            clip_ids.extend(str(c) for c in df["clip_id"])
+        offsets.append(len(clip_ids))
+    if not banks:
+        raise ValueError("no embedding vector under " + str(parquet_dir))
+    return KeywordEmbeddings(np.ascontiguousarray(np.concatenate(banks), dtype=np.float32), clip_ids, np.asarray(offsets, np.int64))
+
+
+def stratified_shuffle_splits(labels, n_splits, train_size, seed):
+    """A plain NumPy stand-in for sklearn.model_selection.StratifiedShuffleSplit(n_splits, train_size=train_size, random_state=seed)
+    .split(X, labels) for hosts without sklearn (the draws are NOT sklearn's: pass its splits where the reference's are wanted).
+    train_size rows in all, every class represented in proportion (largest remainders first, ties to the lower class), the rest is the
+    validation fold.  -> [(train_ixs, val_ixs)] of int64 index arrays, each shuffled."""
+    labels = np.asarray(labels)
+    classes, inverse = np.unique(labels, return_inverse=True)
+    counts = np.bincount(inverse)
+    n, train_size = labels.size, int(train_size)
+    if not 0 < train_size < n:
+        raise ValueError(f"train_size {train_size} outside (0, {n})")
+    exact = counts * (train_size / n)
+    take = np.floor(exact).astype(np.int64)
+    order = np.argsort(-(exact - take), kind="stable")
+    for c in order[:train_size - int(take.sum())]:
+        take[c] += 1
+    rng = np.random.RandomState(seed)
+    out = []
+    for _ in range(int(n_splits)):
+        tr, va = [], []
+        for c in range(len(classes)):
+            idx = rng.permutation(np.nonzero(inverse == c)[0])
+            tr.append(idx[:take[c]])
+            va.append(idx[take[c]:])
+        out.append((rng.permutation(np.concatenate(tr)).astype(np.int64), rng.permutation(np.concatenate(va)).astype(np.int64)))
+    return out
+
+
+def _push(lists, rows, labels):
+    lists[0].append(rows)
+    lists[1].append(labels)
+    lists[2].append(lists[2][-1] + len(rows))
+
+
+def _lists(experiments, unknown_train_rows, unknown_eval_rows, splits):
+    """The row lists of the reference's loop: -> (n_classes, fit lists (rows, labels, offsets), validation lists, per-experiment dev lists,
+    splits per experiment)."""
+    ut, ue = np.asarray(unknown_train_rows, np.int64).reshape(-1), np.asarray(unknown_eval_rows, np.int64).reshape(-1)
+    if len(splits) != len(experiments):
+        raise ValueError(f"{len(splits)} lists of splits for {len(experiments)} experiments")
+    sizes = {len(e["words"]) for e in experiments}
+    if len(sizes) != 1:
+        raise ValueError("every experiment of one call must name the same number of words")
+    K = sizes.pop() + 1                                              # class 0 is "unknown"
+    fit, val, dev, n_splits = ([], [], [0]), ([], [], [0]), ([], [], [0]), []
+    for e, sp in zip(experiments, splits):
+        words = list(e["words"])
+        if len(e["train_rows"]) != len(words) or len(e["dev_rows"]) != len(words):
+            raise ValueError("train_rows and dev_rows hold one list of bank rows per word")
+        if len(sp) < 1:
+            raise ValueError("an experiment needs at least one split")
+        tr = [np.asarray(r, np.int64).reshape(-1) for r in e["train_rows"]]
+        dv = [np.asarray(r, np.int64).reshape(-1) for r in e["dev_rows"]]
+        train_rows = np.concatenate(tr)
+        train_labels = np.concatenate([np.full(len(r), ix + 1, np.int64) for ix, r in enumerate(tr)])
+        _push(dev, np.concatenate(dv + [ue]), np.concatenate([np.full(len(r), ix + 1, np.int64) for ix, r in enumerate(dv)] + [np.zeros(len(ue), np.int64)]))
+        for train_ixs, val_ixs in sp:
+            train_ixs, val_ixs = np.asarray(train_ixs, np.int64), np.asarray(val_ixs, np.int64)
+            _push(fit, np.concatenate([train_rows[train_ixs], ut]), np.concatenate([train_labels[train_ixs], np.zeros(len(ut), np.int64)]))
+            _push(val, np.concatenate([train_rows[val_ixs], ue]), np.concatenate([train_labels[val_ixs], np.zeros(len(ue), np.int64)]))
+        n_splits.append(len(sp))
+    pack = lambda l: (np.concatenate(l[0]), np.concatenate(l[1]), np.asarray(l[2], np.int64))
+    return K, pack(fit), pack(val), pack(dev), n_splits
+
+
+def _accuracy(correct, offsets):
+    return [int(c) / int(n) if n else 0.0 for c, n in zip(correct, np.diff(offsets))]
+
+
+def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows, splits, classifier="lr", C=1.0, max_iter=300, gtol=1e-6,
+                        on_device=None):
+    """experiment_run of dataperf_test_harness.py:318-408 for a list of experiments on one bank of embedding vectors.
+
+    bank: float32 [rows, dim], numpy or CUDA tensor (load_keyword_embeddings(...).bank).  experiments: dicts with words (the target words;
+    word ix is class ix + 1, class 0 is "unknown"), train_rows and dev_rows (one list of bank rows per word: the reference's
+    get_fvs_by_split "train" and "dev").  unknown_train_rows / unknown_eval_rows: bank rows of the unknown vectors.  splits: for every
+    experiment a list of (train_ixs, val_ixs) into its stacked train rows, e.g. list(StratifiedShuffleSplit(...).split(X, y)) as the
+    reference draws them, or stratified_shuffle_splits.  classifier: "lr" or "lr_scaled" (a StandardScaler in front, fitted on each split's
+    own training rows).  Every experiment of one call names the same number of words.
+
+    Every split's problem is its target train rows plus the unknown train rows; its validation set is the held-out rows plus the unknown
+    eval rows; the split with the best validation score (the first, on ties: np.argmax) is scored on the dev rows plus the unknown
+    eval rows.  -> one dict(words, score, crossfold_scores, best_split) per experiment.
+
+    All splits of all experiments go into one logreg.fit_on_device and two logreg.score_on_device calls.  on_device: None = where a GPU
+    is available; False, or a host without one, takes the same flow through logreg.logreg_host and logreg.predict_host."""
+    import torch
+    from .. import logreg
+    if classifier not in CLASSIFIERS:
+        raise ValueError(f"classifier {classifier!r}: one of {sorted(CLASSIFIERS)} (the SVC half of the reference's ensemble is not built)")
+    standardize = CLASSIFIERS[classifier]
+    experiments = list(experiments)
+    if not experiments:
+        return []
+    K, fit, val, dev, n_splits = _lists(experiments, unknown_train_rows, unknown_eval_rows, splits)
+    first = np.concatenate([[0], np.cumsum(n_splits)])
+    if on_device is None:
+        on_device = torch.cuda.is_available()
+
+    if not on_device:
+        x = bank.cpu().numpy() if torch.is_tensor(bank) else np.asarray(bank)
+        models = [logreg.logreg_host(x, fit[0][a:b], fit[1][a:b], K, C, standardize) for a, b in zip(fit[2][:-1], fit[2][1:])]
+        val_correct = [int((logreg.predict_host(x, val[0][a:b], m.coef, m.intercept)[0] == val[1][a:b]).sum())
+                       for m, a, b in zip(models, val[2][:-1], val[2][1:])]
+        scores = _accuracy(val_correct, val[2])
+        best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
+        dev_correct = [int((logreg.predict_host(x, dev[0][a:b], models[first[e] + best[e]].coef, models[first[e] + best[e]].intercept)[0] == dev[1][a:b]).sum())
+                       for e, (a, b) in enumerate(zip(dev[2][:-1], dev[2][1:]))]
+    else:
+        d_bank = logreg._bank(logreg._check_bank(bank)[0])
+        with torch.cuda.device(d_bank.device):
+            fitted = logreg.fit_on_device(d_bank, fit[0], fit[1], fit[2], K, C=C, standardize=standardize, max_iter=max_iter, gtol=gtol)
+            if (fitted.info[:, 0] != 0).any():
+                raise ValueError(f"problem {int(np.nonzero(fitted.info[:, 0])[0][0])} was refused by the device: a row outside the bank, or no row at all")
+            _, d_correct, _, _ = logreg.score_on_device(d_bank, val[0], val[1], val[2], fitted.d_coef, fitted.d_intercept)
+            scores = _accuracy(d_correct.cpu().numpy(), val[2])
+            best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
+            chosen = torch.from_numpy(np.asarray([first[e] + best[e] for e in range(len(experiments))], np.int64)).to(d_bank.device)
+            _, d_correct, _, _ = logreg.score_on_device(d_bank, dev[0], dev[1], dev[2], fitted.d_coef[chosen].contiguous(), fitted.d_intercept[chosen].contiguous())
+            dev_correct = d_correct.cpu().numpy()
+    final = _accuracy(dev_correct, dev[2])
+    return [dict(words=list(e["words"]), score=final[i], crossfold_scores=scores[first[i]:first[i + 1]], best_split=best[i])
+            for i, e in enumerate(experiments)]
