@@ -933,6 +933,78 @@ int mkws_logreg_score(const float* d_x, int n_rows, int dim, const int32_t* d_ro
                       float* d_probs, float* d_logits, int32_t* d_correct, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K RBF support-vector classifiers on embedding vectors: what the DataPerf selection harness of the reference
+ * (notebooks/dataperf_test_harness.py:224-239) does per split with sklearn.svm.SVC(), for n_problems problems side by side.
+ * multilingual_kws_amd/svc.py (svc_host, decision_host, predict_host) is the specification: C-SVC, k(a, b) = exp(-gamma |a~ - b~|^2) with
+ * a~ = (a - centre) * inv_scale, one machine per pair of present classes i < j (class i is +1), f_ij(x) = sum_t c_t k(x_t, x) - rho_ij,
+ * one-vs-one votes with the lowest class on ties.  A fit is three calls on one stream: mkws_svc_prepare, mkws_svc_kernel with both lists
+ * the training lists and d_out the workspace, mkws_svc_fit.  All four are asynchronous on `stream`, allocate nothing, never synchronise
+ * and use no floating-point atomics: two runs on the same input write the same bytes.
+ * The lists are as in mkws_logreg_fit: problem p owns entries d_offsets[p] .. d_offsets[p+1] of the flat d_rows / d_labels (d_offsets
+ * int32 [n_problems+1], non-decreasing and inside the lists: the caller checks); rows may repeat inside and across problems.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers, negative sizes, dim < 1, n_classes < 2 and the values named below;
+ * MKWS_ERR_UNSUPPORTED above the caps.  n_problems == 0 returns MKWS_OK with nothing launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_SVC_MAX_ROWS 1024             /* rows of one problem */
+#define MKWS_SVC_MAX_CLASSES 8
+#define MKWS_SVC_MAX_DIM 1024
+
+/* Bytes of the Gram workspace of a fit: n_problems * max_rows^2 floats (problem p's n x n matrix starts at float p * max_rows^2). */
+size_t mkws_svc_work_bytes(int n_problems, int max_rows);
+
+/* Per problem: d_centre float32 [n_problems, dim] = the column mean of its own rows (always: the kernel is translation invariant and
+ * distances are formed from centred rows), d_inv_scale float32 [n_problems, dim] = 1 / sigma with standardize = 1 (ddof 0, sigma = 0 ->
+ * 1), ones with 0; d_gamma float32 [n_problems] = `gamma` where that is positive, otherwise sklearn's "scale" 1 / (dim * Var) over all
+ * entries of the matrix the kernel sees (1 where Var = 0), every sum in float64; d_info int32 [n_problems, 4] = {status, present pairs,
+ * 0, 0} and d_gap float32 [n_problems] = 0, which mkws_svc_fit completes.
+ *   status 2 = no row, more than max_rows rows, a label outside [0, n_classes), a row outside [0, n_rows) or fewer than two classes
+ *              with a row: d_info = {2, 0, 0, 0}, nothing else is written for the problem by any of the calls and no bank row of it
+ *              is read.  Neighbouring problems are not affected.
+ * max_rows in [1, MKWS_SVC_MAX_ROWS]: the caller's bound on the rows of one problem (it sizes the workspace and the grids).
+ * standardize other than 0 / 1 and a gamma that is not finite are refused. */
+int mkws_svc_prepare(const float* d_x, int n_rows, int dim, const int32_t* d_rows, const int32_t* d_labels, const int32_t* d_offsets,
+                     int n_problems, int n_classes, int max_rows, int standardize, double gamma, float* d_centre, float* d_inv_scale,
+                     float* d_gamma, int32_t* d_info, float* d_gap, void* stream);
+
+/* The RBF cross-kernel of two gathered row lists per problem: for a in list A_p and b in list B_p
+ *     d_out[p * out_stride + a * nb_p + b] = (float)exp(-gamma_p * max(0, s_a + s_b - 2 a~.b~)),
+ * a~.b~ on the 16x16x4 fp32 matrix instruction (a float32 fused-multiply-add chain per 16 columns, the chains added in float64), the
+ * operands gathered, centred and scaled in float32 as they are staged through LDS, s the float64 sums of squares of the same staged
+ * values, the distance and the device library's exp in float64, rounded once.  NaN where a row is outside [0, n_rows) (never
+ * dereferenced).  max_a / max_b: the caller's bounds on the list lengths (they size the grid; a problem whose lists are longer, or
+ * whose na * nb exceeds out_stride, is skipped); out_stride >= max_a * max_b floats.  d_info (may be NULL): int32 [n_problems, 4]; a
+ * problem whose first word is not 0 is skipped. */
+int mkws_svc_kernel(const float* d_x, int n_rows, int dim, const int32_t* d_rows_a, const int32_t* d_offsets_a, int max_a,
+                    const int32_t* d_rows_b, const int32_t* d_offsets_b, int max_b, int n_problems, const float* d_centre,
+                    const float* d_inv_scale, const float* d_gamma, const int32_t* d_info, float* d_out, size_t out_stride, void* stream);
+
+/* SMO on the Gram matrices d_gram (problem p: n_p x n_p floats at p * gram_stride, as mkws_svc_kernel wrote them), one workgroup per
+ * (problem, pair of classes): libsvm's second-order working-set selection (the later index on ties), clipping and TAU guard, no
+ * shrinking, until m(alpha) - M(alpha) < tol or max_iter iterations.  alpha and the gradient are float64, the kernel values float32.
+ * d_C double [n_problems].  d_coef float32 [list entries, n_classes - 1]: entry t's alpha_t y_t in the machine against the m-th other
+ * class in ascending order (libsvm's dual_coef_, aligned with the flat row list); d_rho float32 [n_problems, n_classes (n_classes-1)/2],
+ * pairs in the order (0,1), (0,2), ...; a pair with an absent class gets zero coefficients and rho = 0.  d_info (from mkws_svc_prepare)
+ * gains {., ., pairs cut at max_iter, the largest iteration count of a pair}, d_gap the largest final m - M of a pair.  A problem with
+ * status 2 is skipped.  max_iter < 1, a NaN or negative tol and gram_stride < max_rows^2 are refused. */
+int mkws_svc_fit(const int32_t* d_labels, const int32_t* d_offsets, int n_problems, int n_classes, int max_rows, const double* d_C,
+                 double tol, int max_iter, const float* d_gram, size_t gram_stride, float* d_coef, float* d_rho, int32_t* d_info,
+                 float* d_gap, void* stream);
+
+/* Every problem scored on its OWN evaluation list (d_rows / d_true int32 [total], d_offsets int32 [n_problems+1]) under model p = its
+ * training lists (d_train_*) and what the fit wrote.  The kernel values come from mkws_svc_kernel's device code (A = training rows,
+ * B = evaluation rows); f_ij = (sum over class i's rows of coef * k + sum over class j's) - rho_ij in float32, the rows in list order;
+ * f_ij > 0 votes i, otherwise j, over pairs of present classes; most votes wins, the lowest class on ties.  d_pred int32 [total];
+ * d_correct int32 [n_problems] = entries with d_pred == d_true, zeroed by the call itself (integer adds); d_decision (optional, may be
+ * NULL) float32 [total, n_classes (n_classes-1)/2], 0 for a pair with an absent class.  An entry outside every list, a row outside
+ * [0, n_rows) and every entry of a problem whose d_info (optional) says status != 0 get d_pred = -1 and NaN decision values, are never
+ * dereferenced and not counted.  max_train / max_eval: the caller's bounds on the list lengths (a longer list is not scored). */
+int mkws_svc_score(const float* d_x, int n_rows, int dim, const int32_t* d_train_rows, const int32_t* d_train_labels,
+                   const int32_t* d_train_offsets, int max_train, const float* d_coef, const float* d_rho, const float* d_gamma,
+                   const float* d_centre, const float* d_inv_scale, const int32_t* d_info, int n_problems, int n_classes,
+                   const int32_t* d_rows, const int32_t* d_true, const int32_t* d_offsets, int total, int max_eval, int32_t* d_pred,
+                   int32_t* d_correct, float* d_decision, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-batch assembly.  Replaces the per-clip tf.data map of AudioDataset.augment /
  * random_timeshift / random_background_sample / add_background
  * (multilingual_kws/embedding/input_data.py:141-157,227-304) and spec_augment (:306-369).

@@ -129,6 +129,11 @@ SYMBOLS = [
     ("mkws_logreg_work_floats", _SZ, [_I, _I, _I]),
     ("mkws_logreg_fit", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _SZ, _P]),
     ("mkws_logreg_score", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    ("mkws_svc_work_bytes", _SZ, [_I, _I]),
+    ("mkws_svc_prepare", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
+    ("mkws_svc_kernel", _I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    ("mkws_svc_fit", _I, [_P, _P, _I, _I, _I, _P, ctypes.c_double, _I, _P, _SZ, _P, _P, _P, _P, _P]),
+    ("mkws_svc_score", _I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     ("mkws_augment_batch", _I, [_P, _P, _P, ctypes.c_int64, _P, _I, _I, _P, _P]),
     ("mkws_specaug_apply", _I, [_P, _P, _I, _I, _I, _P]),
     ("mkws_specaug_apply_n", _I, [_P, _P, _I, _I, _I, _I, _I, _P]),

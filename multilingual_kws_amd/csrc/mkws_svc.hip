@@ -1,0 +1,840 @@
+// K RBF support-vector classifiers on embedding vectors (mkws_svc_prepare / mkws_svc_kernel / mkws_svc_fit / mkws_svc_score,
+// include/mkws.h): what the DataPerf selection harness does per split with sklearn.svm.SVC(), for P problems side by side.
+// multilingual_kws_amd/svc.py (svc_host, decision_host, predict_host) is the specification.
+//
+// prepare  one workgroup per problem: the lists are checked, the column mean and 1 / sigma of the problem's own rows and sklearn's
+//          gamma = 1 / (dim * Var) are formed with float64 accumulation, a thread per column, the rows in list order.
+// kernel   out[a, b] = float32(exp(-gamma * max(0, s_a + s_b - 2 a~.b~))) for two gathered row lists: a 64 x 64 tile per workgroup, a~.b~
+//          on the 16x16x4 fp32 matrix instruction (16 columns per float32 chain, the chains added in float64), the operands staged
+//          through LDS from the gathered rows with centring and scaling applied in the load, the squared norms s summed from the same
+//          loaded values.  rbf_tile is the one piece of device code behind the Gram matrices (A = B = a problem's rows) and the
+//          scorer (A = training rows, B = evaluation rows).
+// fit      one workgroup per (problem, pair of classes): libsvm's SMO (second-order working-set selection, no shrinking) on the pair's
+//          rows of the problem's Gram matrix, its sub-matrix in LDS up to kCacheRows rows and read from the (L2-resident) workspace
+//          above.  The gradient and alpha are float64 as in libsvm; the kernel values are float32 as in libsvm's cache.  Both selections
+//          are wave butterflies plus one LDS exchange; an iteration is three barriers.
+// score    a workgroup per 64 evaluation rows walks the model's training rows tile by tile, sums coef * k per (class, other class) in
+//          list order and votes.
+// No floating-point atomics (the integer ones count, or take a maximum): two calls on the same input write the same bytes.  Every loop is
+// bounded by max_iter, the row count, dim or the class count; no workgroup waits for another.
+#include "mkws_common.h"
+
+#include <cmath>
+#include <cstdint>
+#include <mutex>
+#include <set>
+
+using mkws::fail;
+
+namespace {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int kMaxRows = MKWS_SVC_MAX_ROWS;
+constexpr int kMaxK = MKWS_SVC_MAX_CLASSES;
+constexpr int kMaxDim = MKWS_SVC_MAX_DIM;
+constexpr int kTile = 64;               // rows of either list in one kernel tile
+constexpr int kTileThreads = 256;       // 2 x 2 waves, each 2 x 2 matrix-instruction tiles
+constexpr int kPrepThreads = 1024;
+constexpr int kFitThreads = 256;
+constexpr int kFitWaves = kFitThreads / 64;
+constexpr int kCacheRows = 128;         // a pair of up to this many rows keeps its sub-matrix in LDS (64 KB)
+constexpr double kTau = 1e-12;
+static_assert(kMaxDim == kPrepThreads, "a column per thread in mkws_svc_prepare");
+static_assert(kMaxK == 8, "the class loops are unrolled over 8");
+
+// ------------------------------------------------------------------------------------------------ the kernel tile
+
+struct TileLds {
+  float a[2][kTile][17];                // two stages of [row][k], padded
+  float b[2][kTile][17];
+  double na[kTile], nb[kTile];          // squared norms of the centred and scaled rows
+  int32_t ra[kTile], rb[kTile];         // bank rows, -1 = no row (past the list or outside the bank): its operand is zero
+};
+
+// acc = A~ B~^T for the 64 + 64 rows named in s.ra / s.rb (filled by the caller; this function makes them visible), s.na / s.nb their
+// squared norms.  Wave (wm, wn) holds rows wm * 32 + i * 16 + 4 * (lane >> 4) + r of A against rows wn * 32 + j * 16 + (lane & 15) of
+// B in acc[i][j][r].  The matrix instruction's float32 chain runs over 16 columns at a time and its result is added to a float64 total,
+// the norms are float64 sums of the exact squares: where the classifier it replaces is exact (every alpha at its bound, or a handful
+// of rows) the device is held to the float32 storage of the optimum, and a 1024-term float32 chain alone would spend that.
+// Ends with a barrier: the caller may read s.na / s.nb at once.
+__device__ inline void rbf_tile(const float* __restrict__ x, int dim, const float* __restrict__ centre, const float* __restrict__ inv, TileLds& s,
+                                double (&acc)[2][2][4]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lr = tid >> 4, kk = tid & 15;             // this thread loads rows lr + 16 i, column k0 + kk
+  __syncthreads();
+  const float* pa[4];
+  const float* pb[4];
+  float va[4], vb[4];
+  double sa[4], sb[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int ra = s.ra[lr + 16 * i], rb = s.rb[lr + 16 * i];
+    pa[i] = ra >= 0 ? x + (size_t)ra * dim : nullptr;
+    pb[i] = rb >= 0 ? x + (size_t)rb * dim : nullptr;
+    sa[i] = sb[i] = 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
+  auto fetch = [&](int k0) {
+    const int k = k0 + kk;
+    const bool in = k < dim;
+    const float c = in ? centre[k] : 0.0f, sc = in ? inv[k] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      va[i] = (in && pa[i]) ? (pa[i][k] - c) * sc : 0.0f;
+      vb[i] = (in && pb[i]) ? (pb[i][k] - c) * sc : 0.0f;
+      sa[i] += (double)va[i] * (double)va[i];
+      sb[i] += (double)vb[i] * (double)vb[i];
+    }
+  };
+  auto stash = [&](int st) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      s.a[st][lr + 16 * i][kk] = va[i];
+      s.b[st][lr + 16 * i][kk] = vb[i];
+    }
+  };
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  int st = 0;
+  for (int k0 = 0; k0 < dim; k0 += 16) {
+    const bool more = k0 + 16 < dim;
+    if (more) fetch(k0 + 16);                          // the next step's operands travel while this step multiplies
+    f32x4 part[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) part[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 16; ks += 4) {
+      float a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[i] = s.a[st][wm * 32 + i * 16 + (lane & 15)][ks + (lane >> 4)];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) b[j] = s.b[st][wn * 32 + j * 16 + (lane & 15)][ks + (lane >> 4)];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) part[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], part[i][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[i][j][r] += (double)part[i][j][r];
+    if (more) stash(st ^ 1);
+    __syncthreads();
+    st ^= 1;
+  }
+  // the 16 threads of a row (they differ in the low four lane bits) add their column sums in a fixed butterfly
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) {
+      sa[i] += __shfl_xor(sa[i], m, 64);
+      sb[i] += __shfl_xor(sb[i], m, 64);
+    }
+    if (kk == 0) {
+      s.na[lr + 16 * i] = sa[i];
+      s.nb[lr + 16 * i] = sb[i];
+    }
+  }
+  __syncthreads();
+}
+
+// the distance and the exponential in float64 (exp of the device library), rounded once to float32
+__device__ inline float rbf_value(const TileLds& s, int arow, int brow, double dot, float gamma) {
+  if (s.ra[arow] < 0 || s.rb[brow] < 0) return __builtin_nanf("");
+  const double d2 = fmax(0.0, (s.na[arow] + s.nb[brow]) - 2.0 * dot);
+  return (float)exp(-(double)gamma * d2);
+}
+
+__device__ inline int32_t bank_row(const int32_t* __restrict__ rows, int begin, int idx, int n, int n_rows) {
+  if (idx >= n) return -1;
+  const int32_t r = rows[(size_t)begin + idx];
+  return (unsigned)r < (unsigned)n_rows ? r : -1;
+}
+
+__global__ __launch_bounds__(kTileThreads) void svc_kernel_kernel(const float* __restrict__ x, int n_rows, int dim, const int32_t* __restrict__ rows_a,
+                                                                  const int32_t* __restrict__ off_a, int max_a, const int32_t* __restrict__ rows_b,
+                                                                  const int32_t* __restrict__ off_b, int max_b, int tiles_a, int tiles_b,
+                                                                  const float* __restrict__ centre, const float* __restrict__ inv,
+                                                                  const float* __restrict__ gamma, const int32_t* __restrict__ info,
+                                                                  float* __restrict__ out, size_t out_stride) {
+  __shared__ TileLds s;
+  const int per = tiles_a * tiles_b;
+  const int p = blockIdx.x / per, rem = blockIdx.x % per;
+  const int ta = rem / tiles_b, tb = rem % tiles_b;
+  if (info && info[(size_t)p * 4] != 0) return;
+  const int a0 = off_a[p], na = off_a[p + 1] - a0, b0 = off_b[p], nb = off_b[p + 1] - b0;
+  if (na < 1 || nb < 1 || na > max_a || nb > max_b || (size_t)na * (size_t)nb > out_stride) return;
+  if (ta * kTile >= na || tb * kTile >= nb) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < kTile)
+    s.ra[tid] = bank_row(rows_a, a0, ta * kTile + tid, na, n_rows);
+  else if (tid < 2 * kTile)
+    s.rb[tid - kTile] = bank_row(rows_b, b0, tb * kTile + tid - kTile, nb, n_rows);
+  double acc[2][2][4];
+  rbf_tile(x, dim, centre + (size_t)p * dim, inv + (size_t)p * dim, s, acc);
+  const float g = gamma[p];
+  float* __restrict__ o = out + (size_t)p * out_stride;
+  const int wm = wave >> 1, wn = wave & 1;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int arow = wm * 32 + i * 16 + 4 * (lane >> 4) + r, brow = wn * 32 + j * 16 + (lane & 15);
+        const int ga = ta * kTile + arow, gb = tb * kTile + brow;
+        if (ga < na && gb < nb) o[(size_t)ga * nb + gb] = rbf_value(s, arow, brow, acc[i][j][r], g);
+      }
+}
+
+// ------------------------------------------------------------------------------------------------ prepare
+
+// every thread gets the same sum: wave butterflies, then the wave sums in wave order; two barriers
+__device__ inline double prep_block_sum(double v, double* s_red) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int w = 0; w < kPrepThreads / 64; ++w) t += s_red[w];
+  __syncthreads();
+  return t;
+}
+
+__global__ __launch_bounds__(kPrepThreads) void svc_prepare_kernel(const float* __restrict__ x, int n_rows, int dim, const int32_t* __restrict__ rows,
+                                                                   const int32_t* __restrict__ labels, const int32_t* __restrict__ offsets, int K,
+                                                                   int max_rows, int standardize, double gamma_arg, float* __restrict__ centre,
+                                                                   float* __restrict__ inv, float* __restrict__ gamma, int32_t* __restrict__ info,
+                                                                   float* __restrict__ gap) {
+  __shared__ int32_t s_rows[kMaxRows];
+  __shared__ int s_cnt[kMaxK];
+  __shared__ double s_red[kPrepThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int begin = offsets[p];
+  const int n = offsets[p + 1] - begin;
+  int32_t* __restrict__ pinfo = info + (size_t)p * 4;
+  if (n < 1 || n > max_rows || n > kMaxRows) {                        // nothing of the problem is touched
+    if (tid < 4) pinfo[tid] = tid == 0 ? 2 : 0;
+    return;
+  }
+  if (tid < kMaxK) s_cnt[tid] = 0;
+  __syncthreads();
+  int bad = 0;
+  if (tid < n) {
+    const int r = rows[(size_t)begin + tid], y = labels[(size_t)begin + tid];
+    bad = (unsigned)r >= (unsigned)n_rows || (unsigned)y >= (unsigned)K;
+    s_rows[tid] = r;
+    if (!bad) atomicAdd(&s_cnt[y], 1);                                // (an integer count in LDS)
+  }
+  bad = __syncthreads_or(bad);
+  int present = 0;
+  for (int k = 0; k < K; ++k) present += s_cnt[k] > 0;
+  if (bad || present < 2) {
+    if (tid < 4) pinfo[tid] = tid == 0 ? 2 : 0;
+    return;
+  }
+  // a thread per column, the rows added in list order in float64
+  double cm = 0.0, term = 0.0, ssd = 0.0, inv_d = 1.0;
+  if (tid < dim) {
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) sum += (double)x[(size_t)s_rows[i] * dim + tid];
+    const double mean = sum / (double)n;
+    for (int i = 0; i < n; ++i) {
+      const double d = (double)x[(size_t)s_rows[i] * dim + tid] - mean;
+      ssd += d * d;
+    }
+    if (standardize) {
+      const double sigma = sqrt(ssd / (double)n);
+      inv_d = sigma == 0.0 ? 1.0 : 1.0 / sigma;
+    }
+    centre[(size_t)p * dim + tid] = (float)mean;
+    inv[(size_t)p * dim + tid] = (float)inv_d;
+    cm = standardize ? 0.0 : mean;                                    // the column's mean in the matrix the kernel sees
+  }
+  double g = gamma_arg;
+  if (!(g > 0.0)) {
+    // Var over all n * dim entries = [sum_j ssd_j / sigma_j^2 + n sum_j (mean_j - grand mean)^2] / (n dim)
+    const double grand = prep_block_sum(cm, s_red) / (double)dim;
+    if (tid < dim) term = ssd * inv_d * inv_d + (double)n * (cm - grand) * (cm - grand);
+    const double var = prep_block_sum(term, s_red) / ((double)n * (double)dim);
+    g = var > 0.0 ? 1.0 / ((double)dim * var) : 1.0;
+  }
+  if (tid == 0) {
+    gamma[p] = (float)g;
+    gap[p] = 0.0f;
+    pinfo[0] = 0;
+    pinfo[1] = present * (present - 1) / 2;
+    pinfo[2] = 0;
+    pinfo[3] = 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ fit (SMO)
+
+constexpr size_t kFitLdsFixed = (size_t)kMaxRows * (8 + 8 + 4 + 4 + 4);                 // G, alpha, idx, idx of class j, diagonal
+constexpr size_t kFitLdsBytes = kFitLdsFixed + (size_t)kCacheRows * kCacheRows * 4;
+static_assert(kFitLdsBytes <= 160 * 1024 - 4096, "LDS");
+
+struct FitArgs {
+  const int32_t* labels;
+  const int32_t* offsets;
+  const double* C;
+  const float* gram;
+  size_t gram_stride;
+  float* coef;
+  float* rho;
+  int32_t* info;
+  float* gap;
+  int K, max_rows, max_iter;
+  double tol;
+};
+
+__global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char s_raw[];
+  double* s_G = reinterpret_cast<double*>(s_raw);
+  double* s_alpha = s_G + kMaxRows;
+  int32_t* s_idx = reinterpret_cast<int32_t*>(s_alpha + kMaxRows);    // the pair's rows as positions in the problem's list: class i, then class j
+  int32_t* s_idxJ = s_idx + kMaxRows;
+  float* s_Kd = reinterpret_cast<float*>(s_idxJ + kMaxRows);
+  float* s_K = s_Kd + kMaxRows;                                       // [m, m] when m <= kCacheRows
+  __shared__ double s_exv[kFitWaves], s_exm[kFitWaves], s_exo[kFitWaves], s_red[4][kFitWaves];
+  __shared__ int s_exi[kFitWaves], s_exj[kFitWaves], s_cnt[2];
+
+  const int K = a.K, npairs = K * (K - 1) / 2;
+  const int p = blockIdx.x / npairs, q = blockIdx.x % npairs;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int32_t* __restrict__ pinfo = a.info + (size_t)p * 4;
+  if (pinfo[0] != 0) return;                                          // refused by mkws_svc_prepare: nothing is written
+  const int begin = a.offsets[p];
+  const int n = a.offsets[p + 1] - begin;
+  if (n < 1 || n > a.max_rows || n > kMaxRows) return;
+  int ci = 0, rest = q;                                               // pair q = (ci, cj) in the order (0,1), (0,2), ...
+  for (int k = 0; k < kMaxK && rest >= K - 1 - ci; ++k) {
+    rest -= K - 1 - ci;
+    ++ci;
+  }
+  const int cj = ci + 1 + rest;
+  const int32_t* __restrict__ lab = a.labels + begin;
+
+  if (wave < 2) {                                                     // wave 0 lists class ci, wave 1 class cj, in list order
+    const int cls = wave == 0 ? ci : cj;
+    int32_t* dst = wave == 0 ? s_idx : s_idxJ;
+    int cnt = 0;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+      const int t = c0 + lane;
+      const bool is = t < n && lab[t] == cls;
+      const unsigned long long mask = __ballot(is);
+      if (is) dst[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = t;
+      cnt += __popcll(mask);
+    }
+    if (lane == 0) s_cnt[wave] = cnt;
+  }
+  __syncthreads();
+  const int mi = s_cnt[0], mj = s_cnt[1], m = mi + mj;
+  for (int t = tid; t < mj; t += kFitThreads) s_idx[mi + t] = s_idxJ[t];
+  __syncthreads();
+  float* __restrict__ coef = a.coef + (size_t)begin * (K - 1);
+  if (mi == 0 || mj == 0) {                                           // a class without a row: zero coefficients, rho = 0
+    for (int t = tid; t < m; t += kFitThreads) coef[(size_t)s_idx[t] * (K - 1) + (mi ? cj - 1 : ci)] = 0.0f;
+    if (tid == 0) a.rho[(size_t)p * npairs + q] = 0.0f;
+    return;
+  }
+  const float* __restrict__ gram = a.gram + (size_t)p * a.gram_stride;
+  const bool cached = m <= kCacheRows;
+  if (cached)
+    for (int e = tid; e < m * m; e += kFitThreads) s_K[e] = gram[(size_t)s_idx[e / m] * n + s_idx[e % m]];
+  for (int t = tid; t < m; t += kFitThreads) {
+    s_Kd[t] = gram[(size_t)s_idx[t] * n + s_idx[t]];
+    s_G[t] = -1.0;
+    s_alpha[t] = 0.0;
+  }
+  __syncthreads();
+  auto kval = [&](int r, int t) -> double { return (double)(cached ? s_K[r * m + t] : gram[(size_t)s_idx[r] * n + s_idx[t]]); };
+  const double C = a.C[p];
+  const double inf = __builtin_inf();
+
+  int it = 0, cut = 0;
+  double gapv = 0.0;
+  for (;; ++it) {
+    // ---- i = argmax over I_up of -y G (the later index on ties), M = min over I_low ----
+    double bv = -inf, mn = inf;
+    int bi = -1;
+    for (int t = tid; t < m; t += kFitThreads) {
+      const bool pos = t < mi;
+      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
+      const bool up = pos ? al < C : al > 0.0, low = pos ? al > 0.0 : al < C;
+      if (up && v >= bv) {
+        bv = v;
+        bi = t;
+      }
+      if (low) mn = fmin(mn, v);
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+      const double ov = __shfl_xor(bv, s, 64);
+      const int oi = __shfl_xor(bi, s, 64);
+      if (ov > bv || (ov == bv && oi > bi)) {
+        bv = ov;
+        bi = oi;
+      }
+      mn = fmin(mn, __shfl_xor(mn, s, 64));
+    }
+    if (lane == 0) {
+      s_exv[wave] = bv;
+      s_exi[wave] = bi;
+      s_exm[wave] = mn;
+    }
+    __syncthreads();
+    bv = s_exv[0], bi = s_exi[0], mn = s_exm[0];
+#pragma unroll
+    for (int w = 1; w < kFitWaves; ++w) {
+      if (s_exv[w] > bv || (s_exv[w] == bv && s_exi[w] > bi)) {
+        bv = s_exv[w];
+        bi = s_exi[w];
+      }
+      mn = fmin(mn, s_exm[w]);
+    }
+    const int i = bi;
+    const double gmax = bv;
+    gapv = gmax - mn;
+    if (i < 0 || !(gapv >= a.tol)) break;                             // converged (or nothing can move)
+    if (it >= a.max_iter) {
+      cut = 1;
+      break;
+    }
+    // ---- j = argmin over I_low with -y G < gmax of -(gmax + y G)^2 / (K_ii + K_tt - 2 K_it) ----
+    const double kdi = (double)s_Kd[i];
+    double bo = inf;
+    int bj = -1;
+    for (int t = tid; t < m; t += kFitThreads) {
+      const bool pos = t < mi;
+      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
+      const bool low = pos ? al > 0.0 : al < C;
+      const double gd = gmax - v;
+      if (low && gd > 0.0) {
+        double quad = kdi + (double)s_Kd[t] - 2.0 * kval(i, t);
+        if (!(quad > 0.0)) quad = kTau;
+        const double o = -(gd * gd) / quad;
+        if (o <= bo) {
+          bo = o;
+          bj = t;
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+      const double oo = __shfl_xor(bo, s, 64);
+      const int oj = __shfl_xor(bj, s, 64);
+      if (oo < bo || (oo == bo && oj > bj)) {
+        bo = oo;
+        bj = oj;
+      }
+    }
+    if (lane == 0) {
+      s_exo[wave] = bo;
+      s_exj[wave] = bj;
+    }
+    __syncthreads();
+    bo = s_exo[0], bj = s_exj[0];
+#pragma unroll
+    for (int w = 1; w < kFitWaves; ++w) {
+      if (s_exo[w] < bo || (s_exo[w] == bo && s_exj[w] > bj)) {
+        bo = s_exo[w];
+        bj = s_exj[w];
+      }
+    }
+    const int j = bj;
+    if (j < 0) break;
+    // ---- the two-variable step with libsvm's clipping; every thread computes it ----
+    const double yi = i < mi ? 1.0 : -1.0, yj = j < mi ? 1.0 : -1.0;
+    const double ai = s_alpha[i], aj = s_alpha[j], Gi = s_G[i], Gj = s_G[j];
+    double quad = kdi + (double)s_Kd[j] - 2.0 * kval(i, j);
+    if (!(quad > 0.0)) quad = kTau;
+    double ni, nj;
+    if (yi != yj) {
+      const double delta = (-Gi - Gj) / quad, diff = ai - aj;
+      ni = ai + delta;
+      nj = aj + delta;
+      if (diff > 0.0) {
+        if (nj < 0.0) {
+          nj = 0.0;
+          ni = diff;
+        }
+      } else if (ni < 0.0) {
+        ni = 0.0;
+        nj = -diff;
+      }
+      if (diff > 0.0) {
+        if (ni > C) {
+          ni = C;
+          nj = C - diff;
+        }
+      } else if (nj > C) {
+        nj = C;
+        ni = C + diff;
+      }
+    } else {
+      const double delta = (Gi - Gj) / quad, tot = ai + aj;
+      ni = ai - delta;
+      nj = aj + delta;
+      if (tot > C) {
+        if (ni > C) {
+          ni = C;
+          nj = tot - C;
+        }
+      } else if (nj < 0.0) {
+        nj = 0.0;
+        ni = tot;
+      }
+      if (tot > C) {
+        if (nj > C) {
+          nj = C;
+          ni = tot - C;
+        }
+      } else if (ni < 0.0) {
+        ni = 0.0;
+        nj = tot;
+      }
+    }
+    __syncthreads();                                                  // every thread has read alpha and G of i and j
+    const double dai = ni - ai, daj = nj - aj;
+    for (int t = tid; t < m; t += kFitThreads) {
+      const double yt = t < mi ? 1.0 : -1.0;
+      s_G[t] += yt * (yi * kval(i, t) * dai + yj * kval(j, t) * daj);
+    }
+    if (tid == (i & (kFitThreads - 1))) s_alpha[i] = ni;              // (by the thread that owns the entry)
+    if (tid == (j & (kFitThreads - 1))) s_alpha[j] = nj;
+  }
+
+  // ---- rho by libsvm's rule, the coefficients in the row list's order ----
+  double sum = 0.0, cnt = 0.0, ub = inf, lb = -inf;
+  for (int t = tid; t < m; t += kFitThreads) {
+    const bool pos = t < mi;
+    const double al = s_alpha[t], yG = pos ? s_G[t] : -s_G[t];
+    const bool upper = al >= C, lower = al <= 0.0;
+    if (!upper && !lower) {
+      sum += yG;
+      cnt += 1.0;
+    } else if ((upper && !pos) || (lower && pos)) {
+      ub = fmin(ub, yG);
+    } else {
+      lb = fmax(lb, yG);
+    }
+    coef[(size_t)s_idx[t] * (K - 1) + (pos ? cj - 1 : ci)] = (float)(pos ? al : -al);
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    sum += __shfl_xor(sum, s, 64);
+    cnt += __shfl_xor(cnt, s, 64);
+    ub = fmin(ub, __shfl_xor(ub, s, 64));
+    lb = fmax(lb, __shfl_xor(lb, s, 64));
+  }
+  if (lane == 0) {
+    s_red[0][wave] = sum;
+    s_red[1][wave] = cnt;
+    s_red[2][wave] = ub;
+    s_red[3][wave] = lb;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    sum = s_red[0][0], cnt = s_red[1][0], ub = s_red[2][0], lb = s_red[3][0];
+    for (int w = 1; w < kFitWaves; ++w) {
+      sum += s_red[0][w];
+      cnt += s_red[1][w];
+      ub = fmin(ub, s_red[2][w]);
+      lb = fmax(lb, s_red[3][w]);
+    }
+    a.rho[(size_t)p * npairs + q] = (float)(cnt > 0.0 ? sum / cnt : (ub + lb) / 2.0);
+    if (cut) atomicAdd(pinfo + 2, 1);                                 // integer atomics: their order does not show
+    atomicMax(pinfo + 3, it);
+    atomicMax(reinterpret_cast<int*>(a.gap + p), __float_as_int(fmaxf((float)gapv, 0.0f)));   // (non-negative floats order as their bits)
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ score
+
+struct ScoreArgs {
+  const float* x;
+  const int32_t* train_rows;
+  const int32_t* train_labels;
+  const int32_t* train_offsets;
+  const float* coef;
+  const float* rho;
+  const float* gamma;
+  const float* centre;
+  const float* inv;
+  const int32_t* info;
+  const int32_t* rows;
+  const int32_t* truth;
+  const int32_t* offsets;
+  int32_t* pred;
+  int32_t* correct;
+  float* decision;
+  int n_rows, dim, K, max_train, max_eval, tiles_e;
+};
+
+constexpr int kSlots = kMaxK * (kMaxK - 1);            // (class, other class) sums per evaluation row
+
+__global__ __launch_bounds__(kTileThreads) void svc_score_kernel(ScoreArgs a) {
+  __shared__ TileLds s;
+  __shared__ float s_kt[kTile][kTile + 1];             // [training row][evaluation row] kernel values of the tile
+  __shared__ float s_S[kTile][kSlots + 1];             // [evaluation row][class * (K - 1) + slot]
+  __shared__ float s_coef[kTile][kMaxK - 1];
+  __shared__ int32_t s_lab[kTile];
+  __shared__ int s_present[kMaxK];
+  const int K = a.K, npairs = K * (K - 1) / 2, dim = a.dim;
+  const int p = blockIdx.x / a.tiles_e, te = blockIdx.x % a.tiles_e;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int e0 = a.offsets[p], ne = a.offsets[p + 1] - e0;
+  if (ne > a.max_eval || te * kTile >= ne) return;
+  if (a.info && a.info[(size_t)p * 4] != 0) return;                   // a refused model: pred stays -1
+  const int t0 = a.train_offsets[p], nt = a.train_offsets[p + 1] - t0;
+  if (nt < 1 || nt > a.max_train || nt > kMaxRows) return;
+  if (tid < kMaxK) s_present[tid] = 0;
+  for (int e = tid; e < kTile * (kSlots + 1); e += kTileThreads) (&s_S[0][0])[e] = 0.0f;
+  __syncthreads();
+  for (int t = tid; t < nt; t += kTileThreads) {
+    const int y = a.train_labels[(size_t)t0 + t];
+    if ((unsigned)y < (unsigned)K) s_present[y] = 1;                  // (every writer writes the same value)
+  }
+  const float g = a.gamma[p];
+  const int wm = wave >> 1, wn = wave & 1;
+  const int ev = tid & 63, sl = tid >> 6;                             // the accumulation: evaluation row ev, slots sl and sl + 4
+  for (int tt = 0; tt * kTile < nt; ++tt) {
+    if (tid < kTile) {
+      const int idx = tt * kTile + tid;
+      s.ra[tid] = bank_row(a.train_rows, t0, idx, nt, a.n_rows);
+      s_lab[tid] = idx < nt ? a.train_labels[(size_t)t0 + idx] : -1;
+      for (int k = 0; k < kMaxK - 1; ++k) s_coef[tid][k] = (idx < nt && k < K - 1) ? a.coef[((size_t)t0 + idx) * (K - 1) + k] : 0.0f;
+    } else if (tid < 2 * kTile) {
+      s.rb[tid - kTile] = bank_row(a.rows, e0, te * kTile + tid - kTile, ne, a.n_rows);
+    }
+    double acc[2][2][4];
+    rbf_tile(a.x, dim, a.centre + (size_t)p * dim, a.inv + (size_t)p * dim, s, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int arow = wm * 32 + i * 16 + 4 * (lane >> 4) + r, brow = wn * 32 + j * 16 + (lane & 15);
+          s_kt[arow][brow] = (s.ra[arow] >= 0 && s.rb[brow] >= 0) ? rbf_value(s, arow, brow, acc[i][j][r], g) : 0.0f;
+        }
+    __syncthreads();
+    const int rows_here = min(kTile, nt - tt * kTile);
+    for (int t = 0; t < rows_here; ++t) {                              // the training rows in list order
+      const int y = s_lab[t];
+      if ((unsigned)y >= (unsigned)K) continue;
+      const float kv = s_kt[t][ev];
+      if (sl < K - 1) s_S[ev][y * (K - 1) + sl] = fmaf(s_coef[t][sl], kv, s_S[ev][y * (K - 1) + sl]);
+      if (sl + 4 < K - 1) s_S[ev][y * (K - 1) + sl + 4] = fmaf(s_coef[t][sl + 4], kv, s_S[ev][y * (K - 1) + sl + 4]);
+    }
+    __syncthreads();                                                  // before the next tile overwrites the lists and s_kt
+  }
+  const int idx = te * kTile + tid;
+  if (tid >= kTile || idx >= ne) return;
+  if (bank_row(a.rows, e0, idx, ne, a.n_rows) < 0) return;            // a row outside the bank: pred stays -1, its decision values NaN
+  int votes[kMaxK];
+#pragma unroll
+  for (int k = 0; k < kMaxK; ++k) votes[k] = 0;
+  int qd = 0;
+#pragma unroll
+  for (int i = 0; i < kMaxK; ++i)
+#pragma unroll
+    for (int j = i + 1; j < kMaxK; ++j) {
+      if (j < K) {
+        float f = 0.0f;
+        if (s_present[i] && s_present[j]) {
+          f = (s_S[tid][i * (K - 1) + (j - 1)] + s_S[tid][j * (K - 1) + i]) - a.rho[(size_t)p * npairs + qd];
+          if (f > 0.0f)
+            ++votes[i];
+          else
+            ++votes[j];
+        }
+        if (a.decision) a.decision[((size_t)e0 + idx) * npairs + qd] = f;
+        ++qd;
+      }
+    }
+  int best = -1, arg = -1;
+#pragma unroll
+  for (int k = 0; k < kMaxK; ++k)
+    if (k < K && s_present[k] && votes[k] > best) {                   // the lowest class on ties
+      best = votes[k];
+      arg = k;
+    }
+  a.pred[(size_t)e0 + idx] = arg;
+  if (arg == a.truth[(size_t)e0 + idx]) atomicAdd(a.correct + p, 1);  // an integer count
+}
+
+int check_shape(int n_rows, int dim, int n_problems) {
+  if (n_rows < 0 || n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (dim < 1) return fail(MKWS_ERR_INVALID_ARG, "dim = %d: at least one column", dim);
+  if (dim > kMaxDim) return fail(MKWS_ERR_UNSUPPORTED, "dim = %d: at most %d", dim, kMaxDim);
+  return MKWS_OK;
+}
+
+int check_classes(int n_classes) {
+  if (n_classes < 2) return fail(MKWS_ERR_INVALID_ARG, "n_classes = %d: at least two classes", n_classes);
+  if (n_classes > kMaxK) return fail(MKWS_ERR_UNSUPPORTED, "%d classes: at most %d", n_classes, kMaxK);
+  return MKWS_OK;
+}
+
+int check_rows(int max_rows, const char* what) {
+  if (max_rows < 1) return fail(MKWS_ERR_INVALID_ARG, "%s = %d: at least one row", what, max_rows);
+  if (max_rows > kMaxRows) return fail(MKWS_ERR_UNSUPPORTED, "%s = %d: at most %d", what, max_rows, kMaxRows);
+  return MKWS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t mkws_svc_work_bytes(int n_problems, int max_rows) {
+  if (n_problems < 0 || max_rows < 0) return 0;
+  return (size_t)n_problems * (size_t)max_rows * (size_t)max_rows * sizeof(float);
+}
+
+extern "C" int mkws_svc_prepare(const float* d_x, int n_rows, int dim, const int32_t* d_rows, const int32_t* d_labels, const int32_t* d_offsets,
+                                int n_problems, int n_classes, int max_rows, int standardize, double gamma, float* d_centre, float* d_inv_scale,
+                                float* d_gamma, int32_t* d_info, float* d_gap, void* stream) {
+  if (int rc = check_shape(n_rows, dim, n_problems)) return rc;
+  if (int rc = check_classes(n_classes)) return rc;
+  if (int rc = check_rows(max_rows, "max_rows")) return rc;
+  if (standardize != 0 && standardize != 1) return fail(MKWS_ERR_INVALID_ARG, "standardize = %d: 0 or 1", standardize);
+  if (!std::isfinite(gamma)) return fail(MKWS_ERR_INVALID_ARG, "gamma is not finite");
+  if (n_problems == 0) return MKWS_OK;
+  if (!d_x || !d_rows || !d_labels || !d_offsets || !d_centre || !d_inv_scale || !d_gamma || !d_info || !d_gap)
+    return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  hipLaunchKernelGGL(svc_prepare_kernel, dim3(n_problems), dim3(kPrepThreads), 0, static_cast<hipStream_t>(stream), d_x, n_rows, dim, d_rows, d_labels,
+                     d_offsets, n_classes, max_rows, standardize, gamma, d_centre, d_inv_scale, d_gamma, d_info, d_gap);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+extern "C" int mkws_svc_kernel(const float* d_x, int n_rows, int dim, const int32_t* d_rows_a, const int32_t* d_offsets_a, int max_a,
+                               const int32_t* d_rows_b, const int32_t* d_offsets_b, int max_b, int n_problems, const float* d_centre,
+                               const float* d_inv_scale, const float* d_gamma, const int32_t* d_info, float* d_out, size_t out_stride, void* stream) {
+  if (int rc = check_shape(n_rows, dim, n_problems)) return rc;
+  if (max_a < 0 || max_b < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (n_problems == 0 || max_a == 0 || max_b == 0) return MKWS_OK;
+  if (!d_x || !d_rows_a || !d_offsets_a || !d_rows_b || !d_offsets_b || !d_centre || !d_inv_scale || !d_gamma || !d_out)
+    return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (out_stride < (size_t)max_a * (size_t)max_b)
+    return fail(MKWS_ERR_INVALID_ARG, "out_stride of %zu floats for lists of up to %d and %d rows", out_stride, max_a, max_b);
+  const long long tiles_a = (max_a + kTile - 1) / kTile, tiles_b = (max_b + kTile - 1) / kTile;
+  const long long blocks = tiles_a * tiles_b * (long long)n_problems;
+  if (blocks > 0x7fffffffLL) return fail(MKWS_ERR_UNSUPPORTED, "%lld tiles in one call", blocks);
+  hipLaunchKernelGGL(svc_kernel_kernel, dim3((unsigned)blocks), dim3(kTileThreads), 0, static_cast<hipStream_t>(stream), d_x, n_rows, dim, d_rows_a,
+                     d_offsets_a, max_a, d_rows_b, d_offsets_b, max_b, (int)tiles_a, (int)tiles_b, d_centre, d_inv_scale, d_gamma, d_info, d_out,
+                     out_stride);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+extern "C" int mkws_svc_fit(const int32_t* d_labels, const int32_t* d_offsets, int n_problems, int n_classes, int max_rows, const double* d_C,
+                            double tol, int max_iter, const float* d_gram, size_t gram_stride, float* d_coef, float* d_rho, int32_t* d_info,
+                            float* d_gap, void* stream) {
+  if (n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (int rc = check_classes(n_classes)) return rc;
+  if (int rc = check_rows(max_rows, "max_rows")) return rc;
+  if (max_iter < 1) return fail(MKWS_ERR_INVALID_ARG, "max_iter = %d: at least one iteration", max_iter);
+  if (!(tol >= 0.0)) return fail(MKWS_ERR_INVALID_ARG, "tol is NaN or negative");
+  if (n_problems == 0) return MKWS_OK;
+  if (!d_labels || !d_offsets || !d_C || !d_gram || !d_coef || !d_rho || !d_info || !d_gap) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (gram_stride < (size_t)max_rows * (size_t)max_rows)
+    return fail(MKWS_ERR_INVALID_ARG, "gram_stride of %zu floats for problems of up to %d rows", gram_stride, max_rows);
+  const long long blocks = (long long)n_problems * (n_classes * (n_classes - 1) / 2);
+  if (blocks > 0x7fffffffLL) return fail(MKWS_ERR_UNSUPPORTED, "%lld pairs in one call", blocks);
+  // more than 64 KB of LDS: the limit is raised once per device
+  static std::mutex mu;
+  static std::set<int> done;
+  int dev = 0;
+  MKWS_HIP(hipGetDevice(&dev));
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    if (!done.count(dev)) {
+      MKWS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(svc_fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitLdsBytes));
+      done.insert(dev);
+    }
+  }
+  FitArgs a;
+  a.labels = d_labels;
+  a.offsets = d_offsets;
+  a.C = d_C;
+  a.gram = d_gram;
+  a.gram_stride = gram_stride;
+  a.coef = d_coef;
+  a.rho = d_rho;
+  a.info = d_info;
+  a.gap = d_gap;
+  a.K = n_classes;
+  a.max_rows = max_rows;
+  a.max_iter = max_iter;
+  a.tol = tol;
+  // a call whose problems all fit the LDS cache asks for no more than they need
+  const size_t lds = kFitLdsFixed + (size_t)(max_rows < kCacheRows ? max_rows : kCacheRows) * (max_rows < kCacheRows ? max_rows : kCacheRows) * 4;
+  hipLaunchKernelGGL(svc_fit_kernel, dim3((unsigned)blocks), dim3(kFitThreads), lds, static_cast<hipStream_t>(stream), a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+extern "C" int mkws_svc_score(const float* d_x, int n_rows, int dim, const int32_t* d_train_rows, const int32_t* d_train_labels,
+                              const int32_t* d_train_offsets, int max_train, const float* d_coef, const float* d_rho, const float* d_gamma,
+                              const float* d_centre, const float* d_inv_scale, const int32_t* d_info, int n_problems, int n_classes,
+                              const int32_t* d_rows, const int32_t* d_true, const int32_t* d_offsets, int total, int max_eval, int32_t* d_pred,
+                              int32_t* d_correct, float* d_decision, void* stream) {
+  if (int rc = check_shape(n_rows, dim, n_problems)) return rc;
+  if (int rc = check_classes(n_classes)) return rc;
+  if (total < 0 || max_eval < 0 || max_train < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (max_train > kMaxRows) return fail(MKWS_ERR_UNSUPPORTED, "max_train = %d: at most %d", max_train, kMaxRows);
+  if (!d_offsets || !d_train_offsets) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_problems > 0 && !d_correct) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (total > 0 && (!d_x || !d_rows || !d_true || !d_pred)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_problems > 0) MKWS_HIP(hipMemsetAsync(d_correct, 0, (size_t)n_problems * sizeof(int32_t), s));
+  if (total == 0) return MKWS_OK;
+  // pred = -1 and NaN decision values (all bits set) wherever no workgroup writes: entries outside every list, rows outside the bank, refused models
+  MKWS_HIP(hipMemsetAsync(d_pred, 0xff, (size_t)total * sizeof(int32_t), s));
+  const int npairs = n_classes * (n_classes - 1) / 2;
+  if (d_decision) MKWS_HIP(hipMemsetAsync(d_decision, 0xff, (size_t)total * npairs * sizeof(float), s));
+  if (n_problems == 0 || max_eval == 0 || max_train == 0) return MKWS_OK;
+  if (!d_train_rows || !d_train_labels || !d_coef || !d_rho || !d_gamma || !d_centre || !d_inv_scale) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  const long long tiles_e = (max_eval + kTile - 1) / kTile, blocks = tiles_e * (long long)n_problems;
+  if (blocks > 0x7fffffffLL) return fail(MKWS_ERR_UNSUPPORTED, "%lld tiles in one call", blocks);
+  ScoreArgs a;
+  a.x = d_x;
+  a.train_rows = d_train_rows;
+  a.train_labels = d_train_labels;
+  a.train_offsets = d_train_offsets;
+  a.coef = d_coef;
+  a.rho = d_rho;
+  a.gamma = d_gamma;
+  a.centre = d_centre;
+  a.inv = d_inv_scale;
+  a.info = d_info;
+  a.rows = d_rows;
+  a.truth = d_true;
+  a.offsets = d_offsets;
+  a.pred = d_pred;
+  a.correct = d_correct;
+  a.decision = d_decision;
+  a.n_rows = n_rows;
+  a.dim = dim;
+  a.K = n_classes;
+  a.max_train = max_train;
+  a.max_eval = max_eval;
+  a.tiles_e = (int)tiles_e;
+  hipLaunchKernelGGL(svc_score_kernel, dim3((unsigned)blocks), dim3(kTileThreads), 0, s, a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}

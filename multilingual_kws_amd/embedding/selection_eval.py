@@ -1,15 +1,18 @@
 """The DataPerf selection harness on exported embeddings: what notebooks/dataperf_test_harness.py:318-408 does per
 experiment -- a classifier per cross-validation split on the target words' embedding vectors plus "unknown" vectors, the best split by
-validation score scored on the dev vectors -- for all splits of all experiments at once: one mkws_logreg_fit and two mkws_logreg_score
-launches (multilingual_kws_amd/logreg.py) instead of a multiprocessing.Pool of sklearn fits.
+validation score scored on the dev vectors -- for all splits of all experiments at once: one fit and two score calls on the device
+(multilingual_kws_amd/logreg.py, multilingual_kws_amd/svc.py) instead of a multiprocessing.Pool of sklearn fits.
 
-The classifier is the LogisticRegression half of the reference (dataperf_test_harness.py:242-256: `logistic_regression` = "lr",
-`logistic_regression_with_scaling` = "lr_scaled").  The SVC(probability=True) half of the voting ensemble at :386-393 is NOT built: Platt
-scaling runs an internal 5-fold split with libsvm's own random generator, so there is no specification a device version could be held
-to.  The random forest, gradient boosting and L1 variants of :259-286 are not built either.
+Built: the LogisticRegression classifiers of the reference (dataperf_test_harness.py:242-256: `logistic_regression` = "lr",
+`logistic_regression_with_scaling` = "lr_scaled") and its plain sklearn.svm.SVC() ones (:224-239: `simplest_svm` = "svc",
+`svm_with_scaling` = "svc_scaled": C-SVC, RBF kernel, gamma="scale", one-vs-one votes).  NOT built:
+SVC(probability=True) and with it the voting ensemble at :386-393 -- Platt scaling runs an internal 5-fold split with libsvm's own
+random generator, so there is no specification a device version could be held to -- and the random forest,
+gradient boosting and L1 variants of :259-286.
 
-Every problem is solved to the optimum of sklearn's objective rather than to where sklearn's lbfgs happens to stop (tol 1e-4, 100
-iterations: see logreg.py), so a score can differ from the reference's on rows that sit within that slack of a decision boundary."""
+Every problem is solved to (lr) or to within 1e-5 of (svc) the optimum of sklearn's objective rather than to where sklearn's solver
+happens to stop (lbfgs: tol 1e-4, 100 iterations; libsvm: tol 1e-3), so a score can differ from the reference's on rows that sit
+within that slack of a decision boundary."""
 import os
 from collections import namedtuple
 
@@ -17,7 +20,7 @@ import numpy as np
 
 KeywordEmbeddings = namedtuple("KeywordEmbeddings", "bank clip_ids offsets")
 
-CLASSIFIERS = {"lr": False, "lr_scaled": True}       # name -> standardize
+CLASSIFIERS = {"lr": False, "lr_scaled": True, "svc": False, "svc_scaled": True}       # name -> standardize
 
 
 def load_keyword_embeddings(parquet_dir, words):
@@ -107,28 +110,40 @@ def _accuracy(correct, offsets):
     return [int(c) / int(n) if n else 0.0 for c, n in zip(correct, np.diff(offsets))]
 
 
-def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows, splits, classifier="lr", C=1.0, max_iter=300, gtol=1e-6,
-                        on_device=None):
+def _chosen_models(fit_lists, chosen):
+    """The training lists of the chosen problems as lists of their own -> (positions in the flat fit lists, offsets)."""
+    off = fit_lists[2]
+    take = [np.arange(off[c], off[c + 1]) for c in chosen]
+    return np.concatenate(take), np.concatenate([[0], np.cumsum([len(t) for t in take])]).astype(np.int64)
+
+
+def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows, splits, classifier="lr", C=1.0, max_iter=None, gtol=1e-6,
+                        on_device=None, tol=1e-5):
     """experiment_run of dataperf_test_harness.py:318-408 for a list of experiments on one bank of embedding vectors.
 
     bank: float32 [rows, dim], numpy or CUDA tensor (load_keyword_embeddings(...).bank).  experiments: dicts with words (the target words;
     word ix is class ix + 1, class 0 is "unknown"), train_rows and dev_rows (one list of bank rows per word: the reference's
     get_fvs_by_split "train" and "dev").  unknown_train_rows / unknown_eval_rows: bank rows of the unknown vectors.  splits: for every
     experiment a list of (train_ixs, val_ixs) into its stacked train rows, e.g. list(StratifiedShuffleSplit(...).split(X, y)) as the
-    reference draws them, or stratified_shuffle_splits.  classifier: "lr" or "lr_scaled" (a StandardScaler in front, fitted on each split's
-    own training rows).  Every experiment of one call names the same number of words.
+    reference draws them, or stratified_shuffle_splits.  classifier: "lr" (LogisticRegression) or "svc" (SVC()), "lr_scaled" or "svc_scaled"
+    with a StandardScaler in front, fitted on each split's own training rows.  Every experiment of one call names the same number of words.
+    max_iter: None = 300 conjugate-gradient iterations for lr, 100000 SMO iterations per pair for svc; gtol stops lr, tol stops svc.
 
     Every split's problem is its target train rows plus the unknown train rows; its validation set is the held-out rows plus the unknown
     eval rows; the split with the best validation score (the first, on ties: np.argmax) is scored on the dev rows plus the unknown
     eval rows.  -> one dict(words, score, crossfold_scores, best_split) per experiment.
 
-    All splits of all experiments go into one logreg.fit_on_device and two logreg.score_on_device calls.  on_device: None = where a GPU
-    is available; False, or a host without one, takes the same flow through logreg.logreg_host and logreg.predict_host."""
+    All splits of all experiments go into one fit_on_device and two score_on_device calls (logreg or svc).  on_device: None = where a
+    GPU is available; False, or a host without one, takes the same flow through logreg.logreg_host and logreg.predict_host, or
+    svc.svc_host, svc.decision_host and svc.predict_host."""
     import torch
-    from .. import logreg
+    from .. import logreg, svc
     if classifier not in CLASSIFIERS:
-        raise ValueError(f"classifier {classifier!r}: one of {sorted(CLASSIFIERS)} (the SVC half of the reference's ensemble is not built)")
-    standardize = CLASSIFIERS[classifier]
+        raise ValueError(f"classifier {classifier!r}: one of {sorted(CLASSIFIERS)} (SVC(probability=True), the voting ensemble, random forest, "
+                         "gradient boosting and L1 are not built)")
+    standardize, is_svc = CLASSIFIERS[classifier], classifier.startswith("svc")
+    if max_iter is None:
+        max_iter = 100000 if is_svc else 300
     experiments = list(experiments)
     if not experiments:
         return []
@@ -137,7 +152,36 @@ def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows
     if on_device is None:
         on_device = torch.cuda.is_available()
 
-    if not on_device:
+    if not on_device and is_svc:
+        x = bank.cpu().numpy() if torch.is_tensor(bank) else np.asarray(bank)
+        models = [(fit[0][a:b], fit[1][a:b], svc.svc_host(x, fit[0][a:b], fit[1][a:b], K, C, standardize)) for a, b in zip(fit[2][:-1], fit[2][1:])]
+
+        def host_correct(model, rows, true):
+            tr, ty, m = model
+            return int((svc.predict_host(svc.decision_host(x, rows, tr, ty, K, m.coef, m.rho, m.gamma, m.centre, m.inv_scale), ty, K) == true).sum())
+
+        val_correct = [host_correct(m, val[0][a:b], val[1][a:b]) for m, a, b in zip(models, val[2][:-1], val[2][1:])]
+        scores = _accuracy(val_correct, val[2])
+        best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
+        dev_correct = [host_correct(models[first[e] + best[e]], dev[0][a:b], dev[1][a:b]) for e, (a, b) in enumerate(zip(dev[2][:-1], dev[2][1:]))]
+    elif is_svc:
+        d_bank = svc._bank(bank)
+        with torch.cuda.device(d_bank.device):
+            fitted = svc.fit_on_device(d_bank, fit[0], fit[1], fit[2], K, C=C, standardize=standardize, tol=tol, max_iter=max_iter)
+            if (fitted.info[:, 0] != 0).any():
+                raise ValueError(f"problem {int(np.nonzero(fitted.info[:, 0])[0][0])} was refused by the device: a row outside the bank, no row at all, "
+                                 "or fewer than two classes with a row")
+            model = (fitted.d_coef, fitted.d_rho, fitted.d_gamma, fitted.d_centre, fitted.d_inv_scale)
+            _, d_correct, _ = svc.score_on_device(d_bank, val[0], val[1], val[2], fit[0], fit[1], fit[2], K, *model)
+            scores = _accuracy(d_correct.cpu().numpy(), val[2])
+            best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
+            chosen = np.asarray([first[e] + best[e] for e in range(len(experiments))], np.int64)
+            at, off = _chosen_models(fit, chosen)
+            d_at, d_chosen = torch.from_numpy(at).to(d_bank.device), torch.from_numpy(chosen).to(d_bank.device)
+            _, d_correct, _ = svc.score_on_device(d_bank, dev[0], dev[1], dev[2], fit[0][at], fit[1][at], off, K, model[0][d_at].contiguous(),
+                                                  *(m[d_chosen].contiguous() for m in model[1:]))
+            dev_correct = d_correct.cpu().numpy()
+    elif not on_device:
         x = bank.cpu().numpy() if torch.is_tensor(bank) else np.asarray(bank)
         models = [logreg.logreg_host(x, fit[0][a:b], fit[1][a:b], K, C, standardize) for a, b in zip(fit[2][:-1], fit[2][1:])]
         val_correct = [int((logreg.predict_host(x, val[0][a:b], m.coef, m.intercept)[0] == val[1][a:b]).sum())

@@ -1,0 +1,464 @@
+"""K RBF support-vector classifiers on embeddings: the specification (svc_host, decision_host, predict_host) and the host wrappers over
+mkws_svc_prepare / mkws_svc_kernel / mkws_svc_fit / mkws_svc_score (include/mkws.h).
+
+What the DataPerf selection harness of the reference does with sklearn.svm.SVC() (notebooks/dataperf_test_harness.py:224-239:
+`simplest_svm`, `svm_with_scaling`): C-SVC with the RBF kernel and gamma="scale", one-vs-one over the classes.  For problem p with rows
+R_p into the bank x, labels in [0, K), C, standardize and gamma:
+
+  scaling   x~ = (x - mu) * inv: mu is ALWAYS the column mean of the problem's own rows (the kernel is translation invariant, and distances
+            formed from centred rows cancel against the spread, not against the common offset of these non-negative vectors); inv = 1 / sigma
+            with standardize (ddof 0, sigma = 0 -> 1, as StandardScaler), ones without.
+  gamma     gamma itself where gamma > 0, otherwise sklearn's "scale": 1 / (dim * Var), Var the variance of all n * dim entries of the matrix
+            the kernel sees (x[R_p] raw, or the standardised matrix) in float64; 1 where that variance is 0.
+  kernel    k(a, b) = exp(-gamma * |a~ - b~|^2).
+  pairs     for present classes i < j (class i is +1):  min 1/2 a'Qa - e'a,  0 <= a <= C,  y'a = 0,  Q_st = y_s y_t k(x_s, x_t);
+            c_t = a_t y_t,  f_ij(x) = sum_t c_t k(x_t, x) - rho_ij;  rho by libsvm's rule: the mean of y_t G_t (G = Qa - e) over the free t,
+            the midpoint of the two bounds where none is free.
+  solver    SMO with libsvm's second-order working-set selection (the later index on ties), its clipping and its TAU = 1e-12 guard, without
+            shrinking, until m(a) - M(a) < tol.
+  predict   f_ij > 0 votes i, otherwise j; most votes wins, the lowest class on ties.  A class with no row is never predicted: its pairs
+            carry zero coefficients, rho = 0 and no vote.  Fewer than two present classes is refused.
+
+Coefficients are kept in libsvm's dual_coef_ layout turned on its side and aligned with the row list: coef[t, m] is row t's c_t in the
+machine against the m-th OTHER class in ascending order (m = o for o < label, o - 1 above), zero where it is no support vector.  Decision
+values are in the libsvm convention also for two classes, where sklearn's decision_function returns the negated value.
+
+The dual is a convex QP and the decision function is unique even where a is not, so the float64 optimum (svc_host at tol 1e-10) is what
+a solver is held to: sklearn's default run (tol 1e-3) stops 1e-4 from it, and tests/test_svc_gpu.py asks the device to be at least as
+close.  probability=True (Platt scaling over libsvm's own random folds) is not built.
+Host part: pure NumPy float64 on widened float32 inputs; neither scipy nor sklearn is imported."""
+from collections import namedtuple
+
+import numpy as np
+
+from . import _lib
+
+MAX_ROWS = 1024               # MKWS_SVC_MAX_ROWS: rows of one problem
+MAX_CLASSES = 8               # MKWS_SVC_MAX_CLASSES
+MAX_DIM = 1024                # MKWS_SVC_MAX_DIM
+TAU = 1e-12
+WORK_BUDGET = 512 << 20       # bytes of Gram workspace one fit launch may ask for; a larger call is split into chunks of problems
+
+SvcHost = namedtuple("SvcHost", "coef rho gamma centre inv_scale n_iter gap")
+SvcFit = namedtuple("SvcFit", "coef rho gamma centre inv_scale info gap d_coef d_rho d_gamma d_centre d_inv_scale d_info")
+
+
+def pairs(n_classes):
+    """[(i, j)] in the order of rho and of the decision values: (0, 1), (0, 2), ..."""
+    K = int(n_classes)
+    return [(i, j) for i in range(K) for j in range(i + 1, K)]
+
+
+def _slot(own, other):
+    return other if other < own else other - 1
+
+
+def scaling(x, rows, standardize=False, gamma=0.0):
+    """-> (centre float64 [dim], inv_scale float64 [dim], gamma float64) of one problem, as the module docstring defines them."""
+    X = np.asarray(x)[np.asarray(rows, dtype=np.int64)].astype(np.float64)
+    mu = X.mean(axis=0)
+    inv = np.ones(X.shape[1])
+    if standardize:
+        sigma = np.sqrt(((X - mu) ** 2).mean(axis=0))
+        sigma[sigma == 0.0] = 1.0
+        inv = 1.0 / sigma
+    if float(gamma) > 0.0:
+        return mu, inv, float(gamma)
+    seen = (X - mu) * inv if standardize else X
+    var = float(((seen - seen.mean()) ** 2).mean())
+    return mu, inv, 1.0 / (X.shape[1] * var) if var > 0.0 else 1.0
+
+
+def kernel_host(x, rows_a, rows_b, centre, inv_scale, gamma):
+    """float64 [len(rows_a), len(rows_b)]: exp(-gamma * |a~ - b~|^2) of bank rows under (centre, inv_scale, gamma), the distances formed
+    from the centred and scaled rows."""
+    x = np.asarray(x)
+    c, s = np.asarray(centre, dtype=np.float64), np.asarray(inv_scale, dtype=np.float64)
+    A = (x[np.asarray(rows_a, dtype=np.int64)].astype(np.float64) - c) * s
+    B = (x[np.asarray(rows_b, dtype=np.int64)].astype(np.float64) - c) * s
+    d2 = (A * A).sum(axis=1)[:, None] + (B * B).sum(axis=1)[None, :] - 2.0 * (A @ B.T)
+    return np.exp(-float(gamma) * np.maximum(d2, 0.0))
+
+
+def smo(Kp, y, C, tol, max_iter):
+    """libsvm's Solver (no shrinking) on one pair: Kp float64 [m, m] kernel values, y in {+1, -1}.
+    -> (alpha, G, rho, iterations, final gap m(a) - M(a), cut at max_iter)."""
+    m = len(y)
+    y = np.asarray(y, dtype=np.float64)
+    alpha, G, QD = np.zeros(m), -np.ones(m), np.diag(Kp).copy()
+    pos = y > 0
+    it, gap, cut = 0, np.inf, False
+    for it in range(int(max_iter) + 1):
+        v = -y * G
+        up = np.where(pos, alpha < C, alpha > 0.0)
+        low = np.where(pos, alpha > 0.0, alpha < C)
+        vi = np.where(up, v, -np.inf)
+        i = m - 1 - int(np.argmax(vi[::-1]))
+        gmax = vi[i]
+        gap = gmax - np.where(low, v, np.inf).min()
+        if gap < tol:
+            break
+        if it == max_iter:
+            cut = True
+            break
+        gd = gmax - v
+        quad = QD[i] + QD - 2.0 * Kp[i]
+        quad = np.where(quad > 0.0, quad, TAU)
+        obj = np.where(low & (gd > 0.0), -(gd * gd) / quad, np.inf)
+        j = m - 1 - int(np.argmin(obj[::-1]))
+        if not np.isfinite(obj[j]):
+            break
+        ai, aj = alpha[i], alpha[j]
+        q = Kp[i, i] + Kp[j, j] - 2.0 * Kp[i, j]
+        if q <= 0.0:
+            q = TAU
+        if y[i] != y[j]:
+            delta = (-G[i] - G[j]) / q
+            diff = ai - aj
+            ni, nj = ai + delta, aj + delta
+            if diff > 0.0:
+                if nj < 0.0:
+                    nj, ni = 0.0, diff
+            elif ni < 0.0:
+                ni, nj = 0.0, -diff
+            if diff > 0.0:
+                if ni > C:
+                    ni, nj = C, C - diff
+            elif nj > C:
+                nj, ni = C, C + diff
+        else:
+            delta = (G[i] - G[j]) / q
+            tot = ai + aj
+            ni, nj = ai - delta, aj + delta
+            if tot > C:
+                if ni > C:
+                    ni, nj = C, tot - C
+            elif nj < 0.0:
+                nj, ni = 0.0, tot
+            if tot > C:
+                if nj > C:
+                    nj, ni = C, tot - C
+            elif ni < 0.0:
+                ni, nj = 0.0, tot
+        G += y * (y[i] * Kp[i] * (ni - ai) + y[j] * Kp[j] * (nj - aj))
+        alpha[i], alpha[j] = ni, nj
+    yG = y * G
+    upper, lower = alpha >= C, alpha <= 0.0
+    free = ~upper & ~lower
+    if free.any():
+        rho = float(yG[free].mean())
+    else:
+        ub = np.where((upper & ~pos) | (lower & pos), yG, np.inf).min()
+        lb = np.where((upper & pos) | (lower & ~pos), yG, -np.inf).max()
+        rho = float((ub + lb) / 2.0)
+    return alpha, G, rho, it, float(gap), cut
+
+
+def _problem(x, rows, labels, n_classes):
+    K = int(n_classes)
+    rows, y = np.asarray(rows, dtype=np.int64), np.asarray(labels, dtype=np.int64)
+    x = np.asarray(x)
+    if x.ndim != 2 or rows.ndim != 1 or rows.shape != y.shape or rows.size == 0:
+        raise ValueError("x must be [rows, dim]; rows and labels one non-empty list each, of equal length")
+    if K < 2 or y.min() < 0 or y.max() >= K or rows.min() < 0 or rows.max() >= x.shape[0]:
+        raise ValueError("n_classes below 2, a label outside [0, n_classes) or a row outside the bank")
+    if len(np.unique(y)) < 2:
+        raise ValueError("fewer than two classes have a row")
+    return rows, y, K
+
+
+def svc_host(x, rows, labels, n_classes, C=1.0, standardize=False, gamma=0.0, tol=1e-10, max_iter=10_000_000):
+    """One problem in float64: every present pair's dual by SMO until its gap is below tol.
+    -> SvcHost(coef float64 [len(rows), K - 1], rho float64 [K (K - 1) / 2], gamma, centre [dim], inv_scale [dim], n_iter = the largest
+    iteration count of a pair, gap = the largest final gap)."""
+    rows, y, K = _problem(x, rows, labels, n_classes)
+    C = float(C)
+    if not C > 0.0:
+        raise ValueError("C must be positive")
+    centre, inv, g = scaling(x, rows, standardize, gamma)
+    Kall = kernel_host(x, rows, rows, centre, inv, g)
+    coef, rho = np.zeros((len(rows), K - 1)), np.zeros(K * (K - 1) // 2)
+    n_iter, worst = 0, 0.0
+    for q, (i, j) in enumerate(pairs(K)):
+        ti, tj = np.nonzero(y == i)[0], np.nonzero(y == j)[0]
+        if not len(ti) or not len(tj):
+            continue
+        idx = np.concatenate([ti, tj])
+        sign = np.concatenate([np.ones(len(ti)), -np.ones(len(tj))])
+        alpha, _, r, it, gap, cut = smo(Kall[np.ix_(idx, idx)], sign, C, float(tol), max_iter)
+        if cut:
+            raise RuntimeError(f"svc_host: pair ({i}, {j}) stopped at a gap of {gap:.3e} above {tol:.1e} after {it} iterations")
+        coef[ti, _slot(i, j)] = alpha[:len(ti)]
+        coef[tj, _slot(j, i)] = -alpha[len(ti):]
+        rho[q] = r
+        n_iter, worst = max(n_iter, it), max(worst, gap)
+    return SvcHost(coef, rho, g, centre, inv, n_iter, worst)
+
+
+def decision_host(x, eval_rows, train_rows, train_labels, n_classes, coef, rho, gamma, centre, inv_scale):
+    """float64 [len(eval_rows), K (K - 1) / 2]: f_ij of bank rows `eval_rows` under a model (its training rows and labels, coef
+    [len(train_rows), K - 1], rho, gamma, centre, inv_scale), pairs in the order of pairs(K); 0 for a pair with an absent class.  The
+    expression mkws_svc_score evaluates in float32."""
+    K = int(n_classes)
+    y = np.asarray(train_labels, dtype=np.int64)
+    coef, rho = np.asarray(coef).astype(np.float64), np.asarray(rho).astype(np.float64)
+    kv = kernel_host(x, train_rows, eval_rows, centre, inv_scale, gamma)                      # [train, eval]
+    out = np.zeros((len(np.asarray(eval_rows)), K * (K - 1) // 2))
+    for q, (i, j) in enumerate(pairs(K)):
+        ti, tj = y == i, y == j
+        if ti.any() and tj.any():
+            out[:, q] = coef[ti, _slot(i, j)] @ kv[ti] + coef[tj, _slot(j, i)] @ kv[tj] - rho[q]
+    return out
+
+
+def predict_host(decision, train_labels, n_classes):
+    """int32 [rows]: one-vs-one votes over the pairs of present classes (f_ij > 0 votes i, otherwise j), the lowest class on ties."""
+    K = int(n_classes)
+    present = np.bincount(np.asarray(train_labels, dtype=np.int64), minlength=K) > 0
+    decision = np.asarray(decision)
+    votes = np.zeros((decision.shape[0], K), np.int64)
+    for q, (i, j) in enumerate(pairs(K)):
+        if present[i] and present[j]:
+            win = decision[:, q] > 0
+            votes[:, i] += win
+            votes[:, j] += ~win
+    votes[:, ~present] = -1
+    return votes.argmax(axis=1).astype(np.int32)
+
+
+def check_problems(rows, labels, offsets, n_rows, dim, n_classes, C=1.0):
+    """The refusals of fit_on_device / score_on_device, made before anything is uploaded -> (rows int32, labels int32, offsets int32,
+    C float64 [P]).  Refused: n_classes outside [2, MAX_CLASSES], dim outside [1, MAX_DIM], lists of unequal length, offsets that are not
+    P + 1 non-decreasing integers inside [0, len(rows)], a problem of more than MAX_ROWS rows, a C that is not positive and finite or not
+    one per problem.  What the lists hold is the device's to check: an empty problem, a label outside [0, n_classes), a row outside the
+    bank or fewer than two present classes gives that problem status 2."""
+    K = int(n_classes)
+    if not 2 <= K <= MAX_CLASSES:
+        raise ValueError(f"n_classes {K} outside [2, {MAX_CLASSES}]")
+    if not 1 <= int(dim) <= MAX_DIM:
+        raise ValueError(f"dim {int(dim)} outside [1, {MAX_DIM}]")
+    if int(n_rows) < 0:
+        raise ValueError("a bank of fewer than 0 rows")
+    rows, labels, off = np.asarray(rows), np.asarray(labels), np.asarray(offsets)
+    if rows.size == 0:
+        rows = rows.astype(np.int32)
+    if labels.size == 0:
+        labels = labels.astype(np.int32)
+    for name, a in (("rows", rows), ("labels", labels)):
+        if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must be one flat list of integers")
+    if rows.shape != labels.shape:
+        raise ValueError(f"{rows.size} rows for {labels.size} labels")
+    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError("offsets must be a list of P + 1 integers")
+    off = off.astype(np.int64)
+    if off[0] < 0 or off[-1] > rows.size or (np.diff(off) < 0).any():
+        raise ValueError(f"offsets must be non-decreasing and inside [0, {rows.size}]")
+    sizes = np.diff(off)
+    for p in np.nonzero(sizes > MAX_ROWS)[0][:1]:
+        raise ValueError(f"problem {int(p)} has {int(sizes[p])} rows: at most {MAX_ROWS}")
+    P = off.size - 1
+    Cs = np.full(P, float(C)) if np.ndim(C) == 0 else np.asarray(C, dtype=np.float64).reshape(-1)
+    if Cs.size != P:
+        raise ValueError(f"{Cs.size} values of C for {P} problems")
+    if not (np.isfinite(Cs).all() and (Cs > 0).all()):
+        raise ValueError("C must be positive and finite")
+    clip = lambda a: np.clip(a, -2 ** 31, 2 ** 31 - 1).astype(np.int32)      # (an index out of int32 stays out of every bank)
+    return clip(rows), clip(labels), off.astype(np.int32), Cs.astype(np.float64)
+
+
+def _bank(x):
+    """numpy float32 [rows, dim] is uploaded; a CUDA tensor is taken as it is."""
+    import torch
+    if not torch.is_tensor(x):
+        x = np.asarray(x)
+        if x.dtype != np.float32:
+            raise ValueError("x must be float32")
+        x = np.ascontiguousarray(x)
+        x = torch.from_numpy(x if x.flags.writeable else x.copy()).cuda()
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError("x must be a CUDA tensor or numpy array [rows, dim] of float32")
+    return x.contiguous()
+
+
+def _int_list(a, name, dev):
+    import torch
+    if not torch.is_tensor(a):
+        a = np.asarray(a)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must hold integers")
+        a = torch.from_numpy(np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32).reshape(-1)).to(dev, non_blocking=True)
+    if a.dtype != torch.int32 or a.dim() != 1 or a.device != dev:
+        raise ValueError(f"{name} must be a flat int32 list on the device of x")
+    return a.contiguous()
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def chunks(offsets, budget):
+    """[(first problem, one past the last)]: consecutive runs of problems whose Gram workspace (problems * largest row count squared * 4
+    bytes) stays inside `budget`; a single problem always forms a chunk."""
+    sizes = np.diff(np.asarray(offsets, dtype=np.int64))
+    out, lo, biggest = [], 0, 0
+    for p, n in enumerate(sizes):
+        grown = max(biggest, int(n))
+        if p > lo and (p + 1 - lo) * grown * grown * 4 > int(budget):
+            out.append((lo, p))
+            lo, grown = p, int(n)
+        biggest = grown
+    if len(sizes) > lo:
+        out.append((lo, len(sizes)))
+    return out
+
+
+def fit_on_device(x, rows, labels, offsets, n_classes, C=1.0, standardize=False, gamma=0.0, tol=1e-5, max_iter=100000, work_budget=WORK_BUDGET,
+                  timings=None):
+    """x: CUDA tensor or numpy array [bank rows, dim] float32; problem p trains on bank rows rows[offsets[p] : offsets[p + 1]] with
+    labels[...] in [0, n_classes) (rows may repeat inside and across problems: nothing is copied); C: one value or one per problem;
+    gamma: a positive value, or 0 for sklearn's "scale".
+    -> SvcFit(coef float32 [len(rows), K - 1] aligned with the flat row list (module docstring), rho float32 [P, K (K - 1) / 2], gamma
+    float32 [P], centre and inv_scale float32 [P, dim], info int32 [P, 4] = {status, present pairs, pairs cut at max_iter, largest
+    iteration count of a pair}, gap float32 [P] = the largest final m(a) - M(a) of a pair, and d_* = the same still on the device).
+    status 0 fitted, 2 = no row, a label or row out of range, or fewer than two present classes (nothing else is written for it).
+    Three launches per chunk (mkws_svc_prepare, mkws_svc_kernel for the Gram matrices, mkws_svc_fit) and one copy back.  The Gram
+    matrices take problems * (largest row count)^2 * 4 bytes; a call that would need more than work_budget bytes (default 512 MiB) is
+    run as consecutive chunks of problems, with the same results.  timings: a dict that receives prepare / gram / smo milliseconds
+    (device events; this synchronises).  What check_problems refuses is refused before anything is uploaded."""
+    import torch
+    if not torch.is_tensor(x):
+        x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError("x must be [rows, dim]")
+    n_rows, dim = int(x.shape[0]), int(x.shape[1])
+    K = int(n_classes)
+    rows, labels, off, Cs = check_problems(rows, labels, offsets, n_rows, dim, K, C)
+    if int(max_iter) < 1 or not float(tol) >= 0 or not np.isfinite(float(gamma)) or int(work_budget) < 1:
+        raise ValueError("max_iter must be at least 1, tol non-negative, gamma finite and work_budget positive")
+    P, n_list, npairs = off.size - 1, rows.size, K * (K - 1) // 2
+    x = _bank(x)
+    dev = x.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        d_in, (p_C, p_off, p_rows, p_labels) = _lib.upload_words([Cs, off, rows, labels], dev)
+        # every output in ONE buffer of 4-byte words, so that they cross in one copy
+        at = np.cumsum([0, n_list * (K - 1), P * npairs, P, P * dim, P * dim, 4 * P, P])
+        d_out = torch.zeros(int(at[-1]), dtype=torch.int32, device=dev)
+        ptr = [d_out.data_ptr() + 4 * int(a) for a in at]
+        stream = _lib.current_stream_ptr()
+        marks = []
+        for lo, hi in chunks(off, work_budget) if P else []:
+            n, biggest = hi - lo, int(np.diff(off[lo:hi + 1]).max())
+            d_work = torch.empty(int(L.mkws_svc_work_bytes(n, biggest)) // 4, dtype=torch.float32, device=dev)
+            q_off, q_C = p_off + 4 * lo, p_C + 8 * lo
+            q = lambda i, per: ptr[i] + 4 * lo * per
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
+            if ev:
+                ev[0].record()
+            _lib.check(L.mkws_svc_prepare(x.data_ptr(), n_rows, dim, p_rows, p_labels, q_off, n, K, biggest, int(bool(standardize)), float(gamma),
+                                          q(3, dim), q(4, dim), q(2, 1), q(5, 4), q(6, 1), stream))
+            if ev:
+                ev[1].record()
+            _lib.check(L.mkws_svc_kernel(x.data_ptr(), n_rows, dim, p_rows, q_off, biggest, p_rows, q_off, biggest, n, q(3, dim), q(4, dim), q(2, 1),
+                                         q(5, 4), d_work.data_ptr(), biggest * biggest, stream))
+            if ev:
+                ev[2].record()
+            _lib.check(L.mkws_svc_fit(p_labels, q_off, n, K, biggest, q_C, float(tol), int(max_iter), d_work.data_ptr(), biggest * biggest,
+                                      ptr[0], q(1, npairs), q(5, 4), q(6, 1), stream))
+            if ev:
+                ev[3].record()
+                marks.append(ev)
+        out = d_out.cpu().numpy()                                      # the call's one synchronisation
+        if timings is not None:
+            for k, name in enumerate(("prepare", "gram", "smo")):
+                timings[name] = timings.get(name, 0.0) + sum(ev[k].elapsed_time(ev[k + 1]) for ev in marks)
+    cut = lambda i, dtype, *shape: out[at[i]:at[i + 1]].view(dtype).reshape(*shape)
+    dcut = lambda i, dtype, *shape: d_out[int(at[i]):int(at[i + 1])].view(dtype).view(*shape)
+    f32, t32 = np.float32, torch.float32
+    return SvcFit(cut(0, f32, n_list, K - 1), cut(1, f32, P, npairs), cut(2, f32, P), cut(3, f32, P, dim), cut(4, f32, P, dim),
+                  cut(5, np.int32, P, 4), cut(6, f32, P), dcut(0, t32, n_list, K - 1), dcut(1, t32, P, npairs), dcut(2, t32, P),
+                  dcut(3, t32, P, dim), dcut(4, t32, P, dim), dcut(5, torch.int32, P, 4))
+
+
+def kernel_on_device(x, rows_a, rows_b, centre, inv_scale, gamma):
+    """x: CUDA tensor [bank rows, dim] float32; rows_a / rows_b: CUDA int32 lists or host lists; centre / inv_scale: CUDA float32 [dim]
+    or host arrays; gamma: a float.  -> CUDA float32 [len(rows_a), len(rows_b)] = exp(-gamma * max(0, s_a + s_b - 2 a~.b~)) (float64 exp, rounded once),
+    NaN where a row is outside the bank.  Asynchronous."""
+    import torch
+    x = _bank(x)
+    dev = x.device
+    n_rows, dim = (int(v) for v in x.shape)
+    if not 1 <= dim <= MAX_DIM:
+        raise ValueError(f"dim {dim} outside [1, {MAX_DIM}]")
+    d_a, d_b = _int_list(rows_a, "rows_a", dev), _int_list(rows_b, "rows_b", dev)
+    par = []
+    for name, a in (("centre", centre), ("inv_scale", inv_scale)):
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        if a.dtype != torch.float32 or tuple(a.shape) != (dim,) or a.device != dev:
+            raise ValueError(f"{name} must be float32 [{dim}] on the device of x")
+        par.append(a.contiguous())
+    na, nb = int(d_a.numel()), int(d_b.numel())
+    with torch.cuda.device(dev):
+        d_gamma = torch.full((1,), float(gamma), dtype=torch.float32, device=dev)
+        d_offs = torch.tensor([0, na, 0, nb], dtype=torch.int32, device=dev)
+        out = torch.empty((na, nb), dtype=torch.float32, device=dev)
+        if na and nb:
+            _lib.check(_lib.lib().mkws_svc_kernel(x.data_ptr(), n_rows, dim, d_a.data_ptr(), d_offs.data_ptr(), na, d_b.data_ptr(), d_offs.data_ptr() + 8, nb,
+                                                  1, par[0].data_ptr(), par[1].data_ptr(), d_gamma.data_ptr(), None, out.data_ptr(), na * nb,
+                                                  _lib.current_stream_ptr()))
+    return out
+
+
+def score_on_device(x, rows, true, offsets, train_rows, train_labels, train_offsets, n_classes, coef, rho, gamma, centre, inv_scale, info=None,
+                    want_decision=False, timings=None):
+    """x: CUDA tensor [bank rows, dim] float32; problem p is scored on ITS list rows[offsets[p] : offsets[p + 1]] against true[...] under
+    model p: the flat training lists it was fitted on (train_rows, train_labels, train_offsets) and what fit_on_device left on the device
+    (coef [len(train_rows), K - 1], rho [P, K (K - 1) / 2], gamma [P], centre / inv_scale [P, dim], optionally info [P, 4]).  Lists: CUDA
+    int32 tensors or host lists (uploaded non-blocking).
+    -> (pred int32 [total], correct int32 [P] = rows with pred == true, decision float32 [total, K (K - 1) / 2] or None), CUDA tensors.
+    Asynchronous unless timings (a dict that receives "score" milliseconds) is given.  A row outside the bank, an entry outside every list
+    or a problem whose info says it was refused gets pred -1 (NaN decision values) and is never correct."""
+    import torch
+    x = _bank(x)
+    dev = x.device
+    n_rows, dim = (int(v) for v in x.shape)
+    K = int(n_classes)
+    if not 2 <= K <= MAX_CLASSES or not 1 <= dim <= MAX_DIM:
+        raise ValueError(f"n_classes {K} outside [2, {MAX_CLASSES}] or dim {dim} outside [1, {MAX_DIM}]")
+    npairs = K * (K - 1) // 2
+    d_rows, d_true, d_off = (_int_list(a, n, dev) for a, n in ((rows, "rows"), (true, "true"), (offsets, "offsets")))
+    t_rows, t_labels, t_off = (_int_list(a, n, dev) for a, n in ((train_rows, "train_rows"), (train_labels, "train_labels"), (train_offsets, "train_offsets")))
+    P, total, n_train = int(d_off.numel()) - 1, int(d_rows.numel()), int(t_rows.numel())
+    if P < 0 or d_true.numel() != total or t_off.numel() != P + 1 or t_labels.numel() != n_train:
+        raise ValueError(f"{total} rows, {int(d_true.numel())} labels, {int(d_off.numel())} offsets and {int(t_off.numel())} training offsets")
+    for name, a, shape in (("coef", coef, (n_train, K - 1)), ("rho", rho, (P, npairs)), ("gamma", gamma, (P,)), ("centre", centre, (P, dim)),
+                           ("inv_scale", inv_scale, (P, dim))):
+        if not (torch.is_tensor(a) and a.device == dev and a.dtype == torch.float32 and tuple(a.shape) == shape):
+            raise ValueError(f"{name} must be a CUDA float32 tensor of shape {shape}")
+    if info is not None and not (torch.is_tensor(info) and info.device == dev and info.dtype == torch.int32 and tuple(info.shape) == (P, 4)):
+        raise ValueError(f"info must be a CUDA int32 tensor of shape {(P, 4)}")
+    # the grid is sized by the longest lists: offsets given on the host are read here, device ones are copied back (a synchronisation)
+    longest = lambda a, d: int(np.diff(np.asarray(a)).max()) if not torch.is_tensor(a) else int((d[1:] - d[:-1]).max().item())
+    max_eval = max(longest(offsets, d_off), 0) if P else 0
+    max_train = max(longest(train_offsets, t_off), 0) if P else 0
+    if max_train > MAX_ROWS:
+        raise ValueError(f"a model of {max_train} rows: at most {MAX_ROWS}")
+    coef, rho, gamma, centre, inv_scale = (a.contiguous() for a in (coef, rho, gamma, centre, inv_scale))
+    with torch.cuda.device(dev):
+        pred = torch.empty(total, dtype=torch.int32, device=dev)
+        correct = torch.empty(P, dtype=torch.int32, device=dev)
+        decision = torch.empty((total, npairs), dtype=torch.float32, device=dev) if want_decision else None
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
+        if ev:
+            ev[0].record()
+        _lib.check(_lib.lib().mkws_svc_score(x.data_ptr(), n_rows, dim, _ptr(t_rows), _ptr(t_labels), t_off.data_ptr(), max_train, _ptr(coef), _ptr(rho),
+                                             _ptr(gamma), _ptr(centre), _ptr(inv_scale), _ptr(info.contiguous()) if info is not None else None, P, K,
+                                             _ptr(d_rows), _ptr(d_true), d_off.data_ptr(), total, max_eval, _ptr(pred), _ptr(correct), _ptr(decision),
+                                             _lib.current_stream_ptr()))
+        if ev:
+            ev[1].record()
+            ev[1].synchronize()
+            timings["score"] = timings.get("score", 0.0) + ev[0].elapsed_time(ev[1])
+    return pred, correct, decision
