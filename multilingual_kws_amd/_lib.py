@@ -283,3 +283,48 @@ def upload_words(parts, device):
     words, offsets = pack_words(parts)
     d_words = torch.from_numpy(words).to(device, non_blocking=True)
     return d_words, [d_words.data_ptr() + o for o in offsets]
+
+
+def word_layout(parts):
+    """The host side of "one copy back": parts (name, dtype, shape) of int32, float32 or float64 laid out one after the other in ONE
+    buffer of 4-byte words -> [first word of every part, ..., total words].  An 8-byte part must start on an even word (put them first)."""
+    at = [0]
+    for name, dtype, shape in parts:
+        size = np.dtype(dtype).itemsize
+        if np.dtype(dtype).char not in "ifd":
+            raise TypeError(f"word_layout takes int32, float32 and float64 parts, not {np.dtype(dtype)} ({name})")
+        if size == 8 and at[-1] % 2:
+            raise ValueError(f"8-byte part {name} would start at word {at[-1]}: put the 8-byte parts first")
+        at.append(at[-1] + int(np.prod(shape, dtype=np.int64)) * (size // 4))
+    return at
+
+
+class OutputWords:
+    """Every output of a call in ONE device buffer of 4-byte words (word_layout), so that they cross in one copy.  Every word starts as 0;
+    with fill = {name: int32} those parts are preset and the rest is left for the kernel to write."""
+
+    def __init__(self, parts, device, fill=None):
+        import torch
+        at = word_layout(parts)
+        self.parts = {name: (slice(a, b), np.dtype(dtype), tuple(shape)) for (name, dtype, shape), a, b in zip(parts, at, at[1:])}
+        self.d_words = (torch.empty if fill else torch.zeros)(at[-1], dtype=torch.int32, device=device)
+        for name, value in (fill or {}).items():
+            self.d_words[self.parts[name][0]] = value
+
+    def ptr(self, name, first=0):
+        """Device pointer of element `first` of the flattened part."""
+        cut, dtype, _ = self.parts[name]
+        return self.d_words.data_ptr() + 4 * cut.start + dtype.itemsize * int(first)
+
+    def fetch(self):
+        """The call's one copy back (it synchronises); host() reads from it."""
+        self.words = self.d_words.cpu().numpy()
+
+    def host(self, name):
+        cut, dtype, shape = self.parts[name]
+        return self.words[cut].view(dtype).reshape(shape)
+
+    def device(self, name):
+        import torch
+        cut, dtype, shape = self.parts[name]
+        return self.d_words[cut].view(getattr(torch, dtype.name)).view(shape)

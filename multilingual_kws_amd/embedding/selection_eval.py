@@ -18,6 +18,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from .. import logreg, problems, svc
+
 KeywordEmbeddings = namedtuple("KeywordEmbeddings", "bank clip_ids offsets")
 
 CLASSIFIERS = {"lr": False, "lr_scaled": True, "svc": False, "svc_scaled": True}       # name -> standardize
@@ -110,11 +112,68 @@ def _accuracy(correct, offsets):
     return [int(c) / int(n) if n else 0.0 for c, n in zip(correct, np.diff(offsets))]
 
 
-def _chosen_models(fit_lists, chosen):
-    """The training lists of the chosen problems as lists of their own -> (positions in the flat fit lists, offsets)."""
-    off = fit_lists[2]
-    take = [np.arange(off[c], off[c + 1]) for c in chosen]
-    return np.concatenate(take), np.concatenate([[0], np.cumsum([len(t) for t in take])]).astype(np.int64)
+def _each(lists):
+    """[(rows, labels)] of the problems of flat lists (rows, labels, offsets)."""
+    return [(lists[0][a:b], lists[1][a:b]) for a, b in zip(lists[2][:-1], lists[2][1:])]
+
+
+def _to(device, index):
+    import torch
+    return torch.from_numpy(np.asarray(index, np.int64)).to(device)
+
+
+def _refused(models):
+    """Index of the first problem the device refused (info[:, 0] != 0), or None.  The host solvers raise by themselves."""
+    bad = [] if isinstance(models, list) else np.nonzero(models.info[:, 0])[0]
+    return int(bad[0]) if len(bad) else None
+
+
+def _lr_fit(bank, fit_lists, K, C, standardize, max_iter, gtol, tol):
+    if isinstance(bank, np.ndarray):
+        return [logreg.logreg_host(bank, rows, labels, K, C, standardize) for rows, labels in _each(fit_lists)]
+    return logreg.fit_on_device(bank, *fit_lists, K, C=C, standardize=standardize, max_iter=max_iter, gtol=gtol)
+
+
+def _lr_count_correct(bank, models, which, fit_lists, eval_lists, K):
+    if isinstance(bank, np.ndarray):
+        models = models if which is None else [models[c] for c in which]
+        return [int((logreg.predict_host(bank, rows, m.coef, m.intercept)[0] == true).sum()) for m, (rows, true) in zip(models, _each(eval_lists))]
+    model = (models.d_coef, models.d_intercept)
+    if which is not None:
+        d_which = _to(bank.device, which)
+        model = [m[d_which].contiguous() for m in model]
+    return logreg.score_on_device(bank, *eval_lists, *model)[1].cpu().numpy()
+
+
+def _svc_fit(bank, fit_lists, K, C, standardize, max_iter, gtol, tol):
+    if isinstance(bank, np.ndarray):
+        return [(rows, labels, svc.svc_host(bank, rows, labels, K, C, standardize)) for rows, labels in _each(fit_lists)]
+    return svc.fit_on_device(bank, *fit_lists, K, C=C, standardize=standardize, tol=tol, max_iter=max_iter)
+
+
+def _svc_count_correct(bank, models, which, fit_lists, eval_lists, K):
+    if isinstance(bank, np.ndarray):
+        models = models if which is None else [models[c] for c in which]
+        return [int((svc.predict_host(svc.decision_host(bank, rows, tr, ty, K, m.coef, m.rho, m.gamma, m.centre, m.inv_scale), ty, K) == true).sum())
+                for (tr, ty, m), (rows, true) in zip(models, _each(eval_lists))]
+    model = (models.d_coef, models.d_rho, models.d_gamma, models.d_centre, models.d_inv_scale)
+    if which is not None:
+        # svc's coefficients are per training row: the chosen problems' training lists become lists of their own
+        take = [np.arange(fit_lists[2][c], fit_lists[2][c + 1]) for c in which]
+        at, off = np.concatenate(take), np.concatenate([[0], np.cumsum([len(t) for t in take])]).astype(np.int64)
+        fit_lists = (fit_lists[0][at], fit_lists[1][at], off)
+        d_at, d_which = _to(bank.device, at), _to(bank.device, which)
+        model = [model[0][d_at].contiguous()] + [m[d_which].contiguous() for m in model[1:]]
+    return svc.score_on_device(bank, *eval_lists, *fit_lists, K, *model)[1].cpu().numpy()
+
+
+# What experiment_run_many asks of a classifier.  fit -> models, on the host (a numpy bank: one model per problem, the host solvers raise
+# by themselves) or on the device (a CUDA bank: the *Fit tuple); refused(models) -> the first refused problem or None; count_correct ->
+# correct rows per problem of eval_lists, under model p for list p (which = None) or under model which[p]; max_iter = what None stands for
+Classifier = namedtuple("Classifier", "fit refused count_correct refusal max_iter")
+_LR = Classifier(_lr_fit, _refused, _lr_count_correct, "a row outside the bank, or no row at all", 300)
+_SVC = Classifier(_svc_fit, _refused, _svc_count_correct, "a row outside the bank, no row at all, or fewer than two classes with a row", 100000)
+IMPLEMENTATIONS = {"lr": _LR, "lr_scaled": _LR, "svc": _SVC, "svc_scaled": _SVC}
 
 
 def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows, splits, classifier="lr", C=1.0, max_iter=None, gtol=1e-6,
@@ -137,13 +196,12 @@ def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows
     GPU is available; False, or a host without one, takes the same flow through logreg.logreg_host and logreg.predict_host, or
     svc.svc_host, svc.decision_host and svc.predict_host."""
     import torch
-    from .. import logreg, svc
     if classifier not in CLASSIFIERS:
         raise ValueError(f"classifier {classifier!r}: one of {sorted(CLASSIFIERS)} (SVC(probability=True), the voting ensemble, random forest, "
                          "gradient boosting and L1 are not built)")
-    standardize, is_svc = CLASSIFIERS[classifier], classifier.startswith("svc")
+    standardize, impl = CLASSIFIERS[classifier], IMPLEMENTATIONS[classifier]
     if max_iter is None:
-        max_iter = 100000 if is_svc else 300
+        max_iter = impl.max_iter
     experiments = list(experiments)
     if not experiments:
         return []
@@ -151,57 +209,14 @@ def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows
     first = np.concatenate([[0], np.cumsum(n_splits)])
     if on_device is None:
         on_device = torch.cuda.is_available()
-
-    if not on_device and is_svc:
-        x = bank.cpu().numpy() if torch.is_tensor(bank) else np.asarray(bank)
-        models = [(fit[0][a:b], fit[1][a:b], svc.svc_host(x, fit[0][a:b], fit[1][a:b], K, C, standardize)) for a, b in zip(fit[2][:-1], fit[2][1:])]
-
-        def host_correct(model, rows, true):
-            tr, ty, m = model
-            return int((svc.predict_host(svc.decision_host(x, rows, tr, ty, K, m.coef, m.rho, m.gamma, m.centre, m.inv_scale), ty, K) == true).sum())
-
-        val_correct = [host_correct(m, val[0][a:b], val[1][a:b]) for m, a, b in zip(models, val[2][:-1], val[2][1:])]
-        scores = _accuracy(val_correct, val[2])
-        best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
-        dev_correct = [host_correct(models[first[e] + best[e]], dev[0][a:b], dev[1][a:b]) for e, (a, b) in enumerate(zip(dev[2][:-1], dev[2][1:]))]
-    elif is_svc:
-        d_bank = svc._bank(bank)
-        with torch.cuda.device(d_bank.device):
-            fitted = svc.fit_on_device(d_bank, fit[0], fit[1], fit[2], K, C=C, standardize=standardize, tol=tol, max_iter=max_iter)
-            if (fitted.info[:, 0] != 0).any():
-                raise ValueError(f"problem {int(np.nonzero(fitted.info[:, 0])[0][0])} was refused by the device: a row outside the bank, no row at all, "
-                                 "or fewer than two classes with a row")
-            model = (fitted.d_coef, fitted.d_rho, fitted.d_gamma, fitted.d_centre, fitted.d_inv_scale)
-            _, d_correct, _ = svc.score_on_device(d_bank, val[0], val[1], val[2], fit[0], fit[1], fit[2], K, *model)
-            scores = _accuracy(d_correct.cpu().numpy(), val[2])
-            best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
-            chosen = np.asarray([first[e] + best[e] for e in range(len(experiments))], np.int64)
-            at, off = _chosen_models(fit, chosen)
-            d_at, d_chosen = torch.from_numpy(at).to(d_bank.device), torch.from_numpy(chosen).to(d_bank.device)
-            _, d_correct, _ = svc.score_on_device(d_bank, dev[0], dev[1], dev[2], fit[0][at], fit[1][at], off, K, model[0][d_at].contiguous(),
-                                                  *(m[d_chosen].contiguous() for m in model[1:]))
-            dev_correct = d_correct.cpu().numpy()
-    elif not on_device:
-        x = bank.cpu().numpy() if torch.is_tensor(bank) else np.asarray(bank)
-        models = [logreg.logreg_host(x, fit[0][a:b], fit[1][a:b], K, C, standardize) for a, b in zip(fit[2][:-1], fit[2][1:])]
-        val_correct = [int((logreg.predict_host(x, val[0][a:b], m.coef, m.intercept)[0] == val[1][a:b]).sum())
-                       for m, a, b in zip(models, val[2][:-1], val[2][1:])]
-        scores = _accuracy(val_correct, val[2])
-        best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
-        dev_correct = [int((logreg.predict_host(x, dev[0][a:b], models[first[e] + best[e]].coef, models[first[e] + best[e]].intercept)[0] == dev[1][a:b]).sum())
-                       for e, (a, b) in enumerate(zip(dev[2][:-1], dev[2][1:]))]
-    else:
-        d_bank = logreg._bank(logreg._check_bank(bank)[0])
-        with torch.cuda.device(d_bank.device):
-            fitted = logreg.fit_on_device(d_bank, fit[0], fit[1], fit[2], K, C=C, standardize=standardize, max_iter=max_iter, gtol=gtol)
-            if (fitted.info[:, 0] != 0).any():
-                raise ValueError(f"problem {int(np.nonzero(fitted.info[:, 0])[0][0])} was refused by the device: a row outside the bank, or no row at all")
-            _, d_correct, _, _ = logreg.score_on_device(d_bank, val[0], val[1], val[2], fitted.d_coef, fitted.d_intercept)
-            scores = _accuracy(d_correct.cpu().numpy(), val[2])
-            best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
-            chosen = torch.from_numpy(np.asarray([first[e] + best[e] for e in range(len(experiments))], np.int64)).to(d_bank.device)
-            _, d_correct, _, _ = logreg.score_on_device(d_bank, dev[0], dev[1], dev[2], fitted.d_coef[chosen].contiguous(), fitted.d_intercept[chosen].contiguous())
-            dev_correct = d_correct.cpu().numpy()
-    final = _accuracy(dev_correct, dev[2])
+    # the bank goes where the work is done, and tells the classifier which implementation to take
+    bank = problems.device_bank(bank) if on_device else bank.cpu().numpy() if torch.is_tensor(bank) else np.asarray(bank)
+    models = impl.fit(bank, fit, K, C=C, standardize=standardize, max_iter=max_iter, gtol=gtol, tol=tol)
+    bad = impl.refused(models)
+    if bad is not None:
+        raise ValueError(f"problem {bad} was refused by the device: {impl.refusal}")
+    scores = _accuracy(impl.count_correct(bank, models, None, fit, val, K), val[2])
+    best = [int(np.argmax(scores[first[e]:first[e + 1]])) for e in range(len(experiments))]
+    final = _accuracy(impl.count_correct(bank, models, [first[e] + best[e] for e in range(len(experiments))], fit, dev, K), dev[2])
     return [dict(words=list(e["words"]), score=final[i], crossfold_scores=scores[first[i]:first[i + 1]], best_split=best[i])
             for i, e in enumerate(experiments)]

@@ -14,7 +14,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, problems
 
 MAX_POINTS = 1024             # MKWS_KMEANS_MAX_POINTS
 MAX_CLUSTERS = 16             # MKWS_KMEANS_MAX_CLUSTERS
@@ -148,12 +148,7 @@ def check_groups(offsets, n_rows, dim, n_clusters):
         raise ValueError(f"n_clusters {k} outside [1, {MAX_CLUSTERS}]")
     if dim < 1 or k * dim > MAX_CENTER_VALUES or (k + 1) * dim > MAX_LDS_VALUES:
         raise ValueError(f"n_clusters * dim = {k * dim} above {MAX_CENTER_VALUES}, or (n_clusters + 1) * dim = {(k + 1) * dim} above {MAX_LDS_VALUES}")
-    off = np.asarray(offsets)
-    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError("offsets must be a list of n_groups + 1 integers")
-    off = off.astype(np.int64)
-    if off[0] < 0 or off[-1] > n_rows or (np.diff(off) < 0).any():
-        raise ValueError(f"offsets must be non-decreasing and inside [0, {n_rows}]")
+    off = problems.check_offsets(offsets, n_rows, "group")
     sizes = np.diff(off)
     for g in np.nonzero(sizes < k)[0][:1]:
         raise ValueError(f"group {int(g)} has {int(sizes[g])} points for {k} clusters")
@@ -169,13 +164,7 @@ def kmeans_fit_on_device(x, offsets, n_clusters, seeds, max_iter=300, tol=1e-4, 
     One upload (offsets and draws), one launch, one copy back.  Bad offsets, a group smaller than n_clusters or larger than MAX_POINTS
     and shapes above the caps are refused before anything is uploaded."""
     import torch
-    if not torch.is_tensor(x):
-        x = np.asarray(x)
-        if x.dtype != np.float32:
-            raise ValueError("x must be float32")
-    if x.ndim != 2:
-        raise ValueError("x must be [rows, dim]")
-    rows, dim = (int(v) for v in x.shape)
+    rows, dim = problems.bank_shape(x)
     k = int(n_clusters)
     off = check_groups(offsets, rows, dim, k)
     G = off.size - 1
@@ -186,30 +175,21 @@ def kmeans_fit_on_device(x, offsets, n_clusters, seeds, max_iter=300, tol=1e-4, 
         raise ValueError("max_iter must be at least 1 and tol non-negative")
     T = n_local_trials(k)
     draws = np.stack([kmeans_draws(s, k) for s in seeds]) if G else np.zeros((0, 1 + (k - 1) * T))
-    if not torch.is_tensor(x):
-        x = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    if not x.is_cuda or x.dtype != torch.float32:
-        raise ValueError("x must be a CUDA tensor or numpy array [rows, dim] of float32")
-    x = x.contiguous()
+    x = problems.device_bank(x)
     dev = x.device
     with torch.cuda.device(dev):
         # one upload of 8-byte words: the draws, then the offsets in pairs
         d_in, (p_draws, p_off) = _lib.upload_words([draws, off], dev)
-        # every output in ONE buffer of 4-byte words, so that they cross in one copy: [f64 centres] centres, labels, init, info
-        n64 = 2 * G * k * dim if want_f64 else 0
-        at = np.cumsum([0, n64, G * k * dim, rows, G * k, G * 4])
-        d_out = torch.empty(int(at[-1]), dtype=torch.int32, device=dev)     # (allocations are 8-byte aligned: the float64 part comes first)
-        d_out[int(at[2]):int(at[3])] = -1
-        base = d_out.data_ptr()
-        ptr = [base + 4 * int(a) for a in at]
+        out = _lib.OutputWords([("centers_f64", np.float64, (G, k, dim))] * bool(want_f64) +
+                               [("centers", np.float32, (G, k, dim)), ("labels", np.int32, (rows,)), ("init", np.int32, (G, k)),
+                                ("info", np.int32, (G, 4))], dev, fill={"labels": -1})
         if G:
-            _lib.check(_lib.lib().mkws_kmeans_fit(x.data_ptr(), dim, p_off, G, k, p_draws, T, int(max_iter), float(tol), ptr[1],
-                                                  ptr[0] if want_f64 else None, ptr[2], ptr[3], ptr[4], _lib.current_stream_ptr()))
-        out = d_out.cpu().numpy()                                      # the call's one synchronisation
-    d_centers = d_out[int(at[1]):int(at[2])].view(torch.float32).view(G, k, dim)
-    return KMeansFit(out[at[1]:at[2]].view(np.float32).reshape(G, k, dim),
-                     out[at[0]:at[1]].view(np.float64).reshape(G, k, dim) if want_f64 else None,
-                     out[at[2]:at[3]], out[at[3]:at[4]].reshape(G, k), out[at[4]:at[5]].reshape(G, 4), d_centers)
+            _lib.check(_lib.lib().mkws_kmeans_fit(x.data_ptr(), dim, p_off, G, k, p_draws, T, int(max_iter), float(tol), out.ptr("centers"),
+                                                  out.ptr("centers_f64") if want_f64 else None, out.ptr("labels"), out.ptr("init"),
+                                                  out.ptr("info"), _lib.current_stream_ptr()))
+        out.fetch()                                                    # the call's one synchronisation
+    return KMeansFit(out.host("centers"), out.host("centers_f64") if want_f64 else None, out.host("labels"), out.host("init"), out.host("info"),
+                     out.device("centers"))
 
 
 def nearest_on_device(x, group, centers, out=None):
@@ -217,8 +197,7 @@ def nearest_on_device(x, group, centers, out=None):
     -> (dist float32 [rows], which int32 [rows], invalid int32 [1]) CUDA tensors (`out`: the three to write into).  Asynchronous: nothing
     is copied and nothing waits; a row whose group is outside [0, G) gets NaN / -1 and is counted in `invalid`."""
     import torch
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
-        raise ValueError("x must be a CUDA tensor [rows, dim] of float32")
+    x = problems.device_bank(x, upload=False)
     if not (torch.is_tensor(centers) and centers.is_cuda and centers.dtype == torch.float32 and centers.dim() == 3):
         raise ValueError("centers must be a CUDA tensor [groups, clusters, dim] of float32")
     rows, dim = (int(v) for v in x.shape)
@@ -232,7 +211,7 @@ def nearest_on_device(x, group, centers, out=None):
         group = torch.from_numpy(np.ascontiguousarray(group, dtype=np.int32)).to(dev, non_blocking=True)
     if group.dtype != torch.int32 or group.numel() != rows or group.device != dev:
         raise ValueError("group must hold one int32 per row, on the device of x")
-    x, group, centers = x.contiguous(), group.contiguous(), centers.contiguous()
+    group, centers = group.contiguous(), centers.contiguous()
     with torch.cuda.device(dev):
         if out is None:
             out = (torch.empty(rows, dtype=torch.float32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),

@@ -22,7 +22,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, problems
 
 MAX_ROWS = 1024               # MKWS_LOGREG_MAX_ROWS: rows of one problem
 MAX_CLASSES = 8               # MKWS_LOGREG_MAX_CLASSES
@@ -38,22 +38,11 @@ def kappa(n_classes):
 
 def _scaler(X, standardize):
     """(mu, sigma) of StandardScaler over the rows of X (float64), or (0, 1)."""
-    if not standardize:
-        return np.zeros(X.shape[1]), np.ones(X.shape[1])
-    mu = X.mean(axis=0)
-    sigma = np.sqrt(((X - mu) ** 2).mean(axis=0))
-    sigma[sigma == 0.0] = 1.0
-    return mu, sigma
+    return problems.standard_scaler(X) if standardize else (np.zeros(X.shape[1]), np.ones(X.shape[1]))
 
 
 def _problem(x, rows, labels, n_classes, standardize):
-    K = int(n_classes)
-    rows, y = np.asarray(rows, dtype=np.int64), np.asarray(labels, dtype=np.int64)
-    x = np.asarray(x)
-    if x.ndim != 2 or rows.ndim != 1 or rows.shape != y.shape or rows.size == 0:
-        raise ValueError("x must be [rows, dim]; rows and labels one non-empty list each, of equal length")
-    if K < 2 or y.min() < 0 or y.max() >= K or rows.min() < 0 or rows.max() >= x.shape[0]:
-        raise ValueError("n_classes below 2, a label outside [0, n_classes) or a row outside the bank")
+    x, rows, y, _ = problems.check_one_problem(x, rows, labels, n_classes)
     X = x[rows].astype(np.float64)
     mu, sigma = _scaler(X, standardize)
     return (X - mu) / sigma, y, mu, sigma
@@ -163,66 +152,9 @@ def predict_host(x, rows, coef, intercept):
 
 
 def check_problems(rows, labels, offsets, n_rows, dim, n_classes, C=1.0):
-    """The refusals of fit_on_device / score_on_device, made before anything is uploaded -> (rows int32, labels int32, offsets int32,
-    C float64 [P]).  Refused: n_classes outside [2, MAX_CLASSES], dim outside [1, MAX_DIM], lists of unequal length, offsets that are not
-    P + 1 non-decreasing integers inside [0, len(rows)], a problem of more than MAX_ROWS rows, a C that is not positive and finite or not
-    one per problem.  What the lists hold is the device's to check: an empty problem, a label outside [0, n_classes) or a row outside the
-    bank gives that problem status 2."""
-    K = int(n_classes)
-    if not 2 <= K <= MAX_CLASSES:
-        raise ValueError(f"n_classes {K} outside [2, {MAX_CLASSES}]")
-    if not 1 <= int(dim) <= MAX_DIM:
-        raise ValueError(f"dim {int(dim)} outside [1, {MAX_DIM}]")
-    if int(n_rows) < 0:
-        raise ValueError("a bank of fewer than 0 rows")
-    rows, labels, off = np.asarray(rows), np.asarray(labels), np.asarray(offsets)
-    if rows.size == 0:
-        rows = rows.astype(np.int32)
-    if labels.size == 0:
-        labels = labels.astype(np.int32)
-    for name, a in (("rows", rows), ("labels", labels)):
-        if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError(f"{name} must be one flat list of integers")
-    if rows.shape != labels.shape:
-        raise ValueError(f"{rows.size} rows for {labels.size} labels")
-    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError("offsets must be a list of P + 1 integers")
-    off = off.astype(np.int64)
-    if off[0] < 0 or off[-1] > rows.size or (np.diff(off) < 0).any():
-        raise ValueError(f"offsets must be non-decreasing and inside [0, {rows.size}]")
-    sizes = np.diff(off)
-    for p in np.nonzero(sizes > MAX_ROWS)[0][:1]:
-        raise ValueError(f"problem {int(p)} has {int(sizes[p])} rows: at most {MAX_ROWS}")
-    P = off.size - 1
-    Cs = np.full(P, float(C)) if np.ndim(C) == 0 else np.asarray(C, dtype=np.float64).reshape(-1)
-    if Cs.size != P:
-        raise ValueError(f"{Cs.size} values of C for {P} problems")
-    if not (np.isfinite(Cs).all() and (Cs > 0).all()):
-        raise ValueError("C must be positive and finite")
-    clip = lambda a: np.clip(a, -2 ** 31, 2 ** 31 - 1).astype(np.int32)      # (an index out of int32 stays out of every bank)
-    return clip(rows), clip(labels), off.astype(np.int32), Cs.astype(np.float64)
-
-
-def _bank(x):
-    """numpy float32 [rows, dim] is uploaded; a CUDA tensor is taken as it is."""
-    import torch
-    if not torch.is_tensor(x):
-        x = np.ascontiguousarray(x)
-        x = torch.from_numpy(x if x.flags.writeable else x.copy()).cuda()
-    if not x.is_cuda or x.dtype != torch.float32:
-        raise ValueError("x must be a CUDA tensor or numpy array [rows, dim] of float32")
-    return x.contiguous()
-
-
-def _check_bank(x):
-    import torch
-    if not torch.is_tensor(x):
-        x = np.asarray(x)
-        if x.dtype != np.float32:
-            raise ValueError("x must be float32")
-    if x.ndim != 2:
-        raise ValueError("x must be [rows, dim]")
-    return x, int(x.shape[0]), int(x.shape[1])
+    """The refusals of fit_on_device, made before anything is uploaded: problems.check_problems under this module's caps.  What the lists
+    hold is the device's to check: an empty problem, a label outside [0, n_classes) or a row outside the bank gives that problem status 2."""
+    return problems.check_problems(rows, labels, offsets, n_rows, dim, n_classes, C, MAX_ROWS, MAX_CLASSES, MAX_DIM)
 
 
 def fit_on_device(x, rows, labels, offsets, n_classes, C=1.0, standardize=False, max_iter=300, gtol=1e-5):
@@ -234,32 +166,27 @@ def fit_on_device(x, rows, labels, offsets, n_classes, C=1.0, standardize=False,
     1 = max_iter (sklearn's ConvergenceWarning, not an error).  One upload (lists, offsets, C), one launch, one copy back.  What
     check_problems refuses is refused before anything is uploaded."""
     import torch
-    x, n_rows, dim = _check_bank(x)
+    n_rows, dim = problems.bank_shape(x)
     K = int(n_classes)
     rows, labels, off, Cs = check_problems(rows, labels, offsets, n_rows, dim, K, C)
     if int(max_iter) < 1 or not float(gtol) >= 0:
         raise ValueError("max_iter must be at least 1 and gtol non-negative")
     P = off.size - 1
-    x = _bank(x)
+    x = problems.device_bank(x)
     dev = x.device
     with torch.cuda.device(dev):
         d_in, (p_C, p_off, p_rows, p_labels) = _lib.upload_words([Cs, off, rows, labels], dev)
-        # every output in ONE buffer of 4-byte words, so that they cross in one copy: stats (float64, first: 8-byte aligned), coef,
-        # intercept, info
-        at = np.cumsum([0, 4 * P, P * K * dim, P * K, 4 * P])
-        d_out = torch.zeros(int(at[-1]), dtype=torch.int32, device=dev)
-        ptr = [d_out.data_ptr() + 4 * int(a) for a in at]
+        out = _lib.OutputWords([("stats", np.float64, (P, 2)), ("coef", np.float32, (P, K, dim)), ("intercept", np.float32, (P, K)),
+                                ("info", np.int32, (P, 4))], dev)
         if P:
             L = _lib.lib()
             n_work = int(L.mkws_logreg_work_floats(dim, P, K))
             d_work = torch.empty(n_work, dtype=torch.float32, device=dev)
             _lib.check(L.mkws_logreg_fit(x.data_ptr(), n_rows, dim, p_rows, p_labels, p_off, P, K, p_C, int(bool(standardize)), int(max_iter),
-                                         float(gtol), ptr[1], ptr[2], ptr[3], ptr[0], d_work.data_ptr(), n_work, _lib.current_stream_ptr()))
-        out = d_out.cpu().numpy()                                      # the call's one synchronisation
-    d_coef = d_out[int(at[1]):int(at[2])].view(torch.float32).view(P, K, dim)
-    d_intercept = d_out[int(at[2]):int(at[3])].view(torch.float32).view(P, K)
-    return LogregFit(out[at[1]:at[2]].view(np.float32).reshape(P, K, dim), out[at[2]:at[3]].view(np.float32).reshape(P, K),
-                     out[at[3]:at[4]].reshape(P, 4), out[at[0]:at[1]].view(np.float64).reshape(P, 2), d_coef, d_intercept)
+                                         float(gtol), out.ptr("coef"), out.ptr("intercept"), out.ptr("info"), out.ptr("stats"), d_work.data_ptr(),
+                                         n_work, _lib.current_stream_ptr()))
+        out.fetch()                                                    # the call's one synchronisation
+    return LogregFit(out.host("coef"), out.host("intercept"), out.host("info"), out.host("stats"), out.device("coef"), out.device("intercept"))
 
 
 def score_on_device(x, rows, true, offsets, coef, intercept, want_probs=False, want_logits=False):
@@ -270,8 +197,7 @@ def score_on_device(x, rows, true, offsets, coef, intercept, want_probs=False, w
     None, logits float32 [total, K] or None), CUDA tensors.  Asynchronous: nothing is copied back and nothing waits.  A row outside the
     bank gets pred -1 (probs and logits NaN) and is never correct."""
     import torch
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
-        raise ValueError("x must be a CUDA tensor [rows, dim] of float32")
+    x = problems.device_bank(x, upload=False)
     if not (torch.is_tensor(coef) and coef.is_cuda and coef.dtype == torch.float32 and coef.dim() == 3):
         raise ValueError("coef must be a CUDA tensor [problems, classes, dim] of float32")
     n_rows, dim = (int(v) for v in x.shape)
@@ -283,29 +209,17 @@ def score_on_device(x, rows, true, offsets, coef, intercept, want_probs=False, w
     if not 2 <= K <= MAX_CLASSES or not 1 <= dim <= MAX_DIM:
         raise ValueError(f"n_classes {K} outside [2, {MAX_CLASSES}] or dim {dim} outside [1, {MAX_DIM}]")
     dev = x.device
-    lists = []
-    for name, a in (("rows", rows), ("true", true), ("offsets", offsets)):
-        if not torch.is_tensor(a):
-            a = np.asarray(a)
-            if a.size and not np.issubdtype(a.dtype, np.integer):
-                raise ValueError(f"{name} must hold integers")
-            a = torch.from_numpy(np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32).reshape(-1)).to(dev, non_blocking=True)
-        if a.dtype != torch.int32 or a.dim() != 1 or a.device != dev:
-            raise ValueError(f"{name} must be a flat int32 list on the device of x")
-        lists.append(a.contiguous())
-    d_rows, d_true, d_off = lists
+    d_rows, d_true, d_off = (problems.device_int_list(a, name, dev) for name, a in (("rows", rows), ("true", true), ("offsets", offsets)))
     total = int(d_rows.numel())
     if d_true.numel() != total or d_off.numel() != P + 1:
         raise ValueError(f"{total} rows, {int(d_true.numel())} labels, {int(d_off.numel())} offsets for {P} problems")
-    x, coef, intercept = x.contiguous(), coef.contiguous(), intercept.contiguous()
+    coef, intercept = coef.contiguous(), intercept.contiguous()
+    ptr = problems.ptr_or_none
     with torch.cuda.device(dev):
         pred = torch.empty(total, dtype=torch.int32, device=dev)
         correct = torch.empty(P, dtype=torch.int32, device=dev)
         probs = torch.empty((total, K), dtype=torch.float32, device=dev) if want_probs else None
         logits = torch.empty((total, K), dtype=torch.float32, device=dev) if want_logits else None
-        _lib.check(_lib.lib().mkws_logreg_score(x.data_ptr(), n_rows, dim, d_rows.data_ptr() if total else None, d_true.data_ptr() if total else None,
-                                                d_off.data_ptr(), P, K, coef.data_ptr() if P else None, intercept.data_ptr() if P else None,
-                                                total, pred.data_ptr() if total else None, probs.data_ptr() if want_probs and total else None,
-                                                logits.data_ptr() if want_logits and total else None, correct.data_ptr() if P else None,
-                                                _lib.current_stream_ptr()))
+        _lib.check(_lib.lib().mkws_logreg_score(x.data_ptr(), n_rows, dim, ptr(d_rows), ptr(d_true), d_off.data_ptr(), P, K, ptr(coef), ptr(intercept),
+                                                total, ptr(pred), ptr(probs), ptr(logits), ptr(correct), _lib.current_stream_ptr()))
     return pred, correct, probs, logits

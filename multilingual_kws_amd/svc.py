@@ -31,7 +31,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, problems
 
 MAX_ROWS = 1024               # MKWS_SVC_MAX_ROWS: rows of one problem
 MAX_CLASSES = 8               # MKWS_SVC_MAX_CLASSES
@@ -56,12 +56,8 @@ def _slot(own, other):
 def scaling(x, rows, standardize=False, gamma=0.0):
     """-> (centre float64 [dim], inv_scale float64 [dim], gamma float64) of one problem, as the module docstring defines them."""
     X = np.asarray(x)[np.asarray(rows, dtype=np.int64)].astype(np.float64)
-    mu = X.mean(axis=0)
-    inv = np.ones(X.shape[1])
-    if standardize:
-        sigma = np.sqrt(((X - mu) ** 2).mean(axis=0))
-        sigma[sigma == 0.0] = 1.0
-        inv = 1.0 / sigma
+    mu, sigma = problems.standard_scaler(X)
+    inv = 1.0 / sigma if standardize else np.ones(X.shape[1])
     if float(gamma) > 0.0:
         return mu, inv, float(gamma)
     seen = (X - mu) * inv if standardize else X
@@ -155,13 +151,7 @@ def smo(Kp, y, C, tol, max_iter):
 
 
 def _problem(x, rows, labels, n_classes):
-    K = int(n_classes)
-    rows, y = np.asarray(rows, dtype=np.int64), np.asarray(labels, dtype=np.int64)
-    x = np.asarray(x)
-    if x.ndim != 2 or rows.ndim != 1 or rows.shape != y.shape or rows.size == 0:
-        raise ValueError("x must be [rows, dim]; rows and labels one non-empty list each, of equal length")
-    if K < 2 or y.min() < 0 or y.max() >= K or rows.min() < 0 or rows.max() >= x.shape[0]:
-        raise ValueError("n_classes below 2, a label outside [0, n_classes) or a row outside the bank")
+    _, rows, y, K = problems.check_one_problem(x, rows, labels, n_classes)
     if len(np.unique(y)) < 2:
         raise ValueError("fewer than two classes have a row")
     return rows, y, K
@@ -227,74 +217,10 @@ def predict_host(decision, train_labels, n_classes):
 
 
 def check_problems(rows, labels, offsets, n_rows, dim, n_classes, C=1.0):
-    """The refusals of fit_on_device / score_on_device, made before anything is uploaded -> (rows int32, labels int32, offsets int32,
-    C float64 [P]).  Refused: n_classes outside [2, MAX_CLASSES], dim outside [1, MAX_DIM], lists of unequal length, offsets that are not
-    P + 1 non-decreasing integers inside [0, len(rows)], a problem of more than MAX_ROWS rows, a C that is not positive and finite or not
-    one per problem.  What the lists hold is the device's to check: an empty problem, a label outside [0, n_classes), a row outside the
-    bank or fewer than two present classes gives that problem status 2."""
-    K = int(n_classes)
-    if not 2 <= K <= MAX_CLASSES:
-        raise ValueError(f"n_classes {K} outside [2, {MAX_CLASSES}]")
-    if not 1 <= int(dim) <= MAX_DIM:
-        raise ValueError(f"dim {int(dim)} outside [1, {MAX_DIM}]")
-    if int(n_rows) < 0:
-        raise ValueError("a bank of fewer than 0 rows")
-    rows, labels, off = np.asarray(rows), np.asarray(labels), np.asarray(offsets)
-    if rows.size == 0:
-        rows = rows.astype(np.int32)
-    if labels.size == 0:
-        labels = labels.astype(np.int32)
-    for name, a in (("rows", rows), ("labels", labels)):
-        if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError(f"{name} must be one flat list of integers")
-    if rows.shape != labels.shape:
-        raise ValueError(f"{rows.size} rows for {labels.size} labels")
-    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError("offsets must be a list of P + 1 integers")
-    off = off.astype(np.int64)
-    if off[0] < 0 or off[-1] > rows.size or (np.diff(off) < 0).any():
-        raise ValueError(f"offsets must be non-decreasing and inside [0, {rows.size}]")
-    sizes = np.diff(off)
-    for p in np.nonzero(sizes > MAX_ROWS)[0][:1]:
-        raise ValueError(f"problem {int(p)} has {int(sizes[p])} rows: at most {MAX_ROWS}")
-    P = off.size - 1
-    Cs = np.full(P, float(C)) if np.ndim(C) == 0 else np.asarray(C, dtype=np.float64).reshape(-1)
-    if Cs.size != P:
-        raise ValueError(f"{Cs.size} values of C for {P} problems")
-    if not (np.isfinite(Cs).all() and (Cs > 0).all()):
-        raise ValueError("C must be positive and finite")
-    clip = lambda a: np.clip(a, -2 ** 31, 2 ** 31 - 1).astype(np.int32)      # (an index out of int32 stays out of every bank)
-    return clip(rows), clip(labels), off.astype(np.int32), Cs.astype(np.float64)
-
-
-def _bank(x):
-    """numpy float32 [rows, dim] is uploaded; a CUDA tensor is taken as it is."""
-    import torch
-    if not torch.is_tensor(x):
-        x = np.asarray(x)
-        if x.dtype != np.float32:
-            raise ValueError("x must be float32")
-        x = np.ascontiguousarray(x)
-        x = torch.from_numpy(x if x.flags.writeable else x.copy()).cuda()
-    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
-        raise ValueError("x must be a CUDA tensor or numpy array [rows, dim] of float32")
-    return x.contiguous()
-
-
-def _int_list(a, name, dev):
-    import torch
-    if not torch.is_tensor(a):
-        a = np.asarray(a)
-        if a.size and not np.issubdtype(a.dtype, np.integer):
-            raise ValueError(f"{name} must hold integers")
-        a = torch.from_numpy(np.ascontiguousarray(np.clip(a, -2 ** 31, 2 ** 31 - 1), dtype=np.int32).reshape(-1)).to(dev, non_blocking=True)
-    if a.dtype != torch.int32 or a.dim() != 1 or a.device != dev:
-        raise ValueError(f"{name} must be a flat int32 list on the device of x")
-    return a.contiguous()
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
+    """The refusals of fit_on_device, made before anything is uploaded: problems.check_problems under this module's caps.  What the lists
+    hold is the device's to check: an empty problem, a label outside [0, n_classes), a row outside the bank or fewer than two present
+    classes gives that problem status 2."""
+    return problems.check_problems(rows, labels, offsets, n_rows, dim, n_classes, C, MAX_ROWS, MAX_CLASSES, MAX_DIM)
 
 
 def chunks(offsets, budget):
@@ -327,58 +253,50 @@ def fit_on_device(x, rows, labels, offsets, n_classes, C=1.0, standardize=False,
     run as consecutive chunks of problems, with the same results.  timings: a dict that receives prepare / gram / smo milliseconds
     (device events; this synchronises).  What check_problems refuses is refused before anything is uploaded."""
     import torch
-    if not torch.is_tensor(x):
-        x = np.asarray(x)
-    if x.ndim != 2:
-        raise ValueError("x must be [rows, dim]")
-    n_rows, dim = int(x.shape[0]), int(x.shape[1])
+    n_rows, dim = problems.bank_shape(x)
     K = int(n_classes)
     rows, labels, off, Cs = check_problems(rows, labels, offsets, n_rows, dim, K, C)
     if int(max_iter) < 1 or not float(tol) >= 0 or not np.isfinite(float(gamma)) or int(work_budget) < 1:
         raise ValueError("max_iter must be at least 1, tol non-negative, gamma finite and work_budget positive")
     P, n_list, npairs = off.size - 1, rows.size, K * (K - 1) // 2
-    x = _bank(x)
+    x = problems.device_bank(x)
     dev = x.device
     L = _lib.lib()
+    f32 = np.float32
     with torch.cuda.device(dev):
         d_in, (p_C, p_off, p_rows, p_labels) = _lib.upload_words([Cs, off, rows, labels], dev)
-        # every output in ONE buffer of 4-byte words, so that they cross in one copy
-        at = np.cumsum([0, n_list * (K - 1), P * npairs, P, P * dim, P * dim, 4 * P, P])
-        d_out = torch.zeros(int(at[-1]), dtype=torch.int32, device=dev)
-        ptr = [d_out.data_ptr() + 4 * int(a) for a in at]
+        out = _lib.OutputWords([("coef", f32, (n_list, K - 1)), ("rho", f32, (P, npairs)), ("gamma", f32, (P,)), ("centre", f32, (P, dim)),
+                                ("inv_scale", f32, (P, dim)), ("info", np.int32, (P, 4)), ("gap", f32, (P,))], dev)
         stream = _lib.current_stream_ptr()
         marks = []
         for lo, hi in chunks(off, work_budget) if P else []:
             n, biggest = hi - lo, int(np.diff(off[lo:hi + 1]).max())
             d_work = torch.empty(int(L.mkws_svc_work_bytes(n, biggest)) // 4, dtype=torch.float32, device=dev)
             q_off, q_C = p_off + 4 * lo, p_C + 8 * lo
-            q = lambda i, per: ptr[i] + 4 * lo * per
+            centre, inv_scale, d_gamma = out.ptr("centre", lo * dim), out.ptr("inv_scale", lo * dim), out.ptr("gamma", lo)
+            info, gap = out.ptr("info", lo * 4), out.ptr("gap", lo)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
             if ev:
                 ev[0].record()
             _lib.check(L.mkws_svc_prepare(x.data_ptr(), n_rows, dim, p_rows, p_labels, q_off, n, K, biggest, int(bool(standardize)), float(gamma),
-                                          q(3, dim), q(4, dim), q(2, 1), q(5, 4), q(6, 1), stream))
+                                          centre, inv_scale, d_gamma, info, gap, stream))
             if ev:
                 ev[1].record()
-            _lib.check(L.mkws_svc_kernel(x.data_ptr(), n_rows, dim, p_rows, q_off, biggest, p_rows, q_off, biggest, n, q(3, dim), q(4, dim), q(2, 1),
-                                         q(5, 4), d_work.data_ptr(), biggest * biggest, stream))
+            _lib.check(L.mkws_svc_kernel(x.data_ptr(), n_rows, dim, p_rows, q_off, biggest, p_rows, q_off, biggest, n, centre, inv_scale, d_gamma,
+                                         info, d_work.data_ptr(), biggest * biggest, stream))
             if ev:
                 ev[2].record()
             _lib.check(L.mkws_svc_fit(p_labels, q_off, n, K, biggest, q_C, float(tol), int(max_iter), d_work.data_ptr(), biggest * biggest,
-                                      ptr[0], q(1, npairs), q(5, 4), q(6, 1), stream))
+                                      out.ptr("coef"), out.ptr("rho", lo * npairs), info, gap, stream))
             if ev:
                 ev[3].record()
                 marks.append(ev)
-        out = d_out.cpu().numpy()                                      # the call's one synchronisation
+        out.fetch()                                                    # the call's one synchronisation
         if timings is not None:
             for k, name in enumerate(("prepare", "gram", "smo")):
                 timings[name] = timings.get(name, 0.0) + sum(ev[k].elapsed_time(ev[k + 1]) for ev in marks)
-    cut = lambda i, dtype, *shape: out[at[i]:at[i + 1]].view(dtype).reshape(*shape)
-    dcut = lambda i, dtype, *shape: d_out[int(at[i]):int(at[i + 1])].view(dtype).view(*shape)
-    f32, t32 = np.float32, torch.float32
-    return SvcFit(cut(0, f32, n_list, K - 1), cut(1, f32, P, npairs), cut(2, f32, P), cut(3, f32, P, dim), cut(4, f32, P, dim),
-                  cut(5, np.int32, P, 4), cut(6, f32, P), dcut(0, t32, n_list, K - 1), dcut(1, t32, P, npairs), dcut(2, t32, P),
-                  dcut(3, t32, P, dim), dcut(4, t32, P, dim), dcut(5, torch.int32, P, 4))
+    names = ("coef", "rho", "gamma", "centre", "inv_scale", "info")
+    return SvcFit(*(out.host(part) for part in names + ("gap",)), *(out.device(part) for part in names))
 
 
 def kernel_on_device(x, rows_a, rows_b, centre, inv_scale, gamma):
@@ -386,12 +304,12 @@ def kernel_on_device(x, rows_a, rows_b, centre, inv_scale, gamma):
     or host arrays; gamma: a float.  -> CUDA float32 [len(rows_a), len(rows_b)] = exp(-gamma * max(0, s_a + s_b - 2 a~.b~)) (float64 exp, rounded once),
     NaN where a row is outside the bank.  Asynchronous."""
     import torch
-    x = _bank(x)
+    x = problems.device_bank(x)
     dev = x.device
     n_rows, dim = (int(v) for v in x.shape)
     if not 1 <= dim <= MAX_DIM:
         raise ValueError(f"dim {dim} outside [1, {MAX_DIM}]")
-    d_a, d_b = _int_list(rows_a, "rows_a", dev), _int_list(rows_b, "rows_b", dev)
+    d_a, d_b = problems.device_int_list(rows_a, "rows_a", dev), problems.device_int_list(rows_b, "rows_b", dev)
     par = []
     for name, a in (("centre", centre), ("inv_scale", inv_scale)):
         if not torch.is_tensor(a):
@@ -421,15 +339,15 @@ def score_on_device(x, rows, true, offsets, train_rows, train_labels, train_offs
     Asynchronous unless timings (a dict that receives "score" milliseconds) is given.  A row outside the bank, an entry outside every list
     or a problem whose info says it was refused gets pred -1 (NaN decision values) and is never correct."""
     import torch
-    x = _bank(x)
+    x = problems.device_bank(x)
     dev = x.device
     n_rows, dim = (int(v) for v in x.shape)
     K = int(n_classes)
     if not 2 <= K <= MAX_CLASSES or not 1 <= dim <= MAX_DIM:
         raise ValueError(f"n_classes {K} outside [2, {MAX_CLASSES}] or dim {dim} outside [1, {MAX_DIM}]")
     npairs = K * (K - 1) // 2
-    d_rows, d_true, d_off = (_int_list(a, n, dev) for a, n in ((rows, "rows"), (true, "true"), (offsets, "offsets")))
-    t_rows, t_labels, t_off = (_int_list(a, n, dev) for a, n in ((train_rows, "train_rows"), (train_labels, "train_labels"), (train_offsets, "train_offsets")))
+    d_rows, d_true, d_off = (problems.device_int_list(a, n, dev) for a, n in ((rows, "rows"), (true, "true"), (offsets, "offsets")))
+    t_rows, t_labels, t_off = (problems.device_int_list(a, n, dev) for a, n in ((train_rows, "train_rows"), (train_labels, "train_labels"), (train_offsets, "train_offsets")))
     P, total, n_train = int(d_off.numel()) - 1, int(d_rows.numel()), int(t_rows.numel())
     if P < 0 or d_true.numel() != total or t_off.numel() != P + 1 or t_labels.numel() != n_train:
         raise ValueError(f"{total} rows, {int(d_true.numel())} labels, {int(d_off.numel())} offsets and {int(t_off.numel())} training offsets")
@@ -446,6 +364,7 @@ def score_on_device(x, rows, true, offsets, train_rows, train_labels, train_offs
     if max_train > MAX_ROWS:
         raise ValueError(f"a model of {max_train} rows: at most {MAX_ROWS}")
     coef, rho, gamma, centre, inv_scale = (a.contiguous() for a in (coef, rho, gamma, centre, inv_scale))
+    ptr = problems.ptr_or_none
     with torch.cuda.device(dev):
         pred = torch.empty(total, dtype=torch.int32, device=dev)
         correct = torch.empty(P, dtype=torch.int32, device=dev)
@@ -453,9 +372,9 @@ def score_on_device(x, rows, true, offsets, train_rows, train_labels, train_offs
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
         if ev:
             ev[0].record()
-        _lib.check(_lib.lib().mkws_svc_score(x.data_ptr(), n_rows, dim, _ptr(t_rows), _ptr(t_labels), t_off.data_ptr(), max_train, _ptr(coef), _ptr(rho),
-                                             _ptr(gamma), _ptr(centre), _ptr(inv_scale), _ptr(info.contiguous()) if info is not None else None, P, K,
-                                             _ptr(d_rows), _ptr(d_true), d_off.data_ptr(), total, max_eval, _ptr(pred), _ptr(correct), _ptr(decision),
+        _lib.check(_lib.lib().mkws_svc_score(x.data_ptr(), n_rows, dim, ptr(t_rows), ptr(t_labels), t_off.data_ptr(), max_train, ptr(coef), ptr(rho),
+                                             ptr(gamma), ptr(centre), ptr(inv_scale), ptr(info.contiguous()) if info is not None else None, P, K,
+                                             ptr(d_rows), ptr(d_true), d_off.data_ptr(), total, max_eval, ptr(pred), ptr(correct), ptr(decision),
                                              _lib.current_stream_ptr()))
         if ev:
             ev[1].record()
