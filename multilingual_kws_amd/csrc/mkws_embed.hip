@@ -751,6 +751,109 @@ struct FrontArgs {
 #endif
 };
 
+// Row-strip depthwise item of the big-image blocks (front kernel phase 2, whole-block kernel P2): SEG adjacent outputs of one output row
+// for one channel pair / quad (VT), from E in LDS ([pixel][LDE]) and the taps in LDS ([KS*KS][CC]).  A strip reads each of its
+// KS x NC inputs once.  Where a read lands is decided once, not per read:
+//   columns  the image size is a template constant, so column ci of the strip is inside the image for every row segment, for none, or
+//            (first / last column of a two-segment row only) for some.  The first kind is read at one base register + an immediate
+//            offset, the second at the zero row, and only the third takes a select;
+//   rows     a tap row outside the image is skipped as a whole (one EXEC predicate around its reads and multiply-adds; it used to add
+//            0 * w to every sum, which changes no value), and a tap row that is inside for every output row takes no test at all.
+// The multiply-adds run in the order (tap row, output, tap column), as they always did.  ROW_UNROLL: tap rows per loop trip (KS: unrolled).
+template <int KS, int S, int HT, int WT, int SEG>
+struct StripGeom {
+  static constexpr int HoT = (S == 1) ? HT : (HT + 1) / 2, WoT = (S == 1) ? WT : (WT + 1) / 2;
+  static constexpr int PT = (S == 1) ? KS / 2 : KS / 2 - (1 - HT % 2), PLF = (S == 1) ? KS / 2 : KS / 2 - (1 - WT % 2);
+  static constexpr int NSEG = WoT / SEG;
+  static constexpr int NC = (SEG - 1) * S + KS;
+  static_assert(NSEG * SEG == WoT, "segments tile the output row");
+  __host__ __device__ static constexpr int col_class(int ci) {      // segments whose column ci is inside the image: 1 = all, 0 = none, 2 = some
+    int in = 0;
+    for (int sg = 0; sg < NSEG; ++sg) in += ((unsigned)(sg * SEG * S - PLF + ci) < (unsigned)WT) ? 1 : 0;
+    return in == NSEG ? 1 : (in == 0 ? 0 : 2);
+  }
+  __host__ __device__ static constexpr bool row_always(int i) {     // tap row i is inside the image for every output row
+    return i - PT >= 0 && (HoT - 1) * S - PT + i < HT;
+  }
+};
+
+template <typename VT, int KS, int S, int HT, int WT, int SEG, int LDE, int CC, int ROW_UNROLL>
+__device__ __forceinline__ void dw_strip_(const float* p,         // E at the strip's first input (ih0, iw0), outside the image for a border item (never read there), at the item's channels
+                                          const float* zcol,      // the zero row, at the item's channels
+                                          const float* wd,        // the taps, at the item's channels
+                                          int ih0, int iw0, VT (&acc)[SEG]) {
+  using SG = StripGeom<KS, S, HT, WT, SEG>;
+  constexpr int NC = SG::NC;
+  auto load = [&](int i, VT (&v)[NC]) {
+#pragma unroll
+    for (int ci = 0; ci < NC; ++ci) {
+      const int cls = SG::col_class(ci);
+      const float* q = p + (i * WT + ci) * LDE;
+      if (cls == 0) q = zcol;
+      else if (cls == 2) q = ((unsigned)(iw0 + ci) < (unsigned)WT) ? q : zcol;
+      v[ci] = *reinterpret_cast<const VT*>(q);
+    }
+  };
+  auto mac = [&](int i, const VT (&v)[NC]) {
+    VT w[KS];
+#pragma unroll
+    for (int jx = 0; jx < KS; ++jx) w[jx] = *reinterpret_cast<const VT*>(wd + (i * KS + jx) * CC);
+#pragma unroll
+    for (int o = 0; o < SEG; ++o)
+#pragma unroll
+      for (int jx = 0; jx < KS; ++jx) acc[o] += v[o * S + jx] * w[jx];
+  };
+  if constexpr (ROW_UNROLL == KS) {
+#pragma unroll
+    for (int i = 0; i < KS; ++i) {
+      if (SG::row_always(i) || (unsigned)(ih0 + i) < (unsigned)HT) {
+        VT v[NC];
+        load(i, v);
+        mac(i, v);
+      }
+    }
+  } else {
+#pragma unroll ROW_UNROLL
+    for (int i = 0; i < KS; ++i) {
+      if ((unsigned)(ih0 + i) < (unsigned)HT) {
+        VT v[NC];
+        load(i, v);
+        mac(i, v);
+      }
+    }
+  }
+}
+
+// The form every strip had before dw_strip_: all tap rows run, and every read chooses between its input row and the zero row (index
+// zrow of E).  Kept for the instantiation that measured no faster with dw_strip_ (block 4a, profiles/strip_addressing.txt).
+template <typename VT, int KS, int S, int HT, int WT, int SEG, int LDE, int CC, int ROW_UNROLL>
+__device__ __forceinline__ void dw_strip_per_read_(const float* E0,    // E at the item's channels
+                                                   int row0,           // the item's clip: its first row of E
+                                                   int zrow, const float* wd, int ih0, int iw0, VT (&acc)[SEG]) {
+  constexpr int NC = (SEG - 1) * S + KS;
+  int coff[NC];
+#pragma unroll
+  for (int ci = 0; ci < NC; ++ci) coff[ci] = ((unsigned)(iw0 + ci) < (unsigned)WT) ? iw0 + ci : -1;
+#pragma unroll ROW_UNROLL
+  for (int i = 0; i < KS; ++i) {
+    const int ih = ih0 + i;
+    const bool rok = (unsigned)ih < (unsigned)HT;
+    const int rbase = row0 + ih * WT;
+    VT v[NC], w[KS];
+#pragma unroll
+    for (int ci = 0; ci < NC; ++ci) {
+      const int row = (rok && coff[ci] >= 0) ? rbase + coff[ci] : zrow;
+      v[ci] = *reinterpret_cast<const VT*>(E0 + (size_t)row * LDE);
+    }
+#pragma unroll
+    for (int jx = 0; jx < KS; ++jx) w[jx] = *reinterpret_cast<const VT*>(wd + (i * KS + jx) * CC);
+#pragma unroll
+    for (int o = 0; o < SEG; ++o)
+#pragma unroll
+      for (int jx = 0; jx < KS; ++jx) acc[o] += v[o * S + jx] * w[jx];
+  }
+}
+
 // Template: KS/S depthwise kernel & stride; CC channels per block; KCT > 0: big-image mode with exactly KCT
 // K chunks (weights in registers); KCT == 0: tiny-image mode with compile-time image size HT x WT.
 template <int KS, int S, int CC, int KCT, int HT, int WT>
@@ -961,15 +1064,11 @@ __global__ __launch_bounds__(KCT > 0 ? 256 : 512) void mbconv_front_kernel(Front
     // ---- phase 2: depthwise from LDS ----
     if constexpr (PIXEL_LANES) {
       // Row strips: item = (clip, output row, column segment, channel quad) computes SEG adjacent outputs of one
-      // row.  The image size is a template constant, so a strip reads each of its KS x ((SEG-1)*S + KS) inputs
-      // once (instead of KS*KS per output), column offsets are immediates, out-of-image taps read the LDS zero
-      // row (no branches: all ds_reads of a row are in flight together), and the taps come from LDS.
+      // row (dw_strip_: each of its KS x ((SEG-1)*S + KS) inputs is read once instead of KS*KS times per output,
+      // at an immediate offset from one base register), and the taps come from LDS.
       constexpr int HoT = (S == 1) ? HT : (HT + 1) / 2, WoT = (S == 1) ? WT : (WT + 1) / 2;
-      constexpr int PT = (S == 1) ? KS / 2 : KS / 2 - (1 - HT % 2), PLF = (S == 1) ? KS / 2 : KS / 2 - (1 - WT % 2);
       constexpr int SEG = (WoT % 5 == 0) ? 5 : WoT;
       constexpr int NSEG = WoT / SEG;
-      constexpr int NC = (SEG - 1) * S + KS;
-      static_assert(NSEG * SEG == WoT, "segments tile the output row");
       const int zrow = a.G * HW;
       const int nitems = gvalid * HoT * NSEG * Q;
       for (int item = tid; item < nitems; item += NTHREADS) {
@@ -980,32 +1079,12 @@ __global__ __launch_bounds__(KCT > 0 ? 256 : 512) void mbconv_front_kernel(Front
         f32x4 ssum = {0.f, 0.f, 0.f, 0.f};
         if (tq < nt_valid * 4) {
           const int cq = ch0 + 4 * tq;
-          const float* E0 = s_E + 4 * tq;
-          const int ih0 = oh * S - PT, iw0 = sg * SEG * S - PLF;
-          int coff[NC];
-#pragma unroll
-          for (int ci = 0; ci < NC; ++ci) coff[ci] = ((unsigned)(iw0 + ci) < (unsigned)WT) ? iw0 + ci : -1;
           f32x4 acc[SEG];
 #pragma unroll
           for (int o = 0; o < SEG; ++o) acc[o] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int i = 0; i < KS; ++i) {
-            const int ih = ih0 + i;
-            const bool rok = (unsigned)ih < (unsigned)HT;
-            const int rbase = gi * HW + ih * WT;
-            f32x4 v[NC], w[KS];
-#pragma unroll
-            for (int ci = 0; ci < NC; ++ci) {
-              const int row = (rok && coff[ci] >= 0) ? rbase + coff[ci] : zrow;
-              v[ci] = *reinterpret_cast<const f32x4*>(E0 + (size_t)row * LDE);
-            }
-#pragma unroll
-            for (int jx = 0; jx < KS; ++jx) w[jx] = *reinterpret_cast<const f32x4*>(s_wd + (i * KS + jx) * CC + 4 * tq);
-#pragma unroll
-            for (int o = 0; o < SEG; ++o)
-#pragma unroll
-              for (int jx = 0; jx < KS; ++jx) acc[o] += v[o * S + jx] * w[jx];
-          }
+          using SG = StripGeom<KS, S, HT, WT, SEG>;
+          const int ih0 = oh * S - SG::PT, iw0 = sg * SEG * S - SG::PLF;
+          dw_strip_<f32x4, KS, S, HT, WT, SEG, LDE, CC, KS>(s_E + (gi * HW + ih0 * WT + iw0) * LDE + 4 * tq, s_E + zrow * LDE + 4 * tq, s_wd + 4 * tq, ih0, iw0, acc);
           const f32x4 sc = scd_pre, sh = shd_pre;
           float* yout = a.Y + ((size_t)(b0 + gi) * (HoT * WoT) + oh * WoT + sg * SEG) * a.Cexp + cq;
 #pragma unroll
@@ -1281,12 +1360,15 @@ struct MidGeom {
 template <int KS, int S, int KCT, int HT, int WT, int CEXP, int CC, int NTP, int G, int SEG, int NTHR, int WPE, bool PAIR = false>
 __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
   using GM = MidGeom<KS, S, KCT, HT, WT, CEXP, CC, G, SEG>;
-  constexpr int HW = GM::HW, HoT = GM::HoT, WoT = GM::WoT, HoWo = GM::HoWo, PT = GM::PT, PLF = GM::PLF;
-  constexpr int NSEG = GM::NSEG, NC = GM::NC, Q = GM::Q, NTC = GM::NTC, LDE = GM::LDE, LDD = GM::LDD, NCH = GM::NCH, KC = GM::KC;
+  constexpr int HW = GM::HW, HoT = GM::HoT, WoT = GM::WoT, HoWo = GM::HoWo;
+  constexpr int NSEG = GM::NSEG, Q = GM::Q, NTC = GM::NTC, LDE = GM::LDE, LDD = GM::LDD, NCH = GM::NCH, KC = GM::KC;
   constexpr int MTI = GM::MTI, MTO = GM::MTO, NW4 = GM::NW4, NS1 = GM::NS1, NS2 = GM::NS2;
   constexpr int NW = NTHR / 64;
   constexpr int SE_MAX = 10;                                     // SE units of blocks 2a..4a: 4, 6, 6, 10, 10
-  constexpr int TAP_ROW_UNROLL = (KS == 5) ? 1 : KS;             // 5x5: one tap row at a time (register budget at 4 waves per SIMD)
+  constexpr int TAP_ROW_UNROLL = (KS == 5) ? 1 : KS;             // 5x5: one tap row at a time (two measured no faster: profiles/strip_addressing.txt)
+  // Block 4a (3x3 stride 2 on 7x5) measured no faster with the per-row form of dw_strip_ (profiles/strip_addressing.txt): its strips
+  // keep the per-read form and their decode inside the chunk loop.
+  constexpr bool STRIP_PER_READ = PAIR && KS == 3 && S == 2 && HT == 7 && WT == 5;
   constexpr int UPW = (SE_MAX + NW - 1) / NW;                    // SE reduce FC: units per wave (wave w owns units w, w + NW, ..)
   constexpr int CPL = (CEXP + 63) / 64;                          // ... and channels per lane (lane l takes channels l, l + 64, ..)
   constexpr bool SQ = GM::SQ;                                    // channel sums come from the depthwise phase's strip items
@@ -1406,6 +1488,30 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
     }
   };
   if (!MKWS_ABLATE(16)) request_se();                            // (timing build, MKWS_ABLATE=16: the round-3 position, for the A/B)
+  // P2's strip items: (clip, output row, row segment, channel pair / quad).  Where every thread gets at most one item (ONE_ITEM: all
+  // instantiations so far) it is decoded here, once, and not once per chunk.
+  using VT = std::conditional_t<PAIR, f32x2, f32x4>;
+  constexpr int VW = PAIR ? 2 : 4;                               // channels of an item
+  constexpr int QI = CC / VW;                                    // items across the chunk's channels
+  constexpr int ITEMS_PER_CLIP = HoT * NSEG * QI;
+  constexpr bool ONE_ITEM = G * ITEMS_PER_CLIP <= NTHR;
+  using SG = StripGeom<KS, S, HT, WT, SEG>;
+  struct StripItem { int tc, ih0, iw0, row0, poff, doff, sqoff; };   // row0: the clip's first row of E; poff / doff / sqoff: float offsets into s_E (first input) / s_D (chunk 0) / s_sq
+  auto strip_item = [&](int item) {
+    StripItem it;
+    int r = item / QI;
+    it.tc = item - r * QI;
+    const int sg = r % NSEG; r /= NSEG;
+    const int oh = r % HoT, gi = r / HoT;
+    it.ih0 = oh * S - SG::PT;
+    it.iw0 = sg * SEG * S - SG::PLF;
+    it.row0 = gi * HW;
+    it.poff = (it.row0 + it.ih0 * WT + it.iw0) * LDE + VW * it.tc;
+    it.doff = (gi * HoWo + oh * WoT + sg * SEG) * LDD + VW * it.tc;
+    it.sqoff = ((gi * HoT + oh) * NSEG + sg) * CC + VW * it.tc;
+    return it;
+  };
+  const StripItem it0 = strip_item(tid);
 
   for (int chn = 0; chn < NCH; ++chn) {
     const int ch0 = chn * CC;
@@ -1440,99 +1546,31 @@ __global__ __launch_bounds__(NTHR, WPE) void mbconv_mid_kernel(MidArgs a) {
     MID_STAMP(3 + 4 * chn);
     // ---- P2: depthwise from LDS -> D[:, chunk] ----
     if (chn + 1 < NCH) load1(chn + 1);
-    if constexpr (PAIR) {
-      // Channel PAIRS x row strips.  With one output pixel x channel quad per item (below) the phase is LDS-bound: 25 input + 25 tap
-      // ds_read_b128 per output of a 5x5 kernel, 336 KB per chunk of block 3a = 2 600 LDS cycles, twice that with the CU's second
-      // workgroup in the same phase (measured 2.5 us per chunk).  A strip reads each input of its rows once and each tap once per
-      // strip (90 reads for 5 outputs), and pairs instead of quads keep three waves busy instead of one and a half.
-      constexpr int Q2 = CC / 2;
-      const int zrow = G * HW;
-      const int nitems = MKWS_ABLATE(2) ? 0 : gvalid * HoT * NSEG * Q2;
+    {
+      // Row strips (dw_strip_) of channel PAIRS (2b, 3a, 4a) or quads (2a, 3b).  With one output pixel x channel quad per item the
+      // phase was LDS-bound: 25 input + 25 tap ds_read_b128 per output of a 5x5 kernel, 336 KB per chunk of block 3a = 2 600 LDS cycles,
+      // twice that with the CU's second workgroup in the same phase (measured 2.5 us per chunk).  A strip reads each input of its rows
+      // once and each tap once per strip (90 reads for 5 outputs), and pairs instead of quads keep three waves busy instead of one and
+      // a half.
+      const int nitems = MKWS_ABLATE(2) ? 0 : gvalid * ITEMS_PER_CLIP;
       for (int item = tid; item < nitems; item += NTHR) {
-        int r = item / Q2;
-        const int tp = item - r * Q2;
-        const int sg = r % NSEG; r /= NSEG;
-        const int oh = r % HoT, gi = r / HoT;
-        const float* E0 = s_E + 2 * tp;
-        const int ih0 = oh * S - PT, iw0 = sg * SEG * S - PLF;
-        int coff[NC];
+        const StripItem it = (ONE_ITEM && !STRIP_PER_READ) ? it0 : strip_item(item);
+        VT acc[SEG];
 #pragma unroll
-        for (int ci = 0; ci < NC; ++ci) coff[ci] = ((unsigned)(iw0 + ci) < (unsigned)WT) ? iw0 + ci : -1;
-        f32x2 acc[SEG];
-#pragma unroll
-        for (int o = 0; o < SEG; ++o) acc[o] = (f32x2){0.f, 0.f};
-#pragma unroll TAP_ROW_UNROLL
-        for (int i = 0; i < KS; ++i) {
-          const int ih = ih0 + i;
-          const bool rok = (unsigned)ih < (unsigned)HT;
-          const int rbase = gi * HW + ih * WT;
-          f32x2 v[NC], w[KS];
-#pragma unroll
-          for (int ci = 0; ci < NC; ++ci) {
-            const int row = (rok && coff[ci] >= 0) ? rbase + coff[ci] : zrow;
-            v[ci] = *reinterpret_cast<const f32x2*>(E0 + (size_t)row * LDE);
-          }
-#pragma unroll
-          for (int jx = 0; jx < KS; ++jx) w[jx] = *reinterpret_cast<const f32x2*>(s_wd + (i * KS + jx) * CC + 2 * tp);
-#pragma unroll
-          for (int o = 0; o < SEG; ++o)
-#pragma unroll
-            for (int jx = 0; jx < KS; ++jx) acc[o] += v[o * S + jx] * w[jx];
-        }
-        const f32x2 scd = *reinterpret_cast<const f32x2*>(s_scD + 2 * tp), shd = *reinterpret_cast<const f32x2*>(s_scD + CC + 2 * tp);
-        float* dout = s_D + (size_t)(gi * HoWo + oh * WoT + sg * SEG) * LDD + ch0 + 2 * tp;
-        f32x2 ysum = {0.f, 0.f};
+        for (int o = 0; o < SEG; ++o) acc[o] = VT(0.f);
+        if constexpr (STRIP_PER_READ) dw_strip_per_read_<VT, KS, S, HT, WT, SEG, LDE, CC, TAP_ROW_UNROLL>(s_E + VW * it.tc, it.row0, G * HW, s_wd + VW * it.tc, it.ih0, it.iw0, acc);
+        else dw_strip_<VT, KS, S, HT, WT, SEG, LDE, CC, TAP_ROW_UNROLL>(s_E + it.poff, s_E + G * HW * LDE + VW * it.tc, s_wd + VW * it.tc, it.ih0, it.iw0, acc);
+        const VT scd = *reinterpret_cast<const VT*>(s_scD + VW * it.tc), shd = *reinterpret_cast<const VT*>(s_scD + CC + VW * it.tc);
+        float* dout = s_D + it.doff + ch0;
+        VT ysum = VT(0.f);
 #pragma unroll
         for (int o = 0; o < SEG; ++o) {
-          f32x2 y = acc[o] * scd + shd;
-          y = swish2_(y);
-          *reinterpret_cast<f32x2*>(dout + (size_t)o * LDD) = y;
-          ysum += y;
+          VT y = acc[o] * scd + shd;
+          y = swishv_(y);
+          *reinterpret_cast<VT*>(dout + (size_t)o * LDD) = y;
+          if constexpr (PAIR) ysum += y;
         }
-        *reinterpret_cast<f32x2*>(s_sq + (size_t)((gi * HoT + oh) * NSEG + sg) * CC + 2 * tp) = ysum;
-      }
-    } else {
-      const int zrow = G * HW;
-      const int nitems = MKWS_ABLATE(2) ? 0 : gvalid * HoT * NSEG * Q;
-      for (int item = tid; item < nitems; item += NTHR) {
-        int r = item / Q;
-        const int tq = item - r * Q;
-        const int sg = r % NSEG; r /= NSEG;
-        const int oh = r % HoT, gi = r / HoT;
-        const float* E0 = s_E + 4 * tq;
-        const int ih0 = oh * S - PT, iw0 = sg * SEG * S - PLF;
-        int coff[NC];
-#pragma unroll
-        for (int ci = 0; ci < NC; ++ci) coff[ci] = ((unsigned)(iw0 + ci) < (unsigned)WT) ? iw0 + ci : -1;
-        f32x4 acc[SEG];
-#pragma unroll
-        for (int o = 0; o < SEG; ++o) acc[o] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll TAP_ROW_UNROLL
-        for (int i = 0; i < KS; ++i) {
-          const int ih = ih0 + i;
-          const bool rok = (unsigned)ih < (unsigned)HT;
-          const int rbase = gi * HW + ih * WT;
-          f32x4 v[NC], w[KS];
-#pragma unroll
-          for (int ci = 0; ci < NC; ++ci) {
-            const int row = (rok && coff[ci] >= 0) ? rbase + coff[ci] : zrow;
-            v[ci] = *reinterpret_cast<const f32x4*>(E0 + (size_t)row * LDE);
-          }
-#pragma unroll
-          for (int jx = 0; jx < KS; ++jx) w[jx] = *reinterpret_cast<const f32x4*>(s_wd + (i * KS + jx) * CC + 4 * tq);
-#pragma unroll
-          for (int o = 0; o < SEG; ++o)
-#pragma unroll
-            for (int jx = 0; jx < KS; ++jx) acc[o] += v[o * S + jx] * w[jx];
-        }
-        const f32x4 scd = *reinterpret_cast<const f32x4*>(s_scD + 4 * tq), shd = *reinterpret_cast<const f32x4*>(s_scD + CC + 4 * tq);
-        float* dout = s_D + (size_t)(gi * HoWo + oh * WoT + sg * SEG) * LDD + ch0 + 4 * tq;
-#pragma unroll
-        for (int o = 0; o < SEG; ++o) {
-          f32x4 y = acc[o] * scd + shd;
-          y = swish4_(y);
-          *reinterpret_cast<f32x4*>(dout + (size_t)o * LDD) = y;
-        }
+        if constexpr (PAIR) *reinterpret_cast<VT*>(s_sq + it.sqoff) = ysum;
       }
     }
     MID_STAMP(4 + 4 * chn);

@@ -36,6 +36,8 @@ __device__ __forceinline__ f32x2 swish2_(f32x2 v) {          // the same operati
   t.x = __builtin_amdgcn_rcpf(t.x); t.y = __builtin_amdgcn_rcpf(t.y);
   return v * t;
 }
+__device__ __forceinline__ f32x2 swishv_(f32x2 v) { return swish2_(v); }
+__device__ __forceinline__ f32x4 swishv_(f32x4 v) { return swish4_(v); }
 struct WBuf {
   __amdgpu_buffer_rsrc_t r; unsigned voff;
   __device__ __forceinline__ WBuf(const float* base, unsigned lane_off_floats)
