@@ -1203,6 +1203,37 @@ int mkws_op_step_inc(int* d_step, void* stream);
 int mkws_op_adam_dev(float* d_params, const float* d_grads, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2, float eps,
                      const int* d_step, float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DS-CNN baseline, inference: the MLPerf-Tiny keyword spotter the reference measures the few-shot models against
+ * (notebooks/dscnn_comparison.py:45-102 model_def).  Input [B,49,40] float32 micro-frontend features, no rescaling.
+ *   stem    Conv2D(64, 10x4, stride 2, SAME: pad top 4 / bottom 5 / left 1 / right 1) + bias, BN (eps 1e-3), ReLU  -> [25,20,64]
+ *   4 x     DepthwiseConv2D(3x3, SAME) + bias, BN, ReLU;  Conv2D(64, 1x1) + bias, BN, ReLU                          -> [25,20,64]
+ *   pool    mean over rows 0..23 (AveragePooling2D (24,20), valid: row 24 is computed and NOT pooled)                -> [64]
+ *   dense   Dense(label_count) + bias, softmax
+ * The parameter blob is float32 in Keras variable order and layout, BatchNorm tensors included (mkws_dscnn_weight_manifest);
+ * create folds every BatchNorm into the convolution before it (float64, rounded once to float32), the device holds folded weights only.
+ * One launch per forward: a workgroup keeps a clip's activation in LDS through all nine layers.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mkws_dscnn mkws_dscnn;
+
+/* 24128 + 65 * label_count; 0 for a label_count outside [2, 64]. */
+size_t mkws_dscnn_param_count(int label_count);
+/* JSON {"tensors": [{name, shape, offset, count}]} as mkws_embed_weight_manifest; returns the length needed (without the NUL), or
+ * MKWS_ERR_INVALID_ARG for a label_count outside [2, 64].  Host only. */
+int mkws_dscnn_weight_manifest(int label_count, char* buf, size_t buf_len);
+/* MKWS_ERR_BAD_WEIGHTS for a label_count outside [2, 64], n_floats != mkws_dscnn_param_count(label_count), a non-finite value or a
+ * moving variance below -eps -- all before a device is looked for; then MKWS_ERR_NO_DEVICE without a gfx950. */
+int mkws_dscnn_create(const float* h_params, size_t n_floats, int label_count, int max_batch, mkws_dscnn** out);
+void mkws_dscnn_destroy(mkws_dscnn* h);
+/* Workgroups a forward launches at most; a workgroup takes clips blockIdx, blockIdx + grid, ... */
+int mkws_dscnn_grid(const mkws_dscnn* h);
+/* d_spec [B,49,40] -> d_probs [B,label_count] (softmax) and, unless NULL, d_logits [B,label_count].  Asynchronous on `stream`, one
+ * launch, allocates nothing: capturable.  B == 0 succeeds with nothing launched; B > max_batch is MKWS_ERR_INVALID_ARG. */
+int mkws_dscnn_forward(mkws_dscnn* h, const float* d_spec, int B, float* d_probs, float* d_logits, void* stream);
+/* The same kernel with one store added: stage 0 = stem, 1..4 = the blocks, each d_out [B,25,20,64] after its last ReLU; stage 5 =
+ * the pooled [B,64]. */
+int mkws_dscnn_tap(mkws_dscnn* h, const float* d_spec, int B, int stage, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
