@@ -1234,6 +1234,30 @@ int mkws_dscnn_forward(mkws_dscnn* h, const float* d_spec, int B, float* d_probs
  * the pooled [B,64]. */
 int mkws_dscnn_tap(mkws_dscnn* h, const float* d_spec, int B, int stage, float* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * DS-CNN baseline, training: what one optimizer step of the network above needs beyond the mkws_op_* operators (the reference's
+ * train(), notebooks/dscnn_comparison.py:147-195; the tape is multilingual_kws_amd/dscnn_trainer.py).  Same conventions as those
+ * operators: device float32, NHWC viewed as [M, C], Keras layouts, asynchronous on `stream`, no allocation and no synchronisation
+ * (capturable), cross-workgroup sums two-level and in index order through the bound context's scratch arena (bit-reproducible).
+ * ---------------------------------------------------------------------------------------------- */
+/* Raw Conv2D(64, (10,4), strides 2, SAME: pad top 4 / bottom 5 / left 1 / right 1) without bias: d_spec [B,49,40], d_W [10,4,1,64]
+ * -> d_Z [B,25,20,64], on the fp32 MFMA with the patches gathered on the fly.  BatchNorm + ReLU follow through mkws_op_bn_train_fwd. */
+int mkws_op_dscnn_stem_fwd(const float* d_spec, const float* d_W, float* d_Z, int B, void* stream);
+/* d_dW [40,64] = patches^T . d_dZ [B,25,20,64] (written, not accumulated).  Needs up to 256 * 2560 floats of the scratch arena; folded at once
+ * (it does not join the mkws_op_fold_defer queue). */
+int mkws_op_dscnn_stem_bwd_weight(const float* d_spec, const float* d_dZ, float* d_dW, int B, void* stream);
+/* Dropout without a stored mask: element i is kept when the top 24 bits of splitmix64(base + (i + 1) * 0x9E3779B97F4A7C15) are at least
+ * floor(rate * 2^24), base = splitmix64(splitmix64(splitmix64(seed) + *d_step) + site); kept values are multiplied by the float32
+ * 1 / (1 - rate), the others are zero.  0 <= rate < 1; rate = 0 is the identity.  *d_step is the device counter mkws_op_step_inc
+ * advances, so a captured step draws a fresh mask on every replay; the backward pass is the same launch on the gradient.  In place
+ * (d_out == d_X) is allowed.  dscnn_trainer.dropout_mask_host reproduces the bits on the host. */
+int mkws_op_dropout_fwd(const float* d_X, float* d_out, int64_t n, float rate, uint64_t seed, const int* d_step, int site, void* stream);
+int mkws_op_dropout_bwd(const float* d_dOut, float* d_dX, int64_t n, float rate, uint64_t seed, const int* d_step, int site, void* stream);
+/* Dropout (mask index = the element's index in d_A [B,25,20,64]) fused with the mean over rows 0..23 (480 cells) -> d_pooled [B,64];
+ * the backward writes mask * (1 / (1 - rate) / 480) * d_dpooled into rows 0..23 of d_dA and exact zeros into row 24 (16-byte aligned). */
+int mkws_op_dscnn_pool_fwd(const float* d_A, int B, float rate, uint64_t seed, const int* d_step, int site, float* d_pooled, void* stream);
+int mkws_op_dscnn_pool_bwd(const float* d_dpooled, int B, float rate, uint64_t seed, const int* d_step, int site, float* d_dA, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

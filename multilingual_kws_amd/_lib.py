@@ -141,6 +141,13 @@ SYMBOLS = [
     ("mkws_dscnn_grid", _I, [_P]),
     ("mkws_dscnn_forward", _I, [_P, _P, _I, _P, _P, _P]),
     ("mkws_dscnn_tap", _I, [_P, _P, _I, _I, _P, _P]),
+    # DS-CNN training operators
+    ("mkws_op_dscnn_stem_fwd", _I, [_P, _P, _P, _I, _P]),
+    ("mkws_op_dscnn_stem_bwd_weight", _I, [_P, _P, _P, _I, _P]),
+    ("mkws_op_dropout_fwd", _I, [_P, _P, _I64, _F, ctypes.c_uint64, _P, _I, _P]),
+    ("mkws_op_dropout_bwd", _I, [_P, _P, _I64, _F, ctypes.c_uint64, _P, _I, _P]),
+    ("mkws_op_dscnn_pool_fwd", _I, [_P, _I, _F, ctypes.c_uint64, _P, _I, _P, _P]),
+    ("mkws_op_dscnn_pool_bwd", _I, [_P, _I, _F, ctypes.c_uint64, _P, _I, _P, _P]),
     ("mkws_augment_batch", _I, [_P, _P, _P, ctypes.c_int64, _P, _I, _I, _P, _P]),
     ("mkws_specaug_apply", _I, [_P, _P, _I, _I, _I, _P]),
     ("mkws_specaug_apply_n", _I, [_P, _P, _I, _I, _I, _I, _I, _P]),

@@ -48,4 +48,9 @@ inline int require_device() {
   return MKWS_OK;
 }
 
+// The training operators' bound context (mkws_train.hip), for operators that live in other translation units: `floats` of its scratch
+// arena past whatever queued folds hold (NULL when the arena is missing or too small), and the workgroup cap of an elementwise launch.
+float* train_scratch_at(size_t floats, hipStream_t s);
+int train_grid_cap();
+
 }  // namespace mkws

@@ -1707,6 +1707,12 @@ const bool g_bn_small = [] { const char* e = getenv("MKWS_TRAIN_BN_SMALL"); retu
 inline int row_chunks(int M, int cap) { int c = (M + 127) / 128; if (c > cap) c = cap; if (c < 1) c = 1; return c; }
 }  // namespace
 
+// the bound context for operators in other translation units (mkws_common.h)
+namespace mkws {
+float* train_scratch_at(size_t floats, hipStream_t s) { return scratch_at(floats, s); }
+int train_grid_cap() { return kGridCap; }
+}  // namespace mkws
+
 extern "C" {
 
 int mkws_op_set_scratch(float* d_scratch, size_t floats) {

@@ -3,8 +3,8 @@ inference on the device (mkws_dscnn_* of include/mkws.h, one launch per forward)
 
 Parameters are a flat float32 blob in Keras variable order and layout, BatchNorm tensors included (manifest()).  The device sees folded
 weights only: fold() is the specification of what mkws_dscnn_create does with the blob, dscnn_host the specification of the forward
-pass -- float64 NumPy on the float32 folded weights, written from the layer list in include/mkws.h.  Training the DS-CNN is not built
-(DESIGN.md section 29)."""
+pass -- float64 NumPy on the float32 folded weights, written from the layer list in include/mkws.h.  Training is dscnn_trainer.py
+(DESIGN.md section 30)."""
 import contextlib
 import ctypes
 import json
