@@ -1062,6 +1062,15 @@ int mkws_specaug_apply_n(float* d_spec, const int32_t* d_masks, int n_freq, int 
  * split reduction of mkws_op_gemm, which splits only as far as the arena reaches); ops that need the arena fail with
  * MKWS_ERR_INVALID_ARG when it is missing or too small.  A context is used in stream order (ops on ONE stream share it safely; give
  * concurrent streams separate contexts).
+ * The arena contract (tests/test_train_arena_gpu.py, tests/test_train_arena_cpu.py):
+ *   - a refused call has launched nothing: an operator works out every arena need of the call before its first launch, so
+ *     MKWS_ERR_INVALID_ARG leaves every output buffer as it was.  mkws_last_error() names the float count the call needs;
+ *   - a call touches only the floats it asked for, starting past whatever queued folds (mkws_op_fold_defer) still hold;
+ *   - results do not depend on what the arena held before: every slot a second stage reads was written by its first stage;
+ *   - the arena size selects a route in two places, both functions of the shapes and the size only: the automatic split of mkws_op_gemm
+ *     (ksplit = 0; never refused -- without an arena it does not split), and mkws_op_conv_bn_fwd, whose fused route (statistics in the GEMM
+ *     epilogue) takes ceil(M / 64) * 2 * N floats and whose three-launch sequence takes min(ceil(M / 128), bn_chunk_cap) * 2 * N, never more:
+ *     an arena that holds only the latter runs the sequence (equal up to fp32 summation order), one that holds neither is refused.
  *   mkws_train_ctx_create / _destroy   a context handle owning nothing but its bookkeeping (the arena stays the caller's)
  *   mkws_train_ctx_bind(ctx)           every mkws_op_* call of THIS host thread uses ctx until another bind; NULL = the thread's default
  *                                      context.  Distinct contexts are independent: two trainers on one thread each bind their own before

@@ -1986,7 +1986,9 @@ int mkws_op_bn_train_fwd_res(const float* Z, int M, int C, const float* gamma, c
 
 // 1x1 convolution (NN GEMM) + training-mode BatchNorm (+ activation, + residual branch) as ONE operator: when the GEMM is unsplit and has
 // at most kBnMaxGemmTiles row tiles, its epilogue leaves the BatchNorm chunk statistics (one chunk = one 64-row tile) and the BatchNorm is a
-// single launch; otherwise the three-launch sequence of mkws_op_gemm + mkws_op_bn_train_fwd_res.
+// single launch; otherwise the three-launch sequence of mkws_op_gemm + mkws_op_bn_train_fwd_res.  The arena decides between the two as well:
+// the epilogue's statistics take tiles * 2 * N floats, the sequence's row_chunks * 2 * N (never more); an arena that holds only the latter runs
+// the sequence, one that does not hold the latter is refused before the first launch.
 int mkws_op_conv_bn_fwd(const float* X, const float* W, float* Z, int M, int N, int K, const float* gamma, const float* beta, float eps, int act, float momentum,
                         float* moving_mean, float* moving_var, float* mean, float* var, float* A, const float* res, const float* row_scale, int group,
                         void* stream) {
@@ -1995,6 +1997,8 @@ int mkws_op_conv_bn_fwd(const float* X, const float* W, float* Z, int M, int N, 
   MKWS_REQ(N % 4 == 0, "conv_bn_fwd: N must be a multiple of 4");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int tiles = (M + 63) / 64;
+  const size_t seq_need = (size_t)row_chunks(M, kBnChunkCap) * 2 * N;
+  MKWS_REQ(scratch(seq_need), "conv_bn_fwd: needs %zu floats of scratch (mkws_op_set_scratch)", seq_need);
   float* part = (tiles <= kBnMaxGemmTiles) ? scratch_at((size_t)tiles * 2 * N, s) : nullptr;
   bool fused = false;
   if (int rc = gemm_impl(X, W, Z, M, N, K, K, N, N, 0, 0, 0, 0, nullptr, 0, nullptr, s, part, &fused)) return rc;
@@ -2068,6 +2072,8 @@ int mkws_op_dwconv_bn_fwd(const float* X, const float* W, float* Z, int B, int H
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int M = B * Ho * Wo, chunks = (M + 127) / 128;
   if (chunks > kBnMaxChunks) {
+    const size_t need = (size_t)row_chunks(M, kBnChunkCap) * 2 * C;      // (what mkws_op_bn_train_fwd_res will ask for: refuse before the convolution runs)
+    MKWS_REQ(scratch(need), "dwconv_bn_fwd: needs %zu floats of scratch (mkws_op_set_scratch)", need);
     if (int rc = mkws_op_dwconv_fwd(X, W, Z, B, H, Wd, C, k, s, pt, pl, Ho, Wo, stream)) return rc;
     return mkws_op_bn_train_fwd_res(Z, M, C, gamma, beta, eps, act, momentum, moving_mean, moving_var, mean, var, A, nullptr, nullptr, 1, stream);
   }
@@ -2085,19 +2091,22 @@ int mkws_op_dwconv_bwd(const float* X, const float* W, const float* dZ, float* d
                        int Wo, void* stream) {
   MKWS_REQ(X && W && dZ && (dW || dX) && B > 0 && C % 4 == 0 && (k == 3 || k == 5) && (s == 1 || s == 2), "dwconv_bwd: bad arguments");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dX) hipLaunchKernelGGL(dw_bwd_input_kernel, dim3(grid_for((size_t)B * H * Wd * (C / 4))), dim3(256), 0, st, dZ, W, dX, B, H, Wd, C, k, s, pt, pl, Ho, Wo);
-  if (!dW) {                                                         // input gradient only (the weight gradient is a second call, possibly on another stream)
-    MKWS_HIP(hipGetLastError());
-    return MKWS_OK;
-  }
   // chunks of output positions: 32 positions each (two per position lane) until the grid has ~512 workgroups, at most 256 chunks
   const int xb = (C / 4 + 15) / 16;
   int chunks = (B * Ho * Wo + 31) / 32;
   const int cap = (512 + xb - 1) / xb < 256 ? (512 + xb - 1) / xb : 256;
   if (chunks > cap) chunks = cap;
   if (chunks < 1) chunks = 1;
-  float* part = scratch_at((size_t)chunks * k * k * C, st);
-  MKWS_REQ(part, "dwconv_bwd: needs %zu floats of scratch (mkws_op_set_scratch)", (size_t)chunks * k * k * C);
+  float* part = nullptr;
+  if (dW) {                                                          // (before the input gradient's launch: a refused call has launched nothing)
+    part = scratch_at((size_t)chunks * k * k * C, st);
+    MKWS_REQ(part, "dwconv_bwd: needs %zu floats of scratch (mkws_op_set_scratch)", (size_t)chunks * k * k * C);
+  }
+  if (dX) hipLaunchKernelGGL(dw_bwd_input_kernel, dim3(grid_for((size_t)B * H * Wd * (C / 4))), dim3(256), 0, st, dZ, W, dX, B, H, Wd, C, k, s, pt, pl, Ho, Wo);
+  if (!dW) {                                                         // input gradient only (the weight gradient is a second call, possibly on another stream)
+    MKWS_HIP(hipGetLastError());
+    return MKWS_OK;
+  }
   const dim3 grid(xb, chunks);
   if (k == 3) hipLaunchKernelGGL((dw_bwd_weight_kernel<3>), grid, dim3(256), 0, st, X, dZ, part, B, H, Wd, C, s, pt, pl, Ho, Wo);
   else hipLaunchKernelGGL((dw_bwd_weight_kernel<5>), grid, dim3(256), 0, st, X, dZ, part, B, H, Wd, C, s, pt, pl, Ho, Wo);
@@ -2149,6 +2158,12 @@ int mkws_op_se_bwd(const float* A, const float* g, const float* dOut, float* dA,
 
 // the squeeze-excite parameter gradients: batch rows in chunks of 64 over blockIdx.z; with more than one chunk the kernel writes partial
 // sums to the scratch arena and four fixed-order folds (deferred with the others when deferral is on) produce the gradients
+static size_t se_wgrad_need(int B, int C, int se) {
+  const size_t chunks = (B + 63) / 64;
+  auto r64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  return chunks == 1 ? 0 : 2 * r64(chunks * se * C) + r64(chunks * C) + r64(chunks * se);
+}
+
 static int se_wgrad_launch(const float* mean, const float* R, const float* dYg, const float* dYr, float* dWr, float* dbr, float* dWe, float* dbe, int B, int C, int se,
                            hipStream_t s) {
   const int chunks = (B + 63) / 64;
@@ -2193,6 +2208,8 @@ int mkws_op_se_bwd_fused(const float* A, const float* G, const float* dOut, cons
   MKWS_REQ(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= kSeMaxC && se > 0 && se <= kSeMaxSe, "se_bwd_fused: needs C %% 4 == 0, C <= %d, se <= %d (got C = %d, se = %d)",
            kSeMaxC, kSeMaxSe, C, se);
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const size_t need = dWr ? se_wgrad_need(B, C, se) : 0)         // (what se_wgrad_launch will ask for: refuse before the gate's launch)
+    MKWS_REQ(scratch(need), "se_bwd_fused: needs %zu floats of scratch (mkws_op_set_scratch)", need);
   const dim3 grid((C + kSeSlab - 1) / kSeSlab, B);
   hipLaunchKernelGGL(se_bwd_gate_kernel, grid, dim3(256), 0, s, A, G, dOut, We, dA, dYg, work, HW, C, se);
   hipLaunchKernelGGL(se_bwd_squeeze_kernel, grid, dim3(128), 0, s, work, Yr, Wr, dYr, dmean, C, se);

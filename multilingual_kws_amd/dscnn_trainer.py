@@ -60,8 +60,14 @@ CONV_KERNELS = [k for _, k, _, _ in LAYERS]
 CONV_BIASES = [b for _, _, b, _ in LAYERS]
 
 
+def _arena(torch, t, device):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and t.dim() == 1 and t.is_contiguous() and t.numel() > 0):
+        raise ValueError(f"a scratch arena is a contiguous one-dimensional float32 tensor on {device}")
+    return t
+
+
 class DSCNNTrainer:
-    def __init__(self, params, label_count=None, max_batch=1024, seed=0, weight_decay=1e-4, dropout=(0.2, 0.4), device=None, mode="eager"):
+    def __init__(self, params, label_count=None, max_batch=1024, seed=0, weight_decay=1e-4, dropout=(0.2, 0.4), device=None, mode="eager", scratch=None):
         import torch
         if mode not in ("eager", "hipgraph"):
             raise ValueError(f"mode {mode!r}: 'eager' or 'hipgraph'")
@@ -88,7 +94,8 @@ class DSCNNTrainer:
         self.v = torch.zeros_like(self.params_dev)
         self.d_step = torch.zeros(1, dtype=torch.int32, device=self.device)        # optimizer steps done: Adam's index and the masks' counter
         self.stats = torch.zeros(2, dtype=torch.float32, device=self.device)
-        self._scratch = torch.empty(4 << 20, dtype=torch.float32, device=self.device)
+        # scratch: a caller-provided arena (float32, on this device, contiguous) for the fixed-order reductions; None allocates 4 Mi floats
+        self._scratch = _arena(torch, scratch, self.device) if scratch is not None else torch.empty(4 << 20, dtype=torch.float32, device=self.device)
         self._ctx = ctypes.c_void_p()
         _lib.check(self.L.mkws_train_ctx_create(self._p(self._scratch), self._scratch.numel(), ctypes.byref(self._ctx)))
         self._views, self._ws, self._graphs = {}, {}, {}

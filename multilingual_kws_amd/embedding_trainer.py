@@ -37,7 +37,9 @@ def _down(h, w, k):
 
 
 class EmbeddingTrainer:
-    def __init__(self, weight_blob, device=None):
+    def __init__(self, weight_blob, device=None, scratch=None, scratch_side=None):
+        """scratch / scratch_side: caller-provided arenas (contiguous one-dimensional float32 tensors on the device) for the fixed-order
+        reductions of the caller's stream and of the weight-gradient stream; None allocates 16 Mi floats each, the second on first use."""
         import torch
         self.torch = torch
         self.L = _lib.lib()
@@ -61,7 +63,7 @@ class EmbeddingTrainer:
         self._pool, self._pool_pos, self._pool_B = [], 0, None
         self._stream = None
         # partial sums of the fixed-order reductions (include/mkws.h: mkws_op_set_scratch); 16 Mi floats cover every layer
-        self._scratch = torch.empty(16 << 20, dtype=torch.float32, device=self.device)
+        self._scratch = self._arena(scratch) if scratch is not None else torch.empty(16 << 20, dtype=torch.float32, device=self.device)
         # the trainer's own operator context (arena + deferred-fold queue): independent of other trainers on this thread and of the
         # thread it runs on; bound at the top of every public method (_bind_stream)
         self._ctx = ctypes.c_void_p()
@@ -79,8 +81,14 @@ class EmbeddingTrainer:
         # the fused kernel owns eight rows x 25 taps)
         self.fuse_bn_stats = int(os.environ.get("MKWS_TRAIN_FUSE_BN_STATS", "3"))
         self._side = None
-        self._scratch_side = None
+        self._scratch_side = self._arena(scratch_side) if scratch_side is not None else None
         self._ctx_side = ctypes.c_void_p()
+
+    def _arena(self, t):
+        torch = self.torch
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.dim() == 1 and t.is_contiguous() and t.numel() > 0):
+            raise ValueError(f"a scratch arena is a contiguous one-dimensional float32 tensor on {self.device}")
+        return t
 
     def __del__(self):
         try:
@@ -131,7 +139,8 @@ class EmbeddingTrainer:
             # MKWS_TRAIN_SIDE_PRIORITY = -1 raises the SIDE stream instead (an A/B knob; it lost).
             prio = os.environ.get("MKWS_TRAIN_SIDE_PRIORITY")
             self._side = torch.cuda.Stream(device=self.device, priority=min(int(prio), 0) if prio is not None else 0)
-            self._scratch_side = torch.empty(16 << 20, dtype=torch.float32, device=self.device)
+            if self._scratch_side is None:
+                self._scratch_side = torch.empty(16 << 20, dtype=torch.float32, device=self.device)
             _lib.check(self.L.mkws_train_ctx_create(self._p(self._scratch_side), self._scratch_side.numel(), ctypes.byref(self._ctx_side)))
             self._side_ptr = ctypes.c_void_p(self._side.cuda_stream)
         _lib.check(self.L.mkws_op_stream_wait(self._side_ptr, self._stream))       # (a library call, not torch's wait_stream: TrainStepGraph's tape replays it)
