@@ -14,15 +14,15 @@ dense kernel), loss from logits through log-softmax.
 Conv biases: each of the nine convolutions carries a Keras bias in front of its BatchNorm.  Under batch statistics the batch mean
 removes it, so its true gradient is exactly zero; here it is DEFINED as zero -- the biases never change and are not added to Z.  The
 device keeps the moving mean of Z; params() exports the moving mean of Z + bias, so that dscnn.fold stays right for an imported
-checkpoint with non-zero biases."""
+checkpoint with non-zero biases.
+
+The class sits on op_tape.OpTape (operator context, flat state, layer calls, graph capture; shared with the embedding's trainer)."""
 import ctypes
 
 import numpy as np
 
 from . import _lib, dscnn, synth
-
-BN_EPS, BN_MOMENTUM = 1e-3, 0.99
-ACT_NONE, ACT_RELU = 0, 2
+from .op_tape import ACT_NONE, ACT_RELU, BN_EPS, BN_MOMENTUM, OpTape  # noqa: F401
 H, W, C, PIX = dscnn.OUT_H, dscnn.OUT_W, dscnn.CHANNELS, dscnn.OUT_H * dscnn.OUT_W
 SITE_STEM, SITE_POOL = 0, 1
 _GOLDEN = np.uint64(0x9E3779B97F4A7C15)
@@ -60,18 +60,11 @@ CONV_KERNELS = [k for _, k, _, _ in LAYERS]
 CONV_BIASES = [b for _, _, b, _ in LAYERS]
 
 
-def _arena(torch, t, device):
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and t.dim() == 1 and t.is_contiguous() and t.numel() > 0):
-        raise ValueError(f"a scratch arena is a contiguous one-dimensional float32 tensor on {device}")
-    return t
-
-
-class DSCNNTrainer:
+class DSCNNTrainer(OpTape):
     def __init__(self, params, label_count=None, max_batch=1024, seed=0, weight_decay=1e-4, dropout=(0.2, 0.4), device=None, mode="eager", scratch=None):
-        import torch
         if mode not in ("eager", "hipgraph"):
             raise ValueError(f"mode {mode!r}: 'eager' or 'hipgraph'")
-        self.torch, self.L, self.mode = torch, _lib.lib(), mode
+        self.mode = mode
         blob = np.ascontiguousarray(params, dtype=np.float32).copy()
         self.label_count = int(label_count) if label_count is not None else dscnn.label_count_of(blob)
         if blob.shape[0] != dscnn.param_count(self.label_count):
@@ -82,55 +75,17 @@ class DSCNNTrainer:
         self.rates = (float(dropout[0]), float(dropout[1]))
         if self.max_batch < 1 or not all(0.0 <= r < 1.0 for r in self.rates) or self.weight_decay < 0:
             raise ValueError("max_batch >= 1, dropout rates in [0, 1) and weight_decay >= 0 are required")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-        self.tensors = {t["name"]: t for t in dscnn.manifest(self.label_count)}
+        # scratch: a caller-provided arena (float32, on this device, contiguous) for the fixed-order reductions; None allocates 4 Mi floats
+        OpTape.__init__(self, device, scratch, 4 << 20)
         # the device keeps the moving mean of Z (see the module docstring); the biases themselves stay in the blob untouched
-        host = {n: blob[t["offset"]:t["offset"] + t["count"]] for n, t in self.tensors.items()}
+        host = dscnn.unpack(blob)
         for _, _, bias, bn in LAYERS:
             host[bn + "/moving_mean"] -= host[bias]
-        self.params_dev = torch.from_numpy(blob).to(self.device)
-        self.grads = torch.zeros_like(self.params_dev)         # conv biases and moving statistics: never written, exactly zero
-        self.m = torch.zeros_like(self.params_dev)
-        self.v = torch.zeros_like(self.params_dev)
-        self.d_step = torch.zeros(1, dtype=torch.int32, device=self.device)        # optimizer steps done: Adam's index and the masks' counter
-        self.stats = torch.zeros(2, dtype=torch.float32, device=self.device)
-        # scratch: a caller-provided arena (float32, on this device, contiguous) for the fixed-order reductions; None allocates 4 Mi floats
-        self._scratch = _arena(torch, scratch, self.device) if scratch is not None else torch.empty(4 << 20, dtype=torch.float32, device=self.device)
-        self._ctx = ctypes.c_void_p()
-        _lib.check(self.L.mkws_train_ctx_create(self._p(self._scratch), self._scratch.numel(), ctypes.byref(self._ctx)))
-        self._views, self._ws, self._graphs = {}, {}, {}
+        # grads: conv biases and moving statistics are never written, exactly zero; d_step: optimizer steps done, Adam's index and the masks' counter
+        self.params_dev = self._flat_state(blob, dscnn.manifest(self.label_count))
+        self.stats = self.torch.zeros(2, dtype=self.torch.float32, device=self.device)
+        self._ws, self._graphs = {}, {}
         self._last_B = None
-        self._stream = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self.L.mkws_train_ctx_destroy(self._ctx)
-                self._ctx = None
-        except Exception:
-            pass
-
-    # ---- plumbing -----------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    def _bind(self):
-        self._stream = _lib.current_stream_ptr()
-        _lib.check(self.L.mkws_train_ctx_bind(self._ctx))
-
-    def _view(self, buf, name):
-        v = self._views.get((id(buf), name))
-        if v is None:
-            t = self.tensors[name]
-            v = self._views[(id(buf), name)] = buf[t["offset"]:t["offset"] + t["count"]]
-        return v
-
-    def P(self, name):
-        return self._p(self._view(self.params_dev, name))
-
-    def G(self, name):
-        return self._p(self._view(self.grads, name))
 
     def _workspace(self, B):
         """The tape's buffers for batch B.  Batches that have a captured graph keep theirs; of the others only the last one is kept."""
@@ -170,38 +125,28 @@ class DSCNNTrainer:
         """Forward, loss, backward and L2 on ws['spec'] / ws['labels']: fills self.grads and self.stats."""
         L, p, s, M, Lc = self.L, self._p, self._stream, B * PIX, self.label_count
         seed, d_step = ctypes.c_uint64(self.seed), p(self.d_step)
-        bn = lambda i, leaf: self.P(LAYERS[i][3] + "/" + leaf)
         Z, A, mean, var = ws["Z"], ws["A"], ws["mean"], ws["var"]
         # ---- forward
         _lib.check(L.mkws_op_dscnn_stem_fwd(p(ws["spec"]), self.P("conv2d/kernel"), p(Z[0]), B, s))
-        _lib.check(L.mkws_op_bn_train_fwd(p(Z[0]), M, C, bn(0, "gamma"), bn(0, "beta"), BN_EPS, ACT_RELU, BN_MOMENTUM, bn(0, "moving_mean"),
-                                          bn(0, "moving_variance"), p(mean[0]), p(var[0]), p(A[0]), s))
+        self.bn_fwd(Z[0], M, C, LAYERS[0][3], ACT_RELU, mean[0], var[0], A[0])
         _lib.check(L.mkws_op_dropout_fwd(p(A[0]), p(A[0]), M * C, self.rates[0], seed, d_step, SITE_STEM, s))
         for i in range(1, len(LAYERS)):
-            kind, kernel = LAYERS[i][0], LAYERS[i][1]
+            kind, kernel, _, prefix = LAYERS[i]
             if kind == "dw":
-                _lib.check(L.mkws_op_dwconv_bn_fwd(p(A[i - 1]), self.P(kernel), p(Z[i]), B, H, W, C, 3, 1, 1, 1, H, W, bn(i, "gamma"), bn(i, "beta"), BN_EPS,
-                                                   ACT_RELU, BN_MOMENTUM, bn(i, "moving_mean"), bn(i, "moving_variance"), p(mean[i]), p(var[i]), p(A[i]), s))
+                self.dwconv_bn_fwd(A[i - 1], kernel, Z[i], B, H, W, C, 3, 1, 1, 1, H, W, prefix, ACT_RELU, mean[i], var[i], A[i])
             else:
-                _lib.check(L.mkws_op_conv_bn_fwd(p(A[i - 1]), self.P(kernel), p(Z[i]), M, C, C, bn(i, "gamma"), bn(i, "beta"), BN_EPS, ACT_RELU, BN_MOMENTUM,
-                                                 bn(i, "moving_mean"), bn(i, "moving_variance"), p(mean[i]), p(var[i]), p(A[i]), None, None, 1, s))
+                self.conv_bn_fwd(A[i - 1], kernel, Z[i], M, C, C, prefix, ACT_RELU, mean[i], var[i], A[i])
         _lib.check(L.mkws_op_dscnn_pool_fwd(p(A[-1]), B, self.rates[1], seed, d_step, SITE_POOL, p(ws["pooled"]), s))
         _lib.check(L.mkws_op_gemm(p(ws["pooled"]), self.P("dense/kernel"), p(ws["Zl"]), B, Lc, C, C, Lc, Lc, 0, 0, 0, 0, s))
         _lib.check(L.mkws_op_bias_act_fwd(p(ws["Zl"]), self.P("dense/bias"), ACT_NONE, p(ws["logits"]), B, Lc, s))
-        # ---- loss: logits <- d(mean loss) / d(logits)
-        _lib.check(L.mkws_op_softmax_ce(p(ws["logits"]), p(ws["labels"]), B, Lc, p(ws["rowstat"]), p(self.stats), s))
+        # ---- loss and the dense layer's backward: logits <- d(mean loss) / d(logits)
+        self.dense_ce_bwd(ws["pooled"], ws["Zl"], ws["logits"], ws["labels"], B, C, Lc, "dense", ws["rowstat"], self.stats, ws["dpooled"])
         # ---- backward
-        d = ws["logits"]
-        _lib.check(L.mkws_op_bias_act_bwd(p(ws["Zl"]), self.P("dense/bias"), ACT_NONE, p(d), self.G("dense/bias"), B, Lc, s))
-        _lib.check(L.mkws_op_gemm(p(ws["pooled"]), p(d), self.G("dense/kernel"), C, Lc, B, C, Lc, Lc, 1, 0, 0, 0, s))
-        _lib.check(L.mkws_op_gemm(p(d), self.P("dense/kernel"), p(ws["dpooled"]), B, C, Lc, Lc, Lc, C, 0, 1, 0, 0, s))
         g, other = ws["g"]
         _lib.check(L.mkws_op_dscnn_pool_bwd(p(ws["dpooled"]), B, self.rates[1], seed, d_step, SITE_POOL, p(g), s))
         for i in range(len(LAYERS) - 1, 0, -1):
             kind, kernel, _, prefix = LAYERS[i]
-            # g: dLoss/dA[i] -> dLoss/dZ[i], in place
-            _lib.check(L.mkws_op_bn_act_bwd_ex(p(Z[i]), p(mean[i]), p(var[i]), bn(i, "gamma"), bn(i, "beta"), BN_EPS, ACT_RELU, p(g), p(g), None, None, 0.0, 1,
-                                               self.G(prefix + "/gamma"), self.G(prefix + "/beta"), M, C, s))
+            self.bn_bwd(Z[i], mean[i], var[i], M, C, prefix, ACT_RELU, g, g)          # g: dLoss/dA[i] -> dLoss/dZ[i], in place
             if kind == "pw":
                 _lib.check(L.mkws_op_gemm(p(A[i - 1]), p(g), self.G(kernel), C, C, M, C, C, C, 1, 0, 0, 0, s))
                 _lib.check(L.mkws_op_gemm(p(g), self.P(kernel), p(other), M, C, C, C, C, C, 0, 1, 0, 0, s))
@@ -209,25 +154,23 @@ class DSCNNTrainer:
                 _lib.check(L.mkws_op_dwconv_bwd(p(A[i - 1]), self.P(kernel), p(g), p(other), self.G(kernel), B, H, W, C, 3, 1, 1, 1, H, W, s))
             g, other = other, g
         _lib.check(L.mkws_op_dropout_bwd(p(g), p(g), M * C, self.rates[0], seed, d_step, SITE_STEM, s))
-        _lib.check(L.mkws_op_bn_act_bwd_ex(p(Z[0]), p(mean[0]), p(var[0]), bn(0, "gamma"), bn(0, "beta"), BN_EPS, ACT_RELU, p(g), p(g), None, None, 0.0, 1,
-                                           self.G("batch_normalization/gamma"), self.G("batch_normalization/beta"), M, C, s))
+        self.bn_bwd(Z[0], mean[0], var[0], M, C, LAYERS[0][3], ACT_RELU, g, g)
         _lib.check(L.mkws_op_dscnn_stem_bwd_weight(p(ws["spec"]), p(g), self.G("conv2d/kernel"), B, s))
         # ---- L2 on the nine convolution kernels: grad += 2 * weight_decay * W
         if self.weight_decay > 0:
             for kernel in CONV_KERNELS:
                 _lib.check(L.mkws_op_axpy(self.G(kernel), self.P(kernel), 2.0 * self.weight_decay, self.tensors[kernel]["count"], s))
 
-    def _adam(self, lr, beta1, beta2, eps):
+    def _adam_inc(self, lr, beta1, beta2, eps):
         _lib.check(self.L.mkws_op_step_inc(self._p(self.d_step), self._stream))
-        _lib.check(self.L.mkws_op_adam_dev(self._p(self.params_dev), self._p(self.grads), self._p(self.m), self._p(self.v), self.params_dev.shape[0], lr, beta1, beta2,
-                                           eps, self._p(self.d_step), 1.0, self._stream))
+        self._adam_dev(lr, beta1, beta2, eps)
 
     def forward_backward(self, spec, labels):
         """spec [B,49,40(,1)], labels [B] -> device stats [sum of row losses, #correct]; the gradients are in named_grads().  BatchNorm's
         moving statistics are updated (Keras does it in the training-mode forward pass); the step counter is not."""
         spec, labels, B = self._prep(spec, labels)
         with self.torch.cuda.device(self.device):
-            self._bind()
+            self.bind()
             ws = self._workspace(B)
             ws["spec"].copy_(spec)
             ws["labels"].copy_(labels)
@@ -238,8 +181,8 @@ class DSCNNTrainer:
     def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-7):
         """Keras Adam over the whole blob: conv biases and moving statistics have zero gradient and zero moments and stay put."""
         with self.torch.cuda.device(self.device):
-            self._bind()
-            self._adam(float(lr), beta1, beta2, eps)
+            self.bind()
+            self._adam_inc(float(lr), beta1, beta2, eps)
 
     def step(self, spec, labels, lr):
         """forward_backward + adam_step; in mode "hipgraph" one replay of the graph recorded for (B, lr)."""
@@ -267,39 +210,21 @@ class DSCNNTrainer:
     def _capture(self, B, lr):
         """Records forward + loss + backward + Adam of one step on one stream.  The warm-up runs the step once on a side stream (first
         launches load code objects) on state that is restored afterwards; every counter lives in device memory."""
-        torch, dev = self.torch, self.device
         self._graphs[(B, lr)] = None                           # (pins the workspace of B while it is created)
         ws = self._workspace(B)
-        state = (self.params_dev, self.grads, self.m, self.v, self.d_step, self.stats)
-        snap = [t.clone() for t in state]
 
         def body():
-            self._bind()
+            self.bind()
             self._tape(ws, B)
-            self._adam(lr, 0.9, 0.999, 1e-7)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        for t, c in zip(state, snap):
-            t.copy_(c)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            body()
-        return graph
+            self._adam_inc(lr, 0.9, 0.999, 1e-7)
+        return self.capture_step(body, (self.params_dev, self.grads, self.m, self.v, self.d_step, self.stats))[0]
 
     # ---- reading the state ------------------------------------------------------------------------------------------------
-    def named_grads(self):
-        g = self.grads.cpu().numpy()
-        return {n: g[t["offset"]:t["offset"] + t["count"]].reshape(t["shape"]) for n, t in self.tensors.items()}
-
     def params(self):
         """The Keras-order blob, moving statistics included (the moving means as Keras holds them: of Z + bias), so that
         dscnn.DSCNN(trainer.params()) is the trained classifier."""
         blob = self.params_dev.cpu().numpy().copy()
-        host = {n: blob[t["offset"]:t["offset"] + t["count"]] for n, t in self.tensors.items()}
+        host = dscnn.unpack(blob)
         for _, _, bias, bn in LAYERS:
             host[bn + "/moving_mean"] += host[bias]
         return blob
@@ -320,5 +245,5 @@ class DSCNNTrainer:
         torch = self.torch
         total = torch.zeros((), dtype=torch.float64, device=self.device)
         for kernel in CONV_KERNELS:
-            total = total + self._view(self.params_dev, kernel).double().square().sum()
+            total = total + self.view(kernel).double().square().sum()
         return self.weight_decay * float(total.cpu())

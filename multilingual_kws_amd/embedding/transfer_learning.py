@@ -5,7 +5,8 @@ transfer_learn() keeps the reference's signature and return contract (name, mode
 Dense(18,tanh) -> Dense(3,softmax) head trained with Adam on freshly augmented batches.
 Each step runs augmentation -> micro-frontend -> EfficientNet-B0 forward -> head fwd/bwd/Adam as HIP
 kernels; under torch.distributed the batch is sharded across ranks and the head gradient is
-all-reduced over RCCL (multilingual_kws_amd/parallel.py).
+all-reduced over RCCL (multilingual_kws_amd/parallel.py).  The frozen phase's trainers, for one head and for K side by side,
+sit on one core (_FrozenPhase); the un-frozen phase runs embedding_trainer's tape (on op_tape.OpTape).
 """
 import csv
 import glob
@@ -149,73 +150,53 @@ def steps_per_forward(batch_size, forward_clips=None):
     return max(1, int(FORWARD_CLIPS if forward_clips is None else forward_clips) // max(int(batch_size), 1))
 
 
-class FrozenHeadTrainer:
-    """The first phase of transfer_learn (reference transfer_learning.py:38-93: `embedding.trainable = False`, head fitted with Adam)
-    as a stream of optimizer steps that does not pay for small forward passes.
+class _FrozenPhase:
+    """What the trainers of the frozen phase share (FrozenHeadTrainer, FrozenHeadGroupTrainer): G optimizer steps per forward pass with the
+    group_limit cut, the optional second stream for the optimizer steps, `nbuf` alternating embedding buffers and the events that order
+    their producer (the caller's stream: `ready`) and consumer (the optimizer stream: `consumed`).  A subclass says how a group is drawn and
+    embedded (_refill, between _begin_refill and _hand_over) and what one optimizer step is (_step)."""
 
-    The embedding is frozen, so the forward pass of batch t + 1 is independent of the head update of step t.  G = steps_per_forward
-    consecutive batches are therefore drawn together (input_data.BatchGroups: the same draws in the same order as one batch at a time),
-    augmented / featurised / SpecAugmented by ONE launch each and embedded by ONE forward pass over G * batch_size clips on a handle
-    planned for that size; then the G optimizer steps run one after the other, each on its own batch_size rows and with its own
-    all-reduce under torch.distributed -- the semantics of parallel.dp_step, unchanged.  With overlap=True the optimizer steps (a few
-    small launches each, nowhere near filling the chip) go to a second stream and run under the NEXT group's augmentation, frontend and
-    embedding kernels; two embedding buffers alternate, events order producer and consumer.  Measured on one MI355X at 512 clips per
-    step (profiles/r05_notes.md): with two steps per forward the second stream loses 1 % (853.9 k -> 844.2 k clips/s: the head's few
-    launches only take turns with the embedding's), from four steps per forward it gains 3-4 % (932 k -> 966 k at 4, 958 k -> 984 k at 6):
-    overlap=None switches it on from OVERLAP_FROM_GROUP steps per forward.  Results are bit-identical either way.
-
-    step() performs exactly one optimizer step and returns its [sum of row losses, #correct] (summed over ranks) as a device tensor
-    that is rewritten by the next step() and lives on the trainer's stream: add it up with accumulate(), or read it after finish()
-    (which joins the side stream; call it before reading head parameters elsewhere)."""
-
-    def __init__(self, embedding, head, train_ds, batch_size, lr, group=None, overlap=None):
+    def __init__(self, embedding, batch_size, lr, group, overlap, lead=()):
+        """lead: leading dimensions of the embedding buffers [*lead, G * batch_size, features]."""
         import torch
-        self.embedding, self.head, self.lr = embedding, head, lr
-        self.bs = int(batch_size)
+        self.embedding, self.lr, self.bs, self.device = embedding, lr, int(batch_size), embedding.device
         self.G = max(1, min(int(group) if group is not None else steps_per_forward(self.bs), embedding.max_batch // self.bs))
-        self.groups = train_ds if isinstance(train_ds, input_data.BatchGroups) else input_data.BatchGroups(train_ds)
-        if self.groups.bs != self.bs:
-            raise ValueError(f"dataset is batched by {self.groups.bs}, trainer by {self.bs}")
-        self.device = embedding.device
         self.overlap = (self.G >= OVERLAP_FROM_GROUP) if overlap is None else bool(overlap)
         self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
         nbuf = 2 if self.overlap else 1
-        self.emb = [torch.empty((self.G * self.bs, embedding.output_dim), dtype=torch.float32, device=self.device) for _ in range(nbuf)]
-        self.consumed = [None] * nbuf            # event: every optimizer step that reads emb[k] has run
-        self.k, self.j, self.g, self.cur = -1, 0, 0, None
+        self.emb = [torch.empty((*lead, self.G * self.bs, embedding.output_dim), dtype=torch.float32, device=self.device) for _ in range(nbuf)]
+        self.consumed = [None] * nbuf            # event: every optimizer step that reads buffer k has run
+        self.k, self.j, self.g = -1, 0, 0
         self.forwards = 0
 
-    def _refill(self, g):
-        """Next group of g batches: draws + one launch chain on the caller's stream, hand-over to the optimizer stream."""
+    def _begin_refill(self):
+        """The next buffer, once the steps of two groups ago have finished with it: called in front of the first launch that writes it (the
+        draws and the launches that make the spectrograms do not wait)."""
         import torch
         self.k = (self.k + 1) % len(self.emb)
-        main = torch.cuda.current_stream(self.device)
-        spec, labels = self.groups.take(g)
-        labels = labels.to(torch.int32)
         if self.consumed[self.k] is not None:
-            main.wait_event(self.consumed[self.k])           # the steps of two groups ago have finished with this buffer
-        emb = self.embedding.forward(spec, out=self.emb[self.k][:g * self.bs])
-        self.forwards += 1
+            torch.cuda.current_stream(self.device).wait_event(self.consumed[self.k])
+
+    def _hand_over(self, g):
+        """The group of g steps in buffer k is complete on the caller's stream: the optimizer stream may read it."""
+        import torch
         if self.overlap:
             ready = torch.cuda.Event()
-            ready.record(main)
+            ready.record(torch.cuda.current_stream(self.device))
             self.side.wait_event(ready)
-            labels.record_stream(self.side)
-        self.cur, self.g, self.j = (emb, labels), g, 0
+        self.g, self.j = g, 0
 
     def step(self, group_limit=None):
-        """One optimizer step.  group_limit: steps left before the caller needs the head (end of an epoch): a new group is cut to it."""
+        """One optimizer step.  group_limit: steps left before the caller needs the head(s) (end of an epoch): a new group is cut to it."""
         import torch
-        from .. import parallel
         if self.j >= self.g:
             self._refill(self.G if group_limit is None else max(1, min(self.G, int(group_limit))))
-        emb, labels = self.cur
-        lo, hi = self.j * self.bs, (self.j + 1) * self.bs
+        off = self.j * self.bs
         self.j += 1
         if not self.overlap:
-            return parallel.dp_step(self.head, emb[lo:hi], labels[lo:hi], lr=self.lr)
+            return self._step(off)
         with torch.cuda.stream(self.side):
-            stats = parallel.dp_step(self.head, emb[lo:hi], labels[lo:hi], lr=self.lr)
+            stats = self._step(off)
             if self.j >= self.g:
                 ev = self.consumed[self.k] = self.consumed[self.k] or torch.cuda.Event()
                 ev.record(self.side)
@@ -237,83 +218,93 @@ class FrozenHeadTrainer:
             torch.cuda.current_stream(self.device).wait_stream(self.side)
 
 
-class FrozenHeadGroupTrainer:
+class FrozenHeadTrainer(_FrozenPhase):
+    """The first phase of transfer_learn (reference transfer_learning.py:38-93: `embedding.trainable = False`, head fitted with Adam)
+    as a stream of optimizer steps that does not pay for small forward passes.
+
+    The embedding is frozen, so the forward pass of batch t + 1 is independent of the head update of step t.  G = steps_per_forward
+    consecutive batches are therefore drawn together (input_data.BatchGroups: the same draws in the same order as one batch at a time),
+    augmented / featurised / SpecAugmented by ONE launch each and embedded by ONE forward pass over G * batch_size clips on a handle
+    planned for that size; then the G optimizer steps run one after the other, each on its own batch_size rows and with its own
+    all-reduce under torch.distributed -- the semantics of parallel.dp_step, unchanged.  With overlap=True the optimizer steps (a few
+    small launches each, nowhere near filling the chip) go to a second stream and run under the NEXT group's augmentation, frontend and
+    embedding kernels; two embedding buffers alternate, events order producer and consumer (_FrozenPhase).  Measured on one MI355X at 512
+    clips per step (profiles/r05_notes.md): with two steps per forward the second stream loses 1 % (853.9 k -> 844.2 k clips/s: the head's
+    few launches only take turns with the embedding's), from four steps per forward it gains 3-4 % (932 k -> 966 k at 4, 958 k -> 984 k at
+    6): overlap=None switches it on from OVERLAP_FROM_GROUP steps per forward.  Results are bit-identical either way.
+
+    step() performs exactly one optimizer step and returns its [sum of row losses, #correct] (summed over ranks) as a device tensor
+    that is rewritten by the next step() and lives on the trainer's stream: add it up with accumulate(), or read it after finish()
+    (which joins the side stream; call it before reading head parameters elsewhere)."""
+
+    def __init__(self, embedding, head, train_ds, batch_size, lr, group=None, overlap=None):
+        self.head = head
+        self.groups = train_ds if isinstance(train_ds, input_data.BatchGroups) else input_data.BatchGroups(train_ds)
+        if self.groups.bs != int(batch_size):
+            raise ValueError(f"dataset is batched by {self.groups.bs}, trainer by {int(batch_size)}")
+        _FrozenPhase.__init__(self, embedding, batch_size, lr, group, overlap)
+        self.cur = None
+
+    def _refill(self, g):
+        """Next group of g batches: draws + one launch chain on the caller's stream, hand-over to the optimizer stream."""
+        import torch
+        spec, labels = self.groups.take(g)
+        labels = labels.to(torch.int32)
+        self._begin_refill()
+        emb = self.embedding.forward(spec, out=self.emb[self.k][:g * self.bs])
+        self.forwards += 1
+        self._hand_over(g)
+        if self.overlap:
+            labels.record_stream(self.side)
+        self.cur = (emb, labels)
+
+    def _step(self, off):
+        emb, labels = self.cur
+        return parallel.dp_step(self.head, emb[off:off + self.bs], labels[off:off + self.bs], lr=self.lr)
+
+
+class FrozenHeadGroupTrainer(_FrozenPhase):
     """FrozenHeadTrainer for K keyword heads side by side on ONE frozen embedding (single process).
 
     Heads of different keywords are independent, so step j of all K of them is one set of launches with the head as a grid dimension
     (head.HeadGroup) instead of K times four small dependent ones.  Per group of g steps: every target draws its own g batches from
     its own BatchGroups (its own AudioDataset and generator: the draws of transfer_learn), one forward pass per target writes slab k
     of a [K, G * bs, features] buffer, then g rounds of HeadGroup.loss_grad(offset=j * bs, rows=bs) + adam_step.  group_limit, the
-    second stream with two alternating buffers and the consumed / ready events are FrozenHeadTrainer's.  Every head ends with the bits
-    FrozenHeadTrainer gives it alone.
+    second stream with two alternating buffers and the consumed / ready events are _FrozenPhase's, as for FrozenHeadTrainer.  Every head
+    ends with the bits FrozenHeadTrainer gives it alone.
 
     step() performs one optimizer step of EVERY head and returns a [K, 2] device tensor of their {sum of row losses, #correct}, rewritten
     by the next step()."""
 
     def __init__(self, embedding, heads, train_dss, batch_size, lr, group=None, overlap=None):
         import torch
-        self.embedding, self.lr = embedding, lr
         self.group = heads if isinstance(heads, HeadGroup) else HeadGroup(heads)
         self.K = len(self.group)
-        self.bs = int(batch_size)
-        self.G = max(1, min(int(group) if group is not None else steps_per_forward(self.bs), embedding.max_batch // self.bs))
         self.groups = [d if isinstance(d, input_data.BatchGroups) else input_data.BatchGroups(d) for d in train_dss]
         if len(self.groups) != self.K:
             raise ValueError(f"{self.K} heads but {len(self.groups)} training streams")
         for g in self.groups:
-            if g.bs != self.bs:
-                raise ValueError(f"dataset is batched by {g.bs}, trainer by {self.bs}")
-        self.device = embedding.device
-        self.overlap = (self.G >= OVERLAP_FROM_GROUP) if overlap is None else bool(overlap)
-        self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
-        nbuf = 2 if self.overlap else 1
-        rows = self.G * self.bs
-        self.emb = [torch.empty((self.K, rows, embedding.output_dim), dtype=torch.float32, device=self.device) for _ in range(nbuf)]
-        self.labels = [torch.zeros((self.K, rows), dtype=torch.int32, device=self.device) for _ in range(nbuf)]
-        self.consumed = [None] * nbuf            # event: every optimizer step that reads emb[k] / labels[k] has run
-        self.k, self.j, self.g = -1, 0, 0
-        self.forwards = 0
+            if g.bs != int(batch_size):
+                raise ValueError(f"dataset is batched by {g.bs}, trainer by {int(batch_size)}")
+        _FrozenPhase.__init__(self, embedding, batch_size, lr, group, overlap, lead=(self.K,))
+        self.labels = [torch.zeros(e.shape[:2], dtype=torch.int32, device=self.device) for e in self.emb]
 
     def _refill(self, g):
         """Next group of g batches of every target: draws + launch chains on the caller's stream, hand-over to the optimizer stream."""
-        import torch
-        self.k = (self.k + 1) % len(self.emb)
-        main = torch.cuda.current_stream(self.device)
         n = g * self.bs
         for h, groups in enumerate(self.groups):
             spec, labels = groups.take(g)
-            if h == 0 and self.consumed[self.k] is not None:
-                main.wait_event(self.consumed[self.k])       # the steps of two groups ago have finished with these buffers
+            if h == 0:
+                self._begin_refill()
             self.embedding.forward(spec, out=self.emb[self.k][h, :n])
             self.labels[self.k][h, :n].copy_(labels)         # int64 -> int32
             self.forwards += 1
-        if self.overlap:
-            ready = torch.cuda.Event()
-            ready.record(main)
-            self.side.wait_event(ready)
-        self.g, self.j = g, 0
+        self._hand_over(g)
 
-    def step(self, group_limit=None):
-        """One optimizer step of every head.  group_limit: steps left before the caller needs the heads (end of an epoch)."""
-        import torch
-        if self.j >= self.g:
-            self._refill(self.G if group_limit is None else max(1, min(self.G, int(group_limit))))
-        off = self.j * self.bs
-        self.j += 1
-        if not self.overlap:
-            stats = self.group.loss_grad(self.emb[self.k], self.labels[self.k], rows=self.bs, offset=off)
-            self.group.adam_step(lr=self.lr)
-            return stats
-        with torch.cuda.stream(self.side):
-            stats = self.group.loss_grad(self.emb[self.k], self.labels[self.k], rows=self.bs, offset=off)
-            self.group.adam_step(lr=self.lr)
-            if self.j >= self.g:
-                ev = self.consumed[self.k] = self.consumed[self.k] or torch.cuda.Event()
-                ev.record(self.side)
+    def _step(self, off):
+        stats = self.group.loss_grad(self.emb[self.k], self.labels[self.k], rows=self.bs, offset=off)
+        self.group.adam_step(lr=self.lr)
         return stats
-
-    accumulate = FrozenHeadTrainer.accumulate
-    finish = FrozenHeadTrainer.finish
 
     def close(self):
         """Joins the side stream and drops the group object; the heads stay."""
@@ -556,9 +547,8 @@ def transfer_learn(
     trainer, history = None, None
     for phase, lr in phases:
         if phase == "all":
-            from ..arch import BLOCKS
-            from ..embedding_trainer import DROP_CONNECT_RATE, EmbeddingTrainer
-            trainer = EmbeddingTrainer(blob, device=embedding.device)
+            from ..embedding_trainer import EmbeddingTrainer, TrainStepGraph, drop_connect_rates
+            trainer, rates = EmbeddingTrainer(blob, device=embedding.device), drop_connect_rates()
             head.reset_optimizer()
             graphed = None          # one hipGraph replay per step (single process; the DP phase keeps the launch-by-launch path)
         history = {"loss": [], "accuracy": [], "val_loss": [], "val_accuracy": []}
@@ -573,18 +563,13 @@ def transfer_learn(
                     seen += batch_size * world
                     continue
                 spec, labels = train_groups.take(1)
+                nb = spec.shape[0]
+                masks = {name: audio_dataset.rng.uniform(0, 1, nb) >= rate for name, rate in rates.items()}
                 if world == 1:
-                    nb = spec.shape[0]
-                    masks = {name: audio_dataset.rng.uniform(0, 1, nb) >= DROP_CONNECT_RATE * bi / len(BLOCKS)
-                             for bi, (name, cin, cout, k, s, e) in enumerate(BLOCKS) if s == 1 and cin == cout}
                     if graphed is None or graphed.B != nb:
-                        from ..embedding_trainer import TrainStepGraph
                         graphed = TrainStepGraph(trainer, head, nb, lr)
                     stats = graphed.run(spec, labels, masks)
                 else:
-                    nb = spec.shape[0]
-                    masks = {name: audio_dataset.rng.uniform(0, 1, nb) >= DROP_CONNECT_RATE * bi / len(BLOCKS)
-                             for bi, (name, cin, cout, k, s, e) in enumerate(BLOCKS) if s == 1 and cin == cout}
                     emb = trainer.forward_train(spec, masks)
                     stats = head.loss_grad(emb, labels)
                     trainer.backward(head.input_grad(nb), allreduce=world > 1)

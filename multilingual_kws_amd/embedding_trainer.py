@@ -14,6 +14,8 @@ device buffers in the weight blob's own order and Keras layouts, so the gradient
 contiguous RCCL calls, issued as soon as a range of the buffer is final (the dense layers -- 93 % of the bytes --
 finish first) so they overlap the rest of the backward sweep.
 
+The class sits on op_tape.OpTape (operator context, flat state, layer calls; shared with the DS-CNN trainer and the logits layer).
+
 Round 3: every cross-workgroup reduction of the operators is fixed-order (partials in a scratch arena this class owns), so a step
 is bit-reproducible; BatchNormalization's training forward is two launches instead of eight; the generic GEMM prefetches and
 splits long reductions by itself; and `TrainStepGraph` captures forward + loss + backward + Adam of one step in a hipGraph (the
@@ -26,9 +28,9 @@ import numpy as np
 
 from . import _lib, weights
 from .arch import BLOCKS
+from .op_tape import ACT_NONE, ACT_RELU, ACT_SELU, ACT_SIGMOID, ACT_SWISH, BN_EPS, BN_MOMENTUM, OpTape  # noqa: F401  (the constants' public home is here)
 
-BN_EPS, BN_MOMENTUM, DROP_CONNECT_RATE = 1e-3, 0.99, 0.2
-ACT_NONE, ACT_SWISH, ACT_RELU, ACT_SELU, ACT_SIGMOID = 0, 1, 2, 3, 4
+DROP_CONNECT_RATE = 0.2
 
 
 def _down(h, w, k):
@@ -36,39 +38,24 @@ def _down(h, w, k):
     return (h + pt + k // 2 - k) // 2 + 1, (w + pl + k // 2 - k) // 2 + 1, pt, pl
 
 
-class EmbeddingTrainer:
+class EmbeddingTrainer(OpTape):
     def __init__(self, weight_blob, device=None, scratch=None, scratch_side=None):
         """scratch / scratch_side: caller-provided arenas (contiguous one-dimensional float32 tensors on the device) for the fixed-order
         reductions of the caller's stream and of the weight-gradient stream; None allocates 16 Mi floats each, the second on first use."""
-        import torch
-        self.torch = torch
-        self.L = _lib.lib()
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         blob = np.ascontiguousarray(weight_blob, dtype=np.float32)
         if blob.shape[0] != weights.weight_count():
             raise ValueError(f"blob has {blob.shape[0]} floats, architecture needs {weights.weight_count()}")
-        self.tensors = {t["name"]: t for t in weights.manifest()}
-        self.params = torch.from_numpy(blob.copy()).to(self.device)
-        self.grads = torch.zeros_like(self.params)
-        self.m = torch.zeros_like(self.params)
-        self.v = torch.zeros_like(self.params)
+        # partial sums of the fixed-order reductions (include/mkws.h: mkws_op_set_scratch); 16 Mi floats cover every layer
+        OpTape.__init__(self, device, scratch, 16 << 20)
+        self.params = self._flat_state(blob.copy(), weights.manifest())        # (.d_step: Adam step index for the graph-replayed step)
         self.step_t = 0
         self.norm_mean = float(blob[self.tensors["normalization/mean"]["offset"]])
         self.norm_std = max(float(np.sqrt(blob[self.tensors["normalization/variance"]["offset"]])), 1e-7)
         self.tape = None
         self._pending = []
-        # host-side caches: the tape allocates the same sequence of buffers every step, and parameter / gradient views are
-        # fixed slices of the flat buffers -- re-creating either costs more host time than the small kernels take
-        self._views = {}
+        # host-side cache: the tape allocates the same sequence of buffers every step -- re-creating them costs more host time than the
+        # small kernels take (parameter / gradient pointers: OpTape.P / G)
         self._pool, self._pool_pos, self._pool_B = [], 0, None
-        self._stream = None
-        # partial sums of the fixed-order reductions (include/mkws.h: mkws_op_set_scratch); 16 Mi floats cover every layer
-        self._scratch = self._arena(scratch) if scratch is not None else torch.empty(16 << 20, dtype=torch.float32, device=self.device)
-        # the trainer's own operator context (arena + deferred-fold queue): independent of other trainers on this thread and of the
-        # thread it runs on; bound at the top of every public method (_bind_stream)
-        self._ctx = ctypes.c_void_p()
-        _lib.check(self.L.mkws_train_ctx_create(self._p(self._scratch), self._scratch.numel(), ctypes.byref(self._ctx)))
-        self.d_step = torch.zeros(1, dtype=torch.int32, device=self.device)        # Adam step index for the graph-replayed step
         # Weight gradients off the critical path: nothing in the backward sweep reads a dW before the optimizer (or the all-reduce), and at
         # batch 64 the sweep is a chain of small launches that leaves most of the chip idle.  The weight-gradient launches (dW GEMMs,
         # depthwise / squeeze-excite / stem weight gradients) go to a second stream with its own operator context (scratch arena + fold
@@ -84,31 +71,7 @@ class EmbeddingTrainer:
         self._scratch_side = self._arena(scratch_side) if scratch_side is not None else None
         self._ctx_side = ctypes.c_void_p()
 
-    def _arena(self, t):
-        torch = self.torch
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.dim() == 1 and t.is_contiguous() and t.numel() > 0):
-            raise ValueError(f"a scratch arena is a contiguous one-dimensional float32 tensor on {self.device}")
-        return t
-
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self.L.mkws_train_ctx_destroy(self._ctx)
-                self._ctx = None
-            if getattr(self, "_ctx_side", None):
-                self.L.mkws_train_ctx_destroy(self._ctx_side)
-                self._ctx_side = None
-        except Exception:
-            pass
-
-    # ---- plumbing -----------------------------------------------------------------------------------------------------
-    def _s(self):
-        return self._stream          # bound once per forward_train() / backward() / adam_step(): torch's current stream
-
-    def _bind_stream(self):
-        self._stream = _lib.current_stream_ptr()
-        _lib.check(self.L.mkws_train_ctx_bind(self._ctx))                                          # a thread-local pointer store
-
+    # ---- plumbing (self._stream: latched once per forward_train() / backward() / adam_step() by OpTape.bind) --------------
     _STREAM = object()          # placeholder for "the stream this call is issued on" in a queued operator call
 
     def _wgrad(self, op, *args):
@@ -116,7 +79,7 @@ class EmbeddingTrainer:
         block's buffers), except _STREAM.  _wgrad_go issues the queue: one fork per block of the sweep (or per `wgrad_fork_every` blocks)
         instead of one per launch keeps the event traffic small."""
         if not self.overlap_wgrad:
-            return _lib.check(op(*[self._s() if a is self._STREAM else a for a in args]))
+            return _lib.check(op(*[self._stream if a is self._STREAM else a for a in args]))
         self._wgrad_q.append((op, args))
 
     def _wgrad_go(self, force=True):
@@ -128,7 +91,7 @@ class EmbeddingTrainer:
             return
         self._wgrad_skips = 0
         q, self._wgrad_q = self._wgrad_q, []
-        self._on_side(lambda: [_lib.check(op(*[self._s() if a is self._STREAM else a for a in args])) for op, args in q])
+        self._on_side(lambda: [_lib.check(op(*[self._stream if a is self._STREAM else a for a in args])) for op, args in q])
 
     def _on_side(self, fn):
         torch = self.torch
@@ -139,9 +102,7 @@ class EmbeddingTrainer:
             # MKWS_TRAIN_SIDE_PRIORITY = -1 raises the SIDE stream instead (an A/B knob; it lost).
             prio = os.environ.get("MKWS_TRAIN_SIDE_PRIORITY")
             self._side = torch.cuda.Stream(device=self.device, priority=min(int(prio), 0) if prio is not None else 0)
-            if self._scratch_side is None:
-                self._scratch_side = torch.empty(16 << 20, dtype=torch.float32, device=self.device)
-            _lib.check(self.L.mkws_train_ctx_create(self._p(self._scratch_side), self._scratch_side.numel(), ctypes.byref(self._ctx_side)))
+            self._scratch_side, self._ctx_side = self._new_ctx(self._scratch_side, 16 << 20)
             self._side_ptr = ctypes.c_void_p(self._side.cuda_stream)
         _lib.check(self.L.mkws_op_stream_wait(self._side_ptr, self._stream))       # (a library call, not torch's wait_stream: TrainStepGraph's tape replays it)
         _lib.check(self.L.mkws_train_ctx_bind(self._ctx_side))
@@ -170,24 +131,6 @@ class EmbeddingTrainer:
     _wgrad_q = ()
     _wgrad_skips = 0
 
-    @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    def P(self, name):
-        v = self._views.get(("p", name))
-        if v is None:
-            t = self.tensors[name]
-            v = self._views[("p", name)] = self.params[t["offset"]:t["offset"] + t["count"]]
-        return v
-
-    def G(self, name):
-        v = self._views.get(("g", name))
-        if v is None:
-            t = self.tensors[name]
-            v = self._views[("g", name)] = self.grads[t["offset"]:t["offset"] + t["count"]]
-        return v
-
     def new(self, *shape):
         """Scratch / tape buffer.  Buffers are handed out from a pool in call order: one step's forward + backward makes the
         same sequence of requests as the previous one (same batch size), so after the first step nothing is allocated."""
@@ -203,76 +146,66 @@ class EmbeddingTrainer:
         return buf
 
     def gemm(self, A, B, C, M, N, K, lda, ldb, ldc, ta=0, tb=0, acc=0, ksplit=0):
+        self._gemm(self._p(A), self._p(B), self._p(C), M, N, K, lda, ldb, ldc, ta, tb, acc, ksplit)
+
+    def _gemm(self, pA, pB, pC, M, N, K, lda, ldb, ldc, ta=0, tb=0, acc=0, ksplit=0):
         # ksplit = 0: the library splits a long reduction over workgroups when the grid is small (fixed-order fold through the scratch)
-        _lib.check(self.L.mkws_op_gemm(self._p(A), self._p(B), self._p(C), M, N, K, lda, ldb, ldc, ta, tb, acc, ksplit, self._s()))
+        _lib.check(self.L.mkws_op_gemm(pA, pB, pC, M, N, K, lda, ldb, ldc, ta, tb, acc, ksplit, self._stream))
 
     def blob(self):
         """Current parameters (incl. updated BatchNorm moving statistics) as a host weight blob."""
         return self.params.cpu().numpy()
 
-    # ---- layers ---------------------------------------------------------------------------------------------------------
+    # ---- layers: buffers from the pool, the call itself is OpTape's, the tape record for backward() ------------------------
     def _bn_fwd(self, Z, M, C, prefix, act, res=None, row_scale=None, group=1):
         """Training-mode BN + activation; res / row_scale [M // group]: the residual branch A = row_scale * act(BN(Z)) + res in the same launch."""
         mean, var = self.new(C), self.new(C)
         A = self.new(M, C)
-        # batch statistics + moving-average update (Keras does it during the training-mode forward pass) + normalise / activate
-        _lib.check(self.L.mkws_op_bn_train_fwd_res(self._p(Z), M, C, self._p(self.P(prefix + "/gamma")), self._p(self.P(prefix + "/beta")), BN_EPS, act, BN_MOMENTUM,
-                                                   self._p(self.P(prefix + "/moving_mean")), self._p(self.P(prefix + "/moving_variance")), self._p(mean), self._p(var),
-                                                   self._p(A), self._p(res) if res is not None else None, self._p(row_scale) if row_scale is not None else None,
-                                                   group, self._s()))
+        self.bn_fwd(Z, M, C, prefix, act, mean, var, A, res, row_scale, group)
         return A, (Z, mean, var, M, C, prefix, act)
 
     def _bn_bwd(self, rec, dA, src="same", row_scale=None, bcast=None, bscale=0.0, group=1):
         """dLoss/dA -> dLoss/dZ in dA [M,C]; writes dgamma / dbeta.  The incoming gradient is src (default: dA itself; None: none)
         * row_scale[row // group] + bcast[row // group] * bscale, assembled inside the first launch."""
-        Z, mean, var, M, C, prefix, act = rec
-        if src == "same":
-            src = dA
-        _lib.check(self.L.mkws_op_bn_act_bwd_ex(self._p(Z), self._p(mean), self._p(var), self._p(self.P(prefix + "/gamma")), self._p(self.P(prefix + "/beta")), BN_EPS, act,
-                                                self._p(dA), self._p(src) if src is not None else None, self._p(row_scale) if row_scale is not None else None,
-                                                self._p(bcast) if bcast is not None else None, float(bscale), group,
-                                                self._p(self.G(prefix + "/gamma")), self._p(self.G(prefix + "/beta")), M, C, self._s()))
+        self.bn_bwd(*rec, dA, dA if src == "same" else src, row_scale, bcast, bscale, group)
         return dA
 
     def _conv_bn_fwd(self, X, M, K, N, wname, prefix, act, res=None, row_scale=None, group=1):
-        """1x1 convolution + training-mode BN (+ activation / residual branch) as one operator: the GEMM's epilogue leaves the BN's chunk
-        statistics whenever it can (mkws_op_conv_bn_fwd).  Returns (A, BN tape record) like _bn_fwd."""
+        """1x1 convolution + training-mode BN (+ activation / residual branch) as one operator (OpTape.conv_bn_fwd), or as a GEMM and a BN
+        (fuse_bn_stats bit 0 clear).  Returns (A, BN tape record) like _bn_fwd."""
         if not self.fuse_bn_stats & 1:
             return self._bn_fwd(self._conv_fwd(X, M, K, N, wname), M, N, prefix, act, res=res, row_scale=row_scale, group=group)
         Z, mean, var, A = self.new(M, N), self.new(N), self.new(N), self.new(M, N)
-        _lib.check(self.L.mkws_op_conv_bn_fwd(self._p(X), self._p(self.P(wname)), self._p(Z), M, N, K, self._p(self.P(prefix + "/gamma")),
-                                              self._p(self.P(prefix + "/beta")), BN_EPS, act, BN_MOMENTUM, self._p(self.P(prefix + "/moving_mean")),
-                                              self._p(self.P(prefix + "/moving_variance")), self._p(mean), self._p(var), self._p(A),
-                                              self._p(res) if res is not None else None, self._p(row_scale) if row_scale is not None else None, group, self._s()))
+        self.conv_bn_fwd(X, wname, Z, M, N, K, prefix, act, mean, var, A, res, row_scale, group)
         return A, (Z, mean, var, M, N, prefix, act)
 
     def _conv_fwd(self, X, M, K, N, wname):
         Z = self.new(M, N)
-        self.gemm(X, self.P(wname), Z, M, N, K, K, N, N)
+        self._gemm(self._p(X), self.P(wname), self._p(Z), M, N, K, K, N, N)
         return Z
 
     def _conv_bwd(self, X, dZ, M, K, N, wname, need_dx=True, add_into=None):
         """dW = X^T dZ (the long reduction over the rows is split by the library), dX = dZ W^T (+ add_into, in place: the shortcut's
         gradient of a residual block joins in the GEMM epilogue instead of a separate launch)."""
-        # every weight is used once per step: written, not accumulated (ksplit = 0: see gemm())
-        self._wgrad(self.L.mkws_op_gemm, self._p(X), self._p(dZ), self._p(self.G(wname)), K, N, M, K, N, N, 1, 0, 0, 0, self._STREAM)
+        # every weight is used once per step: written, not accumulated (ksplit = 0: see _gemm())
+        self._wgrad(self.L.mkws_op_gemm, self._p(X), self._p(dZ), self.G(wname), K, N, M, K, N, N, 1, 0, 0, 0, self._STREAM)
         if not need_dx:
             return None
         if add_into is not None:
-            self.gemm(dZ, self.P(wname), add_into, M, K, N, N, N, K, ta=0, tb=1, acc=1)
+            self._gemm(self._p(dZ), self.P(wname), self._p(add_into), M, K, N, N, N, K, ta=0, tb=1, acc=1)
             return add_into
         dX = self.new(M, K)
-        self.gemm(dZ, self.P(wname), dX, M, K, N, N, N, K, ta=0, tb=1)
+        self._gemm(self._p(dZ), self.P(wname), self._p(dX), M, K, N, N, N, K, ta=0, tb=1)
         return dX
 
     def _fc_fwd(self, X, M, K, N, prefix, act):
         Z, A = self.new(M, N), self.new(M, N)
-        _lib.check(self.L.mkws_op_dense_fwd(self._p(X), self._p(self.P(prefix + "/kernel")), self._p(self.P(prefix + "/bias")), act, self._p(Z), self._p(A), M, N, K, self._s()))
+        _lib.check(self.L.mkws_op_dense_fwd(self._p(X), self.P(prefix + "/kernel"), self.P(prefix + "/bias"), act, self._p(Z), self._p(A), M, N, K, self._stream))
         return A, (X, Z, M, K, N, prefix, act)
 
     def _fc_bwd(self, rec, dA, need_dx=True):
         X, Z, M, K, N, prefix, act = rec
-        _lib.check(self.L.mkws_op_bias_act_bwd(self._p(Z), self._p(self.P(prefix + "/bias")), act, self._p(dA), self._p(self.G(prefix + "/bias")), M, N, self._s()))
+        _lib.check(self.L.mkws_op_bias_act_bwd(self._p(Z), self.P(prefix + "/bias"), act, self._p(dA), self.G(prefix + "/bias"), M, N, self._stream))
         return self._conv_bwd(X, dA, M, K, N, prefix + "/kernel", need_dx)
 
     # ---- forward (training mode) ------------------------------------------------------------------------------------------
@@ -282,7 +215,7 @@ class EmbeddingTrainer:
         keep_scales: the same information as device tensors {block name: float32 [B] = kept / (1 - rate)} that the caller owns and
         refills between steps (what a graph-replayed step needs: no host-to-device traffic inside the step)."""
         torch = self.torch
-        self._bind_stream()
+        self.bind()
         spec = spec.to(self.device, dtype=torch.float32)
         if spec.dim() == 4:
             spec = spec[..., 0]
@@ -294,7 +227,7 @@ class EmbeddingTrainer:
         tape = {"spec": spec, "B": B, "blocks": []}
         H, W = 25, 20
         Z = self.new(B * H * W, 32)
-        _lib.check(self.L.mkws_op_stem_fwd(self._p(spec), self._p(self.P("stem_conv/kernel")), self.norm_mean, self.norm_std, self._p(Z), B, self._s()))
+        _lib.check(self.L.mkws_op_stem_fwd(self._p(spec), self.P("stem_conv/kernel"), self.norm_mean, self.norm_std, self._p(Z), B, self._stream))
         x, tape["stem_bn"] = self._bn_fwd(Z, B * H * W, 32, "stem_bn", ACT_SWISH)
         for bi, (name, cin, cout, k, s, e) in enumerate(BLOCKS):
             p = "block" + name
@@ -314,22 +247,19 @@ class EmbeddingTrainer:
             # depthwise conv + BN + swish: the conv launch leaves the BN chunk statistics (mkws_op_dwconv_bn_fwd)
             if self.fuse_bn_stats & (2 if k == 3 else 4):
                 Zd, dmean_, dvar_, Ad = self.new(Mout, ce), self.new(ce), self.new(ce), self.new(Mout, ce)
-                _lib.check(self.L.mkws_op_dwconv_bn_fwd(self._p(Ae), self._p(self.P(p + "_dwconv/depthwise_kernel")), self._p(Zd), B, H, W, ce, k, s, pt, pl, Ho, Wo,
-                                                        self._p(self.P(p + "_bn/gamma")), self._p(self.P(p + "_bn/beta")), BN_EPS, ACT_SWISH, BN_MOMENTUM,
-                                                        self._p(self.P(p + "_bn/moving_mean")), self._p(self.P(p + "_bn/moving_variance")), self._p(dmean_),
-                                                        self._p(dvar_), self._p(Ad), self._s()))
+                self.dwconv_bn_fwd(Ae, p + "_dwconv/depthwise_kernel", Zd, B, H, W, ce, k, s, pt, pl, Ho, Wo, p + "_bn", ACT_SWISH, dmean_, dvar_, Ad)
                 rec["dw_bn"] = (Zd, dmean_, dvar_, Mout, ce, p + "_bn", ACT_SWISH)
             else:
                 Zd = self.new(Mout, ce)
-                _lib.check(self.L.mkws_op_dwconv_fwd(self._p(Ae), self._p(self.P(p + "_dwconv/depthwise_kernel")), self._p(Zd), B, H, W, ce, k, s, pt, pl, Ho, Wo,
-                                                     self._s()))
+                _lib.check(self.L.mkws_op_dwconv_fwd(self._p(Ae), self.P(p + "_dwconv/depthwise_kernel"), self._p(Zd), B, H, W, ce, k, s, pt, pl, Ho, Wo,
+                                                     self._stream))
                 Ad, rec["dw_bn"] = self._bn_fwd(Zd, Mout, ce, p + "_bn", ACT_SWISH)
             # the squeeze-excite branch (pool, two 1x1 convolutions, excite multiply): two launches, a workgroup per (clip, channel slab)
             mean, Yr, R, Gt, As = self.new(B, ce), self.new(B, se), self.new(B, se), self.new(B, ce), self.new(Mout, ce)
             work = self.new(B, (ce + 127) // 128 * se)
-            _lib.check(self.L.mkws_op_se_fwd(self._p(Ad), self._p(self.P(p + "_se_reduce/kernel")), self._p(self.P(p + "_se_reduce/bias")),
-                                             self._p(self.P(p + "_se_expand/kernel")), self._p(self.P(p + "_se_expand/bias")),
-                                             self._p(mean), self._p(Yr), self._p(R), self._p(Gt), self._p(As), self._p(work), B, Ho * Wo, ce, se, self._s()))
+            _lib.check(self.L.mkws_op_se_fwd(self._p(Ad), self.P(p + "_se_reduce/kernel"), self.P(p + "_se_reduce/bias"),
+                                             self.P(p + "_se_expand/kernel"), self.P(p + "_se_expand/bias"),
+                                             self._p(mean), self._p(Yr), self._p(R), self._p(Gt), self._p(As), self._p(work), B, Ho * Wo, ce, se, self._stream))
             rec.update(Ad=Ad, Gt=Gt, As=As, se_mean=mean, se_Yr=Yr, se_R=R, se_work=work)
             rec["residual"] = (s == 1 and cin == cout)
             if rec["residual"]:
@@ -353,7 +283,7 @@ class EmbeddingTrainer:
         tape["top_in"], tape["HW"] = x, HW
         At, tape["top_bn"] = self._conv_bn_fwd(x, B * HW, 320, 1280, "top_conv/kernel", "top_bn", ACT_SWISH)
         gap = self.new(B, 1280)
-        _lib.check(self.L.mkws_op_pool_hw(self._p(At), self._p(gap), B, HW, 1280, self._s()))
+        _lib.check(self.L.mkws_op_pool_hw(self._p(At), self._p(gap), B, HW, 1280, self._stream))
         a, tape["dense"] = self._fc_fwd(gap, B, 1280, 2048, "dense", ACT_RELU)
         a, tape["dense_1"] = self._fc_fwd(a, B, 2048, 2048, "dense_1", ACT_RELU)
         emb, tape["dense_2"] = self._fc_fwd(a, B, 2048, 1024, "dense_2", ACT_SELU)
@@ -368,10 +298,10 @@ class EmbeddingTrainer:
         tape = self.tape
         if tape is None:
             raise RuntimeError("backward() needs a forward_train() first")
-        self._bind_stream()
+        self.bind()
         # second stages of the gradient reductions wait in a queue and run a batch at a time (mkws_op_fold_defer): nobody reads a weight
         # gradient before the all-reduce / the optimizer
-        _lib.check(self.L.mkws_op_fold_defer(1, self._s()))
+        _lib.check(self.L.mkws_op_fold_defer(1, self._stream))
         done = False
         try:
             self._backward_sweep(tape, d_emb, allreduce)
@@ -379,7 +309,7 @@ class EmbeddingTrainer:
         finally:
             if not done:        # an operator raised mid-sweep: do not leave the contexts deferring (the queues are dropped by the next fold_defer(1))
                 self.L.mkws_train_ctx_bind(self._ctx)
-                self.L.mkws_op_fold_defer(0, self._s())
+                self.L.mkws_op_fold_defer(0, self._stream)
                 try:
                     self._join_wgrad()
                 except Exception:
@@ -398,7 +328,7 @@ class EmbeddingTrainer:
         ones = self._views.get(("ones", B))
         if ones is None:
             ones = self._views[("ones", B)] = torch.ones(B, dtype=torch.float32, device=self.device)
-        _lib.check(self.L.mkws_op_row_scale_add(self._p(src), self._p(ones), None, self._p(d), B, src.shape[1], self._s()))
+        _lib.check(self.L.mkws_op_row_scale_add(self._p(src), self._p(ones), None, self._p(d), B, src.shape[1], self._stream))
         d = self._fc_bwd(tape["dense_2"], d)
         self._wgrad_go()
         d = self._fc_bwd(tape["dense_1"], d)
@@ -427,31 +357,31 @@ class EmbeddingTrainer:
             # squeeze-excite backward: two launches for dAd / dmean / the pre-activation gradients + one for the four parameter gradients
             dAd, dmean, dYg, dYr = self.new(Mout, ce), self.new(B, ce), self.new(B, ce), self.new(B, se)
             _lib.check(self.L.mkws_op_se_bwd_fused(self._p(rec["Ad"]), self._p(rec["Gt"]), self._p(dAs), self._p(rec["se_mean"]), self._p(rec["se_Yr"]),
-                                                   self._p(rec["se_R"]), self._p(self.P(p + "_se_reduce/kernel")), self._p(self.P(p + "_se_expand/kernel")),
+                                                   self._p(rec["se_R"]), self.P(p + "_se_reduce/kernel"), self.P(p + "_se_expand/kernel"),
                                                    self._p(dAd), self._p(dmean), self._p(dYg), self._p(dYr), None, None, None, None,
-                                                   self._p(rec["se_work"]), B, Ho * Wo, ce, se, self._s()))
+                                                   self._p(rec["se_work"]), B, Ho * Wo, ce, se, self._stream))
             self._wgrad(self.L.mkws_op_se_wgrad, self._p(rec["se_mean"]), self._p(rec["se_R"]), self._p(dYg), self._p(dYr),
-                        self._p(self.G(p + "_se_reduce/kernel")), self._p(self.G(p + "_se_reduce/bias")),
-                        self._p(self.G(p + "_se_expand/kernel")), self._p(self.G(p + "_se_expand/bias")), B, ce, se, self._STREAM)
+                        self.G(p + "_se_reduce/kernel"), self.G(p + "_se_reduce/bias"),
+                        self.G(p + "_se_expand/kernel"), self.G(p + "_se_expand/bias"), B, ce, se, self._STREAM)
             dZd = self._bn_bwd(rec["dw_bn"], dAd, bcast=dmean, bscale=1.0 / (Ho * Wo), group=Ho * Wo)     # + the squeeze's gradient, spread over the pixels
             dAe = self.new(Min, ce)
-            self._wgrad(self.L.mkws_op_dwconv_bwd, self._p(rec["Ae"]), self._p(self.P(p + "_dwconv/depthwise_kernel")), self._p(dZd), None,
-                        self._p(self.G(p + "_dwconv/depthwise_kernel")), B, H, W, ce, k, s, rec["pt"], rec["pl"], Ho, Wo, self._STREAM)
-            _lib.check(self.L.mkws_op_dwconv_bwd(self._p(rec["Ae"]), self._p(self.P(p + "_dwconv/depthwise_kernel")), self._p(dZd), self._p(dAe),
-                                                 None, B, H, W, ce, k, s, rec["pt"], rec["pl"], Ho, Wo, self._s()))
+            self._wgrad(self.L.mkws_op_dwconv_bwd, self._p(rec["Ae"]), self.P(p + "_dwconv/depthwise_kernel"), self._p(dZd), None,
+                        self.G(p + "_dwconv/depthwise_kernel"), B, H, W, ce, k, s, rec["pt"], rec["pl"], Ho, Wo, self._STREAM)
+            _lib.check(self.L.mkws_op_dwconv_bwd(self._p(rec["Ae"]), self.P(p + "_dwconv/depthwise_kernel"), self._p(dZd), self._p(dAe),
+                                                 None, B, H, W, ce, k, s, rec["pt"], rec["pl"], Ho, Wo, self._stream))
             if "expand_bn" in rec:
                 dZe = self._bn_bwd(rec["expand_bn"], dAe)
                 d_in = self._conv_bwd(rec["inp"], dZe, Min, cin, ce, p + "_expand_conv/kernel", add_into=d_out if rec["residual"] else None)
             else:
                 d_in = dAe
                 if rec["residual"]:
-                    _lib.check(self.L.mkws_op_axpy(self._p(d_in), self._p(d_out), 1.0, d_in.numel(), self._s()))
+                    _lib.check(self.L.mkws_op_axpy(self._p(d_in), self._p(d_out), 1.0, d_in.numel(), self._stream))
             d = d_in
             self._wgrad_go(force=False)
         dZ0 = self._bn_bwd(tape["stem_bn"], d)
-        self._wgrad(self.L.mkws_op_stem_bwd_weight, self._p(tape["spec"]), self._p(dZ0), self.norm_mean, self.norm_std, self._p(self.G("stem_conv/kernel")), B,
+        self._wgrad(self.L.mkws_op_stem_bwd_weight, self._p(tape["spec"]), self._p(dZ0), self.norm_mean, self.norm_std, self.G("stem_conv/kernel"), B,
                     self._STREAM)
-        _lib.check(self.L.mkws_op_fold_defer(0, self._s()))           # flush: every gradient is final from here on
+        _lib.check(self.L.mkws_op_fold_defer(0, self._stream))           # flush: every gradient is final from here on
         self._join_wgrad()
         if allreduce:
             self._allreduce_range(0, self.tensors["top_conv/kernel"]["offset"])
@@ -468,26 +398,20 @@ class EmbeddingTrainer:
             _lib.check(self.L.mkws_op_fold_flush(self._side_ptr))
             _lib.check(self.L.mkws_train_ctx_bind(self._ctx))
             _lib.check(self.L.mkws_op_stream_wait(self._stream, self._side_ptr))
-        _lib.check(self.L.mkws_op_fold_flush(self._s()))
+        _lib.check(self.L.mkws_op_fold_flush(self._stream))
         if dist.is_available() and dist.is_initialized():
             self._pending.append(dist.all_reduce(self.grads[lo:hi], op=dist.ReduceOp.SUM, async_op=True))
 
     def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
         """Keras Adam over the whole blob (moving statistics / Normalization constants have zero gradient and stay put)."""
         self.step_t += 1
-        self._bind_stream()
-        _lib.check(self.L.mkws_op_adam(self._p(self.params), self._p(self.grads), self._p(self.m), self._p(self.v), self.params.shape[0], lr, beta1, beta2, eps,
-                                       self.step_t, grad_scale, self._s()))
+        self.bind()
+        self._adam(lr, beta1, beta2, eps, self.step_t, grad_scale)
 
     def adam_step_dev(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
         """The same update with the step index read from self.d_step on the device (see TrainStepGraph)."""
-        self._bind_stream()
-        _lib.check(self.L.mkws_op_adam_dev(self._p(self.params), self._p(self.grads), self._p(self.m), self._p(self.v), self.params.shape[0], lr, beta1, beta2, eps,
-                                           self._p(self.d_step), grad_scale, self._s()))
-
-    def named_grads(self):
-        g = self.grads.cpu().numpy()
-        return {n: g[t["offset"]:t["offset"] + t["count"]].reshape(t["shape"]) for n, t in self.tensors.items()}
+        self.bind()
+        self._adam_dev(lr, beta1, beta2, eps, grad_scale)
 
 
 def drop_connect_rates():
@@ -544,31 +468,22 @@ class TrainStepGraph:
         if mode == "eager":
             return
         # warm-up: fills the trainer's buffer pool for this batch size and every lazily created view, on state that is restored
-        # afterwards (parameters, moving statistics, Adam moments, step counters)
-        snap = [t.clone() for t in (trainer.params, trainer.m, trainer.v, trainer.d_step)]
-        hstate, hstep = head.state_view().clone(), head.step_t          # parameters AND Adam moments of the head (set_params would zero m / v)
+        # afterwards (parameters, moving statistics, Adam moments, step counters; parameters AND Adam moments of the head: set_params
+        # would zero m / v)
+        state, hstep = (trainer.params, trainer.m, trainer.v, trainer.d_step, head.state_view()), head.step_t
 
-        def restore():
-            torch.cuda.synchronize(dev)
-            for t, c in zip((trainer.params, trainer.m, trainer.v, trainer.d_step), snap):
-                t.copy_(c)
-            head.state_view().copy_(hstate)
+        def restore_host():
             head.step_t = hstep
         if mode == "hipgraph":
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                self._body(overlap=False)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            restore()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.stats = self._body(overlap=False)
-            self.graph = g
+            self.graph, self.stats = trainer.capture_step(lambda: self._body(overlap=False), state, restore_host)
             return
+        snap = [t.clone() for t in state]
         self._body()
         self._record()
-        restore()
+        torch.cuda.synchronize(dev)
+        for t, c in zip(state, snap):
+            t.copy_(c)
+        restore_host()
 
     def _record(self):
         """Log one step's library calls on the current stream (the pool buffers, views and streams they name stay put from here on)."""

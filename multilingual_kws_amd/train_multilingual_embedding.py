@@ -9,7 +9,7 @@ basename + ".{epoch:03d}-{val_accuracy:.4f}", monitor="val_accuracy", mode="max"
 
 Everything numerical runs in the HIP operators of include/mkws.h: the embedding in TRAINING mode (batch-statistics BatchNorm with
 moving-average updates, drop-connect: multilingual_kws_amd/embedding_trainer.py), the logits layer as `mkws_op_dense_fwd` +
-`mkws_op_softmax_ce` + two `mkws_op_gemm` calls, Keras Adam over both; validation runs the inference kernels on the current weights.
+`mkws_op_softmax_ce` + two `mkws_op_gemm` calls (both on op_tape.OpTape), Keras Adam over both; validation runs the inference kernels on the current weights.
 Under torch.distributed (one process per GPU) every rank trains on its own shard of the files and the gradients are all-reduced
 (the embedding's in three overlapped ranges, the classifier's in one more call).
 
@@ -17,7 +17,6 @@ This is the tail of SURVEY.md section 8 row f4; the dataset preparation around i
 bookkeeping) stays out of scope.
 """
 import csv
-import ctypes
 import json
 import os
 import pickle
@@ -27,6 +26,7 @@ import numpy as np
 from . import _lib, parallel, weights
 from .embedding_model import EmbeddingModel
 from .embedding_trainer import ACT_NONE, EmbeddingTrainer, drop_connect_rates
+from .op_tape import OpTape
 
 
 def checkpoint_name(basename, epoch, val_accuracy):
@@ -34,55 +34,35 @@ def checkpoint_name(basename, epoch, val_accuracy):
     return f"{basename}.{epoch:03d}-{val_accuracy:.4f}"
 
 
-class LogitsLayer:
+class LogitsLayer(OpTape):
     """Dense(num_labels) on the 1024-D embedding (Keras defaults: glorot_uniform kernel, zero bias; no activation: the loss takes
-    logits).  Parameters | gradients | Adam moments are flat device buffers  W[1024, N] | b[N]."""
+    logits).  Parameters | gradients | Adam moments are flat device buffers  W[1024, N] | b[N]  on op_tape.OpTape, which also holds the
+    layer's own operator context (a 4 Mi float arena for the fixed-order reductions of the operators below)."""
 
     def __init__(self, num_labels, in_dim=1024, device=None, seed=None, params=None):
-        import torch
-        self.torch, self.L = torch, _lib.lib()
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.in_dim, self.n = int(in_dim), int(num_labels)
         if params is None:
             rng = np.random.default_rng(seed)
             lim = np.sqrt(6.0 / (self.in_dim + self.n))
             params = np.concatenate([rng.uniform(-lim, lim, self.in_dim * self.n), np.zeros(self.n)]).astype(np.float32)
-        self.params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(self.device)
-        if self.params.numel() != self.in_dim * self.n + self.n:
-            raise ValueError(f"logits layer needs {self.in_dim * self.n + self.n} parameters, got {self.params.numel()}")
-        self.grads, self.m, self.v = (torch.zeros_like(self.params) for _ in range(3))
-        self.W, self.b = self.params[:self.in_dim * self.n], self.params[self.in_dim * self.n:]
-        self.dW, self.db = self.grads[:self.in_dim * self.n], self.grads[self.in_dim * self.n:]
-        self._stats = torch.zeros(2, dtype=torch.float32, device=self.device)
-        # the layer's own operator context (arena for the fixed-order reductions of the operators below; include/mkws.h, mkws_train_ctx)
-        self._scratch = torch.empty(4 << 20, dtype=torch.float32, device=self.device)
-        self._ctx = ctypes.c_void_p()
-        _lib.check(self.L.mkws_train_ctx_create(self._p(self._scratch), self._scratch.numel(), ctypes.byref(self._ctx)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self.L.mkws_train_ctx_destroy(self._ctx)
-                self._ctx = None
-        except Exception:
-            pass
-
-    def _bind(self):
-        _lib.check(self.L.mkws_train_ctx_bind(self._ctx))
-
-    @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        params, nw = np.ascontiguousarray(params, dtype=np.float32), self.in_dim * self.n
+        if params.size != nw + self.n:
+            raise ValueError(f"logits layer needs {nw + self.n} parameters, got {params.size}")
+        OpTape.__init__(self, device, None, 4 << 20)
+        self.params = self._flat_state(params, [dict(name="logits/kernel", shape=[self.in_dim, self.n], offset=0, count=nw),
+                                                dict(name="logits/bias", shape=[self.n], offset=nw, count=self.n)])
+        self.W, self.b = self.view("logits/kernel"), self.view("logits/bias")
+        self.dW, self.db = self.view("logits/kernel", self.grads), self.view("logits/bias", self.grads)
+        self._stats = self.torch.zeros(2, dtype=self.torch.float32, device=self.device)
 
     def forward(self, emb):
         """emb CUDA [B, in] -> logits CUDA [B, N]."""
-        torch = self.torch
-        emb = emb.contiguous()
+        torch, emb = self.torch, emb.contiguous()
         B = emb.shape[0]
-        self._bind()
+        self.bind()
         Z, A = torch.empty((B, self.n), device=self.device), torch.empty((B, self.n), device=self.device)
-        _lib.check(self.L.mkws_op_dense_fwd(self._p(emb), self._p(self.W), self._p(self.b), ACT_NONE, self._p(Z), self._p(A), B, self.n, self.in_dim,
-                                            _lib.current_stream_ptr()))
+        _lib.check(self.L.mkws_op_dense_fwd(self._p(emb), self.P("logits/kernel"), self.P("logits/bias"), ACT_NONE, self._p(Z), self._p(A), B, self.n, self.in_dim,
+                                            self._stream))
         return A
 
     def loss_grad(self, emb, labels):
@@ -91,22 +71,14 @@ class LogitsLayer:
         torch = self.torch
         emb = emb.contiguous()
         B = emb.shape[0]
-        s = _lib.current_stream_ptr()
-        logits = self.forward(emb)
-        rowstat = torch.empty((B, 2), device=self.device)
-        labels = labels.to(torch.int32).contiguous()
-        _lib.check(self.L.mkws_op_softmax_ce(self._p(logits), self._p(labels), B, self.n, self._p(rowstat), self._p(self._stats), s))
-        d = logits                                                    # now d(mean loss)/d(logits)
-        # db = column sums of d (bias_act_bwd with the identity activation leaves d untouched), dW = emb^T d, d_emb = d W^T
-        _lib.check(self.L.mkws_op_bias_act_bwd(self._p(d), self._p(self.b), ACT_NONE, self._p(d), self._p(self.db), B, self.n, s))
-        _lib.check(self.L.mkws_op_gemm(self._p(emb), self._p(d), self._p(self.dW), self.in_dim, self.n, B, self.in_dim, self.n, self.n, 1, 0, 0, 0, s))
-        d_emb = torch.empty((B, self.in_dim), device=self.device)
-        _lib.check(self.L.mkws_op_gemm(self._p(d), self._p(self.W), self._p(d_emb), B, self.in_dim, self.n, self.n, self.n, self.in_dim, 0, 1, 0, 0, s))
+        logits = self.forward(emb)                                    # becomes d(mean loss)/d(logits)
+        rowstat, d_emb = torch.empty((B, 2), device=self.device), torch.empty((B, self.in_dim), device=self.device)
+        self.dense_ce_bwd(emb, logits, logits, labels.to(torch.int32).contiguous(), B, self.in_dim, self.n, "logits", rowstat, self._stats, d_emb)
         return self._stats, d_emb
 
     def adam_step(self, lr, step_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
-        _lib.check(self.L.mkws_op_adam(self._p(self.params), self._p(self.grads), self._p(self.m), self._p(self.v), self.params.numel(), lr, beta1, beta2, eps,
-                                       int(step_t), grad_scale, _lib.current_stream_ptr()))
+        self._stream = _lib.current_stream_ptr()
+        self._adam(lr, beta1, beta2, eps, int(step_t), grad_scale)
 
 
 class EmbeddingClassifier:
