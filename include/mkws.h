@@ -1004,6 +1004,48 @@ int mkws_svc_score(const float* d_x, int n_rows, int dim, const int32_t* d_train
                    const int32_t* d_rows, const int32_t* d_true, const int32_t* d_offsets, int total, int max_eval, int32_t* d_pred,
                    int32_t* d_correct, float* d_decision, void* stream);
 
+/* SVC(probability=True), given the folds (multilingual_kws_amd/svc.py: cv_folds, cv_decision_host, platt_host, couple_host).  The same
+ * conventions as the four calls above. */
+#define MKWS_SVC_MAX_FOLDS 16
+
+/* The cross-validated decision values, on the Gram matrices of mkws_svc_kernel and with the SMO of mkws_svc_fit, one workgroup per
+ * (problem, pair, fold): d_folds int32 [list entries] in [0, n_folds), n_folds in [2, MKWS_SVC_MAX_FOLDS].  d_cv_decision float32
+ * [list entries, n_classes - 1], laid out as d_coef: entry t against its m-th other class holds f_ij(x_t) (positive means the lower
+ * class i) of the pair's machine trained on the pair's entries of the other folds; where those hold no entry of either class 0, only
+ * class i's +1, only class j's -1 (libsvm's svm_binary_svc_probability); 0 where the other class is absent from the problem.  d_info
+ * (from mkws_svc_prepare) is read only.  d_cv_info int32 [n_problems, 4], zeroed by the call itself = {status, sub-fits solved,
+ * sub-fits cut at max_iter, the largest iteration count of a sub-fit}; status 2 = the problem's d_info status is not 0, or one of its
+ * fold values is outside [0, n_folds): nothing is written to d_cv_decision for it. */
+int mkws_svc_fit_cv(const int32_t* d_labels, const int32_t* d_offsets, const int32_t* d_folds, int n_folds, int n_problems, int n_classes,
+                    int max_rows, const double* d_C, double tol, int max_iter, const float* d_gram, size_t gram_stride,
+                    const int32_t* d_info, float* d_cv_decision, int32_t* d_cv_info, void* stream);
+
+/* Platt's sigmoids, one wave per (problem, pair): (A, B) minimising sum t z + log(1 + exp(-z)), z = A f + B, over the pair's entries of
+ * d_cv_decision (class i is +1; targets (N+ + 1) / (N+ + 2) and 1 / (N- + 2)), by Newton steps from (0, log((N- + 1) / (N+ + 1))) with
+ * a ridge of 1e-12, at most 100 iterations of at most 10 halvings, in float64, until |gradient|_inf < eps.  d_probA / d_probB double
+ * [n_problems, n_classes (n_classes - 1) / 2], both 0 for a pair with an absent class; d_present (optional, may be NULL) int32
+ * [n_problems]: bit k set where class k has an entry.  d_info / d_cv_info (optional, may be NULL): a problem whose first word in
+ * either is not 0 is skipped and nothing is written for it; so is one of more than max_rows entries. */
+int mkws_svc_platt(const int32_t* d_labels, const int32_t* d_offsets, int n_problems, int n_classes, int max_rows, const float* d_cv_decision,
+                   const int32_t* d_info, const int32_t* d_cv_info, double eps, double* d_probA, double* d_probB, int32_t* d_present,
+                   void* stream);
+
+/* Pairwise coupling, a thread per evaluation entry (its problem by bisection of d_offsets): d_decision float32 [total, pairs] as
+ * mkws_svc_score writes it; r_ij = 1 / (1 + exp(A_ij f_ij + B_ij)) clipped to [1e-7, 1 - 1e-7] over the classes of d_present[p];
+ * p = argmin sum_i sum_{j != i} (r_ji p_i - r_ij p_j)^2 with sum p = 1 (Wu, Lin and Weng 2004, method 2), solved directly in float64.
+ * d_probs float32 [total, n_classes], 0 for an absent class; d_pred = its first argmax; d_correct int32 [n_problems] = entries with
+ * d_pred == d_true, zeroed by the call itself (integer adds).  An entry outside every list, one with a NaN decision value and one whose
+ * problem has fewer than two present classes keep NaN probabilities and d_pred = -1. */
+int mkws_svc_couple(const float* d_decision, const int32_t* d_true, const int32_t* d_offsets, int n_problems, int n_classes, int total,
+                    const double* d_probA, const double* d_probB, const int32_t* d_present, float* d_probs, int32_t* d_pred,
+                    int32_t* d_correct, void* stream);
+
+/* The soft vote of two classifiers: d_pred int32 [total] = the first argmax over the classes of 0.5f * (a + b) in float32 for two
+ * probability arrays float32 [total, n_classes]; d_correct as above; d_mean (optional, may be NULL) float32 [total, n_classes] = that
+ * mean.  An entry outside every list or with a NaN in either row gets d_pred = -1 and is not counted. */
+int mkws_soft_vote(const float* d_probs_a, const float* d_probs_b, const int32_t* d_true, const int32_t* d_offsets, int n_problems,
+                   int n_classes, int total, int32_t* d_pred, int32_t* d_correct, float* d_mean, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training-batch assembly.  Replaces the per-clip tf.data map of AudioDataset.augment /
  * random_timeshift / random_background_sample / add_background

@@ -134,6 +134,10 @@ SYMBOLS = [
     ("mkws_svc_kernel", _I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     ("mkws_svc_fit", _I, [_P, _P, _I, _I, _I, _P, ctypes.c_double, _I, _P, _SZ, _P, _P, _P, _P, _P]),
     ("mkws_svc_score", _I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    ("mkws_svc_fit_cv", _I, [_P, _P, _P, _I, _I, _I, _I, _P, ctypes.c_double, _I, _P, _SZ, _P, _P, _P, _P]),
+    ("mkws_svc_platt", _I, [_P, _P, _I, _I, _I, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P]),
+    ("mkws_svc_couple", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    ("mkws_soft_vote", _I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     ("mkws_dscnn_param_count", _SZ, [_I]),
     ("mkws_dscnn_weight_manifest", _I, [_I, ctypes.c_char_p, _SZ]),
     ("mkws_dscnn_create", _I, [_P, _SZ, _I, _I, ctypes.POINTER(_P)]),

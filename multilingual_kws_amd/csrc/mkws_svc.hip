@@ -678,6 +678,588 @@ __global__ __launch_bounds__(kTileThreads) void svc_score_kernel(ScoreArgs a) {
   if (arg == a.truth[(size_t)e0 + idx]) atomicAdd(a.correct + p, 1);  // an integer count
 }
 
+// ------------------------------------------------------------------------------------------------ probability=True: cross-validated fit
+
+// pair q = (ci, cj) in the order (0,1), (0,2), ...
+__device__ inline void pair_of(int q, int K, int& ci, int& cj) {
+  int rest = q;
+  ci = 0;
+  for (int k = 0; k < kMaxK && rest >= K - 1 - ci; ++k) {
+    rest -= K - 1 - ci;
+    ++ci;
+  }
+  cj = ci + 1 + rest;
+}
+
+struct FitCvArgs {
+  const int32_t* labels;
+  const int32_t* offsets;
+  const int32_t* folds;
+  const double* C;
+  const float* gram;
+  size_t gram_stride;
+  const int32_t* info;
+  float* cv_decision;
+  int32_t* cv_info;
+  int K, F, max_rows, max_iter;
+  double tol;
+};
+
+// svc_fit_kernel's SMO for one (problem, pair, fold): the pair's entries of that fold are held out by the box [0, 0], which libsvm's
+// selection rules never pick, so the sub-matrix is not compacted and the float64 gradient the loop maintains for EVERY entry of the
+// pair is the held-out decision value: f(x_t) = y_t (G_t + 1) - rho.  Nothing but those values is written.  The same LDS as the
+// fit: the held-out flags take the list of class j's entries once that has been appended to class i's.
+__global__ __launch_bounds__(kFitThreads) void svc_fit_cv_kernel(FitCvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char s_raw[];
+  double* s_G = reinterpret_cast<double*>(s_raw);
+  double* s_alpha = s_G + kMaxRows;
+  int32_t* s_idx = reinterpret_cast<int32_t*>(s_alpha + kMaxRows);
+  int32_t* s_idxJ = s_idx + kMaxRows;
+  float* s_Kd = reinterpret_cast<float*>(s_idxJ + kMaxRows);
+  float* s_K = s_Kd + kMaxRows;
+  __shared__ double s_exv[kFitWaves], s_exm[kFitWaves], s_exo[kFitWaves], s_red[4][kFitWaves];
+  __shared__ int s_exi[kFitWaves], s_exj[kFitWaves], s_cnt[2], s_act[3];
+
+  const int K = a.K, F = a.F, npairs = K * (K - 1) / 2;
+  const int p = blockIdx.x / (npairs * F), q = (blockIdx.x / F) % npairs, fold = blockIdx.x % F;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int32_t* __restrict__ cinfo = a.cv_info + (size_t)p * 4;
+  const bool first = q == 0 && fold == 0;
+  const int begin = a.offsets[p];
+  const int n = a.offsets[p + 1] - begin;
+  if (a.info[(size_t)p * 4] != 0 || n < 1 || n > a.max_rows || n > kMaxRows) {      // refused by mkws_svc_prepare
+    if (first && tid == 0) cinfo[0] = 2;
+    return;
+  }
+  const int32_t* __restrict__ lab = a.labels + begin;
+  const int32_t* __restrict__ fo = a.folds + begin;
+  int bad = 0;
+  for (int t = tid; t < n; t += kFitThreads) bad |= (unsigned)fo[t] >= (unsigned)F;
+  if (__syncthreads_or(bad)) {                                        // every workgroup of the problem sees it: nothing else is written
+    if (first && tid == 0) cinfo[0] = 2;
+    return;
+  }
+  int ci, cj;
+  pair_of(q, K, ci, cj);
+
+  if (wave < 2) {
+    const int cls = wave == 0 ? ci : cj;
+    int32_t* dst = wave == 0 ? s_idx : s_idxJ;
+    int cnt = 0;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+      const int t = c0 + lane;
+      const bool is = t < n && lab[t] == cls;
+      const unsigned long long mask = __ballot(is);
+      if (is) dst[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = t;
+      cnt += __popcll(mask);
+    }
+    if (lane == 0) s_cnt[wave] = cnt;
+  }
+  if (tid < 3) s_act[tid] = 0;
+  __syncthreads();
+  const int mi = s_cnt[0], mj = s_cnt[1], m = mi + mj;
+  for (int t = tid; t < mj; t += kFitThreads) s_idx[mi + t] = s_idxJ[t];
+  __syncthreads();
+  int32_t* s_out = s_idxJ;                                            // 1 = held out
+  {
+    int ni = 0, nj = 0, no = 0;                                       // training entries of either class, held-out entries
+    for (int t = tid; t < m; t += kFitThreads) {
+      const int out = fo[s_idx[t]] == fold;
+      s_out[t] = out;
+      no += out;
+      if (!out) (t < mi ? ni : nj) += 1;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+      ni += __shfl_xor(ni, s, 64);
+      nj += __shfl_xor(nj, s, 64);
+      no += __shfl_xor(no, s, 64);
+    }
+    if (lane == 0) {                                                  // (integer counts in LDS)
+      atomicAdd(&s_act[0], ni);
+      atomicAdd(&s_act[1], nj);
+      atomicAdd(&s_act[2], no);
+    }
+  }
+  __syncthreads();
+  const int act_i = s_act[0], act_j = s_act[1];
+  if (s_act[2] == 0) return;                                          // the fold holds no entry of the pair
+  float* __restrict__ dec = a.cv_decision + (size_t)begin * (K - 1);
+  auto slot = [&](int t) -> size_t { return (size_t)s_idx[t] * (K - 1) + (t < mi ? cj - 1 : ci); };
+  if (act_i == 0 || act_j == 0) {
+    // a class absent from the problem: 0; libsvm's svm_binary_svc_probability otherwise: 0 without any training entry, +1 with class i's
+    // alone, -1 with class j's alone
+    const float v = (mi == 0 || mj == 0 || act_i == act_j) ? 0.0f : act_i ? 1.0f : -1.0f;
+    for (int t = tid; t < m; t += kFitThreads)
+      if (s_out[t]) dec[slot(t)] = v;
+    return;
+  }
+  const float* __restrict__ gram = a.gram + (size_t)p * a.gram_stride;
+  const bool cached = m <= kCacheRows;
+  if (cached)
+    for (int e = tid; e < m * m; e += kFitThreads) s_K[e] = gram[(size_t)s_idx[e / m] * n + s_idx[e % m]];
+  for (int t = tid; t < m; t += kFitThreads) {
+    s_Kd[t] = gram[(size_t)s_idx[t] * n + s_idx[t]];
+    s_G[t] = -1.0;
+    s_alpha[t] = 0.0;
+  }
+  __syncthreads();
+  auto kval = [&](int r, int t) -> double { return (double)(cached ? s_K[r * m + t] : gram[(size_t)s_idx[r] * n + s_idx[t]]); };
+  const double C = a.C[p];
+  const double inf = __builtin_inf();
+
+  int it = 0, cut = 0;
+  for (;; ++it) {
+    double bv = -inf, mn = inf;
+    int bi = -1;
+    for (int t = tid; t < m; t += kFitThreads) {
+      const bool pos = t < mi;
+      const double Ct = s_out[t] ? 0.0 : C;
+      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
+      const bool up = pos ? al < Ct : al > 0.0, low = pos ? al > 0.0 : al < Ct;
+      if (up && v >= bv) {
+        bv = v;
+        bi = t;
+      }
+      if (low) mn = fmin(mn, v);
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+      const double ov = __shfl_xor(bv, s, 64);
+      const int oi = __shfl_xor(bi, s, 64);
+      if (ov > bv || (ov == bv && oi > bi)) {
+        bv = ov;
+        bi = oi;
+      }
+      mn = fmin(mn, __shfl_xor(mn, s, 64));
+    }
+    if (lane == 0) {
+      s_exv[wave] = bv;
+      s_exi[wave] = bi;
+      s_exm[wave] = mn;
+    }
+    __syncthreads();
+    bv = s_exv[0], bi = s_exi[0], mn = s_exm[0];
+#pragma unroll
+    for (int w = 1; w < kFitWaves; ++w) {
+      if (s_exv[w] > bv || (s_exv[w] == bv && s_exi[w] > bi)) {
+        bv = s_exv[w];
+        bi = s_exi[w];
+      }
+      mn = fmin(mn, s_exm[w]);
+    }
+    const int i = bi;
+    const double gmax = bv;
+    if (i < 0 || !(gmax - mn >= a.tol)) break;
+    if (it >= a.max_iter) {
+      cut = 1;
+      break;
+    }
+    const double kdi = (double)s_Kd[i];
+    double bo = inf;
+    int bj = -1;
+    for (int t = tid; t < m; t += kFitThreads) {
+      const bool pos = t < mi;
+      const double Ct = s_out[t] ? 0.0 : C;
+      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
+      const bool low = pos ? al > 0.0 : al < Ct;
+      const double gd = gmax - v;
+      if (low && gd > 0.0) {
+        double quad = kdi + (double)s_Kd[t] - 2.0 * kval(i, t);
+        if (!(quad > 0.0)) quad = kTau;
+        const double o = -(gd * gd) / quad;
+        if (o <= bo) {
+          bo = o;
+          bj = t;
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+      const double oo = __shfl_xor(bo, s, 64);
+      const int oj = __shfl_xor(bj, s, 64);
+      if (oo < bo || (oo == bo && oj > bj)) {
+        bo = oo;
+        bj = oj;
+      }
+    }
+    if (lane == 0) {
+      s_exo[wave] = bo;
+      s_exj[wave] = bj;
+    }
+    __syncthreads();
+    bo = s_exo[0], bj = s_exj[0];
+#pragma unroll
+    for (int w = 1; w < kFitWaves; ++w) {
+      if (s_exo[w] < bo || (s_exo[w] == bo && s_exj[w] > bj)) {
+        bo = s_exo[w];
+        bj = s_exj[w];
+      }
+    }
+    const int j = bj;
+    if (j < 0) break;
+    // both i and j are training entries: their box is [0, C]
+    const double yi = i < mi ? 1.0 : -1.0, yj = j < mi ? 1.0 : -1.0;
+    const double ai = s_alpha[i], aj = s_alpha[j], Gi = s_G[i], Gj = s_G[j];
+    double quad = kdi + (double)s_Kd[j] - 2.0 * kval(i, j);
+    if (!(quad > 0.0)) quad = kTau;
+    double ni, nj;
+    if (yi != yj) {
+      const double delta = (-Gi - Gj) / quad, diff = ai - aj;
+      ni = ai + delta;
+      nj = aj + delta;
+      if (diff > 0.0) {
+        if (nj < 0.0) {
+          nj = 0.0;
+          ni = diff;
+        }
+      } else if (ni < 0.0) {
+        ni = 0.0;
+        nj = -diff;
+      }
+      if (diff > 0.0) {
+        if (ni > C) {
+          ni = C;
+          nj = C - diff;
+        }
+      } else if (nj > C) {
+        nj = C;
+        ni = C + diff;
+      }
+    } else {
+      const double delta = (Gi - Gj) / quad, tot = ai + aj;
+      ni = ai - delta;
+      nj = aj + delta;
+      if (tot > C) {
+        if (ni > C) {
+          ni = C;
+          nj = tot - C;
+        }
+      } else if (nj < 0.0) {
+        nj = 0.0;
+        ni = tot;
+      }
+      if (tot > C) {
+        if (nj > C) {
+          nj = C;
+          ni = tot - C;
+        }
+      } else if (ni < 0.0) {
+        ni = 0.0;
+        nj = tot;
+      }
+    }
+    __syncthreads();
+    const double dai = ni - ai, daj = nj - aj;
+    for (int t = tid; t < m; t += kFitThreads) {                      // (the held-out entries too: their G is what is asked for)
+      const double yt = t < mi ? 1.0 : -1.0;
+      s_G[t] += yt * (yi * kval(i, t) * dai + yj * kval(j, t) * daj);
+    }
+    if (tid == (i & (kFitThreads - 1))) s_alpha[i] = ni;
+    if (tid == (j & (kFitThreads - 1))) s_alpha[j] = nj;
+  }
+
+  // ---- rho by libsvm's rule over the training entries ----
+  double sum = 0.0, cnt = 0.0, ub = inf, lb = -inf;
+  for (int t = tid; t < m; t += kFitThreads) {
+    if (s_out[t]) continue;
+    const bool pos = t < mi;
+    const double al = s_alpha[t], yG = pos ? s_G[t] : -s_G[t];
+    const bool upper = al >= C, lower = al <= 0.0;
+    if (!upper && !lower) {
+      sum += yG;
+      cnt += 1.0;
+    } else if ((upper && !pos) || (lower && pos)) {
+      ub = fmin(ub, yG);
+    } else {
+      lb = fmax(lb, yG);
+    }
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    sum += __shfl_xor(sum, s, 64);
+    cnt += __shfl_xor(cnt, s, 64);
+    ub = fmin(ub, __shfl_xor(ub, s, 64));
+    lb = fmax(lb, __shfl_xor(lb, s, 64));
+  }
+  if (lane == 0) {
+    s_red[0][wave] = sum;
+    s_red[1][wave] = cnt;
+    s_red[2][wave] = ub;
+    s_red[3][wave] = lb;
+  }
+  __syncthreads();
+  sum = s_red[0][0], cnt = s_red[1][0], ub = s_red[2][0], lb = s_red[3][0];
+  for (int w = 1; w < kFitWaves; ++w) {
+    sum += s_red[0][w];
+    cnt += s_red[1][w];
+    ub = fmin(ub, s_red[2][w]);
+    lb = fmax(lb, s_red[3][w]);
+  }
+  const double rho = cnt > 0.0 ? sum / cnt : (ub + lb) / 2.0;
+  for (int t = tid; t < m; t += kFitThreads)
+    if (s_out[t]) dec[slot(t)] = (float)((t < mi ? s_G[t] + 1.0 : -(s_G[t] + 1.0)) - rho);
+  if (tid == 0) {
+    atomicAdd(cinfo + 1, 1);                                          // integer atomics: their order does not show
+    if (cut) atomicAdd(cinfo + 2, 1);
+    atomicMax(cinfo + 3, it);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ probability=True: the sigmoids
+
+struct PlattArgs {
+  const int32_t* labels;
+  const int32_t* offsets;
+  const float* cv_decision;
+  const int32_t* info;
+  const int32_t* cv_info;
+  double* probA;
+  double* probB;
+  int32_t* present;
+  int K, max_rows;
+  double eps;
+};
+
+struct PlattPoint {
+  double f, g1, g2, h11, h21, h22;
+};
+
+// One wave per (problem, pair): Lin, Lin and Weng's Newton iteration on (A, B), float64 throughout.  The pair's entries are found by
+// their labels on every pass over the problem's list (in list order; the values are a few KB and stay in cache), the six sums of a
+// pass are per-lane partial sums added by one butterfly, so every lane holds the same bits and takes the same branches.
+__global__ __launch_bounds__(64) void svc_platt_kernel(PlattArgs a) {
+  const int K = a.K, npairs = K * (K - 1) / 2;
+  const int p = blockIdx.x / npairs, q = blockIdx.x % npairs, lane = threadIdx.x;
+  if (a.info && a.info[(size_t)p * 4] != 0) return;
+  if (a.cv_info && a.cv_info[(size_t)p * 4] != 0) return;
+  const int begin = a.offsets[p];
+  const int n = a.offsets[p + 1] - begin;
+  if (n < 1 || n > a.max_rows || n > kMaxRows) return;
+  int ci, cj;
+  pair_of(q, K, ci, cj);
+  const int32_t* __restrict__ lab = a.labels + begin;
+  const float* __restrict__ dec = a.cv_decision + (size_t)begin * (K - 1);
+  int np_ = 0, nn_ = 0, mask = 0;
+  for (int t = lane; t < n; t += 64) {
+    const int y = lab[t];
+    np_ += y == ci;
+    nn_ += y == cj;
+    if ((unsigned)y < (unsigned)K) mask |= 1 << y;
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    np_ += __shfl_xor(np_, s, 64);
+    nn_ += __shfl_xor(nn_, s, 64);
+    mask |= __shfl_xor(mask, s, 64);
+  }
+  if (q == 0 && lane == 0 && a.present) a.present[p] = mask;
+  double* __restrict__ outA = a.probA + (size_t)p * npairs + q;
+  double* __restrict__ outB = a.probB + (size_t)p * npairs + q;
+  if (np_ == 0 || nn_ == 0) {
+    if (lane == 0) *outA = *outB = 0.0;
+    return;
+  }
+  const double hi = ((double)np_ + 1.0) / ((double)np_ + 2.0), lo = 1.0 / ((double)nn_ + 2.0);
+  auto pass = [&](double A, double B) -> PlattPoint {
+    PlattPoint s = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int t = lane; t < n; t += 64) {
+      const int y = lab[t];
+      if (y != ci && y != cj) continue;
+      const double d = (double)dec[(size_t)t * (K - 1) + (y == ci ? cj - 1 : ci)];
+      const double tg = y == ci ? hi : lo;
+      const double z = A * d + B, e = exp(-fabs(z));
+      s.f += (z >= 0.0 ? tg : tg - 1.0) * z + log1p(e);
+      const double pr = (z >= 0.0 ? e : 1.0) / (1.0 + e);              // 1 / (1 + exp(z))
+      const double d1 = tg - pr, d2 = pr * (1.0 - pr);
+      s.g1 += d * d1;
+      s.g2 += d1;
+      s.h11 += d * d * d2;
+      s.h21 += d * d2;
+      s.h22 += d2;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      s.f += __shfl_xor(s.f, m, 64);
+      s.g1 += __shfl_xor(s.g1, m, 64);
+      s.g2 += __shfl_xor(s.g2, m, 64);
+      s.h11 += __shfl_xor(s.h11, m, 64);
+      s.h21 += __shfl_xor(s.h21, m, 64);
+      s.h22 += __shfl_xor(s.h22, m, 64);
+    }
+    return s;
+  };
+  double A = 0.0, B = log(((double)nn_ + 1.0) / ((double)np_ + 1.0));
+  PlattPoint at = pass(A, B);
+  for (int it = 0; it < 100; ++it) {
+    const double gn = fmax(fabs(at.g1), fabs(at.g2));
+    if (!(gn >= a.eps)) break;                                        // |g|_inf < eps (or NaN values: nothing to iterate on)
+    const double h11 = at.h11 + 1e-12, h22 = at.h22 + 1e-12, h21 = at.h21;
+    const double det = h11 * h22 - h21 * h21;
+    const double dA = -(h22 * at.g1 - h21 * at.g2) / det, dB = -(-h21 * at.g1 + h11 * at.g2) / det;
+    const double slope = at.g1 * dA + at.g2 * dB;
+    double step = 1.0;
+    bool moved = false;
+    for (int hv = 0; hv <= 10; ++hv) {
+      const PlattPoint to = pass(A + step * dA, B + step * dB);
+      // at the rounding floor of f the sufficient-decrease test is noise: there a step that shrinks the gradient is taken
+      if (to.f < at.f + 1e-4 * step * slope ||
+          (fmax(fabs(to.g1), fabs(to.g2)) < gn && to.f <= at.f + 1e-9 * fmax(1.0, fabs(at.f)))) {
+        A += step * dA;
+        B += step * dB;
+        at = to;
+        moved = true;
+        break;
+      }
+      step *= 0.5;
+    }
+    if (!moved) break;
+  }
+  if (lane == 0) {
+    *outA = A;
+    *outB = B;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ probability=True: pairwise coupling
+
+// the problem whose list holds entry e: the last p with offsets[p] <= e; -1 where e is outside every list
+__device__ inline int problem_of(const int32_t* __restrict__ offsets, int P, int e) {
+  if (P < 1 || e < offsets[0] || e >= offsets[P]) return -1;
+  int lo = 0, hi = P;                                                 // offsets[lo] <= e < offsets[hi]
+  for (int k = 0; k < 32 && hi - lo > 1; ++k) {
+    const int mid = lo + (hi - lo) / 2;
+    if (offsets[mid] <= e)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+struct CoupleArgs {
+  const float* decision;
+  const int32_t* truth;
+  const int32_t* offsets;
+  const double* probA;
+  const double* probB;
+  const int32_t* present;
+  float* probs;
+  int32_t* pred;
+  int32_t* correct;
+  int P, total;
+};
+
+// A thread per entry.  Wu, Lin and Weng's method 2: p minimises p'Qp on the plane e'p = 1.  The minimiser is Q'^{-1} e scaled to sum
+// 1 with Q' = Q + e e' (Q p = -b e and e'p = 1 give Q'p = (1 - b) e), and Q' is positive definite (a null vector of Q has entries of one
+// sign), so the bordered KKT system of couple_host is solved here by a Cholesky factorisation without pivoting, every index a
+// compile-time constant: the lower triangle lives in registers.  An absent class's row is that of the identity with a zero right side.
+template <int K>
+__global__ __launch_bounds__(256) void svc_couple_kernel(CoupleArgs a) {
+  constexpr int npairs = K * (K - 1) / 2;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.total) return;
+  const int p = problem_of(a.offsets, a.P, e);
+  if (p < 0) return;                                                  // pred -1, NaN probabilities (the call's presets)
+  const int present = a.present[p];
+  double L[K][K];                                                     // lower triangle of Q', then of its factor
+#pragma unroll
+  for (int i = 0; i < K; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) L[i][j] = (i == j || (((present >> i) & 1) && ((present >> j) & 1))) ? 1.0 : 0.0;   // e e', or the identity
+  bool nan = __popc(present & ((1 << K) - 1)) < 2;
+  {
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+#pragma unroll
+      for (int j = i + 1; j < K; ++j, ++q) {
+        const double f = (double)a.decision[(size_t)e * npairs + q];
+        nan = nan || !(f == f);
+        if (((present >> i) & 1) && ((present >> j) & 1)) {
+          const double z = a.probA[(size_t)p * npairs + q] * f + a.probB[(size_t)p * npairs + q];
+          nan = nan || !(z == z);
+          const double ex = exp(-fabs(z));
+          double r = (z >= 0.0 ? ex : 1.0) / (1.0 + ex);              // r_ij = 1 / (1 + exp(z))
+          r = fmin(fmax(r, 1e-7), 1.0 - 1e-7);
+          const double rji = 1.0 - r;
+          L[i][i] += rji * rji;
+          L[j][j] += r * r;
+          L[j][i] -= r * rji;
+        }
+      }
+  }
+  if (nan) return;
+  // Cholesky in place, then L y = e, L' x = y
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+#pragma unroll
+    for (int k = 0; k < j; ++k) L[j][j] -= L[j][k] * L[j][k];
+    L[j][j] = sqrt(L[j][j]);
+#pragma unroll
+    for (int i = j + 1; i < K; ++i) {
+#pragma unroll
+      for (int k = 0; k < j; ++k) L[i][j] -= L[i][k] * L[j][k];
+      L[i][j] /= L[j][j];
+    }
+  }
+  double x[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    x[i] = ((present >> i) & 1) ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 0; k < i; ++k) x[i] -= L[i][k] * x[k];
+    x[i] /= L[i][i];
+  }
+#pragma unroll
+  for (int i = K - 1; i >= 0; --i) {
+#pragma unroll
+    for (int k = i + 1; k < K; ++k) x[i] -= L[k][i] * x[k];
+    x[i] /= L[i][i];
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; ++i) sum += x[i];
+  double best = -1.0;
+  int arg = -1;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const float pr = ((present >> i) & 1) ? (float)(x[i] / sum) : 0.0f;
+    a.probs[(size_t)e * K + i] = pr;
+    if (((present >> i) & 1) && (double)pr > best) {                  // the first argmax of what is written
+      best = (double)pr;
+      arg = i;
+    }
+  }
+  a.pred[e] = arg;
+  if (arg >= 0 && arg == a.truth[e]) atomicAdd(a.correct + p, 1);      // an integer count
+}
+
+__global__ __launch_bounds__(256) void soft_vote_kernel(const float* __restrict__ pa, const float* __restrict__ pb, const int32_t* __restrict__ truth,
+                                                        const int32_t* __restrict__ offsets, int P, int K, int total,
+                                                        int32_t* __restrict__ pred, int32_t* __restrict__ correct, float* __restrict__ mean) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int p = problem_of(offsets, P, e);
+  if (p < 0) return;
+  float best = 0.0f;
+  int arg = -1;
+  bool nan = false;
+  for (int k = 0; k < K; ++k) {
+    const float u = pa[(size_t)e * K + k], v = pb[(size_t)e * K + k];
+    nan = nan || !(u == u) || !(v == v);
+    const float m = 0.5f * (u + v);
+    if (mean) mean[(size_t)e * K + k] = m;
+    if (arg < 0 || m > best) {                                        // the first argmax
+      best = m;
+      arg = k;
+    }
+  }
+  if (nan) return;                                                    // pred stays -1
+  pred[e] = arg;
+  if (arg == truth[e]) atomicAdd(correct + p, 1);                     // an integer count
+}
+
 int check_shape(int n_rows, int dim, int n_problems) {
   if (n_rows < 0 || n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
   if (dim < 1) return fail(MKWS_ERR_INVALID_ARG, "dim = %d: at least one column", dim);
@@ -835,6 +1417,151 @@ extern "C" int mkws_svc_score(const float* d_x, int n_rows, int dim, const int32
   a.max_eval = max_eval;
   a.tiles_e = (int)tiles_e;
   hipLaunchKernelGGL(svc_score_kernel, dim3((unsigned)blocks), dim3(kTileThreads), 0, s, a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ probability=True
+
+extern "C" int mkws_svc_fit_cv(const int32_t* d_labels, const int32_t* d_offsets, const int32_t* d_folds, int n_folds, int n_problems,
+                               int n_classes, int max_rows, const double* d_C, double tol, int max_iter, const float* d_gram,
+                               size_t gram_stride, const int32_t* d_info, float* d_cv_decision, int32_t* d_cv_info, void* stream) {
+  if (n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (int rc = check_classes(n_classes)) return rc;
+  if (int rc = check_rows(max_rows, "max_rows")) return rc;
+  if (n_folds < 2) return fail(MKWS_ERR_INVALID_ARG, "n_folds = %d: at least two folds", n_folds);
+  if (n_folds > MKWS_SVC_MAX_FOLDS) return fail(MKWS_ERR_UNSUPPORTED, "n_folds = %d: at most %d", n_folds, MKWS_SVC_MAX_FOLDS);
+  if (max_iter < 1) return fail(MKWS_ERR_INVALID_ARG, "max_iter = %d: at least one iteration", max_iter);
+  if (!(tol >= 0.0)) return fail(MKWS_ERR_INVALID_ARG, "tol is NaN or negative");
+  if (n_problems == 0) return MKWS_OK;
+  if (!d_labels || !d_offsets || !d_folds || !d_C || !d_gram || !d_info || !d_cv_decision || !d_cv_info) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (gram_stride < (size_t)max_rows * (size_t)max_rows)
+    return fail(MKWS_ERR_INVALID_ARG, "gram_stride of %zu floats for problems of up to %d rows", gram_stride, max_rows);
+  const long long blocks = (long long)n_problems * (n_classes * (n_classes - 1) / 2) * n_folds;
+  if (blocks > 0x7fffffffLL) return fail(MKWS_ERR_UNSUPPORTED, "%lld sub-fits in one call", blocks);
+  static std::mutex mu;
+  static std::set<int> done;
+  int dev = 0;
+  MKWS_HIP(hipGetDevice(&dev));
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    if (!done.count(dev)) {
+      MKWS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(svc_fit_cv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitLdsBytes));
+      done.insert(dev);
+    }
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  MKWS_HIP(hipMemsetAsync(d_cv_info, 0, (size_t)n_problems * 4 * sizeof(int32_t), s));
+  FitCvArgs a;
+  a.labels = d_labels;
+  a.offsets = d_offsets;
+  a.folds = d_folds;
+  a.C = d_C;
+  a.gram = d_gram;
+  a.gram_stride = gram_stride;
+  a.info = d_info;
+  a.cv_decision = d_cv_decision;
+  a.cv_info = d_cv_info;
+  a.K = n_classes;
+  a.F = n_folds;
+  a.max_rows = max_rows;
+  a.max_iter = max_iter;
+  a.tol = tol;
+  const size_t lds = kFitLdsFixed + (size_t)(max_rows < kCacheRows ? max_rows : kCacheRows) * (max_rows < kCacheRows ? max_rows : kCacheRows) * 4;
+  hipLaunchKernelGGL(svc_fit_cv_kernel, dim3((unsigned)blocks), dim3(kFitThreads), lds, s, a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+extern "C" int mkws_svc_platt(const int32_t* d_labels, const int32_t* d_offsets, int n_problems, int n_classes, int max_rows,
+                              const float* d_cv_decision, const int32_t* d_info, const int32_t* d_cv_info, double eps, double* d_probA,
+                              double* d_probB, int32_t* d_present, void* stream) {
+  if (n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (int rc = check_classes(n_classes)) return rc;
+  if (int rc = check_rows(max_rows, "max_rows")) return rc;
+  if (!(eps >= 0.0)) return fail(MKWS_ERR_INVALID_ARG, "eps is NaN or negative");
+  if (n_problems == 0) return MKWS_OK;
+  if (!d_labels || !d_offsets || !d_cv_decision || !d_probA || !d_probB) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  const long long blocks = (long long)n_problems * (n_classes * (n_classes - 1) / 2);
+  if (blocks > 0x7fffffffLL) return fail(MKWS_ERR_UNSUPPORTED, "%lld pairs in one call", blocks);
+  PlattArgs a;
+  a.labels = d_labels;
+  a.offsets = d_offsets;
+  a.cv_decision = d_cv_decision;
+  a.info = d_info;
+  a.cv_info = d_cv_info;
+  a.probA = d_probA;
+  a.probB = d_probB;
+  a.present = d_present;
+  a.K = n_classes;
+  a.max_rows = max_rows;
+  a.eps = eps;
+  hipLaunchKernelGGL(svc_platt_kernel, dim3((unsigned)blocks), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+namespace {
+
+// d_correct zeroed, d_pred = -1 and NaN probabilities (all bits set) wherever no thread writes
+int preset_scores(int n_problems, int n_classes, int total, int32_t* d_pred, int32_t* d_correct, float* d_probs, hipStream_t s) {
+  if (n_problems > 0) MKWS_HIP(hipMemsetAsync(d_correct, 0, (size_t)n_problems * sizeof(int32_t), s));
+  if (total > 0) MKWS_HIP(hipMemsetAsync(d_pred, 0xff, (size_t)total * sizeof(int32_t), s));
+  if (total > 0 && d_probs) MKWS_HIP(hipMemsetAsync(d_probs, 0xff, (size_t)total * n_classes * sizeof(float), s));
+  return MKWS_OK;
+}
+
+}  // namespace
+
+extern "C" int mkws_svc_couple(const float* d_decision, const int32_t* d_true, const int32_t* d_offsets, int n_problems, int n_classes,
+                               int total, const double* d_probA, const double* d_probB, const int32_t* d_present, float* d_probs,
+                               int32_t* d_pred, int32_t* d_correct, void* stream) {
+  if (n_problems < 0 || total < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (int rc = check_classes(n_classes)) return rc;
+  if (!d_offsets) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_problems > 0 && (!d_correct || !d_probA || !d_probB || !d_present)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (total > 0 && (!d_decision || !d_true || !d_probs || !d_pred)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = preset_scores(n_problems, n_classes, total, d_pred, d_correct, d_probs, s)) return rc;
+  if (total == 0 || n_problems == 0) return MKWS_OK;
+  CoupleArgs a;
+  a.decision = d_decision;
+  a.truth = d_true;
+  a.offsets = d_offsets;
+  a.probA = d_probA;
+  a.probB = d_probB;
+  a.present = d_present;
+  a.probs = d_probs;
+  a.pred = d_pred;
+  a.correct = d_correct;
+  a.P = n_problems;
+  a.total = total;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  switch (n_classes) {
+    case 2: hipLaunchKernelGGL(svc_couple_kernel<2>, grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(svc_couple_kernel<3>, grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL(svc_couple_kernel<4>, grid, block, 0, s, a); break;
+    case 5: hipLaunchKernelGGL(svc_couple_kernel<5>, grid, block, 0, s, a); break;
+    case 6: hipLaunchKernelGGL(svc_couple_kernel<6>, grid, block, 0, s, a); break;
+    case 7: hipLaunchKernelGGL(svc_couple_kernel<7>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(svc_couple_kernel<8>, grid, block, 0, s, a); break;
+  }
+  MKWS_HIP(hipGetLastError());
+  return MKWS_OK;
+}
+
+extern "C" int mkws_soft_vote(const float* d_probs_a, const float* d_probs_b, const int32_t* d_true, const int32_t* d_offsets, int n_problems,
+                              int n_classes, int total, int32_t* d_pred, int32_t* d_correct, float* d_mean, void* stream) {
+  if (n_problems < 0 || total < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (int rc = check_classes(n_classes)) return rc;
+  if (!d_offsets) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (n_problems > 0 && !d_correct) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  if (total > 0 && (!d_probs_a || !d_probs_b || !d_true || !d_pred)) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = preset_scores(n_problems, n_classes, total, d_pred, d_correct, d_mean, s)) return rc;
+  if (total == 0 || n_problems == 0) return MKWS_OK;
+  hipLaunchKernelGGL(soft_vote_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_probs_a, d_probs_b, d_true, d_offsets, n_problems,
+                     n_classes, total, d_pred, d_correct, d_mean);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }

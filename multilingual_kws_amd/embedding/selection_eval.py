@@ -5,10 +5,11 @@ validation score scored on the dev vectors -- for all splits of all experiments 
 
 Built: the LogisticRegression classifiers of the reference (dataperf_test_harness.py:242-256: `logistic_regression` = "lr",
 `logistic_regression_with_scaling` = "lr_scaled") and its plain sklearn.svm.SVC() ones (:224-239: `simplest_svm` = "svc",
-`svm_with_scaling` = "svc_scaled": C-SVC, RBF kernel, gamma="scale", one-vs-one votes).  NOT built:
-SVC(probability=True) and with it the voting ensemble at :386-393 -- Platt scaling runs an internal 5-fold split with libsvm's own
-random generator, so there is no specification a device version could be held to -- and the random forest,
-gradient boosting and L1 variants of :259-286.
+`svm_with_scaling` = "svc_scaled": C-SVC, RBF kernel, gamma="scale", one-vs-one votes), and the one
+configuration experiment_run itself fits (:386-393), "vote": VotingClassifier([SVC(probability=True), LogisticRegression()],
+voting="soft"), with the folds of Platt scaling's internal cross-validation as an INPUT (svc.cv_folds draws them; libsvm draws its own
+from an unseeded generator, which nothing can be held to) and everything after them to a float64 specification.
+NOT built: SVC(probability=True) as a classifier of its own, and the random forest, gradient boosting and L1 variants of :259-286.
 
 Every problem is solved to (lr) or to within 1e-5 of (svc) the optimum of sklearn's objective rather than to where sklearn's solver
 happens to stop (lbfgs: tol 1e-4, 100 iterations; libsvm: tol 1e-3), so a score can differ from the reference's on rows that sit
@@ -22,7 +23,7 @@ from .. import logreg, problems, svc
 
 KeywordEmbeddings = namedtuple("KeywordEmbeddings", "bank clip_ids offsets")
 
-CLASSIFIERS = {"lr": False, "lr_scaled": True, "svc": False, "svc_scaled": True}       # name -> standardize
+CLASSIFIERS = {"lr": False, "lr_scaled": True, "svc": False, "svc_scaled": True, "vote": False}       # name -> standardize
 
 
 def load_keyword_embeddings(parquet_dir, words):
@@ -156,7 +157,14 @@ def _svc_count_correct(bank, models, which, fit_lists, eval_lists, K):
         models = models if which is None else [models[c] for c in which]
         return [int((svc.predict_host(svc.decision_host(bank, rows, tr, ty, K, m.coef, m.rho, m.gamma, m.centre, m.inv_scale), ty, K) == true).sum())
                 for (tr, ty, m), (rows, true) in zip(models, _each(eval_lists))]
-    model = (models.d_coef, models.d_rho, models.d_gamma, models.d_centre, models.d_inv_scale)
+    fit_lists, model = _svc_take(bank, models, which, fit_lists, ())
+    return svc.score_on_device(bank, *eval_lists, *fit_lists, K, *model)[1].cpu().numpy()
+
+
+def _svc_take(bank, models, which, fit_lists, more):
+    """-> (training lists, [d_coef, d_rho, d_gamma, d_centre, d_inv_scale] + the d_* fields named in `more`) of the problems `which`
+    (None = all)."""
+    model = [getattr(models, "d_" + name) for name in ("coef", "rho", "gamma", "centre", "inv_scale") + tuple(more)]
     if which is not None:
         # svc's coefficients are per training row: the chosen problems' training lists become lists of their own
         take = [np.arange(fit_lists[2][c], fit_lists[2][c + 1]) for c in which]
@@ -164,20 +172,67 @@ def _svc_count_correct(bank, models, which, fit_lists, eval_lists, K):
         fit_lists = (fit_lists[0][at], fit_lists[1][at], off)
         d_at, d_which = _to(bank.device, at), _to(bank.device, which)
         model = [model[0][d_at].contiguous()] + [m[d_which].contiguous() for m in model[1:]]
-    return svc.score_on_device(bank, *eval_lists, *fit_lists, K, *model)[1].cpu().numpy()
+    return fit_lists, model
+
+
+def _vote_fit(bank, fit_lists, K, C, standardize, max_iter, gtol, tol, folds=None, n_folds=5, fold_seed=0):
+    """(the logistic models, the SVC(probability=True) models) of every problem; folds: one value per entry of the fit lists, None =
+    svc.cv_folds(labels, offsets, n_folds, fold_seed)."""
+    lr = _lr_fit(bank, fit_lists, K, C, standardize, max_iter or _LR.max_iter, gtol, tol)
+    if folds is None:
+        folds = svc.cv_folds(fit_lists[1], fit_lists[2], n_folds, fold_seed)
+    folds = np.asarray(folds)
+    if folds.shape != fit_lists[0].shape:
+        raise ValueError(f"folds: one value per training entry of every split ({fit_lists[0].size}), not {folds.shape}")
+    if isinstance(bank, np.ndarray):
+        each = zip(_each(fit_lists), zip(fit_lists[2][:-1], fit_lists[2][1:]))
+        return lr, [(rows, labels, svc.svc_proba_host(bank, rows, labels, K, folds[a:b], n_folds, C, standardize)) for (rows, labels), (a, b) in each]
+    return lr, svc.fit_proba_on_device(bank, *fit_lists, K, folds=folds, n_folds=n_folds, C=C, standardize=standardize, tol=tol,
+                                       max_iter=max_iter or _SVC.max_iter)
+
+
+def _vote_refused(models):
+    bad = [_refused(models[0]), _refused(models[1])]
+    if not isinstance(models[1], list) and bad[1] is None:
+        cv = np.nonzero(models[1].cv_info[:, 0])[0]
+        bad.append(int(cv[0]) if len(cv) else None)
+    bad = [b for b in bad if b is not None]
+    return min(bad) if bad else None
+
+
+def _vote_count_correct(bank, models, which, fit_lists, eval_lists, K):
+    """VotingClassifier(voting="soft", weights=None).predict: the first argmax of the mean of the two predict_proba."""
+    lr, sv = models
+    if isinstance(bank, np.ndarray):
+        pick = lambda ms: ms if which is None else [ms[c] for c in which]
+        out = []
+        for m, (tr, ty, s), (rows, true) in zip(pick(lr), pick(sv), _each(eval_lists)):
+            p_svc = svc.proba_host(bank, rows, tr, ty, K, None, model=s)
+            out.append(int((svc.soft_vote_host(p_svc, logreg.predict_host(bank, rows, m.coef, m.intercept)[1])[0] == true).sum()))
+        return out
+    lr_model = (lr.d_coef, lr.d_intercept)
+    if which is not None:
+        d_which = _to(bank.device, which)
+        lr_model = [m[d_which].contiguous() for m in lr_model]
+    p_lr = logreg.score_on_device(bank, *eval_lists, *lr_model, want_probs=True)[2]
+    fit_lists, model = _svc_take(bank, sv, which, fit_lists, ("probA", "probB", "present"))
+    p_svc = svc.proba_on_device(bank, *eval_lists, *fit_lists, K, *model)[2]
+    return svc.soft_vote_on_device(p_svc, p_lr, eval_lists[1], eval_lists[2])[1].cpu().numpy()
 
 
 # What experiment_run_many asks of a classifier.  fit -> models, on the host (a numpy bank: one model per problem, the host solvers raise
 # by themselves) or on the device (a CUDA bank: the *Fit tuple); refused(models) -> the first refused problem or None; count_correct ->
-# correct rows per problem of eval_lists, under model p for list p (which = None) or under model which[p]; max_iter = what None stands for
-Classifier = namedtuple("Classifier", "fit refused count_correct refusal max_iter")
+# correct rows per problem of eval_lists, under model p for list p (which = None) or under model which[p]; max_iter = what None stands for;
+# folds = its fit also takes experiment_run_many's folds, n_folds and fold_seed
+Classifier = namedtuple("Classifier", "fit refused count_correct refusal max_iter folds", defaults=(False,))
 _LR = Classifier(_lr_fit, _refused, _lr_count_correct, "a row outside the bank, or no row at all", 300)
 _SVC = Classifier(_svc_fit, _refused, _svc_count_correct, "a row outside the bank, no row at all, or fewer than two classes with a row", 100000)
-IMPLEMENTATIONS = {"lr": _LR, "lr_scaled": _LR, "svc": _SVC, "svc_scaled": _SVC}
+_VOTE = Classifier(_vote_fit, _vote_refused, _vote_count_correct, _SVC.refusal + ", or a fold outside [0, n_folds)", None, True)
+IMPLEMENTATIONS = {"lr": _LR, "lr_scaled": _LR, "svc": _SVC, "svc_scaled": _SVC, "vote": _VOTE}
 
 
 def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows, splits, classifier="lr", C=1.0, max_iter=None, gtol=1e-6,
-                        on_device=None, tol=1e-5):
+                        on_device=None, tol=1e-5, folds=None, n_folds=5, fold_seed=0):
     """experiment_run of dataperf_test_harness.py:318-408 for a list of experiments on one bank of embedding vectors.
 
     bank: float32 [rows, dim], numpy or CUDA tensor (load_keyword_embeddings(...).bank).  experiments: dicts with words (the target words;
@@ -185,8 +240,12 @@ def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows
     get_fvs_by_split "train" and "dev").  unknown_train_rows / unknown_eval_rows: bank rows of the unknown vectors.  splits: for every
     experiment a list of (train_ixs, val_ixs) into its stacked train rows, e.g. list(StratifiedShuffleSplit(...).split(X, y)) as the
     reference draws them, or stratified_shuffle_splits.  classifier: "lr" (LogisticRegression) or "svc" (SVC()), "lr_scaled" or "svc_scaled"
-    with a StandardScaler in front, fitted on each split's own training rows.  Every experiment of one call names the same number of words.
+    with a StandardScaler in front, fitted on each split's own training rows; "vote" = the soft vote of SVC(probability=True) and
+    LogisticRegression that the reference's experiment_run fits (:386-393).  Every experiment of one call names the same number of words.
     max_iter: None = 300 conjugate-gradient iterations for lr, 100000 SMO iterations per pair for svc; gtol stops lr, tol stops svc.
+    folds / n_folds / fold_seed ("vote" only): the folds of Platt scaling's internal cross-validation, one value in [0, n_folds) per
+    training entry of every split, in the order of the splits (split s of experiment e trains on its target rows, then the unknown
+    train rows); None = svc.cv_folds(..., n_folds, fold_seed).
 
     Every split's problem is its target train rows plus the unknown train rows; its validation set is the held-out rows plus the unknown
     eval rows; the split with the best validation score (the first, on ties: np.argmax) is scored on the dev rows plus the unknown
@@ -197,8 +256,8 @@ def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows
     svc.svc_host, svc.decision_host and svc.predict_host."""
     import torch
     if classifier not in CLASSIFIERS:
-        raise ValueError(f"classifier {classifier!r}: one of {sorted(CLASSIFIERS)} (SVC(probability=True), the voting ensemble, random forest, "
-                         "gradient boosting and L1 are not built)")
+        raise ValueError(f"classifier {classifier!r}: one of {sorted(CLASSIFIERS)} (SVC(probability=True) on its own is built only inside "
+                         "\"vote\", the voting ensemble; random forest, gradient boosting and L1 are not built)")
     standardize, impl = CLASSIFIERS[classifier], IMPLEMENTATIONS[classifier]
     if max_iter is None:
         max_iter = impl.max_iter
@@ -211,7 +270,8 @@ def experiment_run_many(bank, experiments, unknown_train_rows, unknown_eval_rows
         on_device = torch.cuda.is_available()
     # the bank goes where the work is done, and tells the classifier which implementation to take
     bank = problems.device_bank(bank) if on_device else bank.cpu().numpy() if torch.is_tensor(bank) else np.asarray(bank)
-    models = impl.fit(bank, fit, K, C=C, standardize=standardize, max_iter=max_iter, gtol=gtol, tol=tol)
+    cv = dict(folds=folds, n_folds=n_folds, fold_seed=fold_seed) if impl.folds else {}
+    models = impl.fit(bank, fit, K, C=C, standardize=standardize, max_iter=max_iter, gtol=gtol, tol=tol, **cv)
     bad = impl.refused(models)
     if bad is not None:
         raise ValueError(f"problem {bad} was refused by the device: {impl.refusal}")
