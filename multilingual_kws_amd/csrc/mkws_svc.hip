@@ -1,6 +1,7 @@
-// K RBF support-vector classifiers on embedding vectors (mkws_svc_prepare / mkws_svc_kernel / mkws_svc_fit / mkws_svc_score,
-// include/mkws.h): what the DataPerf selection harness does per split with sklearn.svm.SVC(), for P problems side by side.
-// multilingual_kws_amd/svc.py (svc_host, decision_host, predict_host) is the specification.
+// K RBF support-vector classifiers on embedding vectors (mkws_svc_prepare / mkws_svc_kernel / mkws_svc_fit / mkws_svc_score, and for
+// probability=True mkws_svc_fit_cv / mkws_svc_platt / mkws_svc_couple, with mkws_soft_vote; include/mkws.h): what the DataPerf selection
+// harness does per split with sklearn.svm.SVC(), for P problems side by side.  multilingual_kws_amd/svc.py (svc_host, decision_host,
+// predict_host; cv_decision_host, platt_host, couple_host, soft_vote_host) is the specification.
 //
 // prepare  one workgroup per problem: the lists are checked, the column mean and 1 / sigma of the problem's own rows and sklearn's
 //          gamma = 1 / (dim * Var) are formed with float64 accumulation, a thread per column, the rows in list order.
@@ -15,6 +16,14 @@
 //          are wave butterflies plus one LDS exchange; an iteration is three barriers.
 // score    a workgroup per 64 evaluation rows walks the model's training rows tile by tile, sums coef * k per (class, other class) in
 //          list order and votes.
+// fit_cv   one workgroup per (problem, pair, fold): the fit's solver with that fold's entries of the pair held out (the box [0, 0]);
+//          their decision values are what is written.  fit and fit_cv are the two instantiations of one solver, smo_pair<HELD>: without
+//          held-out entries no flag is read.
+// platt    one wave per (problem, pair): Newton's iteration with backtracking on the sigmoid's (A, B) over the pair's fit_cv values,
+//          float64, every pass's sums by one butterfly.
+// couple   a thread per evaluation entry: pairwise probabilities from the sigmoids, coupled by a Cholesky solve in registers (templated
+//          on the class count), the first argmax.
+// soft_vote  a thread per evaluation entry: the mean of two probability rows and its first argmax.
 // No floating-point atomics (the integer ones count, or take a maximum): two calls on the same input write the same bytes.  Every loop is
 // bounded by max_iter, the row count, dim or the class count; no workgroup waits for another.
 #include "mkws_common.h"
@@ -301,36 +310,46 @@ struct FitArgs {
   double tol;
 };
 
-__global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char s_raw[];
-  double* s_G = reinterpret_cast<double*>(s_raw);
-  double* s_alpha = s_G + kMaxRows;
-  int32_t* s_idx = reinterpret_cast<int32_t*>(s_alpha + kMaxRows);    // the pair's rows as positions in the problem's list: class i, then class j
-  int32_t* s_idxJ = s_idx + kMaxRows;
-  float* s_Kd = reinterpret_cast<float*>(s_idxJ + kMaxRows);
-  float* s_K = s_Kd + kMaxRows;                                       // [m, m] when m <= kCacheRows
-  __shared__ double s_exv[kFitWaves], s_exm[kFitWaves], s_exo[kFitWaves], s_red[4][kFitWaves];
-  __shared__ int s_exi[kFitWaves], s_exj[kFitWaves], s_cnt[2];
-
-  const int K = a.K, npairs = K * (K - 1) / 2;
-  const int p = blockIdx.x / npairs, q = blockIdx.x % npairs;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int32_t* __restrict__ pinfo = a.info + (size_t)p * 4;
-  if (pinfo[0] != 0) return;                                          // refused by mkws_svc_prepare: nothing is written
-  const int begin = a.offsets[p];
-  const int n = a.offsets[p + 1] - begin;
-  if (n < 1 || n > a.max_rows || n > kMaxRows) return;
-  int ci = 0, rest = q;                                               // pair q = (ci, cj) in the order (0,1), (0,2), ...
+// pair q = (ci, cj) in the order (0,1), (0,2), ...
+__device__ inline void pair_of(int q, int K, int& ci, int& cj) {
+  int rest = q;
+  ci = 0;
   for (int k = 0; k < kMaxK && rest >= K - 1 - ci; ++k) {
     rest -= K - 1 - ci;
     ++ci;
   }
-  const int cj = ci + 1 + rest;
-  const int32_t* __restrict__ lab = a.labels + begin;
+  cj = ci + 1 + rest;
+}
 
-  if (wave < 2) {                                                     // wave 0 lists class ci, wave 1 class cj, in list order
+// the dynamic LDS of one pair's workgroup (kFitLdsFixed, then the cache)
+struct PairLds {
+  double* G;                            // the gradient
+  double* alpha;
+  int32_t* idx;                         // the pair's entries as positions in the problem's list: class i, then class j
+  int32_t* idxJ;                        // class j's entries while list_pair appends them; smo_pair<true>'s held-out flags after that
+  float* Kd;                            // the diagonal
+  float* K;                             // [m, m] when m <= kCacheRows
+};
+
+__device__ inline PairLds pair_lds(char* raw) {
+  PairLds lds;
+  lds.G = reinterpret_cast<double*>(raw);
+  lds.alpha = lds.G + kMaxRows;
+  lds.idx = reinterpret_cast<int32_t*>(lds.alpha + kMaxRows);
+  lds.idxJ = lds.idx + kMaxRows;
+  lds.Kd = reinterpret_cast<float*>(lds.idxJ + kMaxRows);
+  lds.K = lds.Kd + kMaxRows;
+  return lds;
+}
+
+// lds.idx = the list positions of class ci's entries, then class cj's, each in list order; mi = class ci's count, -> the pair's.
+// Two barriers, the second at the end.
+__device__ inline int list_pair(const int32_t* __restrict__ lab, int n, int ci, int cj, const PairLds& lds, int& mi) {
+  __shared__ int s_cnt[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (wave < 2) {                                                     // wave 0 lists class ci, wave 1 class cj
     const int cls = wave == 0 ? ci : cj;
-    int32_t* dst = wave == 0 ? s_idx : s_idxJ;
+    int32_t* dst = wave == 0 ? lds.idx : lds.idxJ;
     int cnt = 0;
     for (int c0 = 0; c0 < n; c0 += 64) {
       const int t = c0 + lane;
@@ -342,27 +361,42 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
     if (lane == 0) s_cnt[wave] = cnt;
   }
   __syncthreads();
-  const int mi = s_cnt[0], mj = s_cnt[1], m = mi + mj;
-  for (int t = tid; t < mj; t += kFitThreads) s_idx[mi + t] = s_idxJ[t];
+  mi = s_cnt[0];
+  const int mj = s_cnt[1];
+  for (int t = tid; t < mj; t += kFitThreads) lds.idx[mi + t] = lds.idxJ[t];
   __syncthreads();
-  float* __restrict__ coef = a.coef + (size_t)begin * (K - 1);
-  if (mi == 0 || mj == 0) {                                           // a class without a row: zero coefficients, rho = 0
-    for (int t = tid; t < m; t += kFitThreads) coef[(size_t)s_idx[t] * (K - 1) + (mi ? cj - 1 : ci)] = 0.0f;
-    if (tid == 0) a.rho[(size_t)p * npairs + q] = 0.0f;
-    return;
-  }
-  const float* __restrict__ gram = a.gram + (size_t)p * a.gram_stride;
+  return mi + mj;
+}
+
+struct PairFit {
+  int it, cut;                          // iterations taken; 1 = stopped by max_iter
+  double gap, rho;                      // the last m(a) - M(a); libsvm's rho
+};
+
+// libsvm's SMO on the m entries list_pair left in lds.idx (the first mi are the +1 class), on problem rows of the n x n matrix gram, and
+// libsvm's rho: the one solver behind svc_fit_kernel (HELD = false) and svc_fit_cv_kernel (HELD = true).  With HELD the entries flagged
+// in lds.idxJ get the box [0, 0], which the selection rules never pick, so nothing is compacted and the gradient kept for EVERY entry
+// is a held-out entry's decision value: f(x_t) = y_t (G_t + 1) - rho; rho's rule skips them.  Without HELD no flag is read.
+// each(t, t is of the +1 class, alpha_t) is called once per training entry, by thread t % kFitThreads, before rho's reduction (its
+// stores travel meanwhile).  Every thread returns the same values.  Entry t's G and alpha are written by that thread alone: it may
+// read them after the call without a barrier.
+template <bool HELD, class Each>
+__device__ inline PairFit smo_pair(const PairLds& lds, const float* __restrict__ gram, int n, int mi, int m, double C, double tol, int max_iter,
+                                   Each each) {
+  __shared__ double s_exv[kFitWaves], s_exm[kFitWaves], s_exo[kFitWaves], s_red[4][kFitWaves];
+  __shared__ int s_exi[kFitWaves], s_exj[kFitWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t* s_out = lds.idxJ;                                    // 1 = held out
   const bool cached = m <= kCacheRows;
   if (cached)
-    for (int e = tid; e < m * m; e += kFitThreads) s_K[e] = gram[(size_t)s_idx[e / m] * n + s_idx[e % m]];
+    for (int e = tid; e < m * m; e += kFitThreads) lds.K[e] = gram[(size_t)lds.idx[e / m] * n + lds.idx[e % m]];
   for (int t = tid; t < m; t += kFitThreads) {
-    s_Kd[t] = gram[(size_t)s_idx[t] * n + s_idx[t]];
-    s_G[t] = -1.0;
-    s_alpha[t] = 0.0;
+    lds.Kd[t] = gram[(size_t)lds.idx[t] * n + lds.idx[t]];
+    lds.G[t] = -1.0;
+    lds.alpha[t] = 0.0;
   }
   __syncthreads();
-  auto kval = [&](int r, int t) -> double { return (double)(cached ? s_K[r * m + t] : gram[(size_t)s_idx[r] * n + s_idx[t]]); };
-  const double C = a.C[p];
+  auto kval = [&](int r, int t) -> double { return (double)(cached ? lds.K[r * m + t] : gram[(size_t)lds.idx[r] * n + lds.idx[t]]); };
   const double inf = __builtin_inf();
 
   int it = 0, cut = 0;
@@ -373,8 +407,9 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
     int bi = -1;
     for (int t = tid; t < m; t += kFitThreads) {
       const bool pos = t < mi;
-      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
-      const bool up = pos ? al < C : al > 0.0, low = pos ? al > 0.0 : al < C;
+      const double Ct = (HELD && s_out[t]) ? 0.0 : C;
+      const double al = lds.alpha[t], v = pos ? -lds.G[t] : lds.G[t];
+      const bool up = pos ? al < Ct : al > 0.0, low = pos ? al > 0.0 : al < Ct;
       if (up && v >= bv) {
         bv = v;
         bi = t;
@@ -409,22 +444,23 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
     const int i = bi;
     const double gmax = bv;
     gapv = gmax - mn;
-    if (i < 0 || !(gapv >= a.tol)) break;                             // converged (or nothing can move)
-    if (it >= a.max_iter) {
+    if (i < 0 || !(gapv >= tol)) break;                               // converged (or nothing can move)
+    if (it >= max_iter) {
       cut = 1;
       break;
     }
     // ---- j = argmin over I_low with -y G < gmax of -(gmax + y G)^2 / (K_ii + K_tt - 2 K_it) ----
-    const double kdi = (double)s_Kd[i];
+    const double kdi = (double)lds.Kd[i];
     double bo = inf;
     int bj = -1;
     for (int t = tid; t < m; t += kFitThreads) {
       const bool pos = t < mi;
-      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
-      const bool low = pos ? al > 0.0 : al < C;
+      const double Ct = (HELD && s_out[t]) ? 0.0 : C;
+      const double al = lds.alpha[t], v = pos ? -lds.G[t] : lds.G[t];
+      const bool low = pos ? al > 0.0 : al < Ct;
       const double gd = gmax - v;
       if (low && gd > 0.0) {
-        double quad = kdi + (double)s_Kd[t] - 2.0 * kval(i, t);
+        double quad = kdi + (double)lds.Kd[t] - 2.0 * kval(i, t);
         if (!(quad > 0.0)) quad = kTau;
         const double o = -(gd * gd) / quad;
         if (o <= bo) {
@@ -457,10 +493,10 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
     }
     const int j = bj;
     if (j < 0) break;
-    // ---- the two-variable step with libsvm's clipping; every thread computes it ----
+    // ---- the two-variable step with libsvm's clipping; every thread computes it (i and j are never held out: their box is [0, C]) ----
     const double yi = i < mi ? 1.0 : -1.0, yj = j < mi ? 1.0 : -1.0;
-    const double ai = s_alpha[i], aj = s_alpha[j], Gi = s_G[i], Gj = s_G[j];
-    double quad = kdi + (double)s_Kd[j] - 2.0 * kval(i, j);
+    const double ai = lds.alpha[i], aj = lds.alpha[j], Gi = lds.G[i], Gj = lds.G[j];
+    double quad = kdi + (double)lds.Kd[j] - 2.0 * kval(i, j);
     if (!(quad > 0.0)) quad = kTau;
     double ni, nj;
     if (yi != yj) {
@@ -510,19 +546,20 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
     }
     __syncthreads();                                                  // every thread has read alpha and G of i and j
     const double dai = ni - ai, daj = nj - aj;
-    for (int t = tid; t < m; t += kFitThreads) {
+    for (int t = tid; t < m; t += kFitThreads) {                      // (the held-out entries too: their G is what is asked for)
       const double yt = t < mi ? 1.0 : -1.0;
-      s_G[t] += yt * (yi * kval(i, t) * dai + yj * kval(j, t) * daj);
+      lds.G[t] += yt * (yi * kval(i, t) * dai + yj * kval(j, t) * daj);
     }
-    if (tid == (i & (kFitThreads - 1))) s_alpha[i] = ni;              // (by the thread that owns the entry)
-    if (tid == (j & (kFitThreads - 1))) s_alpha[j] = nj;
+    if (tid == (i & (kFitThreads - 1))) lds.alpha[i] = ni;            // (by the thread that owns the entry)
+    if (tid == (j & (kFitThreads - 1))) lds.alpha[j] = nj;
   }
 
-  // ---- rho by libsvm's rule, the coefficients in the row list's order ----
+  // ---- rho by libsvm's rule over the training entries, each handed to the caller on the way ----
   double sum = 0.0, cnt = 0.0, ub = inf, lb = -inf;
   for (int t = tid; t < m; t += kFitThreads) {
+    if (HELD && s_out[t]) continue;
     const bool pos = t < mi;
-    const double al = s_alpha[t], yG = pos ? s_G[t] : -s_G[t];
+    const double al = lds.alpha[t], yG = pos ? lds.G[t] : -lds.G[t];
     const bool upper = al >= C, lower = al <= 0.0;
     if (!upper && !lower) {
       sum += yG;
@@ -532,7 +569,7 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
     } else {
       lb = fmax(lb, yG);
     }
-    coef[(size_t)s_idx[t] * (K - 1) + (pos ? cj - 1 : ci)] = (float)(pos ? al : -al);
+    each(t, pos, al);
   }
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) {
@@ -548,18 +585,44 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
     s_red[3][wave] = lb;
   }
   __syncthreads();
+  sum = s_red[0][0], cnt = s_red[1][0], ub = s_red[2][0], lb = s_red[3][0];
+  for (int w = 1; w < kFitWaves; ++w) {
+    sum += s_red[0][w];
+    cnt += s_red[1][w];
+    ub = fmin(ub, s_red[2][w]);
+    lb = fmax(lb, s_red[3][w]);
+  }
+  return {it, cut, gapv, cnt > 0.0 ? sum / cnt : (ub + lb) / 2.0};
+}
+
+__global__ __launch_bounds__(kFitThreads) void svc_fit_kernel(FitArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char s_raw[];
+  const PairLds lds = pair_lds(s_raw);
+  const int K = a.K, npairs = K * (K - 1) / 2;
+  const int p = blockIdx.x / npairs, q = blockIdx.x % npairs;
+  const int tid = threadIdx.x;
+  int32_t* __restrict__ pinfo = a.info + (size_t)p * 4;
+  if (pinfo[0] != 0) return;                                          // refused by mkws_svc_prepare: nothing is written
+  const int begin = a.offsets[p];
+  const int n = a.offsets[p + 1] - begin;
+  if (n < 1 || n > a.max_rows || n > kMaxRows) return;
+  int ci, cj, mi;
+  pair_of(q, K, ci, cj);
+  const int m = list_pair(a.labels + begin, n, ci, cj, lds, mi);
+  float* __restrict__ coef = a.coef + (size_t)begin * (K - 1);
+  if (mi == 0 || mi == m) {                                           // a class without a row: zero coefficients, rho = 0
+    for (int t = tid; t < m; t += kFitThreads) coef[(size_t)lds.idx[t] * (K - 1) + (mi ? cj - 1 : ci)] = 0.0f;
+    if (tid == 0) a.rho[(size_t)p * npairs + q] = 0.0f;
+    return;
+  }
+  const PairFit f = smo_pair<false>(lds, a.gram + (size_t)p * a.gram_stride, n, mi, m, a.C[p], a.tol, a.max_iter, [&](int t, bool pos, double al) {
+    coef[(size_t)lds.idx[t] * (K - 1) + (pos ? cj - 1 : ci)] = (float)(pos ? al : -al);     // the coefficients in the row list's order
+  });
   if (tid == 0) {
-    sum = s_red[0][0], cnt = s_red[1][0], ub = s_red[2][0], lb = s_red[3][0];
-    for (int w = 1; w < kFitWaves; ++w) {
-      sum += s_red[0][w];
-      cnt += s_red[1][w];
-      ub = fmin(ub, s_red[2][w]);
-      lb = fmax(lb, s_red[3][w]);
-    }
-    a.rho[(size_t)p * npairs + q] = (float)(cnt > 0.0 ? sum / cnt : (ub + lb) / 2.0);
-    if (cut) atomicAdd(pinfo + 2, 1);                                 // integer atomics: their order does not show
-    atomicMax(pinfo + 3, it);
-    atomicMax(reinterpret_cast<int*>(a.gap + p), __float_as_int(fmaxf((float)gapv, 0.0f)));   // (non-negative floats order as their bits)
+    a.rho[(size_t)p * npairs + q] = (float)f.rho;
+    if (f.cut) atomicAdd(pinfo + 2, 1);                               // integer atomics: their order does not show
+    atomicMax(pinfo + 3, f.it);
+    atomicMax(reinterpret_cast<int*>(a.gap + p), __float_as_int(fmaxf((float)f.gap, 0.0f)));   // (non-negative floats order as their bits)
   }
 }
 
@@ -680,17 +743,6 @@ __global__ __launch_bounds__(kTileThreads) void svc_score_kernel(ScoreArgs a) {
 
 // ------------------------------------------------------------------------------------------------ probability=True: cross-validated fit
 
-// pair q = (ci, cj) in the order (0,1), (0,2), ...
-__device__ inline void pair_of(int q, int K, int& ci, int& cj) {
-  int rest = q;
-  ci = 0;
-  for (int k = 0; k < kMaxK && rest >= K - 1 - ci; ++k) {
-    rest -= K - 1 - ci;
-    ++ci;
-  }
-  cj = ci + 1 + rest;
-}
-
 struct FitCvArgs {
   const int32_t* labels;
   const int32_t* offsets;
@@ -705,24 +757,16 @@ struct FitCvArgs {
   double tol;
 };
 
-// svc_fit_kernel's SMO for one (problem, pair, fold): the pair's entries of that fold are held out by the box [0, 0], which libsvm's
-// selection rules never pick, so the sub-matrix is not compacted and the float64 gradient the loop maintains for EVERY entry of the
-// pair is the held-out decision value: f(x_t) = y_t (G_t + 1) - rho.  Nothing but those values is written.  The same LDS as the
-// fit: the held-out flags take the list of class j's entries once that has been appended to class i's.
+// smo_pair<true> for one (problem, pair, fold): the pair's entries of that fold are held out, and nothing but their decision values
+// is written.  The same LDS as the fit: the held-out flags take the list of class j's entries once that has been appended to class i's.
 __global__ __launch_bounds__(kFitThreads) void svc_fit_cv_kernel(FitCvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char s_raw[];
-  double* s_G = reinterpret_cast<double*>(s_raw);
-  double* s_alpha = s_G + kMaxRows;
-  int32_t* s_idx = reinterpret_cast<int32_t*>(s_alpha + kMaxRows);
-  int32_t* s_idxJ = s_idx + kMaxRows;
-  float* s_Kd = reinterpret_cast<float*>(s_idxJ + kMaxRows);
-  float* s_K = s_Kd + kMaxRows;
-  __shared__ double s_exv[kFitWaves], s_exm[kFitWaves], s_exo[kFitWaves], s_red[4][kFitWaves];
-  __shared__ int s_exi[kFitWaves], s_exj[kFitWaves], s_cnt[2], s_act[3];
+  const PairLds lds = pair_lds(s_raw);
+  __shared__ int s_act[3];
 
   const int K = a.K, F = a.F, npairs = K * (K - 1) / 2;
   const int p = blockIdx.x / (npairs * F), q = (blockIdx.x / F) % npairs, fold = blockIdx.x % F;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   int32_t* __restrict__ cinfo = a.cv_info + (size_t)p * 4;
   const bool first = q == 0 && fold == 0;
   const int begin = a.offsets[p];
@@ -739,32 +783,15 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_cv_kernel(FitCvArgs a) {
     if (first && tid == 0) cinfo[0] = 2;
     return;
   }
-  int ci, cj;
+  int ci, cj, mi;
   pair_of(q, K, ci, cj);
-
-  if (wave < 2) {
-    const int cls = wave == 0 ? ci : cj;
-    int32_t* dst = wave == 0 ? s_idx : s_idxJ;
-    int cnt = 0;
-    for (int c0 = 0; c0 < n; c0 += 64) {
-      const int t = c0 + lane;
-      const bool is = t < n && lab[t] == cls;
-      const unsigned long long mask = __ballot(is);
-      if (is) dst[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = t;
-      cnt += __popcll(mask);
-    }
-    if (lane == 0) s_cnt[wave] = cnt;
-  }
   if (tid < 3) s_act[tid] = 0;
-  __syncthreads();
-  const int mi = s_cnt[0], mj = s_cnt[1], m = mi + mj;
-  for (int t = tid; t < mj; t += kFitThreads) s_idx[mi + t] = s_idxJ[t];
-  __syncthreads();
-  int32_t* s_out = s_idxJ;                                            // 1 = held out
+  const int m = list_pair(lab, n, ci, cj, lds, mi), mj = m - mi;
+  int32_t* s_out = lds.idxJ;                                          // 1 = held out
   {
     int ni = 0, nj = 0, no = 0;                                       // training entries of either class, held-out entries
     for (int t = tid; t < m; t += kFitThreads) {
-      const int out = fo[s_idx[t]] == fold;
+      const int out = fo[lds.idx[t]] == fold;
       s_out[t] = out;
       no += out;
       if (!out) (t < mi ? ni : nj) += 1;
@@ -785,7 +812,7 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_cv_kernel(FitCvArgs a) {
   const int act_i = s_act[0], act_j = s_act[1];
   if (s_act[2] == 0) return;                                          // the fold holds no entry of the pair
   float* __restrict__ dec = a.cv_decision + (size_t)begin * (K - 1);
-  auto slot = [&](int t) -> size_t { return (size_t)s_idx[t] * (K - 1) + (t < mi ? cj - 1 : ci); };
+  auto slot = [&](int t) -> size_t { return (size_t)lds.idx[t] * (K - 1) + (t < mi ? cj - 1 : ci); };
   if (act_i == 0 || act_j == 0) {
     // a class absent from the problem: 0; libsvm's svm_binary_svc_probability otherwise: 0 without any training entry, +1 with class i's
     // alone, -1 with class j's alone
@@ -794,215 +821,13 @@ __global__ __launch_bounds__(kFitThreads) void svc_fit_cv_kernel(FitCvArgs a) {
       if (s_out[t]) dec[slot(t)] = v;
     return;
   }
-  const float* __restrict__ gram = a.gram + (size_t)p * a.gram_stride;
-  const bool cached = m <= kCacheRows;
-  if (cached)
-    for (int e = tid; e < m * m; e += kFitThreads) s_K[e] = gram[(size_t)s_idx[e / m] * n + s_idx[e % m]];
-  for (int t = tid; t < m; t += kFitThreads) {
-    s_Kd[t] = gram[(size_t)s_idx[t] * n + s_idx[t]];
-    s_G[t] = -1.0;
-    s_alpha[t] = 0.0;
-  }
-  __syncthreads();
-  auto kval = [&](int r, int t) -> double { return (double)(cached ? s_K[r * m + t] : gram[(size_t)s_idx[r] * n + s_idx[t]]); };
-  const double C = a.C[p];
-  const double inf = __builtin_inf();
-
-  int it = 0, cut = 0;
-  for (;; ++it) {
-    double bv = -inf, mn = inf;
-    int bi = -1;
-    for (int t = tid; t < m; t += kFitThreads) {
-      const bool pos = t < mi;
-      const double Ct = s_out[t] ? 0.0 : C;
-      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
-      const bool up = pos ? al < Ct : al > 0.0, low = pos ? al > 0.0 : al < Ct;
-      if (up && v >= bv) {
-        bv = v;
-        bi = t;
-      }
-      if (low) mn = fmin(mn, v);
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-      const double ov = __shfl_xor(bv, s, 64);
-      const int oi = __shfl_xor(bi, s, 64);
-      if (ov > bv || (ov == bv && oi > bi)) {
-        bv = ov;
-        bi = oi;
-      }
-      mn = fmin(mn, __shfl_xor(mn, s, 64));
-    }
-    if (lane == 0) {
-      s_exv[wave] = bv;
-      s_exi[wave] = bi;
-      s_exm[wave] = mn;
-    }
-    __syncthreads();
-    bv = s_exv[0], bi = s_exi[0], mn = s_exm[0];
-#pragma unroll
-    for (int w = 1; w < kFitWaves; ++w) {
-      if (s_exv[w] > bv || (s_exv[w] == bv && s_exi[w] > bi)) {
-        bv = s_exv[w];
-        bi = s_exi[w];
-      }
-      mn = fmin(mn, s_exm[w]);
-    }
-    const int i = bi;
-    const double gmax = bv;
-    if (i < 0 || !(gmax - mn >= a.tol)) break;
-    if (it >= a.max_iter) {
-      cut = 1;
-      break;
-    }
-    const double kdi = (double)s_Kd[i];
-    double bo = inf;
-    int bj = -1;
-    for (int t = tid; t < m; t += kFitThreads) {
-      const bool pos = t < mi;
-      const double Ct = s_out[t] ? 0.0 : C;
-      const double al = s_alpha[t], v = pos ? -s_G[t] : s_G[t];
-      const bool low = pos ? al > 0.0 : al < Ct;
-      const double gd = gmax - v;
-      if (low && gd > 0.0) {
-        double quad = kdi + (double)s_Kd[t] - 2.0 * kval(i, t);
-        if (!(quad > 0.0)) quad = kTau;
-        const double o = -(gd * gd) / quad;
-        if (o <= bo) {
-          bo = o;
-          bj = t;
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-      const double oo = __shfl_xor(bo, s, 64);
-      const int oj = __shfl_xor(bj, s, 64);
-      if (oo < bo || (oo == bo && oj > bj)) {
-        bo = oo;
-        bj = oj;
-      }
-    }
-    if (lane == 0) {
-      s_exo[wave] = bo;
-      s_exj[wave] = bj;
-    }
-    __syncthreads();
-    bo = s_exo[0], bj = s_exj[0];
-#pragma unroll
-    for (int w = 1; w < kFitWaves; ++w) {
-      if (s_exo[w] < bo || (s_exo[w] == bo && s_exj[w] > bj)) {
-        bo = s_exo[w];
-        bj = s_exj[w];
-      }
-    }
-    const int j = bj;
-    if (j < 0) break;
-    // both i and j are training entries: their box is [0, C]
-    const double yi = i < mi ? 1.0 : -1.0, yj = j < mi ? 1.0 : -1.0;
-    const double ai = s_alpha[i], aj = s_alpha[j], Gi = s_G[i], Gj = s_G[j];
-    double quad = kdi + (double)s_Kd[j] - 2.0 * kval(i, j);
-    if (!(quad > 0.0)) quad = kTau;
-    double ni, nj;
-    if (yi != yj) {
-      const double delta = (-Gi - Gj) / quad, diff = ai - aj;
-      ni = ai + delta;
-      nj = aj + delta;
-      if (diff > 0.0) {
-        if (nj < 0.0) {
-          nj = 0.0;
-          ni = diff;
-        }
-      } else if (ni < 0.0) {
-        ni = 0.0;
-        nj = -diff;
-      }
-      if (diff > 0.0) {
-        if (ni > C) {
-          ni = C;
-          nj = C - diff;
-        }
-      } else if (nj > C) {
-        nj = C;
-        ni = C + diff;
-      }
-    } else {
-      const double delta = (Gi - Gj) / quad, tot = ai + aj;
-      ni = ai - delta;
-      nj = aj + delta;
-      if (tot > C) {
-        if (ni > C) {
-          ni = C;
-          nj = tot - C;
-        }
-      } else if (nj < 0.0) {
-        nj = 0.0;
-        ni = tot;
-      }
-      if (tot > C) {
-        if (nj > C) {
-          nj = C;
-          ni = tot - C;
-        }
-      } else if (ni < 0.0) {
-        ni = 0.0;
-        nj = tot;
-      }
-    }
-    __syncthreads();
-    const double dai = ni - ai, daj = nj - aj;
-    for (int t = tid; t < m; t += kFitThreads) {                      // (the held-out entries too: their G is what is asked for)
-      const double yt = t < mi ? 1.0 : -1.0;
-      s_G[t] += yt * (yi * kval(i, t) * dai + yj * kval(j, t) * daj);
-    }
-    if (tid == (i & (kFitThreads - 1))) s_alpha[i] = ni;
-    if (tid == (j & (kFitThreads - 1))) s_alpha[j] = nj;
-  }
-
-  // ---- rho by libsvm's rule over the training entries ----
-  double sum = 0.0, cnt = 0.0, ub = inf, lb = -inf;
-  for (int t = tid; t < m; t += kFitThreads) {
-    if (s_out[t]) continue;
-    const bool pos = t < mi;
-    const double al = s_alpha[t], yG = pos ? s_G[t] : -s_G[t];
-    const bool upper = al >= C, lower = al <= 0.0;
-    if (!upper && !lower) {
-      sum += yG;
-      cnt += 1.0;
-    } else if ((upper && !pos) || (lower && pos)) {
-      ub = fmin(ub, yG);
-    } else {
-      lb = fmax(lb, yG);
-    }
-  }
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    sum += __shfl_xor(sum, s, 64);
-    cnt += __shfl_xor(cnt, s, 64);
-    ub = fmin(ub, __shfl_xor(ub, s, 64));
-    lb = fmax(lb, __shfl_xor(lb, s, 64));
-  }
-  if (lane == 0) {
-    s_red[0][wave] = sum;
-    s_red[1][wave] = cnt;
-    s_red[2][wave] = ub;
-    s_red[3][wave] = lb;
-  }
-  __syncthreads();
-  sum = s_red[0][0], cnt = s_red[1][0], ub = s_red[2][0], lb = s_red[3][0];
-  for (int w = 1; w < kFitWaves; ++w) {
-    sum += s_red[0][w];
-    cnt += s_red[1][w];
-    ub = fmin(ub, s_red[2][w]);
-    lb = fmax(lb, s_red[3][w]);
-  }
-  const double rho = cnt > 0.0 ? sum / cnt : (ub + lb) / 2.0;
+  const PairFit f = smo_pair<true>(lds, a.gram + (size_t)p * a.gram_stride, n, mi, m, a.C[p], a.tol, a.max_iter, [](int, bool, double) {});
   for (int t = tid; t < m; t += kFitThreads)
-    if (s_out[t]) dec[slot(t)] = (float)((t < mi ? s_G[t] + 1.0 : -(s_G[t] + 1.0)) - rho);
+    if (s_out[t]) dec[slot(t)] = (float)((t < mi ? lds.G[t] + 1.0 : -(lds.G[t] + 1.0)) - f.rho);
   if (tid == 0) {
     atomicAdd(cinfo + 1, 1);                                          // integer atomics: their order does not show
-    if (cut) atomicAdd(cinfo + 2, 1);
-    atomicMax(cinfo + 3, it);
+    if (f.cut) atomicAdd(cinfo + 2, 1);
+    atomicMax(cinfo + 3, f.it);
   }
 }
 
@@ -1279,6 +1104,37 @@ int check_rows(int max_rows, const char* what) {
   return MKWS_OK;
 }
 
+// what mkws_svc_fit and mkws_svc_fit_cv refuse alike
+int check_fit(int n_problems, int n_classes, int max_rows, int max_iter, double tol, size_t gram_stride) {
+  if (n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
+  if (int rc = check_classes(n_classes)) return rc;
+  if (int rc = check_rows(max_rows, "max_rows")) return rc;
+  if (max_iter < 1) return fail(MKWS_ERR_INVALID_ARG, "max_iter = %d: at least one iteration", max_iter);
+  if (!(tol >= 0.0)) return fail(MKWS_ERR_INVALID_ARG, "tol is NaN or negative");
+  if (n_problems > 0 && gram_stride < (size_t)max_rows * (size_t)max_rows)
+    return fail(MKWS_ERR_INVALID_ARG, "gram_stride of %zu floats for problems of up to %d rows", gram_stride, max_rows);
+  return MKWS_OK;
+}
+
+// the pair kernels ask for more than 64 KB of LDS: the limit is raised once per device, in the set the caller keeps for its kernel
+int allow_fit_lds(const void* kernel, std::set<int>& done) {
+  static std::mutex mu;
+  int dev = 0;
+  MKWS_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  if (!done.count(dev)) {
+    MKWS_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitLdsBytes));
+    done.insert(dev);
+  }
+  return MKWS_OK;
+}
+
+// a call whose problems all fit the LDS cache asks for no more than they need
+size_t fit_lds_bytes(int max_rows) {
+  const size_t side = max_rows < kCacheRows ? max_rows : kCacheRows;
+  return kFitLdsFixed + side * side * 4;
+}
+
 }  // namespace
 
 extern "C" size_t mkws_svc_work_bytes(int n_problems, int max_rows) {
@@ -1326,29 +1182,13 @@ extern "C" int mkws_svc_kernel(const float* d_x, int n_rows, int dim, const int3
 extern "C" int mkws_svc_fit(const int32_t* d_labels, const int32_t* d_offsets, int n_problems, int n_classes, int max_rows, const double* d_C,
                             double tol, int max_iter, const float* d_gram, size_t gram_stride, float* d_coef, float* d_rho, int32_t* d_info,
                             float* d_gap, void* stream) {
-  if (n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
-  if (int rc = check_classes(n_classes)) return rc;
-  if (int rc = check_rows(max_rows, "max_rows")) return rc;
-  if (max_iter < 1) return fail(MKWS_ERR_INVALID_ARG, "max_iter = %d: at least one iteration", max_iter);
-  if (!(tol >= 0.0)) return fail(MKWS_ERR_INVALID_ARG, "tol is NaN or negative");
+  if (int rc = check_fit(n_problems, n_classes, max_rows, max_iter, tol, gram_stride)) return rc;
   if (n_problems == 0) return MKWS_OK;
   if (!d_labels || !d_offsets || !d_C || !d_gram || !d_coef || !d_rho || !d_info || !d_gap) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
-  if (gram_stride < (size_t)max_rows * (size_t)max_rows)
-    return fail(MKWS_ERR_INVALID_ARG, "gram_stride of %zu floats for problems of up to %d rows", gram_stride, max_rows);
   const long long blocks = (long long)n_problems * (n_classes * (n_classes - 1) / 2);
   if (blocks > 0x7fffffffLL) return fail(MKWS_ERR_UNSUPPORTED, "%lld pairs in one call", blocks);
-  // more than 64 KB of LDS: the limit is raised once per device
-  static std::mutex mu;
   static std::set<int> done;
-  int dev = 0;
-  MKWS_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) {
-      MKWS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(svc_fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitLdsBytes));
-      done.insert(dev);
-    }
-  }
+  if (int rc = allow_fit_lds(reinterpret_cast<const void*>(svc_fit_kernel), done)) return rc;
   FitArgs a;
   a.labels = d_labels;
   a.offsets = d_offsets;
@@ -1363,9 +1203,7 @@ extern "C" int mkws_svc_fit(const int32_t* d_labels, const int32_t* d_offsets, i
   a.max_rows = max_rows;
   a.max_iter = max_iter;
   a.tol = tol;
-  // a call whose problems all fit the LDS cache asks for no more than they need
-  const size_t lds = kFitLdsFixed + (size_t)(max_rows < kCacheRows ? max_rows : kCacheRows) * (max_rows < kCacheRows ? max_rows : kCacheRows) * 4;
-  hipLaunchKernelGGL(svc_fit_kernel, dim3((unsigned)blocks), dim3(kFitThreads), lds, static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(svc_fit_kernel, dim3((unsigned)blocks), dim3(kFitThreads), fit_lds_bytes(max_rows), static_cast<hipStream_t>(stream), a);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }
@@ -1426,30 +1264,15 @@ extern "C" int mkws_svc_score(const float* d_x, int n_rows, int dim, const int32
 extern "C" int mkws_svc_fit_cv(const int32_t* d_labels, const int32_t* d_offsets, const int32_t* d_folds, int n_folds, int n_problems,
                                int n_classes, int max_rows, const double* d_C, double tol, int max_iter, const float* d_gram,
                                size_t gram_stride, const int32_t* d_info, float* d_cv_decision, int32_t* d_cv_info, void* stream) {
-  if (n_problems < 0) return fail(MKWS_ERR_INVALID_ARG, "negative size");
-  if (int rc = check_classes(n_classes)) return rc;
-  if (int rc = check_rows(max_rows, "max_rows")) return rc;
+  if (int rc = check_fit(n_problems, n_classes, max_rows, max_iter, tol, gram_stride)) return rc;
   if (n_folds < 2) return fail(MKWS_ERR_INVALID_ARG, "n_folds = %d: at least two folds", n_folds);
   if (n_folds > MKWS_SVC_MAX_FOLDS) return fail(MKWS_ERR_UNSUPPORTED, "n_folds = %d: at most %d", n_folds, MKWS_SVC_MAX_FOLDS);
-  if (max_iter < 1) return fail(MKWS_ERR_INVALID_ARG, "max_iter = %d: at least one iteration", max_iter);
-  if (!(tol >= 0.0)) return fail(MKWS_ERR_INVALID_ARG, "tol is NaN or negative");
   if (n_problems == 0) return MKWS_OK;
   if (!d_labels || !d_offsets || !d_folds || !d_C || !d_gram || !d_info || !d_cv_decision || !d_cv_info) return fail(MKWS_ERR_INVALID_ARG, "NULL buffer");
-  if (gram_stride < (size_t)max_rows * (size_t)max_rows)
-    return fail(MKWS_ERR_INVALID_ARG, "gram_stride of %zu floats for problems of up to %d rows", gram_stride, max_rows);
   const long long blocks = (long long)n_problems * (n_classes * (n_classes - 1) / 2) * n_folds;
   if (blocks > 0x7fffffffLL) return fail(MKWS_ERR_UNSUPPORTED, "%lld sub-fits in one call", blocks);
-  static std::mutex mu;
   static std::set<int> done;
-  int dev = 0;
-  MKWS_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!done.count(dev)) {
-      MKWS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(svc_fit_cv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitLdsBytes));
-      done.insert(dev);
-    }
-  }
+  if (int rc = allow_fit_lds(reinterpret_cast<const void*>(svc_fit_cv_kernel), done)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   MKWS_HIP(hipMemsetAsync(d_cv_info, 0, (size_t)n_problems * 4 * sizeof(int32_t), s));
   FitCvArgs a;
@@ -1467,8 +1290,7 @@ extern "C" int mkws_svc_fit_cv(const int32_t* d_labels, const int32_t* d_offsets
   a.max_rows = max_rows;
   a.max_iter = max_iter;
   a.tol = tol;
-  const size_t lds = kFitLdsFixed + (size_t)(max_rows < kCacheRows ? max_rows : kCacheRows) * (max_rows < kCacheRows ? max_rows : kCacheRows) * 4;
-  hipLaunchKernelGGL(svc_fit_cv_kernel, dim3((unsigned)blocks), dim3(kFitThreads), lds, s, a);
+  hipLaunchKernelGGL(svc_fit_cv_kernel, dim3((unsigned)blocks), dim3(kFitThreads), fit_lds_bytes(max_rows), s, a);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
 }
