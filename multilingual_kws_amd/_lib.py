@@ -20,6 +20,14 @@ class MkwsError(RuntimeError):
         self.code = code
 
 
+class MkwsValueError(MkwsError, ValueError):
+    """A wrapper's own refusal of what the library refuses as well (MKWS_ERR_INVALID_ARG), made before any device call: a ValueError like
+    every refusal of a wrapper, and still the MkwsError a caller of the earlier wrapper caught."""
+
+    def __init__(self, msg):
+        MkwsError.__init__(self, -1, msg)
+
+
 class FrontendCfg(ctypes.Structure):
     """mkws_frontend_cfg (include/mkws.h)."""
     _fields_ = [
@@ -271,6 +279,16 @@ def check(code):
     if code < 0:
         raise MkwsError(code, lib().mkws_last_error().decode("utf-8", "replace"))
     return code
+
+
+def indexed_device(device=None):
+    """The torch.device a handle lives on, always with its index ("cuda" and None mean the current device), so that it compares equal
+    to the .device of the tensors allocated there."""
+    import torch
+    d = torch.device(device if device is not None else "cuda")
+    if d.type == "cuda" and d.index is None:
+        d = torch.device("cuda", torch.cuda.current_device())
+    return d
 
 
 def current_stream_ptr():

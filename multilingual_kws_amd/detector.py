@@ -380,12 +380,9 @@ def detect_live_step(state, probs, meta, d_thresholds, average_window_duration_m
     THIS push.  scores: optional CUDA float64 [N, max_new].  Steps whose windows add up to a stream give, concatenated, detect_on_device
     on the whole stream byte for byte.  Asynchronous, allocation-free when `out` is passed in, one launch: capturable."""
     import torch
-    if probs.dim() != 3 or not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
+    if not torch.is_tensor(probs) or not probs.is_cuda:
         raise ValueError("probs must be a contiguous CUDA float32 tensor [heads, max_new, classes]")
-    N, max_new, C = probs.shape
-    T = int(d_thresholds.numel())
-    if d_thresholds.dtype != torch.float64 or not d_thresholds.is_cuda or meta.dtype != torch.int64 or meta.numel() < 2 + max_new:
-        raise ValueError("d_thresholds must be CUDA float64 [T] and meta CUDA int64 [2 + max_new]")
+    N, max_new, C, T = check_live_step(probs.device, state, probs, meta, d_thresholds, history, out, scores)
     if out is None:
         out = torch.zeros(live_out_words(N, T, max_new), dtype=torch.int64, device=probs.device)
     base = out.data_ptr()
@@ -395,6 +392,37 @@ def detect_live_step(state, probs, meta, d_thresholds, average_window_duration_m
             float(average_window_duration_ms), float(suppression_ms), int(minimum_count), int(bool(fired_only)), int(history),
             base + 8 * ((N * T + 1) // 2), base, scores.data_ptr() if scores is not None else None, _lib.current_stream_ptr()))
     return out
+
+
+def check_live_step(device, state, probs, meta, d_thresholds, history, out=None, scores=None):
+    """What detect_live_step refuses, decided before any device call -> (N, max_new, classes, T).  probs contiguous float32 [N, max_new,
+    classes]; d_thresholds contiguous float64 of T values; meta contiguous int64 of at least 2 + max_new elements; state a contiguous
+    int64 tensor of at least mkws_detect_live_state_bytes(N, T, history) bytes (a size of 0 for N > 0 = arguments the C call refuses in its
+    own words, before it looks at a buffer: the state's size is then not judged here); out (if given) contiguous int64 of at least
+    live_out_words(N, T, max_new) words; scores (if given) contiguous float64 of at least N * max_new values; all on `device`.
+    ValueError otherwise."""
+    import torch
+    from .frontend import _describe
+    if not torch.is_tensor(probs) or probs.dim() != 3 or probs.dtype != torch.float32 or not probs.is_contiguous() or probs.device != device:
+        raise ValueError(f"detect_live_step: probs must be a contiguous float32 tensor [heads, max_new, classes] on {device}, got {_describe(probs)}")
+    N, max_new, C = (int(v) for v in probs.shape)
+    if not torch.is_tensor(d_thresholds) or d_thresholds.dtype != torch.float64 or not d_thresholds.is_contiguous() or \
+            d_thresholds.device != device:
+        raise ValueError(f"detect_live_step: d_thresholds must be a contiguous float64 tensor [T] on {device}, got {_describe(d_thresholds)}")
+    T = int(d_thresholds.numel())
+    if not torch.is_tensor(meta) or meta.dtype != torch.int64 or meta.numel() < 2 + max_new or not meta.is_contiguous() or meta.device != device:
+        raise ValueError(f"detect_live_step: meta must be a contiguous int64 tensor [2 + max_new = {2 + max_new}] on {device}, got {_describe(meta)}")
+    need = _lib.lib().mkws_detect_live_state_bytes(N, T, int(history))
+    if not torch.is_tensor(state) or state.dtype != torch.int64 or not state.is_contiguous() or 8 * state.numel() < need or state.device != device:
+        raise ValueError(f"detect_live_step: state must be a contiguous int64 tensor of at least {(need + 7) // 8} words on {device} "
+                         f"(live_detector_state({N}, {T}, {int(history)})), got {_describe(state)}")
+    words = live_out_words(N, T, max_new)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.int64 or out.numel() < words or not out.is_contiguous() or out.device != device):
+        raise ValueError(f"detect_live_step: out must be a contiguous int64 tensor of {words} words (live_out_words) on {device}, got {_describe(out)}")
+    if scores is not None and (not torch.is_tensor(scores) or scores.dtype != torch.float64 or scores.numel() < N * max_new or not scores.is_contiguous()
+                               or scores.device != device):
+        raise ValueError(f"detect_live_step: scores must be a contiguous float64 tensor [{N}, {max_new}] on {device}, got {_describe(scores)}")
+    return N, max_new, C, T
 
 
 # Many streams in lockstep (mkws_detect_live_step_many): S detectors stepped in one launch.  The host specification is one
@@ -433,7 +461,7 @@ def detect_live_step_many(states, probs, meta, d_thresholds, average_window_dura
     For every stream this is detect_live_step on its own slice, byte for byte; a meta row with count == 0 leaves its stream as it is.
     Asynchronous, allocation-free when `out` is passed in, one launch for any S: capturable."""
     import torch
-    from .frontend import check_live_many
+    from .frontend import check_live_many, check_live_many_tensors
     if meta.dim() != 2 or meta.shape[1] < 2:
         raise ValueError("meta must be an int64 tensor [streams, 2 + max_new]")
     max_new = int(meta.shape[1]) - 2
@@ -448,12 +476,16 @@ def detect_live_step_many(states, probs, meta, d_thresholds, average_window_dura
     if d_thresholds.dtype != torch.float64 or not d_thresholds.is_cuda or meta.dtype != torch.int64 or not meta.is_cuda or not meta.is_contiguous():
         raise ValueError("d_thresholds must be CUDA float64 [T] and meta contiguous CUDA int64 [streams, 2 + max_new]")
     words = live_out_words_many(S, N, T, max_new)
-    if out is None:
-        out = torch.zeros(words, dtype=torch.int64, device=probs.device)
-    elif out.numel() != words or out.dtype != torch.int64 or not out.is_contiguous():
+    if out is not None and (out.numel() != words or out.dtype != torch.int64 or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous int64 tensor of {words} words (live_out_words_many)")
     if scores is not None and (scores.numel() != S * N * max_new or scores.dtype != torch.float64 or not scores.is_contiguous()):
         raise ValueError(f"scores must be a contiguous float64 tensor [{S}, {N}, {max_new}]")
+    check_live_many_tensors("detect_live_step_many", probs.device, states=(states, torch.int64), meta=(meta, torch.int64),
+                            d_thresholds=(d_thresholds, torch.float64), out=(out, torch.int64), scores=(scores, torch.float64))
+    if not d_thresholds.is_contiguous():
+        raise ValueError("detect_live_step_many: d_thresholds must be contiguous")
+    if out is None:                            # (nothing is allocated before everything the caller gave has been accepted)
+        out = torch.zeros(words, dtype=torch.int64, device=probs.device)
     base = out.data_ptr()
     with torch.cuda.device(probs.device):
         _lib.check(_lib.lib().mkws_detect_live_step_many(
@@ -529,6 +561,9 @@ def detect_live_step_routes(states, probs, meta, route_slot, d_thresholds, avera
     for name, t in (("probs", probs), ("meta", meta), ("route_slot", route_slot), ("d_thresholds", d_thresholds), ("states", states)):
         if not t.is_cuda:
             raise ValueError(f"{name} must be a CUDA tensor")
+    for name, t in (("meta", meta), ("route_slot", route_slot), ("d_thresholds", d_thresholds), ("states", states), ("out", out), ("scores", scores)):
+        if t is not None and t.device != probs.device:
+            raise ValueError(f"{name} must live on the device of probs ({probs.device}), not {t.device}")
     if out is None:
         out = torch.zeros(live_out_words_routes(R, T, max_new), dtype=torch.int64, device=probs.device)
     base = out.data_ptr()

@@ -17,6 +17,25 @@ OUTPUT_LAYERS = {"dense_2": ("dense_2", 1024), "dense_1": ("dense_1", 2048), "de
                  "global_average_pooling2d": ("gap", 1280)}
 
 
+def check_forward(output_dim, device, spec, out=None):
+    """What EmbeddingModel.forward refuses, decided before any device call: spec (a tensor, or anything numpy gives a shape; _prep
+    converts its dtype and device) shaped [B,49,40] or [B,49,40,1]; `out` (if given) a contiguous float32 tensor [rows >= B, output_dim]
+    on `device`: every chunk of max_batch rows is written through out[s:s + n], B * output_dim contiguous floats in all.  -> B.
+    ValueError otherwise."""
+    import torch
+    shape = tuple(spec.shape) if hasattr(spec, "shape") else np.shape(spec)
+    if len(shape) == 4 and shape[-1] == 1:
+        shape = shape[:-1]
+    if len(shape) != 3 or tuple(shape[1:]) != SPEC_SHAPE:
+        raise ValueError(f"EmbeddingModel.forward: spec must be [B,49,40] or [B,49,40,1], got {tuple(shape)}")
+    B = int(shape[0])
+    if out is not None and (not torch.is_tensor(out) or out.dim() != 2 or out.shape[1] != output_dim or out.shape[0] < B or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.device != device):
+        got = f"{out.dtype} {tuple(out.shape)} (strides {out.stride()}) on {out.device}" if torch.is_tensor(out) else type(out).__name__
+        raise ValueError(f"EmbeddingModel.forward: out must be a contiguous float32 tensor [{B}, {output_dim}] on {device}, got {got}")
+    return B
+
+
 class EmbeddingModel:
     def __init__(self, weight_blob, max_batch=1024, device=None, output="dense_2"):
         import torch
@@ -25,7 +44,7 @@ class EmbeddingModel:
         self.output, (self.output_stage, self.output_dim) = output, OUTPUT_LAYERS[output]
         self.L = _lib.lib()
         blob = np.ascontiguousarray(weight_blob, dtype=np.float32)
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.indexed_device(device)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.L.mkws_embed_create(blob.ctypes.data, blob.shape[0], int(max_batch), ctypes.byref(h)))
@@ -78,8 +97,8 @@ class EmbeddingModel:
     def forward(self, spec, out=None):
         """spec CUDA tensor [B,49,40(,1)] -> CUDA tensor [B,1024].  B may exceed max_batch (chunked)."""
         import torch
+        B = check_forward(self.output_dim, self.device, spec, out)
         spec = self._prep(spec)
-        B = spec.shape[0]
         emb = out if out is not None else torch.empty((B, self.output_dim), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             for s in range(0, B, self.max_batch):

@@ -38,6 +38,38 @@ def _down(h, w, k):
     return (h + pt + k // 2 - k) // 2 + 1, (w + pl + k // 2 - k) // 2 + 1, pt, pl
 
 
+def check_forward_train(device, spec, drop_masks=None, keep_scales=None):
+    """What EmbeddingTrainer.forward_train refuses, decided before any device call: spec a tensor [B,49,40] or [B,49,40,1] (its dtype and
+    device are converted by the wrapper; the stem kernel reads 49 x 40 values per row); every value of keep_scales a float32 vector [B] on
+    `device` (the residual kernels read B floats through it as it is; a strided one is made contiguous by the wrapper); every value of
+    drop_masks a flat list, array or tensor of B entries (the wrapper converts and uploads it).  -> B.  ValueError otherwise."""
+    import torch
+    shape = tuple(spec.shape) if torch.is_tensor(spec) else None
+    if shape is not None and len(shape) == 4 and shape[-1] == 1:
+        shape = shape[:-1]
+    if shape is None or len(shape) != 3 or shape[1:] != (49, 40):
+        raise ValueError(f"EmbeddingTrainer.forward_train: spec must be a tensor [B,49,40] or [B,49,40,1], got {shape if shape is not None else type(spec).__name__}")
+    B = int(shape[0])
+    for name, t in (keep_scales or {}).items():
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (B,) or t.device != device:
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"EmbeddingTrainer.forward_train: keep_scales[{name!r}] must be a float32 vector [{B}] on {device}, got {got}")
+    for name, m in (drop_masks or {}).items():
+        got = tuple(m.shape) if hasattr(m, "shape") else np.shape(m)
+        if tuple(got) != (B,):
+            raise ValueError(f"EmbeddingTrainer.forward_train: drop_masks[{name!r}] must hold {B} entries, one per row of spec, got {tuple(got)}")
+    return B
+
+
+def check_backward(B, d_emb):
+    """What EmbeddingTrainer.backward refuses, decided before any device call: d_emb a tensor [B, 1024] with the B of the forward_train()
+    batch (its dtype and device are converted by the wrapper; the sweep reads B x 1024 values).  ValueError otherwise."""
+    import torch
+    if not torch.is_tensor(d_emb) or tuple(d_emb.shape) != (int(B), 1024):
+        got = tuple(d_emb.shape) if torch.is_tensor(d_emb) else type(d_emb).__name__
+        raise ValueError(f"EmbeddingTrainer.backward: d_emb must be a tensor [{int(B)}, 1024], the batch of forward_train(), got {got}")
+
+
 class EmbeddingTrainer(OpTape):
     def __init__(self, weight_blob, device=None, scratch=None, scratch_side=None):
         """scratch / scratch_side: caller-provided arenas (contiguous one-dimensional float32 tensors on the device) for the fixed-order
@@ -215,12 +247,12 @@ class EmbeddingTrainer(OpTape):
         keep_scales: the same information as device tensors {block name: float32 [B] = kept / (1 - rate)} that the caller owns and
         refills between steps (what a graph-replayed step needs: no host-to-device traffic inside the step)."""
         torch = self.torch
+        B = check_forward_train(self.device, spec, drop_masks, keep_scales)
         self.bind()
         spec = spec.to(self.device, dtype=torch.float32)
         if spec.dim() == 4:
             spec = spec[..., 0]
         spec = spec.contiguous()
-        B = spec.shape[0]
         if self._pool_B != B:
             self._pool, self._pool_B = [], B
         self._pool_pos = 0
@@ -298,6 +330,7 @@ class EmbeddingTrainer(OpTape):
         tape = self.tape
         if tape is None:
             raise RuntimeError("backward() needs a forward_train() first")
+        check_backward(tape["B"], d_emb)
         self.bind()
         # second stages of the gradient reductions wait in a queue and run a batch at a time (mkws_op_fold_defer): nobody reads a weight
         # gradient before the all-reduce / the optimizer

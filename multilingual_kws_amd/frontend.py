@@ -68,13 +68,12 @@ class Frontend:
         """audio: CUDA tensor [B, n] float32 in [-1,1] or int16 PCM -> float32 [B, frames, channels]
         (= to_micro_spectrogram); with want_raw also the op's raw integers (int16 storage of uint16)."""
         import torch
-        if not audio.is_cuda:
+        if not torch.is_tensor(audio) or not audio.is_cuda:
             raise ValueError("Frontend.forward needs a CUDA tensor (no CPU path)")
+        B, n, F = check_forward(self.cfg, audio.device, audio, out)
         if audio.dim() == 1:
             audio = audio[None]
         audio = audio.contiguous()
-        B, n = audio.shape
-        F = num_frames(self.cfg, n)
         spec = out if out is not None else torch.empty((B, F, self.num_channels), dtype=torch.float32, device=audio.device)
         raw = torch.empty((B, F, self.num_channels), dtype=torch.int16, device=audio.device) if want_raw else None
         rp = ctypes.c_void_p(raw.data_ptr()) if want_raw else None
@@ -95,10 +94,10 @@ class Frontend:
         """One long recording [n] float32 -> [num_windows, frames, channels], window w covering
         samples [w*hop, w*hop+window) -- batch_streaming_analysis.py:99-117 with frame sharing."""
         import torch
+        if not torch.is_tensor(audio) or not audio.is_cuda:
+            raise ValueError("Frontend.stream: audio must be a CUDA tensor (no CPU path)")
+        n, F, nw = check_stream(self.cfg, audio.device, audio, window_samples, hop_samples)
         audio = audio.contiguous()
-        n = audio.shape[0]
-        F = num_frames(self.cfg, window_samples)
-        nw = 0 if n < window_samples else 1 + (n - window_samples) // hop_samples
         spec = torch.empty((nw, F, self.num_channels), dtype=torch.float32, device=audio.device)
         raw = torch.empty((nw, F, self.num_channels), dtype=torch.int16, device=audio.device) if want_raw else None
         if nw > 0:
@@ -129,9 +128,11 @@ class Frontend:
         (static buffers of a captured graph), and the state advances on the device: a replay is a push."""
         import torch
         h = int(hops_per_push)
-        if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.numel() != h * int(hop_samples):
-            raise ValueError(f"live_push takes a contiguous CUDA float32 tensor of {h} x {int(hop_samples)} new samples")
-        F = num_frames(self.cfg, window_samples)
+        if not torch.is_tensor(audio) or not audio.is_cuda:
+            raise ValueError(f"live_push: audio must be a contiguous CUDA float32 tensor of {h} x {int(hop_samples)} new samples")
+        # (a size of 0 = a geometry the push refuses: the C call says why, before it looks at a buffer)
+        need = self.L.mkws_frontend_live_state_bytes(self.h, int(window_samples), int(hop_samples), h)
+        F = check_live_push(self.cfg, audio.device, need, state, audio, window_samples, hop_samples, h, spec, raw, meta)
         if spec is None:
             spec = torch.zeros((h, F, self.num_channels), dtype=torch.float32, device=audio.device)
         if raw is None and want_raw:
@@ -172,15 +173,17 @@ class Frontend:
         if active is not None and (not active.is_cuda or active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != S):
             raise ValueError(f"active must be a contiguous CUDA int32 tensor [{S}]")
         F = num_frames(self.cfg, window_samples)
-        if spec is None:
+        for name, t, n in (("spec", spec, S * h * F * self.num_channels), ("raw", raw, S * h * F * self.num_channels), ("meta", meta, S * (2 + h))):
+            if t is not None and (t.numel() != n or not t.is_contiguous()):
+                raise ValueError(f"{name} must be contiguous with {n} elements")
+        check_live_many_tensors("live_push_many", audio.device, states=(states, torch.int64), active=(active, torch.int32), spec=(spec, torch.float32),
+                                raw=(raw, torch.int16), meta=(meta, torch.int64))
+        if spec is None:                       # (nothing is allocated before everything the caller gave has been accepted)
             spec = torch.zeros((S * h, F, self.num_channels), dtype=torch.float32, device=audio.device)
         if raw is None and want_raw:
             raw = torch.zeros((S * h, F, self.num_channels), dtype=torch.int16, device=audio.device)
         if meta is None:
             meta = torch.zeros((S, 2 + h), dtype=torch.int64, device=audio.device)
-        for name, t, n in (("spec", spec, S * h * F * self.num_channels), ("raw", raw, S * h * F * self.num_channels), ("meta", meta, S * (2 + h))):
-            if t is not None and (t.numel() != n or not t.is_contiguous()):
-                raise ValueError(f"{name} must be contiguous with {n} elements")
         with torch.cuda.device(audio.device):
             _lib.check(self.L.mkws_frontend_live_push_many_f32(
                 self.h, ctypes.c_void_p(states.data_ptr()), 8 * int(states.stride(0)), S,
@@ -188,6 +191,62 @@ class Frontend:
                 int(window_samples), int(hop_samples), h, ctypes.c_void_p(spec.data_ptr()),
                 ctypes.c_void_p(raw.data_ptr()) if raw is not None else None, ctypes.c_void_p(meta.data_ptr()), _lib.current_stream_ptr()))
         return spec, raw, meta
+
+
+def _describe(t):
+    import torch
+    return f"{t.dtype} {tuple(t.shape)} (strides {t.stride()}) on {t.device}" if torch.is_tensor(t) else type(t).__name__
+
+
+def check_forward(cfg, device, audio, out=None):
+    """What Frontend.forward refuses, decided before any device call: audio a float32 or int16 tensor [B, n] or [n] on `device` (a
+    strided view is made contiguous by the wrapper; TypeError for another dtype); `out` (if given) a contiguous float32 tensor
+    [rows >= B, frames, channels] on `device`.  -> (B, n, frames).  ValueError otherwise."""
+    import torch
+    if not torch.is_tensor(audio) or audio.dim() not in (1, 2) or audio.device != device:
+        raise ValueError(f"Frontend.forward: audio must be a tensor [B, n] or [n] on {device}, got {_describe(audio)}")
+    if audio.dtype not in (torch.float32, torch.int16):
+        raise TypeError(f"audio must be float32 or int16, got {audio.dtype}")
+    B, n = (1, int(audio.shape[0])) if audio.dim() == 1 else (int(audio.shape[0]), int(audio.shape[1]))
+    F = num_frames(cfg, n)
+    C = cfg.num_channels
+    if out is not None and (not torch.is_tensor(out) or out.dim() != 3 or tuple(out.shape[1:]) != (F, C) or out.shape[0] < B or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.device != device):
+        raise ValueError(f"Frontend.forward: out must be a contiguous float32 tensor [{B}, {F}, {C}] on {device}, got {_describe(out)}")
+    return B, n, F
+
+
+def check_stream(cfg, device, audio, window_samples, hop_samples):
+    """What Frontend.stream refuses, decided before any device call: audio a float32 vector [n] on `device` (a strided view is made
+    contiguous by the wrapper), a window and a hop of at least one sample.  -> (n, frames, num_windows).  ValueError otherwise."""
+    import torch
+    if not torch.is_tensor(audio) or audio.dim() != 1 or audio.dtype != torch.float32 or audio.device != device:
+        raise ValueError(f"Frontend.stream: audio must be a float32 vector [n] on {device}, got {_describe(audio)}")
+    if int(window_samples) < 1 or int(hop_samples) < 1:
+        raise ValueError(f"Frontend.stream: window_samples={window_samples}, hop_samples={hop_samples}")
+    n = int(audio.shape[0])
+    return n, num_frames(cfg, int(window_samples)), live_windows(n, int(window_samples), int(hop_samples))
+
+
+def check_live_push(cfg, device, state_bytes, state, audio, window_samples, hop_samples, hops_per_push, spec=None, raw=None, meta=None):
+    """What Frontend.live_push refuses, decided before any device call.  state_bytes: mkws_frontend_live_state_bytes for this geometry (0: the
+    geometry itself is refused by the C call, and the state's size is not judged here).  state a contiguous int64 tensor of at least
+    state_bytes bytes; audio a contiguous float32 tensor of hops_per_push * hop_samples samples; spec (if given) contiguous float32 and raw
+    (if given) contiguous int16 of at least hops_per_push * frames * channels elements; meta (if given) contiguous int64 of at least
+    2 + hops_per_push elements; all on `device`.  -> frames.  ValueError otherwise."""
+    import torch
+    h = int(hops_per_push)
+    if not torch.is_tensor(audio) or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.numel() != h * int(hop_samples) or audio.device != device:
+        raise ValueError(f"live_push: audio must be a contiguous float32 tensor of {h} x {int(hop_samples)} new samples on {device}, got {_describe(audio)}")
+    if not torch.is_tensor(state) or state.dtype != torch.int64 or not state.is_contiguous() or 8 * state.numel() < int(state_bytes) or state.device != device:
+        raise ValueError(f"live_push: state must be a contiguous int64 tensor of at least {(int(state_bytes) + 7) // 8} words on {device} (live_state), "
+                         f"got {_describe(state)}")
+    F = num_frames(cfg, int(window_samples))
+    rows = h * F * cfg.num_channels
+    for name, t, dtype, n in (("spec", spec, torch.float32, rows), ("raw", raw, torch.int16, rows), ("meta", meta, torch.int64, 2 + h)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous() or t.numel() < n or t.device != device):
+            raise ValueError(f"live_push: {name} must be a contiguous {dtype} tensor of {n} elements on {device}, got {_describe(t)}")
+    return F
 
 
 def check_live_many(states, shape, row, what):
@@ -200,6 +259,15 @@ def check_live_many(states, shape, row, what):
                          "(live_state_many / live_detector_state_many)")
     if shape is None or tuple(shape) != (int(states.shape[0]), int(row)):
         raise ValueError(f"{what} must have the shape [{int(states.shape[0])}, {int(row)}]: one row per stream of the state tensor")
+
+
+def check_live_many_tensors(who, device, **tensors):
+    """name=(tensor or None, dtype): what a many-stream call still has to refuse once shapes and strides are settled -- a tensor of another
+    dtype, or one that does not live on `device` (the kernel would read it as `dtype` through a pointer of another device, or of the host).
+    ValueError naming it."""
+    for name, (t, dtype) in tensors.items():
+        if t is not None and (t.dtype != dtype or t.device != device):
+            raise ValueError(f"{who}: {name} must be a {dtype} tensor on {device}, got {t.dtype} on {t.device}")
 
 
 def live_windows(n_samples, window_samples, hop_samples):

@@ -25,7 +25,7 @@ class Head:
         import torch
         self.L = _lib.lib()
         self.in_dim, self.hidden, self.classes = in_dim, hidden, classes
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.indexed_device(device)
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.L.mkws_head_create(in_dim, hidden, classes, int(max_batch), ctypes.byref(h)))
@@ -92,8 +92,8 @@ class Head:
     def forward(self, emb):
         """emb CUDA [B,in] -> probs CUDA [B,classes]."""
         import torch
+        B = check_forward(self.in_dim, self.device, emb)
         emb = emb.contiguous()
-        B = emb.shape[0]
         probs = torch.empty((B, self.classes), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.L.mkws_head_forward(self.h, ctypes.c_void_p(emb.data_ptr()), B, ctypes.c_void_p(probs.data_ptr()),
@@ -106,8 +106,8 @@ class Head:
         (multi-keyword serving on a shared embedding pass)."""
         import torch
         heads = list(heads)
+        _, B = check_forward_many(heads, emb)
         emb = emb.contiguous()
-        B = emb.shape[0]
         h0 = heads[0]
         probs = torch.empty((len(heads), B, h0.classes), dtype=torch.float32, device=h0.device)
         table = (ctypes.c_void_p * len(heads))(*[h.h.value for h in heads])
@@ -120,11 +120,12 @@ class Head:
         """Fills the grad buffer with d(mean CE over these rows)/d(params); returns a CUDA tensor
         [2] = {sum of row losses, number correct} (asynchronous; .tolist() syncs)."""
         import torch
+        B = check_loss_grad(self.in_dim, self.device, emb, labels)
         emb = emb.contiguous()
         labels = labels.to(torch.int32).contiguous()
         with torch.cuda.device(self.device):
             _lib.check(self.L.mkws_head_loss_grad(self.h, ctypes.c_void_p(emb.data_ptr()), ctypes.c_void_p(labels.data_ptr()),
-                                                  emb.shape[0], ctypes.c_void_p(self._stats.data_ptr()), _lib.current_stream_ptr()))
+                                                  B, ctypes.c_void_p(self._stats.data_ptr()), _lib.current_stream_ptr()))
         return self._stats
 
     def input_grad(self, B):
@@ -142,6 +143,7 @@ class Head:
     def adam_step_dev(self, lr, d_step, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
         """Adam with the step index read from the int32 device tensor d_step (graph-replayed steps: embedding_trainer.TrainStepGraph)."""
         import torch
+        check_adam_step_dev(self.device, d_step)
         with torch.cuda.device(self.device):
             _lib.check(self.L.mkws_head_adam_step_dev(self.h, lr, beta1, beta2, eps, ctypes.c_void_p(d_step.data_ptr()), grad_scale, _lib.current_stream_ptr()))
 
@@ -150,6 +152,69 @@ class Head:
         self.step_t += 1
         with torch.cuda.device(self.device):
             _lib.check(self.L.mkws_head_adam_step(self.h, lr, beta1, beta2, eps, self.step_t, grad_scale, _lib.current_stream_ptr()))
+
+
+def _check_emb(who, in_dim, device, emb):
+    """emb as the single-head kernels read it once the wrapper has made it contiguous: a float32 tensor [B, in_dim] on `device` (any
+    strides).  -> B."""
+    import torch
+    if not torch.is_tensor(emb) or emb.dim() != 2 or emb.shape[1] != in_dim or emb.dtype != torch.float32 or emb.device != device:
+        got = f"{emb.dtype} {tuple(emb.shape)} on {emb.device}" if torch.is_tensor(emb) else type(emb).__name__
+        raise ValueError(f"{who}: emb must be a float32 tensor [B, {in_dim}] on {device}, got {got}")
+    return int(emb.shape[0])
+
+
+def check_forward(in_dim, device, emb, who="Head.forward"):
+    """What Head.forward refuses, decided before any device call: emb a float32 tensor [B, in_dim] on `device` (a strided view is made
+    contiguous by the wrapper).  -> B.  ValueError otherwise."""
+    return _check_emb(who, in_dim, device, emb)
+
+
+def check_forward_many(heads, emb):
+    """What Head.forward_many refuses, decided before any device call: `heads` a non-empty list of open heads (objects with in_dim,
+    hidden, classes, device and a handle h) of equal dimensions on one device, emb as check_forward for them.  -> (N, B).  ValueError
+    otherwise."""
+    if len(heads) == 0:
+        raise ValueError("Head.forward_many: heads is empty")
+    if any(getattr(hd, "h", None) is None for hd in heads):
+        raise ValueError("Head.forward_many: a head in heads is closed")
+    h0 = heads[0]
+    for k, hd in enumerate(heads):
+        if (hd.in_dim, hd.hidden, hd.classes) != (h0.in_dim, h0.hidden, h0.classes):
+            # (the library refuses this too, and callers caught its error before the wrapper looked: both at once)
+            raise _lib.MkwsValueError(f"Head.forward_many: heads[{k}] is {hd.in_dim} x {hd.hidden} x {hd.classes}, heads[0] {h0.in_dim} x {h0.hidden} x "
+                                      f"{h0.classes}: the heads must have equal dimensions")
+        if hd.device != h0.device:
+            raise ValueError(f"Head.forward_many: heads[{k}] lives on {hd.device}, heads[0] on {h0.device}")
+    return len(heads), _check_emb("Head.forward_many", h0.in_dim, h0.device, emb)
+
+
+def _check_labels(who, device, labels, B):
+    """labels as the loss kernels read them once the wrapper has converted them to contiguous int32: an integer tensor [B] on `device`."""
+    import torch
+    if not torch.is_tensor(labels) or labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or \
+            labels.device != device:
+        got = f"{labels.dtype} {tuple(labels.shape)} on {labels.device}" if torch.is_tensor(labels) else type(labels).__name__
+        raise ValueError(f"{who}: labels must be an integer vector [B] on {device}, got {got}")
+    if int(labels.shape[0]) != B:
+        raise ValueError(f"{who}: {int(labels.shape[0])} labels for the {B} rows of emb")
+
+
+def check_loss_grad(in_dim, device, emb, labels, who="Head.loss_grad"):
+    """What Head.loss_grad refuses, decided before any device call: emb as check_forward; labels an integer tensor [B] on `device` (the
+    wrapper converts it to contiguous int32 there), one label per row of emb.  -> B.  ValueError otherwise."""
+    B = _check_emb(who, in_dim, device, emb)
+    _check_labels(who, device, labels, B)
+    return B
+
+
+def check_adam_step_dev(device, d_step):
+    """What Head.adam_step_dev refuses, decided before any device call: d_step an int32 tensor of one element on `device` (the kernel
+    reads the step index through it).  ValueError otherwise."""
+    import torch
+    if not torch.is_tensor(d_step) or d_step.dtype != torch.int32 or d_step.numel() != 1 or d_step.device != device:
+        got = f"{d_step.dtype} {tuple(d_step.shape)} on {d_step.device}" if torch.is_tensor(d_step) else type(d_step).__name__
+        raise ValueError(f"Head.adam_step_dev: d_step must be an int32 tensor of one element on {device}, got {got}")
 
 
 def check_forward_routes(in_dim, classes, device, emb, route_slot, route_head, rows_per_slot, n_slots, out=None, invalid=None):

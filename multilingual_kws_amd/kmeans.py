@@ -192,6 +192,18 @@ def kmeans_fit_on_device(x, offsets, n_clusters, seeds, max_iter=300, tol=1e-4, 
                      out.device("centers"))
 
 
+def check_nearest_out(rows, device, out):
+    """What nearest_on_device refuses of `out`, decided before any device call: three tensors on `device` -- dist contiguous float32 and
+    which contiguous int32 of `rows` elements each, invalid int32 of one element.  ValueError otherwise."""
+    import torch
+    if not isinstance(out, (tuple, list)) or len(out) != 3 or not all(torch.is_tensor(t) for t in out):
+        raise ValueError("out must be the three tensors (dist, which, invalid)")
+    for name, t, dtype, n in (("dist", out[0], torch.float32, int(rows)), ("which", out[1], torch.int32, int(rows)), ("invalid", out[2], torch.int32, 1)):
+        if t.dtype != dtype or t.numel() != n or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"out: {name} must be a contiguous {dtype} tensor of {n} elements on {device}, got {t.dtype} {tuple(t.shape)} "
+                             f"(strides {t.stride()}) on {t.device}")
+
+
 def nearest_on_device(x, group, centers, out=None):
     """x: CUDA tensor [rows, dim] float32; group: CUDA tensor or array int32 [rows]; centers: CUDA tensor [G, k, dim] float32.
     -> (dist float32 [rows], which int32 [rows], invalid int32 [1]) CUDA tensors (`out`: the three to write into).  Asynchronous: nothing
@@ -207,7 +219,13 @@ def nearest_on_device(x, group, centers, out=None):
     if not 1 <= k <= MAX_CLUSTERS:
         raise ValueError(f"n_clusters {k} outside [1, {MAX_CLUSTERS}]")
     dev = x.device
-    if not torch.is_tensor(group):
+    if centers.device != dev:
+        raise ValueError(f"centers must live on the device of x ({dev}), not {centers.device}")
+    if out is not None:
+        check_nearest_out(rows, dev, out)
+    if not torch.is_tensor(group):                 # (uploaded only once everything else the caller gave has been accepted)
+        if np.size(group) != rows:
+            raise ValueError("group must hold one int32 per row, on the device of x")
         group = torch.from_numpy(np.ascontiguousarray(group, dtype=np.int32)).to(dev, non_blocking=True)
     if group.dtype != torch.int32 or group.numel() != rows or group.device != dev:
         raise ValueError("group must hold one int32 per row, on the device of x")
@@ -217,8 +235,6 @@ def nearest_on_device(x, group, centers, out=None):
             out = (torch.empty(rows, dtype=torch.float32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
                    torch.zeros(1, dtype=torch.int32, device=dev))
         dist, which, invalid = out
-        if dist.numel() != rows or which.numel() != rows or not (dist.is_contiguous() and which.is_contiguous()):
-            raise ValueError("out must hold one contiguous value per row")
         _lib.check(_lib.lib().mkws_kmeans_nearest(x.data_ptr(), dim, rows, group.data_ptr(), centers.data_ptr() if G else None, G, k,
                                                   dist.data_ptr(), which.data_ptr(), invalid.data_ptr(), _lib.current_stream_ptr()))
     return dist, which, invalid

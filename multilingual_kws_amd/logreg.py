@@ -209,6 +209,8 @@ def score_on_device(x, rows, true, offsets, coef, intercept, want_probs=False, w
     if not 2 <= K <= MAX_CLASSES or not 1 <= dim <= MAX_DIM:
         raise ValueError(f"n_classes {K} outside [2, {MAX_CLASSES}] or dim {dim} outside [1, {MAX_DIM}]")
     dev = x.device
+    if coef.device != dev or intercept.device != dev:
+        raise ValueError(f"coef and intercept must live on the device of x ({dev}), not {coef.device} / {intercept.device}")
     d_rows, d_true, d_off = (problems.device_int_list(a, name, dev) for name, a in (("rows", rows), ("true", true), ("offsets", offsets)))
     total = int(d_rows.numel())
     if d_true.numel() != total or d_off.numel() != P + 1:

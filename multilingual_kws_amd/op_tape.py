@@ -27,7 +27,7 @@ class OpTape:
         """scratch: the caller's arena for the fixed-order reductions (mkws_train_ctx), None allocates scratch_floats floats."""
         import torch
         self.torch, self.L = torch, _lib.lib()
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device = _lib.indexed_device(device)
         self._stream = None
         self._views, self._ptrs, self._bn = {}, {}, {}
         # the tape's own operator context (arena + deferred-fold queue): independent of other tapes on this thread and of the thread it

@@ -115,8 +115,9 @@ class Resampler:
         n_out = self.out_samples(n)
         if out is None:
             out = torch.empty((B, n_out), dtype=torch.float32, device=rows.device)
-        elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, n_out) or (n_out > 1 and out.stride(1) != 1):
-            raise ValueError(f"out must be a CUDA float32 tensor [{B}, {n_out}] with contiguous rows")
+        elif not out.is_cuda or out.device != rows.device or out.dtype != torch.float32 or tuple(out.shape) != (B, n_out) or (n_out > 1 and out.stride(1) != 1) \
+                or (B > 1 and out.stride(0) < n_out):
+            raise ValueError(f"out must be a CUDA float32 tensor [{B}, {n_out}] with contiguous rows that do not overlap, on the device of audio")
         if B and n:
             with torch.cuda.device(rows.device):
                 _lib.check(self.L.mkws_resample_forward(
@@ -150,7 +151,7 @@ class Resampler:
         [S, out_samples], the next out_samples causal output samples of each active stream (the rows of the others are untouched).
         Asynchronous, allocation-free when out is passed in, one launch for any S."""
         import torch
-        from .frontend import check_live_many
+        from .frontend import check_live_many, check_live_many_tensors
         n_in = self.live_in_samples(out_samples)
         check_live_many(states, audio.shape if audio.dim() == 2 else None, n_in, "audio")
         S = int(states.shape[0])
@@ -158,10 +159,11 @@ class Resampler:
             raise ValueError(f"live_push_many takes a contiguous CUDA float32 or int16 tensor [{S}, {n_in}] of new samples")
         if active is not None and (not active.is_cuda or active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != S):
             raise ValueError(f"active must be a contiguous CUDA int32 tensor [{S}]")
-        if out is None:
-            out = torch.zeros((S, int(out_samples)), dtype=torch.float32, device=audio.device)
-        elif not out.is_cuda or out.dtype != torch.float32 or out.numel() != S * int(out_samples) or not out.is_contiguous():
+        if out is not None and (not out.is_cuda or out.dtype != torch.float32 or out.numel() != S * int(out_samples) or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous CUDA float32 tensor of {S} x {int(out_samples)} samples")
+        check_live_many_tensors("live_push_many", audio.device, states=(states, torch.int64), active=(active, torch.int32), out=(out, torch.float32))
+        if out is None:                        # (nothing is allocated before everything the caller gave has been accepted)
+            out = torch.zeros((S, int(out_samples)), dtype=torch.float32, device=audio.device)
         with torch.cuda.device(audio.device):
             _lib.check(self.L.mkws_resample_live_push_many(
                 self.h, ctypes.c_void_p(states.data_ptr()), 8 * int(states.stride(0)), S,

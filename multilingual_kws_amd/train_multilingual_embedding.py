@@ -23,7 +23,7 @@ import pickle
 
 import numpy as np
 
-from . import _lib, parallel, weights
+from . import _lib, head, parallel, weights
 from .embedding_model import EmbeddingModel
 from .embedding_trainer import ACT_NONE, EmbeddingTrainer, drop_connect_rates
 from .op_tape import OpTape
@@ -57,8 +57,9 @@ class LogitsLayer(OpTape):
 
     def forward(self, emb):
         """emb CUDA [B, in] -> logits CUDA [B, N]."""
-        torch, emb = self.torch, emb.contiguous()
-        B = emb.shape[0]
+        torch = self.torch
+        B = head.check_forward(self.in_dim, self.device, emb, who="LogitsLayer.forward")
+        emb = emb.contiguous()
         self.bind()
         Z, A = torch.empty((B, self.n), device=self.device), torch.empty((B, self.n), device=self.device)
         _lib.check(self.L.mkws_op_dense_fwd(self._p(emb), self.P("logits/kernel"), self.P("logits/bias"), ACT_NONE, self._p(Z), self._p(A), B, self.n, self.in_dim,
@@ -69,8 +70,8 @@ class LogitsLayer(OpTape):
         """Mean sparse CE from logits over these rows: fills the gradient buffer, returns (stats [sum of row losses, #correct],
         d(mean loss)/d(emb) [B, in])."""
         torch = self.torch
+        B = head.check_loss_grad(self.in_dim, self.device, emb, labels, who="LogitsLayer.loss_grad")
         emb = emb.contiguous()
-        B = emb.shape[0]
         logits = self.forward(emb)                                    # becomes d(mean loss)/d(logits)
         rowstat, d_emb = torch.empty((B, 2), device=self.device), torch.empty((B, self.in_dim), device=self.device)
         self.dense_ce_bwd(emb, logits, logits, labels.to(torch.int32).contiguous(), B, self.in_dim, self.n, "logits", rowstat, self._stats, d_emb)
