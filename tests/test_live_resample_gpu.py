@@ -154,28 +154,30 @@ def _models(max_batch):
     return [tl.TransferLearnedModel(emb, Head(max_batch=max_batch, seed=s), blob, "synthetic") for s in (1, 2, 3)]
 
 
-def test_live_session_at_48k():
-    """LiveSession(input_rate=48000) fed 48 kHz audio in ragged chunks = the session without input_rate, on the same handle, fed the
-    causal conversion of the same audio: the same rows, the same records (scores bit-equal)."""
-    models = _models(1)
-    x = _speechlike(48000, 2.0, 3)
-    x[:4800] = (np.round(x[:4800] * 32768) / 32768).astype(np.float32)      # the first chunk is also fed as int16 PCM
-    rs = Resampler(48000)
+def _session_against_converted(rate, push, hops, delay_ms):
+    """LiveSession(input_rate=rate, hops_per_push=hops) fed audio at `rate` in ragged chunks = the session without input_rate, on the same
+    handle, fed the causal conversion of the same audio: the same rows, the same records (scores bit-equal)."""
+    models = _models(hops)
+    x = _speechlike(rate, 2.0, 3)
+    first = 5 * push
+    x[:first] = (np.round(x[:first] * 32768) / 32768).astype(np.float32)     # the first chunk is also fed as int16 PCM
+    rs = Resampler(rate)
     y = rs.forward(x, centred=False)
     assert y.shape == (32000,)
-    plain = bsa.LiveSession(models, THRESHOLDS, fired_only=False)
+    plain = bsa.LiveSession(models, THRESHOLDS, fired_only=False, hops_per_push=hops)
     assert not hasattr(plain, "resampler")
     want_rows, want_records = [], []
     for at in range(0, y.size, 1280):
         want_rows += plain.feed(y[at:at + 1280])
         want_records += plain.last_records
     assert plain.windows_seen == 51 and len(want_records) >= 3
-    sess = bsa.LiveSession(models, THRESHOLDS, fired_only=False, input_rate=48000)
-    assert sess.resampler.delay_ms == 2.0 and sess.in_push_samples == 960 and sess.graph is not None
+    sess = bsa.LiveSession(models, THRESHOLDS, fired_only=False, input_rate=rate, hops_per_push=hops)
+    assert sess.resampler.delay_ms == delay_ms and sess.graph is not None
+    assert sess.in_push_samples == push and sess.push_samples == HOP * hops
     import torch
     for as_i16 in (False, True):
         rows, records, at = [], [], 0
-        sizes = [4800, 1, 959, 960, 12345, 7, 30000]
+        sizes = [first, 1, push - 1, push, 12 * push + 825, 7, 31 * push + 240]
         k = 0
         while at < x.size:
             n = sizes[k % len(sizes)]
@@ -188,13 +190,50 @@ def test_live_session_at_48k():
             records += sess.last_records
             at += n
             k += 1
-            assert sess.samples_seen == min(at, x.size) and sess.windows_seen == max(0, (min(at, x.size) // 960 * 320 - 16000) // 320 + 1)
+            assert sess.samples_seen == min(at, x.size)
+            assert sess.windows_seen == max(0, (min(at, x.size) // push * HOP * hops - 16000) // 320 + 1)
         assert rows == want_rows and records == want_records
-        assert sess.windows_seen == 51 and sess.samples_seen == 96000
+        assert sess.windows_seen == 51 and sess.samples_seen == 2 * rate
         sess.reset()
         assert sess.samples_seen == 0 and not bool(sess.rstate.any().cpu())
     for s in (sess, plain):
         s.close()
+    rs.close()
+
+
+@pytest.mark.parametrize("rate,push", [(48000, 960), (22050, 441), (96000, 1920)])
+def test_live_session_at_48k(rate, push):
+    """At 48 kHz (chunks of 4800, 1, 959, 960, 12345, 7 and 30000 samples), at 22 050 Hz (L = 320) and at 96 kHz (a history of 384
+    samples, longer than the resampler's workgroup)."""
+    _session_against_converted(rate, push, 1, 2.0)
+
+
+def test_live_session_at_11025_with_two_hops_per_push():
+    """The session the refusal of LiveSession(input_rate=11025) recommends (test_live_session_input_rate_of_the_model_changes_nothing):
+    hops_per_push=2, pushes of 441 samples for 640; the delay is 32 / 11025 s, half / (L * rate_in)."""
+    _session_against_converted(11025, 441, 2, 1000.0 * 20480 / (640 * 11025))
+
+
+@pytest.mark.parametrize("rate", [22050, 96000])
+def test_read_wav_at_other_rates(rate, tmp_path):
+    """input_data.read_wav_at on a WAV at `rate` = Resampler(rate).forward(centred=True) over the decoded file, which
+    tests/test_resample_geometries_gpu.py holds to the emulator."""
+    from multilingual_kws_amd import synth
+    from multilingual_kws_amd.embedding import input_data
+    pcm = np.round(_speechlike(rate, 0.5, 8) * 20000).astype(np.int16)
+    path = str(tmp_path / f"clip_{rate}.wav")
+    with open(path, "wb") as fh:
+        fh.write(synth.wav_bytes(pcm, rate=rate))
+    with open(path, "rb") as fh:
+        x, got_rate = input_data.decode_wav(fh.read())
+    assert got_rate == rate and np.array_equal(x, pcm.astype(np.float32) / np.float32(32768))
+    rs = Resampler(rate)
+    want = rs.forward(x, centred=True)
+    assert want.shape == (8000,) and want.dtype == np.float32 and np.abs(want).max() > 0.1
+    assert np.array_equal(want.view(np.uint32), rs.forward(pcm, centred=True).view(np.uint32))
+    got = input_data.read_wav_at(path)
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(input_data.read_wav_at(path, 16000, 9000)[:8000], want) and not input_data.read_wav_at(path, 16000, 9000)[8000:].any()
     rs.close()
 
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from multilingual_kws_amd import _lib, resample
-from tests.util_resample import noise_f32, noise_i16, polyphase
+from tests.util_resample import _around_tile, _check, noise_f32, noise_i16, polyphase
 
 pytestmark = pytest.mark.gpu
 RATES = (48000, 44100, 8000)          # L = 1; L = 160, M = 441; up by 2
@@ -20,26 +20,6 @@ def handles():
     yield hs
     for h in hs.values():
         h.close()
-
-
-def _around_tile(rs, n_out):
-    """Input lengths whose outputs end one each side of n_out samples and on it (an upsampler's lengths step by more than one)."""
-    g = rs.geometry
-    first, last = (n_out - 1) * g["M"] // g["L"] + 1, n_out * g["M"] // g["L"]          # the smallest and largest n_in that give n_out
-    assert rs.out_samples(first) == rs.out_samples(last) == n_out and rs.out_samples(first - 1) < n_out < rs.out_samples(last + 1)
-    return sorted({first - 1, first, last, last + 1})
-
-
-def _check(rs, x_rows, got_rows, centred):
-    g, tab = rs.geometry, rs.taps()
-    off = g["half"] if centred else 0
-    for x, got in zip(x_rows, got_rows):
-        xf = x.astype(np.float32) / np.float32(32768) if x.dtype == np.int16 else x
-        want = polyphase(xf, tab, g["M"], off, np.float32)
-        assert got.shape == want.shape and got.dtype == np.float32
-        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (rs.rate_in, len(x), centred, int((got != want).sum()))
-        exact, mag = polyphase(xf, tab, g["M"], off, np.float64, want_abs=True)
-        assert np.all(np.abs(got - exact) <= (g["T"] + 1) * 2.0 ** -24 * mag)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "int16"])

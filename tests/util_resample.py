@@ -25,6 +25,28 @@ def polyphase(x, tab, M, off, dtype, ns=None, want_abs=False):
     return (acc, mag) if want_abs else acc
 
 
+def _around_tile(rs, n_out):
+    """Input lengths whose outputs end one each side of n_out samples and on it (an upsampler's lengths step by more than one)."""
+    g = rs.geometry
+    first, last = (n_out - 1) * g["M"] // g["L"] + 1, n_out * g["M"] // g["L"]          # the smallest and largest n_in that give n_out
+    assert rs.out_samples(first) == rs.out_samples(last) == n_out and rs.out_samples(first - 1) < n_out < rs.out_samples(last + 1)
+    return sorted({first - 1, first, last, last + 1})
+
+
+def _check(rs, x_rows, got_rows, centred, tab=None):
+    """Every row of a device result against the emulator on the handle's own taps (tab: rs.taps(), when the caller keeps it): bit-equal
+    to the float32 form and within (T + 1) * 2^-24 * sum_j |tab * x| of the float64 form."""
+    g, tab = rs.geometry, rs.taps() if tab is None else tab
+    off = g["half"] if centred else 0
+    for x, got in zip(x_rows, got_rows):
+        xf = x.astype(np.float32) / np.float32(32768) if x.dtype == np.int16 else x
+        want = polyphase(xf, tab, g["M"], off, np.float32)
+        assert got.shape == want.shape and got.dtype == np.float32
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (rs.rate_in, len(x), centred, int((got != want).sum()))
+        exact, mag = polyphase(xf, tab, g["M"], off, np.float64, want_abs=True)
+        assert np.all(np.abs(got - exact) <= (g["T"] + 1) * 2.0 ** -24 * mag)
+
+
 def splitmix(n, seed):
     """uint64 [n] of splitmix64 from `seed`."""
     with np.errstate(over="ignore"):
