@@ -158,6 +158,93 @@ int mkws_frontend_live_push_many_f32(mkws_frontend* fe, void* d_states, size_t s
                                      uint16_t* d_raw, int64_t* d_meta, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The mfcc and average feature modes.  Replaces the non-micro branch of the reference's pipeline,
+ *   tf_v1_speechcommands/input_data_fix_bg.py:444-475
+ * audio_ops.audio_spectrogram(window_size, stride, magnitude_squared=True), then audio_ops.mfcc(spectrogram, sample_rate,
+ * dct_coefficient_count) or tf.nn.pool(AVG, SAME) over average_window_width bins.  The arithmetic, from TensorFlow's spectrogram.cc,
+ * mfcc_mel_filterbank.cc, mfcc_dct.cc and mfcc.cc; tables are built on the host in double and rounded once to float, the device works in
+ * fp32 with unfused multiplies and adds:
+ *   window    periodic Hann, w[i] = 0.5 - 0.5 cos(2 pi i / window); the frame is zero padded to fft_size = next_power_of_two(window);
+ *             bins = fft_size / 2 + 1; power[k] = re^2 + im^2.  Frame f covers samples [f * stride, f * stride + window); trailing
+ *             samples that do not fill a window are ignored.  int16 input is x / 32768 exactly.
+ *   mel       mel(f) = 1127 ln(1 + f / 700); centre[i] = mel(lower) + (i + 1) * (mel(upper) - mel(lower)) / (channels + 1), i <= channels;
+ *             hz_per_bin = 0.5 * sample_rate / (bins - 1); start = int(1.5 + lower / hz_per_bin), end = int(upper / hz_per_bin); bins
+ *             outside [start, end] contribute nothing.  Bin i inside: band b = index of the last centre below mel(i * hz_per_bin) or -1;
+ *             weight = (centre[b+1] - mel) / (centre[b+1] - centre[b]), for b == -1 (centre[0] - mel) / (centre[0] - mel(lower)); it adds
+ *             sqrt(power[i]) * weight to channel b if b >= 0 and sqrt(power[i]) * (1 - weight) to channel b + 1 if b + 1 < channels.
+ *             Every channel is summed in ascending bin order.
+ *   log, DCT  lg[j] = ln(max(mel_out[j], 1e-12)); feat[k] = sum_j sqrt(2 / channels) * cos(k * pi / channels * (j + 0.5)) * lg[j],
+ *             k < num_features, summed in ascending j.
+ *   average   output o = the mean of power[o * w .. min((o + 1) * w, bins)), w = average_window_width: SAME pooling pads on the right only
+ *             and divides by the number of real bins.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_SPECTRAL_MFCC 0
+#define MKWS_SPECTRAL_AVERAGE 1
+typedef struct mkws_spectral_cfg {
+  int32_t sample_rate;            /* 16000 */
+  int32_t window_size_samples;    /* 480  (model_settings["window_size_samples"]) */
+  int32_t window_stride_samples;  /* 320  (model_settings["window_stride_samples"]) */
+  int32_t mode;                   /* MKWS_SPECTRAL_MFCC */
+  int32_t num_features;           /* 40   mfcc: dct_coefficient_count (model_settings["fingerprint_width"]);
+                                          average: ceil(bins / average_window_width), checked */
+  int32_t filterbank_channels;    /* 40   (audio_ops.mfcc default); mfcc mode only */
+  float lower_frequency_limit;    /* 20 */
+  float upper_frequency_limit;    /* 4000 */
+  int32_t average_window_width;   /* 1    average mode only (model_settings["average_window_width"]) */
+} mkws_spectral_cfg;
+
+typedef struct mkws_spectral mkws_spectral;
+
+/* Fills *cfg with the defaults above. */
+void mkws_spectral_default_cfg(mkws_spectral_cfg* cfg);
+
+/* Host only.  Supported: fft_size in {256, 512, 1024} (windows of 129 .. 1024 samples; MKWS_ERR_UNSUPPORTED otherwise), a stride of at
+ * least one sample; mfcc mode: 1 <= num_features <= filterbank_channels <= 64 (more than 64 channels: MKWS_ERR_UNSUPPORTED), 0 <= lower <
+ * upper <= sample_rate / 2; average mode: average_window_width >= 1 and num_features == ceil(bins / average_window_width).  Everything
+ * else is MKWS_ERR_INVALID_ARG; the message names the field.  Any of the three outputs may be NULL; width = num_features. */
+int mkws_spectral_geometry(const mkws_spectral_cfg* cfg, int* fft_size, int* bins, int* width);
+
+/* Host only: n_samples < window ? 0 : 1 + (n_samples - window) / stride. */
+int mkws_spectral_num_frames(const mkws_spectral_cfg* cfg, int n_samples);
+
+/* Host only: copies table `which` into dst (at most cap_bytes) and returns its size in bytes, or a negative mkws_status.  The mel
+ * weights, the band mapper and the DCT exist in mfcc mode only (MKWS_ERR_INVALID_ARG in average mode). */
+enum {
+  MKWS_ST_WINDOW = 0,       /* float32[window] */
+  MKWS_ST_MEL_WEIGHTS = 1,  /* float32[bins], 0 outside [start, end] */
+  MKWS_ST_BAND_MAPPER = 2,  /* int32[bins], -2 outside [start, end] */
+  MKWS_ST_DCT = 3,          /* float32[num_features * channels] */
+  MKWS_ST_SCALARS = 4       /* int32[8]: window, stride, fft_size, bins, width, channels (0 in average mode), start, end */
+};
+int mkws_spectral_host_table(const mkws_spectral_cfg* cfg, int which, void* dst, size_t cap_bytes);
+
+/* Builds the tables, uploads them once and allocates the streaming form's workspace (the frames of max_samples).  The refusals of
+ * mkws_spectral_geometry come first, then MKWS_ERR_NO_DEVICE without a gfx950 device. */
+int mkws_spectral_create(const mkws_spectral_cfg* cfg, int max_samples, mkws_spectral** out);
+void mkws_spectral_destroy(mkws_spectral* h);
+
+/* d_audio [B, n_samples], float32 or int16 PCM -> d_feat float32 [B, frames, width].  Two optional taps, either may be NULL and then
+ * costs nothing: d_power float32 [B, frames, bins], the squared-magnitude spectrogram (what audio_spectrogram returns), and, in mfcc mode
+ * only (MKWS_ERR_INVALID_ARG in average mode), d_mel float32 [B, frames, channels], the filterbank outputs before the log.  d_feat has
+ * the same bits with and without taps, a clip's rows do not depend on the batch it is in, and rows of any alignment are taken.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers, negative sizes and n_samples > max_samples; B == 0 or zero frames returns MKWS_OK
+ * with nothing launched.  One launch, asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_spectral_forward_f32(mkws_spectral* h, const float* d_audio, int B, int n_samples, float* d_feat, float* d_power, float* d_mel,
+                              void* stream);
+int mkws_spectral_forward_i16(mkws_spectral* h, const int16_t* d_audio, int B, int n_samples, float* d_feat, float* d_power, float* d_mel,
+                              void* stream);
+
+/* Streaming form: one recording d_audio [n_samples], windows of window_samples every hop_samples.  Frames carry no recurrence in these
+ * modes, so window w is exactly frames [w * hop_samples / stride, + frames_per_window) of the recording: every frame is computed once
+ * and d_feat [num_windows, frames_per_window, width] is materialised from them, row w bit-equal to the forward call on the cut window.
+ * hop_samples must be a positive multiple of the stride (MKWS_ERR_UNSUPPORTED otherwise).  Returns num_windows = n_samples <
+ * window_samples ? 0 : 1 + (n_samples - window_samples) / hop_samples (nothing launched when 0, or when the window holds no frame) or a
+ * negative mkws_status; MKWS_ERR_INVALID_ARG for num_windows > max_windows, n_samples > max_samples, NULL pointers and non-positive
+ * sizes.  Two launches, asynchronous on `stream`, allocates nothing, never synchronises: capturable. */
+int mkws_spectral_stream_f32(mkws_spectral* h, const float* d_audio, int n_samples, int window_samples, int hop_samples, float* d_feat,
+                             int max_windows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sample-rate conversion in front of the frontend: a rational-ratio polyphase FIR resampler.  The reference converts its 48 kHz
  * sources outside Python (`sox ... convert(samplerate=16000)`, luganda/luganda.py:145, notebooks/clean_msc_gsc.py:71); here it is a
  * device stage with a stated filter.  With g = gcd(rate_in, rate_out): L = rate_out / g, M = rate_in / g, big = max(L, M),

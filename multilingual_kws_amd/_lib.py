@@ -53,6 +53,13 @@ class ResampleCfg(ctypes.Structure):
                 ("kaiser_beta", ctypes.c_float), ("rolloff", ctypes.c_float)]
 
 
+class SpectralCfg(ctypes.Structure):
+    """mkws_spectral_cfg (include/mkws.h)."""
+    _fields_ = [("sample_rate", ctypes.c_int32), ("window_size_samples", ctypes.c_int32), ("window_stride_samples", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("num_features", ctypes.c_int32), ("filterbank_channels", ctypes.c_int32),
+                ("lower_frequency_limit", ctypes.c_float), ("upper_frequency_limit", ctypes.c_float), ("average_window_width", ctypes.c_int32)]
+
+
 class PcmItem(ctypes.Structure):
     """mkws_pcm_item (include/mkws.h)."""
     _fields_ = [("byte_offset", ctypes.c_int64), ("n_frames", ctypes.c_int64), ("out_offset", ctypes.c_int64), ("out_len", ctypes.c_int64),
@@ -83,6 +90,7 @@ class StreamDesc(ctypes.Structure):
 _P, _I, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _CFG = ctypes.POINTER(FrontendCfg)
 _RCFG, _I64 = ctypes.POINTER(ResampleCfg), ctypes.c_int64
+_SCFG, _IP = ctypes.POINTER(SpectralCfg), ctypes.POINTER(ctypes.c_int)
 SYMBOLS = [
     ("mkws_abi_version", _I, []),
     ("mkws_last_error", ctypes.c_char_p, []),
@@ -98,6 +106,15 @@ SYMBOLS = [
     ("mkws_frontend_live_state_bytes", _SZ, [_P, _I, _I, _I]),
     ("mkws_frontend_live_push_f32", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     ("mkws_frontend_live_push_many_f32", _I, [_P, _P, _SZ, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    ("mkws_spectral_default_cfg", None, [_SCFG]),
+    ("mkws_spectral_geometry", _I, [_SCFG, _IP, _IP, _IP]),
+    ("mkws_spectral_num_frames", _I, [_SCFG, _I]),
+    ("mkws_spectral_host_table", _I, [_SCFG, _I, _P, _SZ]),
+    ("mkws_spectral_create", _I, [_SCFG, _I, ctypes.POINTER(_P)]),
+    ("mkws_spectral_destroy", None, [_P]),
+    ("mkws_spectral_forward_f32", _I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    ("mkws_spectral_forward_i16", _I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    ("mkws_spectral_stream_f32", _I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     ("mkws_resample_default_cfg", None, [_RCFG, _I, _I]),
     ("mkws_resample_geometry", _I, [_RCFG, _P]),
     ("mkws_resample_host_taps", _I, [_RCFG, _P, _SZ]),

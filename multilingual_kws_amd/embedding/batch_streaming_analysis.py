@@ -75,7 +75,10 @@ def stream_spectrograms(model_settings, audio, clip_duration_samples, clip_strid
     frames, chans = model_settings["spectrogram_length"], model_settings["fingerprint_width"]
     if nwin <= 0:
         return torch.empty((0, frames, chans), dtype=torch.float32, device=audio_t.device)
-    fe = input_data._frontend_for(model_settings, n)
+    if model_settings.get("preprocess", "micro") != "micro":      # mfcc / average: the same dispatch as input_data.to_features
+        fe = input_data._spectral_for(model_settings, n)
+    else:
+        fe = input_data._frontend_for(model_settings, n)
     if clip_stride_samples % model_settings["window_stride_samples"] != 0:
         # hop not a multiple of the frame step: no frame sharing possible, fall back to explicit windows
         idx = (torch.arange(clip_duration_samples, device=audio_t.device)[None]

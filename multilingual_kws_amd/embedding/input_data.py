@@ -4,6 +4,8 @@ Same names, arguments and label conventions as the reference module; tensors are
 (ROCm) instead of TensorFlow, and all sample-level work runs in libmkws_hip.so:
 
   to_micro_spectrogram  -> mkws_frontend_forward_*   (reference :19-35, the AudioMicrofrontend op)
+  to_features           -> the above for preprocess="micro", mkws_spectral_forward_* for "mfcc" / "average"
+                           (tf_v1_speechcommands/input_data_fix_bg.py:444-475)
   AudioDataset.augment  -> mkws_augment_batch        (reference :141-157, 227-304)
   spec_augment          -> mkws_specaug_apply_n      (reference :306-369)
 
@@ -69,6 +71,65 @@ def to_micro_spectrogram(model_settings, audio):
     if single:
         out = out[0]
     return out.cpu().numpy() if is_np else out
+
+
+_spectral_frontends = {}
+
+
+def _spectral_for(model_settings, max_samples):
+    """The cached SpectralFrontend of mfcc / average settings (reference: tf_v1_speechcommands/input_data_fix_bg.py:444-475), keyed like
+    _frontends."""
+    import torch
+    from ..spectral import SpectralFrontend
+    mode = model_settings["preprocess"]
+    key = (mode, model_settings["sample_rate"], model_settings["window_size_samples"], model_settings["window_stride_samples"],
+           model_settings["fingerprint_width"], model_settings["average_window_width"], torch.cuda.current_device())
+    fe = _spectral_frontends.get(key)
+    if fe is None or fe.max_samples < max_samples:
+        fe = SpectralFrontend(max_samples=max(max_samples, 16000), sample_rate=model_settings["sample_rate"],
+                              window_size_samples=model_settings["window_size_samples"],
+                              window_stride_samples=model_settings["window_stride_samples"], mode=mode,
+                              num_features=model_settings["fingerprint_width"],
+                              average_window_width=max(1, model_settings["average_window_width"]))
+        _spectral_frontends[key] = fe
+    return fe
+
+
+def to_features(model_settings, audio):
+    """The features model_settings["preprocess"] asks for.  "micro": to_micro_spectrogram, called with the same arguments and its result
+    returned untouched; "mfcc" / "average": the reference's audio_spectrogram + mfcc / average pool on the device, under
+    to_micro_spectrogram's rules -- [samples] or [B, samples], numpy in -> numpy out, torch in -> CUDA torch out."""
+    mode = model_settings["preprocess"]
+    if mode == "micro":
+        return to_micro_spectrogram(model_settings, audio)
+    if mode not in ("mfcc", "average"):
+        raise ValueError('Unknown preprocess mode "%s" (should be "mfcc", "average", or "micro")' % (mode))
+    import torch
+    is_np = not torch.is_tensor(audio)
+    t = torch.as_tensor(np.asarray(audio, dtype=np.float32)) if is_np else audio
+    if t.dtype not in (torch.float32, torch.int16):
+        t = t.to(torch.float32)
+    single = t.dim() == 1
+    if single:
+        t = t[None]
+    if not t.is_cuda:
+        t = t.cuda()
+    out = _spectral_for(model_settings, t.shape[1]).forward(t)
+    if single:
+        out = out[0]
+    return out.cpu().numpy() if is_np else out
+
+
+def get_features_range(model_settings):
+    """(min, max) of the features of a preprocess mode, as the reference's get_features_range (input_data_fix_bg.py:160-187) states them."""
+    mode = model_settings["preprocess"]
+    if mode == "average":
+        return 0.0, 127.5
+    if mode == "mfcc":
+        return -247.0, 30.0
+    if mode == "micro":
+        return 0.0, 26.0
+    raise ValueError('Unknown preprocess mode "%s" (should be "mfcc", "average", or "micro")' % (mode))
 
 
 def decode_wav(data, desired_samples=-1):
@@ -448,7 +509,7 @@ def check_one_second_16k(filepath):
 def file2spec(model_settings, filepath):
     """WAV file -> spectrogram [frames, channels] (numpy); background-noise variant: AudioDataset.file2spec_w_bg."""
     audio = _read_wav(filepath, model_settings["desired_samples"])
-    return to_micro_spectrogram(model_settings, audio)
+    return to_features(model_settings, audio)
 
 
 def _next_power_of_two(x):
@@ -872,7 +933,7 @@ class AudioDataset:
                 ctypes.c_void_p(bank0.data_ptr()), ctypes.c_void_p(bank1.data_ptr()) if bank1 is not None else None,
                 ctypes.c_void_p(bg.data_ptr()) if bg is not None else None, bg.shape[1] if bg is not None else 0,
                 ctypes.c_void_p(d_items.data_ptr()), B, n, ctypes.c_void_p(audio.data_ptr()), _lib.current_stream_ptr()))
-            spec = to_micro_spectrogram(self.model_settings, audio)
+            spec = to_features(self.model_settings, audio)
             self.last_masks = masks
             if use_masks:
                 sp = self.spec_aug_params
@@ -964,7 +1025,7 @@ class AudioDataset:
         return _read_wav(file_path, self.model_settings["desired_samples"]), self.commands[-1]
 
     def get_spectrogram_and_label_id(self, audio, label):
-        return to_micro_spectrogram(self.model_settings, audio), self._label_id(label)
+        return to_features(self.model_settings, audio), self._label_id(label)
 
     def add_channel(self, spectrogram, label_id):
         return spectrogram[..., None], label_id
@@ -976,7 +1037,7 @@ class AudioDataset:
 
     def file2spec_w_bg(self, filepath):
         audio = _read_wav(filepath, self.model_settings["desired_samples"])
-        return to_micro_spectrogram(self.model_settings, self._add_bg(audio)).cpu().numpy()
+        return to_features(self.model_settings, self._add_bg(audio)).cpu().numpy()
 
     def spec_augment(self, spectrogram):
         """Single spectrogram [frames, channels] (numpy or torch) -> masked copy (host-side convenience;

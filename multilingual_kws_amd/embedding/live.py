@@ -65,6 +65,16 @@ class _CapturedChain:
         self.graph.replay()
 
 
+def _require_micro(model_settings, who):
+    """The live chains are built on the micro frontend's live push: settings of another preprocess mode are refused (they used to be
+    served micro features without a word).  -> the settings."""
+    mode = model_settings.get("preprocess", "micro")
+    if mode != "micro":
+        raise ValueError(f'{who}: the live chain is micro-only, model_settings["preprocess"] is {mode!r} '
+                         "(input_data.to_features and stream_spectrograms serve the mfcc and average modes)")
+    return model_settings
+
+
 def _embedding_and_heads(models, embedding, heads):
     """models: TransferLearnedModel(s) sharing one embedding, or None for embedding= and heads= as they are -> (embedding, [heads])."""
     if models is not None:
@@ -90,7 +100,7 @@ class StreamingSession(_CapturedChain):
         self.batch = int(batch)
         if self.batch > self.embedding.max_batch:
             raise ValueError(f"StreamingSession(batch={batch}) exceeds the embedding handle's max_batch={self.embedding.max_batch}")
-        ms = model_settings or input_data.standard_microspeech_model_settings(3)
+        ms = _require_micro(model_settings or input_data.standard_microspeech_model_settings(3), "StreamingSession")
         self.samples = ms["desired_samples"]
         self.fe = input_data._frontend_for(ms, self.samples)
         self.audio = torch.zeros((self.batch, self.samples), dtype=torch.float32, device=self.embedding.device)      # static graph input
@@ -261,7 +271,7 @@ class _LiveChain(_CapturedChain):
             raise ValueError("The results for recognition should contain {} elements, but there are {} produced".format(
                 len(self.flags.labels()), self.heads[0].classes))
         self.fired_only = bool(fired_only)
-        ms = model_settings or input_data.standard_microspeech_model_settings(3)
+        ms = _require_micro(model_settings or input_data.standard_microspeech_model_settings(3), type(self).__name__)
         self.sample_rate = ms["sample_rate"]
         self.window_samples = int(self.flags.clip_duration_ms * self.sample_rate / 1000)
         self.hop_samples = int(self.flags.clip_stride_ms * self.sample_rate / 1000)
