@@ -922,6 +922,52 @@ int mkws_roc_count(const float* d_probs, int n_heads, int n_rows, int classes, c
                    int pos_class, int neg_class, int32_t* d_counts, int32_t* d_invalid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Classification point scores: what Keras' model.evaluate(ds) (sparse categorical cross-entropy + accuracy) and
+ * tf.math.confusion_matrix report, for n_models classifiers over n_rows shared rows, ADDED to accumulators that the caller zeroed once:
+ * a dataset is scored by one call per batch and read with one synchronisation at the end.  multilingual_kws_amd/scoring.py (score_host)
+ * is the specification.
+ * d_scores float32 [n_models, n_rows, classes]; d_labels int32, [n_rows] shared by the models (labels_per_model = 0) or
+ * [n_models, n_rows] (labels_per_model = 1); d_groups int32 [n_rows] shared by the models, or NULL: no groups (n_groups and
+ * d_group_tally are then ignored).
+ *   prediction: the first index of the row's maximum over the float32 scores (np.argmax); a NaN wins, among several NaNs the first.  An
+ *     exact function of the row's bits.
+ *   row loss, float64 from the float32 scores:
+ *     mode 0 (probabilities, Keras' backend formula): -log(min(max(p[y], lo), hi)), lo = (double)(float)1e-7 and
+ *       hi = (double)(1.0f - (float)1e-7) = 1 - 2^-23 -- Keras' float32 epsilon and its float32 1 - epsilon, widened; the clip is made on
+ *       the float32 value, the log is taken in double.  A NaN p[y] gives NaN.
+ *     mode 1 (logits): (log(sum_c exp(z[c] - max z)) + max z) - z[y].  A NaN anywhere in the row gives NaN; so does a maximum of +inf
+ *       (inf - inf), as in the float64 specification.
+ *     The loss of row (m, r) is a function of that row alone: the same bits in every batch that holds it.
+ *   labels: -1 means "ignore this row" (batch padding): counted in `ignored`, tallied nowhere else.  Any other label outside
+ *     [0, classes) is never used as an index: counted in `invalid`, tallied nowhere else; with d_groups, a group outside [0, n_groups)
+ *     makes the row invalid in the same way (label -1 is looked at first).
+ * Outputs, all of them += except the last two:
+ *   d_loss double [n_models]: every row's loss goes to the workspace first (0 for ignored and invalid rows); a second kernel adds a
+ *     model's n_rows values in an order that depends on n_rows alone and adds that sum to d_loss[m].  No floating-point atomics: two
+ *     runs give the same bits.  A NaN row loss reaches d_loss.
+ *   d_tally int64 [n_models, 4] = {rows tallied, correct (prediction == label), ignored, invalid};
+ *   d_confusion int64 [n_models, classes, classes] or NULL, row = true class, column = prediction;
+ *   d_group_tally int64 [n_models, n_groups, 2] = {rows, correct} or NULL.
+ *     The integers are exact and do not depend on how the rows were cut into calls.  classes <= 32: a workgroup keeps its matrix in LDS
+ *     and flushes its non-zero cells with 64-bit atomics; above, every row adds its cell with a 64-bit atomic in global memory.
+ *   d_row_loss double [n_models, n_rows] or NULL: written (not added), NaN for ignored and invalid rows;
+ *   d_pred int32 [n_models, n_rows] or NULL: written for every row.
+ * d_work: mkws_score_work_bytes(n_models, n_rows) bytes (8 per row and model), 8-byte aligned, caller-owned, contents unspecified.
+ * MKWS_ERR_INVALID_ARG for NULL required pointers (d_scores, d_labels, d_loss, d_tally, d_work), negative sizes, classes < 2, a mode
+ * or labels_per_model other than 0 / 1, n_groups < 0 and d_groups given with n_groups == 0; MKWS_ERR_UNSUPPORTED for classes above
+ * MKWS_SCORE_MAX_CLASSES and for more than 2^31 - 1 workgroups (n_models * ceil(n_rows / 256), classes > 32: n_rows / 32).
+ * n_models == 0 or n_rows == 0 returns MKWS_OK with nothing launched and the accumulators untouched (the buffers may then be NULL).
+ * Asynchronous on `stream`, allocates nothing, never synchronises: capturable like every other call.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_SCORE_MAX_CLASSES 4096
+/* Host only: bytes of d_work for one call (0 for non-positive sizes). */
+size_t mkws_score_work_bytes(int n_models, int n_rows);
+int mkws_score_accumulate(const float* d_scores, int n_models, int n_rows, int classes, int mode, const int32_t* d_labels,
+                          int labels_per_model, const int32_t* d_groups, int n_groups, double* d_loss, int64_t* d_tally,
+                          int64_t* d_confusion, int64_t* d_group_tally, double* d_row_loss, int32_t* d_pred, void* d_work,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * k-means of the MSWC outlier filter: what distance_filtering.cluster_and_sort
  * (multilingual_kws/embedding/distance_filtering.py:30-83) does per keyword with sklearn.cluster.KMeans(n_clusters, random_state).fit
  * and np.linalg.norm, for n_groups keywords in one launch.  multilingual_kws_amd/kmeans.py (kmeans_host) is the specification:

@@ -149,6 +149,8 @@ SYMBOLS = [
     ("mkws_detect_segments", _I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _I, _P, _P, _P, _P]),
     ("mkws_detect_score_segments", _I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_double, _P, _P]),
     ("mkws_roc_count", _I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    ("mkws_score_work_bytes", _SZ, [_I, _I]),
+    ("mkws_score_accumulate", _I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("mkws_kmeans_fit", _I, [_P, _I, _P, _I, _I, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
     ("mkws_kmeans_nearest", _I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     ("mkws_logreg_work_floats", _SZ, [_I, _I, _I]),

@@ -59,6 +59,26 @@ def _numbered(kind, i):
     return kind if i == 0 else f"{kind}_{i}"
 
 
+WEIGHT_DECAY = 1e-4               # the reference's model_def: L2(1e-4) on every convolution kernel
+
+
+def conv_kernel_names():
+    """The nine convolution kernels in layer order (stem, then depthwise and pointwise of every block): what the L2 penalty covers."""
+    names = ["conv2d/kernel"]
+    for b in range(N_BLOCKS):
+        names += [_numbered("depthwise_conv2d", b) + "/depthwise_kernel", _numbered("conv2d", b + 1) + "/kernel"]
+    return names
+
+
+def l2_penalty(kernels, weight_decay):
+    """weight_decay * the sum of the squared entries of `kernels` (torch tensors on any device), each kernel summed in float64: the
+    one formula behind DSCNNTrainer.regularization_loss and DSCNN.evaluate."""
+    total = 0.0
+    for w in kernels:
+        total = total + w.double().square().sum()
+    return float(weight_decay) * float(total)
+
+
 _KINDS = {"conv2d": 1 + N_BLOCKS, "depthwise_conv2d": N_BLOCKS, "batch_normalization": 1 + 2 * N_BLOCKS, "dense": 1}
 _LEAVES = {"conv2d": ("kernel", "bias"), "depthwise_conv2d": ("depthwise_kernel", "bias"),
            "batch_normalization": ("gamma", "beta", "moving_mean", "moving_variance"), "dense": ("kernel", "bias")}
@@ -385,3 +405,28 @@ class DSCNN:
             raise ValueError(f"expected [B,49,40] or [B,49,40,1], got {tuple(x.shape)}")
         out = [self.forward(x[s:s + self.max_batch]).cpu().numpy() for s in range(0, x.shape[0], self.max_batch)]
         return np.concatenate(out) if out else np.zeros((0, self.label_count), np.float32)
+
+    def predict_device(self, spec):
+        """CUDA [N,49,40(,1)] -> CUDA probabilities [N, label_count], in launches of max_batch."""
+        import torch
+        outs = [self.forward(spec[s:s + self.max_batch]) for s in range(0, spec.shape[0], self.max_batch)]
+        return torch.cat(outs) if outs else torch.empty((0, self.label_count), dtype=torch.float32, device=self.device)
+
+    def regularization_loss(self, weight_decay=WEIGHT_DECAY):
+        """What Keras adds to the loss evaluate reports: the L2 penalty of the nine convolution kernels (l2_penalty)."""
+        import torch
+        host = unpack(self.params)
+        return l2_penalty([torch.from_numpy(np.ascontiguousarray(host[name])) for name in conv_kernel_names()], weight_decay)
+
+    def score(self, x, y=None, batch_size=32):
+        """The point scores over a ClipDataset or an array [N,49,40(,1)] with labels y: scoring.Scorer.result(), tallied on the device
+        (the loss without the L2 penalty)."""
+        from . import scoring
+        return scoring.score_model(self.predict_device, self.device, self.label_count, 0, x, y, batch_size)
+
+    def evaluate(self, x, y=None, batch_size=32, verbose=0, return_dict=False, weight_decay=WEIGHT_DECAY):
+        """Keras' model.evaluate for the reference's compile (sparse categorical cross-entropy, SparseCategoricalAccuracy):
+        [loss, sparse_categorical_accuracy] or the dict; the loss includes the L2 penalty, as Keras' does."""
+        from . import scoring
+        return scoring.keras_metrics(self.score(x, y, batch_size), ("loss", "sparse_categorical_accuracy"), return_dict,
+                                     extra_loss=self.regularization_loss(weight_decay))

@@ -242,8 +242,4 @@ class DSCNNTrainer(OpTape):
 
     def regularization_loss(self):
         """weight_decay * sum of the squared entries of the nine convolution kernels (what Keras adds to the reported loss)."""
-        torch = self.torch
-        total = torch.zeros((), dtype=torch.float64, device=self.device)
-        for kernel in CONV_KERNELS:
-            total = total + self.view(kernel).double().square().sum()
-        return self.weight_decay * float(total.cpu())
+        return dscnn.l2_penalty([self.view(kernel) for kernel in CONV_KERNELS], self.weight_decay)

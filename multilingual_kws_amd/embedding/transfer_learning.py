@@ -75,6 +75,18 @@ class TransferLearnedModel:
         # the copy to the host has synchronised anyway, so the host API looks at the handle now and never returns the poisoned batch
         return self.embedding.checked(lambda: self.predict_device(x).cpu().numpy())
 
+    def score(self, x, y=None, batch_size=32):
+        """The point scores of the model over a ClipDataset (eval_with_silence_unknown(...).batch(32)) or an array [N,49,40(,1)] with
+        labels y: scoring.Scorer.result() -- loss, accuracy, rows, confusion_matrix -- tallied on the device, one copy at the end."""
+        from .. import scoring
+        return scoring.score_model(self.predict_device, self.embedding.device, self.head.classes, 0, x, y, batch_size, self.embedding.checked)
+
+    def evaluate(self, x, y=None, batch_size=32, verbose=0, return_dict=False):
+        """Keras' model.evaluate for a model compiled with sparse categorical cross-entropy on probabilities and metrics=["accuracy"]:
+        [loss, accuracy], or {"loss", "accuracy"} with return_dict."""
+        from .. import scoring
+        return scoring.keras_metrics(self.score(x, y, batch_size), ("loss", "accuracy"), return_dict)
+
     def save(self, path):
         """Directory with head.npz (+ a copy of / pointer to the base weights)."""
         os.makedirs(path, exist_ok=True)
@@ -695,6 +707,78 @@ def evaluate_files_many(files_to_evaluate: List[os.PathLike], models, model_sett
 
     # the exchange-failure check of TransferLearnedModel.predict: a poisoned batch is never handed back
     return embedding.checked(run)
+
+
+def keyword_labels(keyword_of_clip, n_keywords):
+    """Which keyword every clip says (an id in [0, n_keywords), -1 for silence, anything else -- n_keywords and above -- for a word no
+    model spots) -> int32 [n_keywords, N]: model k's label of clip n is 2 where the clip is keyword k, 0 where it is silence, 1
+    (unknown) otherwise.  With it one evaluate_many pass yields every keyword's 3 x 3 matrix."""
+    ids = np.asarray(keyword_of_clip)
+    if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+        raise ValueError("keyword_of_clip must be a vector of integer keyword ids")
+    if int(n_keywords) < 1:
+        raise ValueError(f"n_keywords = {n_keywords}")
+    ids = ids.astype(np.int64)
+    if ids.size and ids.min() < -1:
+        raise ValueError(f"keyword id {int(ids.min())}: -1 is silence, there is no other negative id")
+    labels = np.ones((int(n_keywords), ids.size), np.int32)
+    labels[:, ids == -1] = 0
+    labels[ids[None, :] == np.arange(int(n_keywords))[:, None]] = 2
+    return labels
+
+
+def evaluate_many(models, x, y=None, labels=None, batch_size=1024, return_dict=True):
+    """model.evaluate for K few-shot models at once.  Models that share an embedding handle (load_models_shared, transfer_learn_many)
+    are scored together: one embedding pass per batch, Head.forward_many to [K, B, 3], one scorer call; models on different handles are
+    grouped by handle, as evaluate_files_many's callers group them, and every group makes its own pass over x.
+    x: a ClipDataset, or an array [N,49,40(,1)] with labels; labels (or y): [N] shared by the models, or [K, N] per model
+    (keyword_labels); with a dataset and labels=None the dataset's own labels are shared.  With labels given for a dataset, they are taken
+    in the order the dataset yields its clips.
+    -> one {"loss", "accuracy", "rows", "confusion_matrix"} per model (return_dict=False: [loss, accuracy] per model)."""
+    import torch
+    from .. import scoring
+    models = list(models)
+    if not models:
+        raise ValueError("at least one model")
+    if labels is None:
+        labels = y
+    by_handle = {}
+    for k, m in enumerate(models):
+        by_handle.setdefault(id(m.embedding), []).append(k)
+    is_array = torch.is_tensor(x) or isinstance(x, (np.ndarray, list, tuple))
+    if is_array and labels is None:
+        raise ValueError("evaluate_many: labels are required when x is an array")
+    lab = None if labels is None else np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+    if lab is not None and (lab.ndim not in (1, 2) or (lab.ndim == 2 and lab.shape[0] != len(models))):
+        raise ValueError(f"evaluate_many: labels must be [N] or [{len(models)}, N], got {lab.shape}")
+    out = [None] * len(models)
+    for ks in by_handle.values():
+        embedding, heads = _shared_embedding([models[k] for k in ks])
+        scorer = scoring.Scorer(len(ks), heads[0].classes, 0, device=embedding.device)
+        d_lab = None
+        if lab is not None:
+            d_lab = torch.from_numpy(np.ascontiguousarray(lab if lab.ndim == 1 else lab[ks]).astype(np.int32)).to(embedding.device)
+
+        def run():
+            scorer.reset()
+            at = 0
+            batches = scoring.eval_batches(x, torch.zeros(len(x), dtype=torch.int32) if is_array else None, batch_size, embedding.device)
+            for spec, own in batches:
+                B = int(spec.shape[0])
+                for s in range(0, B, embedding.max_batch):
+                    e = min(s + embedding.max_batch, B)
+                    probs = Head.forward_many(heads, embedding.forward(spec[s:e]))
+                    scorer.add(probs, own[s:e] if d_lab is None else d_lab[..., at + s:at + e])
+                at += B
+            if d_lab is not None and at != d_lab.shape[-1]:
+                raise ValueError(f"evaluate_many: {d_lab.shape[-1]} labels for {at} clips")
+            return scorer.result()
+
+        res = embedding.checked(run)
+        for i, k in enumerate(ks):
+            out[k] = (dict(loss=float(res.loss[i]), accuracy=float(res.accuracy[i]), rows=int(res.rows[i]), confusion_matrix=res.confusion_matrix[i])
+                      if return_dict else scoring.keras_metrics(res, model=i))
+    return out
 
 
 def classification_curves(models, target_files, unknown_files, model_settings: Optional[Dict] = None, thresholds=None, multiclass=False,

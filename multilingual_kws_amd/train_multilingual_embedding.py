@@ -104,6 +104,17 @@ class EmbeddingClassifier:
             x = x[..., 0]
         return self.predict_device(x).cpu().numpy()
 
+    def score(self, x, y=None, batch_size=32):
+        """The point scores of the classifier over a ClipDataset or an array [N,49,40(,1)] with labels y: scoring.Scorer.result(), the
+        loss taken on the logits (the reference compiles this model with from_logits=True), tallied on the device."""
+        from . import scoring
+        return scoring.score_model(self.predict_device, self.embedding.device, self.num_labels, 1, x, y, batch_size, self.embedding.checked)
+
+    def evaluate(self, x, y=None, batch_size=32, verbose=0, return_dict=False):
+        """Keras' model.evaluate for metrics=["accuracy"]: [loss, accuracy], or {"loss", "accuracy"} with return_dict."""
+        from . import scoring
+        return scoring.keras_metrics(self.score(x, y, batch_size), ("loss", "accuracy"), return_dict)
+
     def save(self, path):
         """A directory transfer_learn(base_model_path=...) accepts (the embedding as a weight container, as tf.keras' SavedModel of
         this model is what the reference's transfer_learn loads and cuts at dense_2) + the classifier layer."""
