@@ -13,7 +13,6 @@
 //   mbconv_front_kernel          expand (MFMA) + BN + swish -> LDS -> depthwise + BN + swish, SE sums
 //   mbconv_back_kernel           SE FCs + gated projection + BN (+ residual) behind the front kernel
 //   mbconv_mid_kernel            whole block, big images (2a .. 4a), depthwise output resident in LDS
-//   mbconv_rows_kernel           whole block 2b / 3b, depthwise output in registers (mkws_embed_rows.hip; option fuse_rows, off)
 //   mbconv_block_kernel          whole block, 4x3 / 2x2 images (4b .. 7a), 4, 2 or 1 clips per workgroup
 //   mbconv_chain_kernel          consecutive 4x3-image blocks in one launch, activations in LDS
 //   mbconv_pair_kernel           whole block, stride-1 2x2 images (6b .. 7a): two workgroups of one XCD share the clips, split the channels
@@ -55,7 +54,6 @@
 // like the MFMA accumulation itself; the build's default (-ffp-contract=off) stays in force for the other files.
 #pragma clang fp contract(fast)
 #include "mkws_embed_dev.h"
-#include "mkws_embed_rows.h"
 
 namespace mkws {
 
@@ -4548,7 +4546,6 @@ struct mkws_embed {
   int fuse_gemv = 1;               // handles of at most 4 planned rows (one clip): dense layers and top conv on gemv_kernel (one launch per layer, K split inside the workgroup); 0 = pw_gemm_kernel + split-K fold
   int fuse_se4 = 1;                // 4x3-image blocks: squeeze-excite FCs on the 4x4x1 matrix instruction + gate applied by the lanes that compute it (Se4); 0 = 16x16x4 streams + gate pass
   int fuse_walk = 1;               // block 2a's front kernel: one workgroup walks the clip's three channel blocks (input read from HBM once); 0 = three workgroups per clip
-  int fuse_rows = 0;               // 1 = stride-1 big-image blocks (2b, 3b) on mbconv_rows_kernel (mkws_embed_rows.hip: depthwise output in registers, a wave per row tile); 0 = fuse_mid / front + back decide
   int fuse_block = 2;              // whole MBConv block in one kernel (mbconv_block_kernel): 1 = 2x2 images only, 2 = 2x2 and 4x3
   int fuse_chain = 1;              // depth-fused chains: 1 = blocks 4b..6a in ONE launch (mbconv_chain_kernel) and 6b..7a in ONE paired launch (mbconv_pair_chain_kernel); 2 / 3 = only the first / second; 0 = one launch per block
   mkws::BlockArgs* d_chain_tab = nullptr;   // device copy of every block's constants (BlockArgs without X / Y / dbg) for the chain kernels
@@ -5264,7 +5261,7 @@ bool mid_enabled(const BlockPlan& b, int fuse_mid) {
   return (b.H == 13 && b.spec.kernel == 5) || (b.H == 7 && b.spec.stride == 2);
 }
 
-// One launch's arguments for the big-image whole-block kernels (mbconv_mid_kernel, mbconv_rows_kernel); what is not set here is zero
+// One launch's arguments for the big-image whole-block kernel (mbconv_mid_kernel); what is not set here is zero
 static MidArgs mid_args(const BlockPlan& b, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
   MidArgs a;
   memset(static_cast<void*>(&a), 0, sizeof(a));
@@ -5288,22 +5285,6 @@ int launch_mid(hipStream_t s, const char* stage, const BlockPlan& b, int one_cli
   if (st == 1) return launch_mid_inst<5, 1, 3, 7, 5, 240, 48, 3, 1, 1, 512, 4>(s, stage, a);                      // 3b
   if (one_clip) return launch_mid_inst<3, 2, 3, 7, 5, 240, 48, 5, 1, 3, 512, 4, true>(s, stage, a);                // 4a on handles of <= 256 clips: a workgroup per clip (two-clip workgroups leave half the CUs idle there)
   return launch_mid_inst<3, 2, 3, 7, 5, 240, 48, 5, 2, 3, 512, 4, true>(s, stage, a);                             // 4a: the same
-}
-
-// Register-resident whole-block kernel (mkws_embed_rows.hip): the stride-1 big-image blocks 2b and 3b.
-int rows_variant(const BlockPlan& b) {
-  if (!b.has_expand || b.se.se > 10 || b.spec.stride != 1 || !b.residual) return -1;
-  const int ks = b.spec.kernel, ci = b.spec.in_ch, co = b.spec.out_ch;
-  if (b.H == 13 && b.W == 10 && ks == 3 && ci == 24 && co == 24 && b.ce == 144 && b.project.NTtot == 2) return kRows2b;
-  if (b.H == 7 && b.W == 5 && ks == 5 && ci == 40 && co == 40 && b.ce == 240 && b.project.NTtot == 3) return kRows3b;
-  return -1;
-}
-
-int launch_rows(hipStream_t s, const char* stage, const BlockPlan& b, int alt, const float* X, float* Y, float* dbg_dw, float* dbg_gate, int B) {
-  const MidArgs a = mid_args(b, X, Y, dbg_dw, dbg_gate, B);
-  const int v = rows_variant(b) + (alt ? 16 : 0);          // fuse_rows = 2: the A/B shapes of mkws_embed_rows.hip (clips per wave / workgroups per CU the other way round)
-  ProfScope ps(stage, rows_kernel_name(v));
-  return launch_rows_variant(s, v, a);
 }
 
 // Back half (SE + gated projection in one launch) for the blocks that keep mbconv_front_kernel: 2a, 2b, 3b -- and 3a / 4a where the whole-block
@@ -5395,7 +5376,6 @@ int check_pair_health(mkws_embed* em, hipStream_t s) {
 // In order of precedence.  The three chain paths run blocks i .. last in one launch; every other path runs block i alone.
 enum class Path {
   Fused1a,        // block 1a inside stem_block1a_kernel (already launched with the stem)
-  Rows,           // mbconv_rows_kernel (option fuse_rows; stride-1 big-image blocks)
   Mid,            // mbconv_mid_kernel (big-image blocks)
   Chain,          // mbconv_chain_kernel (4x3-image blocks)
   PairChain,      // mbconv_pair_chain_kernel (stride-1 2x2-image blocks, + top conv and pool when with_top)
@@ -5420,7 +5400,6 @@ Route route_block(const mkws_embed* em, int i, int B, const char* stop) {
   const BlockPlan& b = em->blocks[i];
   if (i == 0 && fused_1a(em, stop)) return {Path::Fused1a, i, false};
   const bool want_expand_tap = tap_is(stop, b, "_expand");      // only the unfused path materialises the expand output
-  if (em->fuse_rows && rows_variant(b) >= 0 && !want_expand_tap) return {Path::Rows, i, false};
   if (mid_enabled(b, em->fuse_mid) && !want_expand_tap) return {Path::Mid, i, false};
   // depth-fused chains: a block whose output is tapped ends the chain, a block whose inner taps are wanted is not entered
   auto extend = [&](int max_len, bool (*member)(const mkws_embed*, const BlockPlan&), bool (*link_ok)(const BlockPlan&, const BlockPlan&)) {
@@ -5496,7 +5475,6 @@ int run_forward(mkws_embed* em, const float* d_spec, int B, float* d_emb, hipStr
     int rc = MKWS_OK;
     switch (r.path) {
       case Path::Fused1a: break;          // already computed into nxt (= bufB) by stem_block1a_kernel
-      case Path::Rows: rc = launch_rows(s, p.c_str(), b, em->fuse_rows == 2, cur, nxt, dbg_dw, dbg_gate, B); break;
       case Path::Mid: rc = launch_mid(s, p.c_str(), b, em->block_mt43 == 1, cur, nxt, dbg_dw, dbg_gate, B); break;
       case Path::Chain: rc = launch_chain(s, em, i, r.last, cur, nxt, B); break;
       case Path::PairChain:
@@ -5639,7 +5617,6 @@ int mkws_embed_create(const float* h, size_t n_floats, int max_batch, mkws_embed
   // (one-clip handles = live windows: the split front / back kernels put a clip's channel blocks on several CUs where the whole-block
   //  kernel is ONE workgroup: 0.3056 -> 0.3023-0.3041 ms per window, tools/latency_ab.py fuse_mid, two rounds)
   em->fuse_mid = (max_batch == 1) ? 0 : 1;
-  em->fuse_rows = 0;       // measured slower than the mid / front + back kernels so far (profiles/r06_notes.md): an A/B option, not the plan
   em->fuse_back = 1;
   em->fuse_pair = pair_layout_ok() ? 1 : 0;
   // small-batch (live serving) handles: the tiny-image blocks on the 6-way cluster kernel, same dispatch-order premise as the pairs
@@ -5852,7 +5829,6 @@ const EmbedOption kEmbedOptions[] = {
     {"fuse_front", nullptr, [](mkws_embed* em, int v) { em->fuse_front = v != 0; return (int)MKWS_OK; }, [](const mkws_embed* em) { return em->fuse_front ? 1 : 0; }},
     {"fuse_block", &mkws_embed::fuse_block, nullptr, nullptr},
     {"fuse_mid", &mkws_embed::fuse_mid, nullptr, nullptr},
-    {"fuse_rows", &mkws_embed::fuse_rows, nullptr, nullptr},
     {"fuse_walk", &mkws_embed::fuse_walk, nullptr, nullptr},
     {"fuse_se4", nullptr, [](mkws_embed* em, int v) { em->fuse_se4 = v ? 1 : 0; return (int)MKWS_OK; }, [](const mkws_embed* em) { return em->fuse_se4; }},
     {"fuse_gemv", &mkws_embed::fuse_gemv, nullptr, nullptr},

@@ -1,6 +1,6 @@
-// Device-side helpers shared by the embedding kernels' translation units (mkws_embed.hip, mkws_embed_rows.hip):
+// Device-side helpers of the embedding kernels' translation unit (mkws_embed.hip):
 // vector types, the hardware-transcendental sigmoid / swish, the buffer-descriptor weight stream, the argument block of the
-// whole-block kernels.  Include AFTER `#pragma clang fp contract(fast)` (the epilogue arithmetic may fuse in both files alike).
+// whole-block kernels.  Include AFTER `#pragma clang fp contract(fast)` (the epilogue arithmetic of these helpers may fuse like the kernels' own).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,7 +58,6 @@ struct MidArgs {
   int B;
 #ifdef MKWS_FRONT_TIMING
   unsigned long long* dbg_t;
-  int ablate;                      // mbconv_rows_kernel, timing build: MKWS_ABLATE bit mask (phases it skips: wrong results, honest timing of the rest)
 #endif
 };
 

@@ -58,7 +58,7 @@ def _set_options(em, how):
         combo = int(how[5:])
         front, block, mid, pair = COMBOS[combo]
         for k, v in (("fuse_chain", combo & 1), ("fuse_pair", pair), ("fuse_front", front), ("fuse_block", block), ("fuse_mid", mid),
-                     ("fuse_rows", combo & 1), ("fuse_walk", (combo >> 1) & 1), ("fuse_se4", (combo >> 2) & 1), ("fuse_back", 1 if mid != 2 else 0),
+                     ("fuse_walk", (combo >> 1) & 1), ("fuse_se4", (combo >> 2) & 1), ("fuse_back", 1 if mid != 2 else 0),
                      ("fuse_stem", front), ("fuse_gap", front)):
             em.set_option(k, v)
     else:
