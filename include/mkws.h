@@ -1062,6 +1062,43 @@ int mkws_logreg_score(const float* d_x, int n_rows, int dim, const int32_t* d_ro
                       float* d_probs, float* d_logits, int32_t* d_correct, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K L1-regularised logistic regressions on embedding vectors: the reference's `logistic_regression_with_l1_regularization`
+ * (notebooks/dataperf_test_harness.py:277-280), sklearn.linear_model.LogisticRegression(penalty="l1", solver="liblinear"), for
+ * n_problems problems in one launch.  multilingual_kws_amd/lr_l1.py (objective, lr_l1_host) is the specification: liblinear's L1R_LR is
+ * one independent binary problem per class k (one-vs-rest), the bias an extra feature of value 1 that is penalised like a weight,
+ *     f_k(w, b) = |w|_1 + |b| + C[p] * sum_i log(1 + exp(-s_ik (w . x_i + b))),   s_ik = +1 if label i is k, else -1,
+ * and the prediction is the first argmax over k of w_k . x + b_k, which mkws_logreg_score evaluates on d_coef / d_intercept as this
+ * call leaves them.  "violation" is the largest magnitude of the minimum-norm subgradient over the dim weights and the bias: with g
+ * the gradient of the smooth part, |g_j + sign(w_j)| where w_j != 0 and max(|g_j| - 1, 0) where w_j = 0.
+ * The caps are MKWS_LOGREG_MAX_ROWS, MKWS_LOGREG_MAX_CLASSES and MKWS_LOGREG_MAX_DIM.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Floats of workspace mkws_lr_l1_fit needs: none (0) -- the iterates live in registers and LDS. */
+size_t mkws_lr_l1_work_floats(int dim, int n_problems, int n_classes);
+
+/* The bank, the lists, d_offsets and d_C are those of mkws_logreg_fit.  d_coef float32 [n_problems, n_classes, dim] (a weight the solver
+ * holds at zero is exactly 0.0f), d_intercept float32 [n_problems, n_classes], d_info int32 [n_problems, n_classes, 4] = {status, n_iter,
+ * stop reason, non-zero weights among the dim (the bias is not counted)} per class, d_stats double [n_problems, n_classes, 2] = {f_k,
+ * violation} at the returned point, computed from logits formed afresh from the returned weights; stop reason 0 = violation <= vtol
+ * (looked at every 8 iterations and after the last), 1 = max_iter iterations were made (sklearn's ConvergenceWarning, not an error).
+ *   status 0 fitted;
+ *   status 2 = an empty problem, more than MKWS_LOGREG_MAX_ROWS rows, a label outside [0, n_classes) or a row index outside
+ *              [0, n_rows): all n_classes entries of d_info are {2, 0, 0, 0}, nothing else is written for the problem and no bank row is
+ *              read.  Neighbouring problems are not affected.
+ * Two classes: class 1 is solved and class 0 is written as its exact negation (zeros stay +0.0f), with the same info and stats.  Every
+ * class problem is posed, also that of a class with no sample.
+ * The solver is a proximal gradient iteration (FISTA with gradient restart, the step from a power iteration), one workgroup per
+ * (problem, class), no floating-point atomics: two calls on the same input write the same bytes.
+ * d_work / work_floats: mkws_lr_l1_work_floats(...) floats, that is none: d_work may be NULL and is never touched.
+ * MKWS_ERR_INVALID_ARG for NULL pointers (other than d_work), negative sizes, dim < 1, n_classes < 2, max_iter < 1 and a NaN or negative
+ * vtol; MKWS_ERR_UNSUPPORTED above MKWS_LOGREG_MAX_CLASSES or MKWS_LOGREG_MAX_DIM.  n_problems == 0 returns MKWS_OK with nothing
+ * launched.  A refused call writes nothing.  Asynchronous on `stream`, allocates nothing, never synchronises: capturable like every
+ * other call. */
+int mkws_lr_l1_fit(const float* d_x, int n_rows, int dim, const int32_t* d_rows, const int32_t* d_labels, const int32_t* d_offsets,
+                   int n_problems, int n_classes, const double* d_C, int max_iter, double vtol, float* d_coef, float* d_intercept,
+                   int32_t* d_info, double* d_stats, float* d_work, size_t work_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K RBF support-vector classifiers on embedding vectors: what the DataPerf selection harness of the reference
  * (notebooks/dataperf_test_harness.py:224-239) does per split with sklearn.svm.SVC(), for n_problems problems side by side.
  * multilingual_kws_amd/svc.py (svc_host, decision_host, predict_host) is the specification: C-SVC, k(a, b) = exp(-gamma |a~ - b~|^2) with

@@ -156,6 +156,8 @@ SYMBOLS = [
     ("mkws_logreg_work_floats", _SZ, [_I, _I, _I]),
     ("mkws_logreg_fit", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _SZ, _P]),
     ("mkws_logreg_score", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    ("mkws_lr_l1_work_floats", _SZ, [_I, _I, _I]),
+    ("mkws_lr_l1_fit", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, ctypes.c_double, _P, _P, _P, _P, _P, _SZ, _P]),
     ("mkws_svc_work_bytes", _SZ, [_I, _I]),
     ("mkws_svc_prepare", _I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
     ("mkws_svc_kernel", _I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
