@@ -1475,6 +1475,66 @@ int mkws_op_dropout_bwd(const float* d_dOut, float* d_dX, int64_t n, float rate,
 int mkws_op_dscnn_pool_fwd(const float* d_A, int B, float rate, uint64_t seed, const int* d_step, int site, float* d_pooled, void* stream);
 int mkws_op_dscnn_pool_bwd(const float* d_dpooled, int B, float rate, uint64_t seed, const int* d_step, int site, float* d_dA, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * wav2vec 2.0 baseline, inference: the encoder the reference uses as a clip embedding (notebooks/dataperf_wav2vec2.py:43-58:
+ * Wav2Vec2Processor + Wav2Vec2Model, last hidden state max-pooled over time).  Driven by a configuration; float32 throughout.
+ *   0  processor   per clip x <- (x - mean) / sqrt(var + 1e-7), population variance (switchable)
+ *   1  encoder     seven valid 1-D convolutions without bias, kernels (10,3,3,3,3,2,2), strides (5,2,2,2,2,2,2); layer 0 is followed by a
+ *                  GroupNorm with one group per channel (statistics over the clip's T_0 positions, eps 1e-5, affine); every layer ends
+ *                  in the exact GELU.  T_i = (T_{i-1} - k_i) / s_i + 1: 16000 samples -> 49 frames, 400 -> 1.
+ *   2  projection  LayerNorm over conv_dim[6], Linear(conv_dim[6] -> H) with bias
+ *   3  position    grouped convolution over time (H channels, G groups, kernel K, zero padding K / 2, exactly T outputs, bias; the
+ *                  weight-normalised kernel g * v / ||v|| is folded at create in float64), GELU, added to its input, LayerNorm
+ *   4  layers      post-LN transformer layers: h = LN(h + Wo attention(h) + bo), h = LN(h + W2 GELU(W1 h + b1) + b2), attention over
+ *                  all T frames without a mask, q scaled by head_dim^-0.5
+ *   5  outputs     the last hidden state [B,T,H] and its maximum over the T frames [B,H]
+ * The parameter blob is float32 with the names, layouts and order of Hugging Face's Wav2Vec2Model state dict, masked_spec_embed left
+ * out (mkws_w2v2_weight_manifest).  All clips of a call have the same length.  The contractions run on the fp32 MFMA GEMM of
+ * mkws_op_gemm (a long reduction split into slices that a second launch folds in slice order, through the handle's own buffer: no scratch
+ * arena is involved); activations are channels-last, so a strided convolution is one GEMM over
+ * overlapping row views of its input.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mkws_w2v2_cfg {
+  int32_t conv_dim[7];
+  int32_t conv_kernel[7];              /* (10,3,3,3,3,2,2): anything else is refused */
+  int32_t conv_stride[7];              /* (5,2,2,2,2,2,2): anything else is refused */
+  int32_t hidden_size;
+  int32_t num_hidden_layers;
+  int32_t num_attention_heads;         /* must divide hidden_size */
+  int32_t intermediate_size;
+  int32_t num_conv_pos_embeddings;     /* K */
+  int32_t num_conv_pos_embedding_groups; /* G, must divide hidden_size */
+  float layer_norm_eps;
+  int32_t group_norm;                  /* 1: feat_extract_norm == "group" (the only supported value) */
+  int32_t conv_bias;                   /* must be 0 */
+  int32_t stable_layer_norm;           /* must be 0 */
+  int32_t exact_gelu;                  /* 1: both activations are the exact GELU (the only supported value) */
+} mkws_w2v2_cfg;
+typedef struct mkws_w2v2 mkws_w2v2;
+
+/* facebook/wav2vec2-base: conv_dim 512 x 7, H 768, 12 layers, 12 heads, FFN 3072, K 128, G 16, eps 1e-5. */
+void mkws_w2v2_default_cfg(mkws_w2v2_cfg* cfg);
+/* Floats of the blob; 0 for a configuration the build refuses (mkws_last_error says why).  Host only. */
+size_t mkws_w2v2_param_count(const mkws_w2v2_cfg* cfg);
+/* JSON {"tensors": [{name, shape, offset, count}]} in state-dict order; returns the length needed (without the NUL), or a negative
+ * mkws_status for a refused configuration.  Host only. */
+int mkws_w2v2_weight_manifest(const mkws_w2v2_cfg* cfg, char* buf, size_t buf_len);
+/* Frames of a clip of n_samples; 0 or negative for an input shorter than 400 samples (and for a refused configuration).  Host only. */
+int mkws_w2v2_num_frames(const mkws_w2v2_cfg* cfg, int n_samples);
+/* MKWS_ERR_UNSUPPORTED / MKWS_ERR_INVALID_ARG for a refused configuration, max_batch < 1, max_samples < 400 and sizes beyond what one
+ * handle addresses; MKWS_ERR_BAD_WEIGHTS for n_floats != mkws_w2v2_param_count(cfg), a non-finite value and a kernel position of the
+ * positional convolution whose ||v|| is zero -- all before a device is looked for; then MKWS_ERR_NO_DEVICE without a gfx950.  Folds the
+ * weight norm, re-lays the weights out for the kernels and allocates all workspace. */
+int mkws_w2v2_create(const mkws_w2v2_cfg* cfg, const float* h_params, size_t n_floats, int max_batch, int max_samples, mkws_w2v2** out);
+void mkws_w2v2_destroy(mkws_w2v2* h);
+/* d_audio [B, n_samples] -> d_hidden [B,T,H] and / or d_embed [B,H] (either may be NULL, not both).  Asynchronous on `stream`, no
+ * allocation and no synchronisation: capturable.  The same call twice gives the same bits.  B == 0 succeeds with nothing launched;
+ * B > max_batch, n_samples > max_samples and n_samples < 400 are MKWS_ERR_INVALID_ARG. */
+int mkws_w2v2_forward(mkws_w2v2* h, const float* d_audio, int B, int n_samples, int normalize, float* d_hidden, float* d_embed, void* stream);
+/* The same chain stopped after `stage`, whose result goes to d_out: 0 the (normalised) audio [B,n]; 1..7 the convolution layers after
+ * their GELU, [B,T_i,C_i] channels last; 8 the projection [B,T,H]; 9 positional convolution + LayerNorm; 10 + l transformer layer l. */
+int mkws_w2v2_tap(mkws_w2v2* h, const float* d_audio, int B, int n_samples, int normalize, int stage, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

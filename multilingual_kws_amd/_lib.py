@@ -86,11 +86,21 @@ class StreamDesc(ctypes.Structure):
                 ("bed_start", ctypes.c_int64), ("max_frames", ctypes.c_int64), ("first_item", ctypes.c_int32), ("n_items", ctypes.c_int32)]
 
 
+class W2v2Cfg(ctypes.Structure):
+    """mkws_w2v2_cfg (include/mkws.h)."""
+    _fields_ = [("conv_dim", ctypes.c_int32 * 7), ("conv_kernel", ctypes.c_int32 * 7), ("conv_stride", ctypes.c_int32 * 7),
+                ("hidden_size", ctypes.c_int32), ("num_hidden_layers", ctypes.c_int32), ("num_attention_heads", ctypes.c_int32),
+                ("intermediate_size", ctypes.c_int32), ("num_conv_pos_embeddings", ctypes.c_int32),
+                ("num_conv_pos_embedding_groups", ctypes.c_int32), ("layer_norm_eps", ctypes.c_float), ("group_norm", ctypes.c_int32),
+                ("conv_bias", ctypes.c_int32), ("stable_layer_norm", ctypes.c_int32), ("exact_gelu", ctypes.c_int32)]
+
+
 # every symbol include/mkws.h declares: (name, restype, argtypes)
 _P, _I, _F, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _CFG = ctypes.POINTER(FrontendCfg)
 _RCFG, _I64 = ctypes.POINTER(ResampleCfg), ctypes.c_int64
 _SCFG, _IP = ctypes.POINTER(SpectralCfg), ctypes.POINTER(ctypes.c_int)
+_WCFG = ctypes.POINTER(W2v2Cfg)
 SYMBOLS = [
     ("mkws_abi_version", _I, []),
     ("mkws_last_error", ctypes.c_char_p, []),
@@ -174,6 +184,14 @@ SYMBOLS = [
     ("mkws_dscnn_grid", _I, [_P]),
     ("mkws_dscnn_forward", _I, [_P, _P, _I, _P, _P, _P]),
     ("mkws_dscnn_tap", _I, [_P, _P, _I, _I, _P, _P]),
+    ("mkws_w2v2_default_cfg", None, [_WCFG]),
+    ("mkws_w2v2_param_count", _SZ, [_WCFG]),
+    ("mkws_w2v2_weight_manifest", _I, [_WCFG, ctypes.c_char_p, _SZ]),
+    ("mkws_w2v2_num_frames", _I, [_WCFG, _I]),
+    ("mkws_w2v2_create", _I, [_WCFG, _P, _SZ, _I, _I, ctypes.POINTER(_P)]),
+    ("mkws_w2v2_destroy", None, [_P]),
+    ("mkws_w2v2_forward", _I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    ("mkws_w2v2_tap", _I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     # DS-CNN training operators
     ("mkws_op_dscnn_stem_fwd", _I, [_P, _P, _P, _I, _P]),
     ("mkws_op_dscnn_stem_bwd_weight", _I, [_P, _P, _P, _I, _P]),

@@ -52,5 +52,9 @@ inline int require_device() {
 // arena past whatever queued folds hold (NULL when the arena is missing or too small), and the workgroup cap of an elementwise launch.
 float* train_scratch_at(size_t floats, hipStream_t s);
 int train_grid_cap();
+// C [M,N] = A [M,K] . B [K,N] on the fp32 MFMA GEMM of mkws_op_gemm with the reduction split over `ksplit` >= 1 slices of K: the slice sums go
+// to `part` (the caller's, ksplit * M * N floats, 16-byte aligned; unused for ksplit == 1) and a second launch folds them in slice order.
+// Independent of the training operators' context.
+int gemm_split(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int ksplit, float* part, hipStream_t s);
 
 }  // namespace mkws

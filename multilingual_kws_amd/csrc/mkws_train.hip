@@ -1793,7 +1793,7 @@ static bool tn2_wanted(int M, int N, int K) {
 }
 
 static int gemm_impl(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB, int accumulate, int ksplit,
-                     const float* bias, int act, float* Act, hipStream_t s, float* stats = nullptr, bool* stats_done = nullptr) {
+                     const float* bias, int act, float* Act, hipStream_t s, float* stats = nullptr, bool* stats_done = nullptr, float* own_part = nullptr) {
   MKWS_REQ(A && B && C, "gemm: NULL operand");
   MKWS_REQ(M > 0 && N > 0 && K > 0 && ksplit >= 0, "gemm: bad dimensions");
   const int tiles = ((N + 63) / 64) * ((M + 63) / 64);
@@ -1820,7 +1820,7 @@ static int gemm_impl(const float* A, const float* B, float* C, int M, int N, int
   }
   float* part = nullptr;
   if (ksplit > 1) {
-    part = scratch_at((size_t)ksplit * M * N, s);
+    part = own_part ? own_part : scratch_at((size_t)ksplit * M * N, s);      // (own_part: a caller outside the training context brings its slice buffer)
     MKWS_REQ(part, "gemm: ksplit = %d needs %zu floats of scratch (mkws_op_set_scratch)", ksplit, (size_t)ksplit * M * N);
   }
   const dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
@@ -1910,6 +1910,17 @@ static int gemm_impl(const float* A, const float* B, float* C, int M, int N, int
     launch_gemm_reduce(part, ksplit, C, M, N, ldc, accumulate, bias, act, Act, s);
   MKWS_HIP(hipGetLastError());
   return MKWS_OK;
+}
+
+// mkws_common.h: the NN GEMM with the reduction split over `ksplit` >= 1 slices whose sums go to the CALLER's buffer (ksplit * M * N floats,
+// 16-byte aligned) and are folded in slice order -- no context, no arena, nothing deferred
+extern "C++" {
+namespace mkws {
+int gemm_split(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int ksplit, float* part, hipStream_t s) {
+  MKWS_REQ(ksplit >= 1 && (ksplit == 1 || part), "gemm_split: bad arguments");
+  return gemm_impl(A, B, C, M, N, K, lda, ldb, ldc, 0, 0, 0, ksplit, nullptr, 0, nullptr, s, nullptr, nullptr, part);
+}
+}  // namespace mkws
 }
 
 // The launch constants mkws_op_get_option answers (read-only): the values the launchers below route by
