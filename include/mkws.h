@@ -314,6 +314,79 @@ int mkws_resample_live_push_many(mkws_resample* rs, void* d_states, size_t state
                                  const void* d_in, int in_i16, int out_samples, float* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Loudness and true peak: level normalisation of device audio.  The reference leaves it to `ffmpeg -af loudnorm=I=-16:TP=-1.5:LRA=11`
+ * (notebooks/dataperf_validation_filter.py:23-40), to pydub.effects.normalize (label_directory_dataperf.py:56-61) and to `sox ... stat`
+ * (notebooks/dataperf_experiments.py:468-477).  What is built is the MEASUREMENT of ITU-R BS.1770-4 and the linear gain that loudnorm's
+ * two-pass linear mode applies -- not loudnorm's single-pass dynamic compressor, which has no specification.
+ * A row is mono audio at `rate` Hz, float32 or int16 ((float) s / 32768.0f), of len = d_lengths[b] clamped to [0, n] samples (n when
+ * d_lengths is NULL); nothing beyond len is read.
+ *   K-weighting   two biquads by the bilinear form of libebur128 (at 48 kHz: the table of BS.1770), each row from zero state, in double:
+ *                 shelf f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; high-pass f0 = 38.13547087602444,
+ *                 Q = 0.5003270373238773 (the formulas: DESIGN.md section 40; the numbers: mkws_loudness_coeffs).
+ *   blocks        hop = rate / 10, block = 4 hop; block j = filtered samples [j hop, j hop + block), j = 0 .. floor((len - block) / hop);
+ *                 z_j = its mean square, l_j = -0.691 + 10 log10(z_j).
+ *   gates         absolute: l_j > -70; relative: also l_j > -0.691 + 10 log10(mean z over the absolute set) - 10;
+ *                 L = -0.691 + 10 log10(mean z over the relative set), -inf when no block passes the absolute gate.
+ *   true peak     max |y| over the 4 len samples of the row through mkws_resample's filter with L = 4, M = 1, centred, zeros outside the
+ *                 row (the float32 taps and samples, every product and sum in double, j ascending), with this cfg's zero_crossings,
+ *                 kaiser_beta and rolloff.  The sample peak max |x| and the mean square of the unweighted row ride on the same pass.
+ *   gain          loudness mode: g_dB = target_lufs - L; if 20 log10(true_peak) + g_dB > true_peak_db then g_dB = true_peak_db -
+ *                 20 log10(true_peak) (flag PEAK_LIMITED); gain = (float) 10^(g_dB / 20), in double.  L = -inf (silence, a row shorter
+ *                 than a block): gain = 1, flag UNMEASURED.  Peak mode (pydub's rule): gain = (float)(10^(-headroom_db / 20) /
+ *                 sample_peak); an all-zero row: gain = 1, flag UNMEASURED.  Both modes measure everything; the mode selects the rule.
+ * ---------------------------------------------------------------------------------------------- */
+#define MKWS_LOUDNESS_MAX_WORKSPACE_BYTES ((int64_t)1 << 32)
+#define MKWS_LOUDNESS_MAX_ZERO_CROSSINGS 2048
+
+enum { MKWS_LOUDNESS_MODE_LOUDNESS = 0, MKWS_LOUDNESS_MODE_PEAK = 1 };
+enum { MKWS_LOUDNESS_FLAG_UNMEASURED = 1, MKWS_LOUDNESS_FLAG_PEAK_LIMITED = 2 };
+
+typedef struct mkws_loudness_cfg {
+  int32_t rate;            /* 16000 */
+  int32_t mode;            /* MKWS_LOUDNESS_MODE_LOUDNESS */
+  double target_lufs;      /* -16.0 */
+  double true_peak_db;     /* -1.5 */
+  double headroom_db;      /* 0.1 (peak mode; pydub's default) */
+  int32_t zero_crossings;  /* 32 */
+  float kaiser_beta;       /* 9.0 */
+  float rolloff;           /* 0.95 */
+} mkws_loudness_cfg;
+
+typedef struct mkws_loudness mkws_loudness;
+
+/* The defaults above at the given rate. */
+void mkws_loudness_default_cfg(mkws_loudness_cfg* cfg, int rate);
+
+/* Host only (no GPU needed).  coeffs: out = shelf {b0, b1, b2, a1, a2}, high-pass {b0, b1, b2, a1, a2}.  geometry: out = {hop, block,
+ * chunk, tile}: the kernels cut a row into chunks of `chunk` samples (the largest divisor of the hop that is at most 32) and give a
+ * workgroup `tile` = 256 chunks.  MKWS_ERR_INVALID_ARG for NULL pointers, rate < 1, an unknown mode, a non-finite target_lufs,
+ * true_peak_db or headroom_db, zero_crossings < 1, a rolloff outside (0, 1] and a negative or non-finite kaiser_beta;
+ * MKWS_ERR_UNSUPPORTED for a rate that is not a multiple of 10, a rate at or below twice the shelf frequency, and zero_crossings above
+ * MKWS_LOUDNESS_MAX_ZERO_CROSSINGS. */
+int mkws_loudness_coeffs(const mkws_loudness_cfg* cfg, double out[10]);
+int mkws_loudness_geometry(const mkws_loudness_cfg* cfg, int32_t out[4]);
+
+/* The device handle: the tables and a workspace for up to max_rows rows of up to max_samples samples.  Refusals, all before a device is
+ * looked for: those above, MKWS_ERR_INVALID_ARG for max_rows < 1 or max_samples < 1, MKWS_ERR_UNSUPPORTED for a workspace above
+ * MKWS_LOUDNESS_MAX_WORKSPACE_BYTES (about 1.3 bytes per sample of max_rows * max_samples at a chunk of 32). */
+int mkws_loudness_create(const mkws_loudness_cfg* cfg, int max_rows, int64_t max_samples, mkws_loudness** out);
+void mkws_loudness_destroy(mkws_loudness* h);
+
+/* measure: B rows of n samples, row b at d_in + b * in_stride elements; d_lengths int64 [B] or NULL.  Writes, per row, d_stats
+ * float64 [B, 4] = {L, true_peak, sample_peak, mean_square} (linear peaks; mean_square = 0 for len = 0), d_counts int32 [B, 4] =
+ * {blocks, blocks past the absolute gate, blocks past both gates, flags} and d_gain float32 [B].  Five launches (one for n == 0).
+ * apply: d_out row b at d_out + b * out_stride = (float) x * d_gain[b] (one rounding) for the first len samples and 0.0f up to n;
+ * d_gain is read on the device.  d_out may be d_in itself (float32, equal strides); any other overlap is undefined.
+ * MKWS_ERR_INVALID_ARG for NULL pointers, negative sizes, B > max_rows, n > max_samples and strides shorter than the rows; B == 0
+ * returns MKWS_OK with nothing launched.  Every sum and maximum across lanes is taken in a fixed order without atomics: the same call
+ * gives the same bits, and a row's results do not depend on the other rows.  Asynchronous on `stream`, allocates nothing, never
+ * synchronises: capturable. */
+int mkws_loudness_measure(mkws_loudness* h, const void* d_in, int in_i16, int B, int64_t n, int64_t in_stride, const int64_t* d_lengths,
+                          double* d_stats, int32_t* d_counts, float* d_gain, void* stream);
+int mkws_loudness_apply(mkws_loudness* h, const void* d_in, int in_i16, int B, int64_t n, int64_t in_stride, const int64_t* d_lengths,
+                        const float* d_gain, float* d_out, int64_t out_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * WAV sample data decoded on the device: the bytes of a file's `data` chunk, in any common format and channel layout, become float32
  * audio in one launch for a whole batch of files.  The reference leaves formats and channels to `sox` / `soxi` (run.py:259-268,
  * luganda/luganda.py:145, word_extraction.py:223-231).  A FRAME is `channels` consecutive little-endian samples; a sample of b bytes

@@ -53,6 +53,12 @@ class ResampleCfg(ctypes.Structure):
                 ("kaiser_beta", ctypes.c_float), ("rolloff", ctypes.c_float)]
 
 
+class LoudnessCfg(ctypes.Structure):
+    """mkws_loudness_cfg (include/mkws.h)."""
+    _fields_ = [("rate", ctypes.c_int32), ("mode", ctypes.c_int32), ("target_lufs", ctypes.c_double), ("true_peak_db", ctypes.c_double),
+                ("headroom_db", ctypes.c_double), ("zero_crossings", ctypes.c_int32), ("kaiser_beta", ctypes.c_float), ("rolloff", ctypes.c_float)]
+
+
 class SpectralCfg(ctypes.Structure):
     """mkws_spectral_cfg (include/mkws.h)."""
     _fields_ = [("sample_rate", ctypes.c_int32), ("window_size_samples", ctypes.c_int32), ("window_stride_samples", ctypes.c_int32),
@@ -101,6 +107,7 @@ _CFG = ctypes.POINTER(FrontendCfg)
 _RCFG, _I64 = ctypes.POINTER(ResampleCfg), ctypes.c_int64
 _SCFG, _IP = ctypes.POINTER(SpectralCfg), ctypes.POINTER(ctypes.c_int)
 _WCFG = ctypes.POINTER(W2v2Cfg)
+_LCFG = ctypes.POINTER(LoudnessCfg)
 SYMBOLS = [
     ("mkws_abi_version", _I, []),
     ("mkws_last_error", ctypes.c_char_p, []),
@@ -135,6 +142,13 @@ SYMBOLS = [
     ("mkws_resample_live_in_samples", _I, [_P, _I]),
     ("mkws_resample_live_state_bytes", _SZ, [_P]),
     ("mkws_resample_live_push_many", _I, [_P, _P, _SZ, _I, _P, _P, _I, _I, _P, _P]),
+    ("mkws_loudness_default_cfg", None, [_LCFG, _I]),
+    ("mkws_loudness_coeffs", _I, [_LCFG, _P]),
+    ("mkws_loudness_geometry", _I, [_LCFG, _P]),
+    ("mkws_loudness_create", _I, [_LCFG, _I, _I64, ctypes.POINTER(_P)]),
+    ("mkws_loudness_destroy", None, [_P]),
+    ("mkws_loudness_measure", _I, [_P, _P, _I, _I, _I64, _I64, _P, _P, _P, _P, _P]),
+    ("mkws_loudness_apply", _I, [_P, _P, _I, _I, _I64, _I64, _P, _P, _P, _I64, _P]),
     ("mkws_pcm_frame_bytes", _I, [_I, _I]),
     ("mkws_pcm_decode", _I, [_P, _I64, _P, _I, _I64, _P, _I64, _P, _P]),
     ("mkws_pcm_encode", _I, [_P, _I64, _P, _I, _I64, _P, _I64, _P, _P]),

@@ -201,6 +201,66 @@ def to_sample_rate(audio, rate_in, rate_out=16000):
     return _resampler_for(rate_in, rate_out, device).forward(audio, centred=True)
 
 
+_meters = {}
+
+
+def _meter_for(rate, device, rows, samples, options=None):
+    """The process-wide LoudnessMeter of a rate on `device` (default: the current one), as _resampler_for keeps the resamplers: one per
+    (rate, device).  It is replaced by a larger one when a call brings more rows or longer rows than its workspace holds, and by another
+    when a call brings other options (None: normalize_loudness's defaults); nobody who got it from here may close it."""
+    import torch
+    from ..loudness import LoudnessMeter
+    index = torch.cuda.current_device() if device is None else torch.device(device).index
+    if index is None:
+        index = torch.cuda.current_device()
+    key = (int(rate), index)
+    m = _meters.get(key)
+    if options is None:
+        options = dict(target_lufs=-16.0, true_peak_db=-1.5, mode="loudness")
+    if m is None or m.options != options or m.max_rows < rows or m.max_samples < samples:
+        rows, samples = max(int(rows), 1), max(int(samples), 1)
+        with torch.cuda.device(index):
+            try:                                       # room for what came before as well, where that workspace is allowed
+                new = LoudnessMeter(rate, max_rows=max(rows, m.max_rows if m else 0), max_samples=max(samples, m.max_samples if m else 0), **options)
+            except _lib.MkwsError:
+                new = LoudnessMeter(rate, max_rows=rows, max_samples=samples, **options)  # (a refusal leaves the old meter in place)
+            if m is not None:
+                torch.cuda.synchronize()                                                  # nothing queued still reads the old workspace
+                m.close()
+        m = _meters[key] = new
+    return m
+
+
+def _loudness_call(audio):
+    import torch
+    a = audio if torch.is_tensor(audio) else np.asarray(audio)
+    if a.ndim not in (1, 2):
+        raise ValueError("audio must be [n] or [B, n]")
+    rows, samples = (1, a.shape[0]) if a.ndim == 1 else a.shape
+    return (audio.device if torch.is_tensor(audio) and audio.is_cuda else None), int(rows), int(samples)
+
+
+def measure_loudness(audio, sample_rate=16000, lengths=None):
+    """What the reference asks of `sox ... stat` and of loudnorm's first pass: audio [n] or [B, n], float32 or int16, numpy or tensor, at
+    sample_rate -> (stats float64 [B, 4] = BS.1770 integrated loudness in LUFS, true peak, sample peak (linear), mean square; counts int32
+    [B, 4] = blocks, blocks past the absolute gate, blocks past both gates, flags) of loudness.LoudnessMeter.measure (DESIGN.md section
+    40).  lengths: the samples of every row that count.  The flags are those of normalize_loudness's default options, whatever was
+    called before."""
+    device, rows, samples = _loudness_call(audio)
+    return _meter_for(sample_rate, device, rows, samples).measure(audio, lengths)
+
+
+def normalize_loudness(audio, sample_rate=16000, target_lufs=-16.0, true_peak_db=-1.5, mode="loudness", lengths=None):
+    """The level step the reference runs as `ffmpeg -af loudnorm=I=-16:TP=-1.5:LRA=11` (notebooks/dataperf_validation_filter.py:23-40):
+    every row times ONE gain that brings its BS.1770 integrated loudness to target_lufs, lowered where the true peak would pass
+    true_peak_db -- the linear gain of loudnorm's two-pass mode, not its dynamic compressor.  mode="peak" is pydub.effects.normalize
+    (label_directory_dataperf.py:56-61): the sample peak to -0.1 dBFS.  float32 of the same kind and shape; a silent row, and a row
+    shorter than one 400 ms block, comes back as it is.  lengths: the samples of every row that count (the rest comes back as zeros)."""
+    device, rows, samples = _loudness_call(audio)
+    m = _meter_for(sample_rate, device, rows, samples, dict(target_lufs=float(target_lufs), true_peak_db=float(true_peak_db), mode=mode))
+    return m.normalize(audio, lengths)
+
+
 def read_wav_at(path, sample_rate=16000, desired_samples=-1):
     """A PCM16 WAV at any rate -> float32 [samples] at sample_rate: decoded, converted on the device when the file's rate differs
     (to_sample_rate), then zero-padded or truncated to desired_samples as decode_wav does."""
@@ -287,16 +347,19 @@ def _upload_sample_bytes(images, infos, takes, device):
     return _pinned_bytes.upload(total, device), offsets
 
 
-def read_clips(files, sample_rate=16000, desired_samples=16000, channel=0, device=None):
+def read_clips(files, sample_rate=16000, desired_samples=16000, channel=0, device=None, normalize=None):
     """WAV files of any supported format (pcm.wav_info), rate and channel count -> float32 CUDA tensor [len(files), desired_samples] at
     sample_rate: row i is file i's channel `channel` (an int, or "mix" for the mean of the channels), converted on the device when the
     file's rate differs (to_sample_rate's filter, centred), zero-padded or truncated to desired_samples.  The sample bytes of all files
     travel in one upload and are decoded by one mkws_pcm_decode launch; the resampler runs once per distinct rate.  For a 16-bit PCM
     file at sample_rate a row is _read_wav(f, desired_samples) bit for bit, at another rate read_wav_at(f, sample_rate,
-    desired_samples).  An entry of `files` may also be the file's bytes."""
+    desired_samples).  An entry of `files` may also be the file's bytes.  normalize: a dict of normalize_loudness's options (target_lufs,
+    true_peak_db, mode) levels every row on the device, measured over the file's own samples (the zero padding counts for nothing)."""
     import torch
     from .. import pcm
     files, n = list(files), int(desired_samples)
+    if normalize is not None and (not isinstance(normalize, dict) or set(normalize) - {"target_lufs", "true_peak_db", "mode"}):
+        raise ValueError("read_clips: normalize is None or a dict of target_lufs, true_peak_db and mode")
     if n < 1:
         raise ValueError(f"read_clips: desired_samples = {desired_samples} (at least 1)")
     dev, ch = _cuda_device(device), pcm.channel_index(channel)
@@ -343,6 +406,11 @@ def read_clips(files, sample_rate=16000, desired_samples=16000, channel=0, devic
             block = torch.zeros((len(idx), n), dtype=torch.float32, device=dev)
             block[:, :m] = torch.where(keep, y[:, :m], torch.zeros((), dtype=torch.float32, device=dev))
             result.index_copy_(0, meta[0], block)
+    if normalize is not None:
+        own = [min(n, info.frames if info.rate == int(sample_rate) else _resampler_for(info.rate, sample_rate, dev).out_samples(info.frames))
+               for info in infos]
+        with torch.cuda.device(dev):
+            return normalize_loudness(result, sample_rate, lengths=own, **normalize)
     return result.clone() if groups else result      # without the scratch blocks behind it
 
 
